@@ -3,7 +3,7 @@
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats R] [--grid R [--cols C]]
                   [--materials uniform|array|ring] [--boundary mur|pml] [--dtype f32|f64]
-                  [--pmc live|off] [--no-secondary] [--no-cpu-baseline]
+                  [--dump-outputs DIR] [--full [--pmc live|off] [--no-secondary] [--no-cpu-baseline]]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,19 +12,29 @@ source) over the whole grid -- fdtd.py:31-34 of the reference.
 
 Workloads (all synthetic: zero fields, ricker source at the grid centre):
   N = 1  headline: 16384 x 16384 fp32, uniform eps/mu, Mur-5 frame -- the grid BASELINE.json's
-         north_star quotes its 1-GPU target on.  The same JSON line carries, under "secondary",
-         BASELINE configs[1] (4096^2 uniform), configs[2] (8192^2 ring-resonator eps map), the
-         headline grid with eps AND mu as arrays (32 B per cell-step, SURVEY.md M2's byte count), one rank's
+         north_star quotes its 1-GPU target on.  A plain run sets up, warms up, times the K steps and prints the
+         line; everything else is measured only with --full: the roofline's HBM traffic (rocprofv3 child processes),
+         the full-length kernel by itself, clocks (amdsmi, in-kernel probe), the CPU baseline, the tolerance build
+         and, under "secondary", BASELINE configs[1] (4096^2 uniform), configs[2] (8192^2 ring-resonator eps map),
+         the headline grid with eps AND mu as arrays (32 B per cell-step, SURVEY.md M2's byte count), one rank's
          4096 x 32768 slab of configs[4] with the PML, and the reference's own arithmetic type, float64, at
          4096^2 and 16384^2.
+         --dump-outputs DIR: after the timed steps, the fields the last timed step left (Ez, Hx, Hy: what
+         Engine.download() returns to a caller of the timed path) as DIR/<name>.npy in the run's dtype; grids
+         whose three fields exceed 64 MB in all are written as a window around the source (<name>_centre.npy) and
+         a fixed, seeded sample of cells (<name>_sample.npy).  The fields are reset to zero before the untimed runs
+         that precede the timed steps, so the same arguments give the same outputs from run to run and from build
+         to build: those of (ceil(400 / K) + R) * K steps from zero fields.
   N > 1  row slabs of 4096 rows per GPU, columns 4096*N: configs[3] (16384^2 on 4, Mur-5) and
          configs[4] (32768^2 on 8, PML) and their 2-GPU sibling; one process per GPU, halo exchange
          over RCCL.  After the timed run every rank CHECKS the rows next to its cuts against a
          single-engine run of a sub-grid around the cut (cut_bands_identical; exit code 4 when false).
 
-Timing (N = 1): inputs resident in HBM; W untimed warm-up steps; then R repetitions of: device sync,
-K steps, device sync.  value = cells * K / MEDIAN wall time of the repetitions (min / max beside it);
-every repetition also carries the HIP-event time of its K steps on the engine's stream.
+Timing (N = 1): inputs resident in HBM; W untimed warm-up steps, ~30 ms of untimed passes for the clock, the
+fields reset to zero, ceil(400 / K) untimed runs of exactly K steps (the timed run's kernels right before they are timed);
+then R repetitions (default 1, so that K is the number of timed steps) of: device sync, K steps, device sync.
+value = cells * K / MEDIAN wall time of the repetitions (min / max beside it); every repetition also carries the
+HIP-event time of its K steps on the engine's stream.
 
 roofline = the kernels that produced `value` (the passes of ONE run of K steps; with the driver's K = 20 at
 16384^2 that is the 20-step pair k_bulk_split<20> + k_zone<wide>):
@@ -32,7 +42,7 @@ roofline = the kernels that produced `value` (the passes of ONE run of K steps; 
                            against 8.0 TB/s.  A pass keeps 16-20 time levels on chip, so the algorithmic
                            byte count of the step-by-step formulation is not what the kernels move; the
                            fraction that still bounds them is the real one.
-  traffic                  HBM bytes per LAUNCH (= per pass; traffic_per_run / passes_per_run, like avg_launch_ms) from rocprofv3 PMC passes (FETCH_SIZE x 2 per the
+  traffic                  (--full) HBM bytes per LAUNCH (= per pass; traffic_per_run / passes_per_run, like avg_launch_ms) from rocprofv3 PMC passes (FETCH_SIZE x 2 per the
                            gfx950 correction of MI355X_MICROARCH.md, WRITE_SIZE exact), collected by THIS
                            run in child processes running the same K-step plan on the same launch shapes.
   overfetch                traffic / (one read + one write of every field per pass = 24 B x cells (+4 B per
@@ -44,11 +54,11 @@ roofline = the kernels that produced `value` (the passes of ONE run of K steps; 
                            than a one-step-per-pass kernel must move).
   frac_of_copy_rate        achieved / what a plain 16-byte-per-lane copy of the same field arrays reaches on this box in
                            this run (copy_kernel_GBps_before_after): the practical ceiling beside the data sheet's.
-  steady_state             the full-length pass kernel (16 steps) by itself: trimmed mean of
+  steady_state             (--full) the full-length pass kernel (16 steps) by itself: trimmed mean of
                            48 back-to-back launches, each between its own pair of HIP events on the engine's
                            stream (what rocprofv3's kernel trace reports per dispatch), with its own traffic.
-gpu_state = clocks per XCD, memory clock, socket power, temperature and the throttle-residency counters read
-through amdsmi before, DURING (sampling thread, ~1 kHz) and after the timed region.
+gpu_state (--full) = clocks per XCD, memory clock, socket power, temperature and the throttle-residency counters
+read through amdsmi before, DURING (sampling thread, ~1 kHz) and after the timed region.
 """
 import argparse
 import csv
@@ -250,6 +260,7 @@ def make_materials(fd, kind, rows, cols, r0=0, r1=None, dtype=np.float32):
 
 
 CLOCK_WARMUP_MS = 30.0
+REHEARSAL_STEPS = 400     # untimed K-step runs right before the timed ones: ceil(400 / K) of them (~31 ms at 16384^2)
 
 
 def clock_warmup(eng, cyc=0, target_ms=CLOCK_WARMUP_MS):
@@ -291,20 +302,30 @@ def make_engine(fd, rows, cols, materials, device, boundary, shapes=None, autotu
 
 
 def time_single(fd, rows, cols, steps, warmup, materials, device, boundary="mur", shapes=None, autotune=True,
-                dtype=np.float32, repeats=11, gpu=None, clock_groups=0):
-    """One whole-grid engine on one GPU: `repeats` timed runs of `steps` steps, then the full-length pass kernel
-    by itself.  Returns a dict of raw measurements."""
+                dtype=np.float32, repeats=11, gpu=None, clock_groups=0, full=True, outputs=None):
+    """One whole-grid engine on one GPU: `repeats` timed runs of `steps` steps from zero fields; with `full`, then
+    the full-length pass kernel by itself and the copy yardstick.  outputs: directory for dump_outputs() (the fields
+    the timed runs left).  Returns a dict of raw measurements."""
     import torch
     eng = make_engine(fd, rows, cols, materials, device, boundary, shapes, autotune, dtype)
     sr, sc = rows // 2, cols // 2
     eng.prepare(steps, sr, sc)  # launch-shape tuner (trial launches, state untouched): part of set-up
     eng.run(warmup, sr, sc, amplitudes(fd, 0, warmup)).sync()
     cyc = eng.cycle_steps
-    copy = [eng.measure_copy(4)]        # what a plain copy of the same arrays reaches on this device right now
-    walls, events, first = [], [], warmup
+    copy = [eng.measure_copy(4)] if full else []   # what a plain copy of the same arrays reaches on this device right now
     if gpu is not None:
         gpu.sample()
     warm_ms = clock_warmup(eng, cyc)
+    # zero fields, step 0 (memsets on the engine's stream, no idle gap), then untimed runs of exactly the timed run's
+    # length, REHEARSAL_STEPS in all, right before it: the timed steps start from the same state in every run and every
+    # build, however many passes the time-bounded clock warm-up made, and follow runs of their own kernels (the first
+    # K-step runs after other work are the slow ones)
+    eng.reset()
+    first = 0
+    for _ in range(-(-REHEARSAL_STEPS // steps)):
+        eng.run(steps, sr, sc, amplitudes(fd, first, steps))
+        first += steps
+    walls, events = [], []
     l0 = eng.info(16), eng.info(17)
     for _ in range(repeats):
         amps = amplitudes(fd, first, steps)
@@ -321,6 +342,13 @@ def time_single(fd, rows, cols, steps, warmup, materials, device, boundary="mur"
     res = dict(walls=walls, events_ms=events, pass_launches=(eng.info(16) - l0[0]) // repeats,
                step_launches=(eng.info(17) - l0[1]) // repeats, bpc=eng.bytes_per_cell_step, launch_steps=cyc,
                run_shape=list(eng.last_shape), run_last_nt=eng.last_pass_steps, clock_warmup_ms=warm_ms)
+    ssq, amax = eng.reduce("Ez")
+    assert np.isfinite(ssq) and amax > 0, "benchmark produced an empty or non-finite field"
+    if outputs is not None:
+        dump_outputs(outputs, dict(zip(("Ez", "Hx", "Hy"), eng.download())), (sr, sc))
+    if not full:
+        eng.close()
+        return res
     # duration of the full-length pass kernel by itself: single launches, each between its own pair of HIP
     # events on the engine's stream (what rocprofv3's kernel trace reports)
     if cyc:
@@ -351,11 +379,29 @@ def time_single(fd, rows, cols, steps, warmup, materials, device, boundary="mur"
                    hash_rows(0, rows - 1, cols, 3, 1e-3, dtype))
         eng.run(2 * cyc).sync()
         res["clock_vs_launch"]["random_fields"] = groups(clock_groups)
-    Ez, _, _ = eng.download()
-    assert np.isfinite(Ez).all() and np.abs(Ez).max() > 0, "benchmark produced an empty field"
-    del Ez
     eng.close()
     return res
+
+
+OUTPUT_BYTES = 64 << 20       # --dump-outputs: at most this much in all
+CENTRE, SAMPLE = 1024, 1 << 20
+
+
+def dump_outputs(path, fields, src):
+    """fields {name: array} -> path/<name>.npy.  If they exceed OUTPUT_BYTES in all: per field a CENTRE x CENTRE window
+    around the source cell `src` (where the pulse is) as <name>_centre.npy and SAMPLE cells at fixed, seeded positions
+    of the whole field (the Mur frame included) as <name>_sample.npy."""
+    os.makedirs(path, exist_ok=True)
+    whole = sum(a.nbytes for a in fields.values()) <= OUTPUT_BYTES
+    for name, a in fields.items():
+        if whole:
+            np.save(os.path.join(path, f"{name}.npy"), a)
+            continue
+        r0 = min(max(0, src[0] - CENTRE // 2), max(0, a.shape[0] - CENTRE))
+        c0 = min(max(0, src[1] - CENTRE // 2), max(0, a.shape[1] - CENTRE))
+        np.save(os.path.join(path, f"{name}_centre.npy"), np.ascontiguousarray(a[r0:r0 + CENTRE, c0:c0 + CENTRE]))
+        idx = np.sort(np.random.default_rng(12345).integers(0, a.size, SAMPLE))
+        np.save(os.path.join(path, f"{name}_sample.npy"), a.reshape(-1)[idx])
 
 
 # ---- HBM traffic of the pass kernels, measured by this run ---------------------------------------------
@@ -545,14 +591,14 @@ def roofline_block(cells, steps, r, traffic):
 
 
 def single_record(fd, rows, cols, steps, warmup, materials, boundary, device, pmc, note="", dtype="f32",
-                  autotune=True, repeats=11, gpu=None, traffic=None, shapes=None):
+                  autotune=True, repeats=11, gpu=None, traffic=None, shapes=None, full=True, outputs=None):
     """Timing of one whole-grid configuration + its roofline block.  traffic: the live PMC result (dict) or an
     error string if the live measurement failed, or None (pmc off).  shapes: launch shapes given on the command
-    line (else those the PMC children ran)."""
+    line (else those the PMC children ran).  full, outputs: as time_single()."""
     if shapes is None and isinstance(traffic, dict):
         shapes = traffic["shapes"]
     r = time_single(fd, rows, cols, steps, warmup, materials, device, boundary, shapes, autotune, NP_DTYPE[dtype],
-                    repeats, gpu, clock_groups=6 if gpu is not None else 0)
+                    repeats, gpu, clock_groups=6 if gpu is not None else 0, full=full, outputs=outputs)
     cells = rows * cols
     wall = float(np.median(r["walls"]))
     rec = {"value": round(cells * steps / wall / 1e6, 1), "unit": "Mcell-steps/s", "steps": steps,
@@ -560,17 +606,20 @@ def single_record(fd, rows, cols, steps, warmup, materials, boundary, device, pm
            "value_min_max": [round(cells * steps / max(r["walls"]) / 1e6, 1), round(cells * steps / min(r["walls"]) / 1e6, 1)],
            "wall_ms_all": [round(w * 1e3, 4) for w in r["walls"]], "dtype": dtype,
            "clock_warmup": {"ms": r["clock_warmup_ms"],
-                            "how": "untimed full-length passes right before the timed repetitions, after the W warm-up steps and "
-                                   "the set-up around them: the chip needs 10-20 ms of work to hold its clock"},
+                            "how": "untimed full-length passes after the W warm-up steps and the set-up around them: the chip "
+                                   "needs 10-20 ms of work to hold its clock; then the fields are reset to zero and untimed "
+                                   "runs of the K steps (ceil(400 / K) of them) precede the timed repetitions"},
            "config": {"workload": f"{rows}x{cols} {'fp32' if dtype == 'f32' else 'fp64'} TE-mode, {materials} eps/mu, "
                                   + ("Mur-5" if boundary == "mur" else "split-field PML (40 cells)")
                                   + " boundary, ricker point source at the centre" + note,
                       "grid": [rows, cols], "materials": materials, "boundary": boundary},
            "roofline": roofline_block(cells, steps, r, traffic)}
     rl = rec["roofline"]
-    rl["copy_kernel_GBps_before_after"] = r["copy_gbps"]
-    # the same rates against what a plain copy of the same arrays reaches on this box (the practical ceiling)
-    copy = max(r["copy_gbps"]) if r["copy_gbps"] else 0
+    copy = 0
+    if r.get("copy_gbps"):
+        rl["copy_kernel_GBps_before_after"] = r["copy_gbps"]
+        # the same rates against what a plain copy of the same arrays reaches on this box (the practical ceiling)
+        copy = max(r["copy_gbps"])
     if copy > 0:
         if rl.get("achieved"):
             rl["frac_of_copy_rate"] = round(rl["achieved"] / copy, 4)
@@ -654,7 +703,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--warmup", type=int, default=40)
-    ap.add_argument("--repeats", type=int, default=11, help="N=1: timed repetitions of the K steps (median reported)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="N=1: timed repetitions of the K steps (median reported; default 1, the secondary records 11)")
     ap.add_argument("--grid", type=int, default=0, help="rows (default 16384 on one GPU, 4096 per GPU otherwise)")
     ap.add_argument("--cols", type=int, default=0, help="columns (default = rows on one GPU, 4096*gpus otherwise)")
     ap.add_argument("--materials", choices=["uniform", "array", "ring"], default="uniform")
@@ -662,8 +712,14 @@ def main():
     ap.add_argument("--boundary", choices=["mur", "pml"], default=None,
                     help="mur = the reference's 5-px Mur frame; pml = the build-defined split-field PML "
                          "(default: mur, and pml for --gpus 8 = BASELINE configs[4])")
-    ap.add_argument("--pmc", choices=["live", "off"], default="live",
-                    help="roofline.traffic: measured by this run through rocprofv3 child processes, or omitted")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: also measure what the headline figure does not need (module docstring): PMC traffic, "
+                         "the full-length kernel, clocks, the CPU baseline, the tolerance build, the secondary records")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="N=1: write the fields the last timed step left to DIR/<name>.npy (at most 64 MB in all)")
+    ap.add_argument("--pmc", choices=["live", "off"], default=None,
+                    help="roofline.traffic: measured by this run through rocprofv3 child processes, or omitted "
+                         "(default: live with --full, else off)")
     ap.add_argument("--exchange", choices=["overlapped", "plain"], default="overlapped")
     ap.add_argument("--loop", choices=["auto", "c", "python"], default="auto",
                     help="N > 1: the run loop in C with the library's RCCL transport (auto on nccl) or the "
@@ -687,6 +743,10 @@ def main():
         args.cols = args.cols or args.grid
         args.boundary = args.boundary or "mur"
         return pmc_child(args)
+    if args.steps < 1:
+        sys.exit("--steps must be at least 1")
+    args.pmc = args.pmc or ("live" if args.full else "off")
+    repeats = args.repeats or 1
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -696,6 +756,8 @@ def main():
                  f"--nproc-per-node {args.gpus}")
     if os.environ.get("FDTD2D_ONE_GPU"):
         local = 0
+    if world > 1 and args.dump_outputs:
+        sys.exit("--dump-outputs: one GPU only (--gpus 1)")
     boundary = args.boundary or ("pml" if world == 8 else "mur")
 
     if world == 1:
@@ -704,7 +766,7 @@ def main():
         default_cfg = (rows, cols, args.materials, boundary, args.dtype) == (16384, 16384, "uniform", "mur", "f32")
         recs = [(rows, cols, args.steps, args.warmup, args.materials, boundary, args.dtype,
                  " (the grid of BASELINE's 1-GPU target)" if default_cfg else "")]
-        if default_cfg and not args.no_secondary:
+        if args.full and default_cfg and not args.no_secondary:
             recs += [(4096, 4096, 400, 40, "uniform", "mur", "f32", " (BASELINE configs[1])"),
                      (8192, 8192, 160, 32, "ring", "mur", "f32", " (BASELINE configs[2] geometry)"),
                      (16384, 16384, 160, 32, "array", "mur", "f32", " (eps and mu as arrays: 32 B per cell-step)"),
@@ -726,11 +788,11 @@ def main():
         # with FDTD2D_ARITHMETIC=fused -- the library is chosen at import --, also started before this process
         # touches the GPU
         fused_rec = None
-        if default_cfg and not args.no_secondary and os.environ.get("FDTD2D_ARITHMETIC", "exact") == "exact" and \
+        if args.full and default_cfg and not args.no_secondary and os.environ.get("FDTD2D_ARITHMETIC", "exact") == "exact" and \
                 os.path.exists(os.path.join(ROOT, "fdtd-2d_amd", "libfdtd2d_fused.so")):
             try:
                 cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(args.steps), "--warmup", str(args.warmup),
-                       "--repeats", str(args.repeats), "--pmc", args.pmc, "--no-secondary", "--no-cpu-baseline"]
+                       "--repeats", str(repeats), "--pmc", args.pmc, "--full", "--no-secondary", "--no-cpu-baseline"]
                 p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, FDTD2D_ARITHMETIC="fused"))
                 d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
                 fused_rec = {k: d[k] for k in ("value", "unit", "steps", "warmup", "ms_per_step", "repeats", "value_min_max", "roofline")}
@@ -740,8 +802,8 @@ def main():
                 fused_rec["config"] = dict(d["config"], workload=d["config"]["workload"] + " -- tolerance build")
             except Exception as exc:
                 fused_rec = {"arithmetic": "fused", "error": f"{type(exc).__name__}: {exc}"}
-        gpu = GpuState(local)
-        before = gpu.read()
+        gpu = GpuState(local) if args.full else None
+        before = gpu.read() if gpu is not None else None
         import torch
         import fdtd2d_amd as fd
         torch.cuda.set_device(local)
@@ -751,24 +813,27 @@ def main():
         out = []
         for k, ((r_, c_, st, wu, mat, bnd, dt_, note), t) in enumerate(zip(recs, traffic)):
             out.append(single_record(fd, r_, c_, st, wu, mat, bnd, local, args.pmc, note, dt_, not args.no_autotune,
-                                     args.repeats, gpu if k == 0 else None, t, forced if k == 0 else None))
+                                     repeats if k == 0 else args.repeats or 11, gpu if k == 0 else None, t,
+                                     forced if k == 0 else None, full=args.full,
+                                     outputs=args.dump_outputs if k == 0 else None))
         head = out[0]
         res = {"metric": "Mcell-steps/s", "value": head["value"], "unit": "Mcell-steps/s",
                "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": head["ms_per_step"],
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
                "data": "synthetic", "config": head["config"], "repeats": head["repeats"],
                "value_min_max": head["value_min_max"], "wall_ms_all": head["wall_ms_all"],
-               "clock_warmup": head["clock_warmup"], "roofline": head["roofline"],
-               "gpu_state": {"source": "amdsmi gpu_metrics", "partition": getattr(gpu, "partition", None),
-                             "device": getattr(gpu, "device", None),
-                             "before": before, "during_timed_region": head.get("gpu_during"), "after": gpu.read()}}
+               "clock_warmup": head["clock_warmup"], "roofline": head["roofline"]}
+        if gpu is not None:
+            res["gpu_state"] = {"source": "amdsmi gpu_metrics", "partition": getattr(gpu, "partition", None),
+                                "device": getattr(gpu, "device", None),
+                                "before": before, "during_timed_region": head.get("gpu_during"), "after": gpu.read()}
         if len(out) > 1 or fused_rec:
             for o in out[1:]:
                 o.pop("wall_ms_all", None)
             res["secondary"] = out[1:] + ([fused_rec] if fused_rec else [])
         res["arithmetic"] = os.environ.get("FDTD2D_ARITHMETIC", "exact") + \
             (" (one rounding per operation: value-identical to the reference)" if os.environ.get("FDTD2D_ARITHMETIC", "exact") == "exact" else "")
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(rows)
         print(json.dumps(res))
         return
@@ -870,7 +935,7 @@ def main():
         os._exit(3)
     bad = verify["cut_bands_identical"] is False or not finite
     if rank == 0:
-        single = time_single(fd, slab, cols, min(args.steps, 96), 16, args.materials, local, boundary, repeats=3)
+        single = time_single(fd, slab, cols, min(args.steps, 96), 16, args.materials, local, boundary, repeats=3, full=False)
         single_v = slab * cols * min(args.steps, 96) / float(np.median(single["walls"])) / 1e6
         value = cells * args.steps / wall / 1e6
         bpc = single["bpc"]

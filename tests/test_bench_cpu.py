@@ -46,3 +46,33 @@ def test_roofline_block_of_a_run_and_of_the_full_length_kernel():
     # a failed live measurement leaves the timing in place and says why there is no traffic figure
     b2 = bench.roofline_block(cells, steps, r, "live PMC failed (test)")
     assert b2["traffic"] is None and b2["frac"] is None and "traffic_note" in b2 and b2["steady_state"]["value"] == ss["value"]
+
+
+def test_dump_outputs_writes_whole_fields_or_a_fixed_sample(tmp_path):
+    import bench
+    # small fields: written whole, in their own dtype
+    small = {"Ez": np.arange(40 * 50, dtype=np.float32).reshape(40, 50), "Hx": np.ones((40, 49), np.float32),
+             "Hy": np.full((39, 50), 2, np.float32)}
+    bench.dump_outputs(str(tmp_path / "small"), small, (20, 25))
+    for name, a in small.items():
+        got = np.load(tmp_path / "small" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, a)
+    # fields above the budget: a window around the source and a seeded sample of every field, within the budget,
+    # the same positions every time (each cell holds its own flat index, so the sample says where it came from)
+    rows, cols = 3000, 3001
+    big = {"Ez": np.arange(rows * cols, dtype=np.float64).reshape(rows, cols),
+           "Hx": np.arange(rows * (cols - 1), dtype=np.float64).reshape(rows, cols - 1),
+           "Hy": np.arange((rows - 1) * cols, dtype=np.float64).reshape(rows - 1, cols)}
+    assert sum(a.nbytes for a in big.values()) > bench.OUTPUT_BYTES
+    for d in ("big1", "big2"):
+        bench.dump_outputs(str(tmp_path / d), big, (100, 2000))
+    files = sorted(os.listdir(tmp_path / "big1"))
+    assert files == sorted(f"{n}_{k}.npy" for n in big for k in ("centre", "sample"))
+    assert sum(os.path.getsize(tmp_path / "big1" / f) for f in files) <= bench.OUTPUT_BYTES
+    c = bench.CENTRE
+    for name, a in big.items():
+        centre = np.load(tmp_path / "big1" / f"{name}_centre.npy")
+        assert centre.dtype == np.float64 and np.array_equal(centre, a[0:c, 2000 - c // 2:2000 + c // 2])
+        s = np.load(tmp_path / "big1" / f"{name}_sample.npy")
+        assert s.shape == (bench.SAMPLE,) and np.array_equal(s, np.load(tmp_path / "big2" / f"{name}_sample.npy"))
+        assert np.all(np.diff(s) >= 0) and s[0] >= 0 and s[-1] < a.size and len(np.unique(s)) > 0.9 * bench.SAMPLE

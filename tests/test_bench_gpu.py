@@ -1,10 +1,12 @@
 """GPU box: bench.py itself, end to end on a small grid -- the JSON line the driver parses must carry every field of the
-contract, with live PMC traffic (rocprofv3 child processes), clocks and the CPU baseline."""
+contract; with --full also live PMC traffic (rocprofv3 child processes), clocks and the CPU baseline; a plain run measures
+only the headline, and --dump-outputs writes what its timed steps computed."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -19,8 +21,9 @@ def _run(*args):
     return json.loads(lines[0])
 
 
-def test_bench_line_carries_the_contract_fields():
-    d = _run("--grid", "4096", "--steps", "20", "--warmup", "5", "--repeats", "5", "--no-secondary")
+def test_bench_line_carries_the_contract_fields(tmp_path):
+    d = _run("--grid", "4096", "--steps", "20", "--warmup", "5", "--repeats", "5", "--no-secondary", "--full",
+             "--dump-outputs", str(tmp_path))
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline", "gpu_state"):
         assert k in d, k
@@ -41,6 +44,12 @@ def test_bench_line_carries_the_contract_fields():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in c, k
     assert c["kind"] == "port" and c["cores"] == 1 and c["value"] > 1
+    # three 64 MB fields: a window around the source and a seeded sample of each, within the 64 MB budget
+    files = sorted(os.listdir(tmp_path))
+    assert files == sorted(f"{n}_{k}.npy" for n in ("Ez", "Hx", "Hy") for k in ("centre", "sample"))
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64 << 20
+    ez = np.load(tmp_path / "Ez_centre.npy")
+    assert ez.dtype == np.float32 and ez.shape == (1024, 1024) and np.isfinite(ez).all() and np.abs(ez).max() > 0
 
 
 def test_bench_other_dtype_boundary_and_no_pmc():
@@ -50,3 +59,28 @@ def test_bench_other_dtype_boundary_and_no_pmc():
     d = _run("--grid", "2048", "--cols", "4096", "--steps", "32", "--warmup", "16", "--repeats", "3", "--boundary", "pml", "--pmc", "off",
              "--no-secondary", "--no-cpu-baseline")
     assert d["config"]["boundary"] == "pml" and d["value"] > 1e4
+
+
+def test_plain_run_is_lean_and_dumps_what_its_timed_steps_computed(tmp_path):
+    """Without --full the line holds the headline alone (one timed run of exactly K steps), and --dump-outputs writes
+    the fields the timed steps left: those of the untimed K-step runs from zero fields (400 steps in all here) and the K
+    timed steps after them, value-identical to the NumPy oracle's."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import fdtd2d_amd as fd
+    from oracle import fdtd_numpy as onp
+    rows, cols, steps = 320, 400, 40
+    d = _run("--grid", str(rows), "--cols", str(cols), "--steps", str(steps), "--warmup", "8", "--dump-outputs", str(tmp_path))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in d, k
+    for k in ("cpu_baseline", "gpu_state", "secondary"):
+        assert k not in d, k
+    assert d["steps"] == steps and d["repeats"] == 1 and len(d["wall_ms_all"]) == 1 and d["roofline"]["traffic"] is None
+    assert abs(d["ms_per_step"] * steps - d["wall_ms_all"][0]) < 1e-3 * d["wall_ms_all"][0] + 1e-4
+    ref = onp.grid_zeros(rows, cols, np.float32)
+    eps, mu = onp.vacuum_materials(rows, cols, np.float32)
+    total = -(-bench.REHEARSAL_STEPS // steps) * steps + steps
+    onp.leapfrog(*ref, eps, mu, bench.DT, bench.DX, total, rows // 2, cols // 2, amps=bench.amplitudes(fd, 0, total))
+    for name, want in zip(("Ez", "Hx", "Hy"), ref):
+        got = np.load(tmp_path / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, want), name
