@@ -34,6 +34,10 @@ E_ARG, E_NODEVICE, E_NOMEM, E_STATE, E_COURANT = -1, -2, -3, -4, -5
  INFO_STEP_LAUNCHES, INFO_CYCLE_STEPS, INFO_LAST_BAND_ROWS, INFO_LAST_WAVES, INFO_LAST_EDGE_ROWS,
  INFO_LAST_PASS_STEPS, INFO_LAST_SIDE_WAVES, INFO_LAST_XCD_MAP) = range(25)
 
+(BATCH_INFO_COUNT, BATCH_INFO_ROWS, BATCH_INFO_COLS, BATCH_INFO_DTYPE, BATCH_INFO_STEP, BATCH_INFO_RESIDENT,
+ BATCH_INFO_LAUNCHES, BATCH_INFO_RESIDENT_MAX_CELLS, BATCH_INFO_LDS_BYTES, BATCH_INFO_PITCH) = range(10)
+BATCH_OPT_RESIDENT, BATCH_OPT_STEPS_PER_LAUNCH = 0, 1
+
 _vp, _i, _d, _ll = C.c_void_p, C.c_int, C.c_double, C.c_longlong
 
 # name -> (restype, argtypes); every symbol include/fdtd2d.h declares
@@ -92,6 +96,25 @@ SIGNATURES = {
     "fdtd2d_bytes_per_cell_step": (_i, [_vp]),
     "fdtd2d_device_ptr": (_vp, [_vp, _i]),
     "fdtd2d_version": (C.c_char_p, []),
+    # batched grids
+    "fdtd2d_batch_create": (_i, [C.POINTER(_vp), _i, _i, _i, _d, _d, _i, _i, _i]),
+    "fdtd2d_batch_destroy": (None, [_vp]),
+    "fdtd2d_batch_last_error": (C.c_char_p, [_vp]),
+    "fdtd2d_batch_info": (_ll, [_vp, _i]),
+    "fdtd2d_batch_set_option": (_i, [_vp, _i, _ll]),
+    "fdtd2d_batch_set_stream": (_i, [_vp, _vp]),
+    "fdtd2d_batch_set_materials": (_i, [_vp, _vp, _vp, _i]),
+    "fdtd2d_batch_set_materials_uniform": (_i, [_vp, _d, _d]),
+    "fdtd2d_batch_courant": (_i, [_vp, C.POINTER(_d)]),
+    "fdtd2d_batch_upload": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "fdtd2d_batch_download": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "fdtd2d_batch_reset": (_i, [_vp]),
+    "fdtd2d_batch_set_sources": (_i, [_vp, C.POINTER(_i)]),
+    "fdtd2d_batch_run": (_i, [_vp, _i, C.POINTER(_d)]),
+    "fdtd2d_batch_run_waveform": (_i, [_vp, _i, _i, C.POINTER(_d), _ll]),
+    "fdtd2d_batch_set_dft": (_i, [_vp, C.POINTER(_d), _i]),
+    "fdtd2d_batch_read_dft": (_i, [_vp, C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_sync": (_i, [_vp]),
 }
 
 # transport callback of fdtd2d_slab_attach
@@ -151,5 +174,12 @@ def load():
 def check(handle, rc: int):
     if rc != 0:
         msg = load().fdtd2d_last_error(handle)
+        raise Fdtd2dError(rc, msg.decode() if msg else "")
+    return rc
+
+
+def check_batch(handle, rc: int):
+    if rc != 0:
+        msg = load().fdtd2d_batch_last_error(handle)
         raise Fdtd2dError(rc, msg.decode() if msg else "")
     return rc

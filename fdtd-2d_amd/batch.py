@@ -1,0 +1,268 @@
+"""Batched engine: many independent grids of one shape advanced together on one MI355X.
+
+``BatchEngine`` owns one ``fdtd2d_batch`` handle: B members of rows x cols, each with its own materials,
+source rectangle, amplitudes and DFT frequency.  Members small enough for one workgroup's LDS run a whole
+``run(n)`` in one resident launch; larger ones run one launch per half-step for the whole batch.  Every
+member is value-identical to an ``Engine`` run on it.  A thin wrapper over the C ABI, like ``Engine``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _abi
+from .engine import _BOUNDARY, _code, _host
+
+_KIND = {"none": _abi.SRC_NONE, "ricker": _abi.SRC_RICKER, "sinusoidal": _abi.SRC_SINUSOIDAL}
+
+
+def _dptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+class BatchEngine:
+    """``count`` grids of rows x cols resident on one MI355X.
+
+    Host arrays are member-major: Ez (B, R, C), Hx (B, R, C-1), Hy (B, R-1, C), eps / mu (B, R, C).
+    boundary: "mur" (reference, main.py:29-61) or "none".
+    """
+
+    def __init__(self, count, rows, cols, dt=5e-14, dx=1e-4, dtype=np.float32, boundary="mur", device=0):
+        self._lib = _abi.load()
+        self._h = C.c_void_p()
+        self.count, self.rows, self.cols = int(count), int(rows), int(cols)
+        self.dt, self.dx = float(dt), float(dx)
+        self.dtype = np.dtype(dtype)
+        self.boundary = boundary
+        if boundary not in _BOUNDARY:
+            raise ValueError(f"unknown boundary {boundary!r}")
+        rc = self._lib.fdtd2d_batch_create(C.byref(self._h), self.count, self.rows, self.cols, self.dt, self.dx,
+                                           _code(dtype), _BOUNDARY[boundary], int(device))
+        if rc != 0:
+            msg = self._lib.fdtd2d_batch_last_error(None).decode()
+            self._h = C.c_void_p()
+            raise _abi.Fdtd2dError(rc, msg)
+
+    # -- lifetime -------------------------------------------------------------------
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.fdtd2d_batch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _ck(self, rc):
+        return _abi.check_batch(self._h, rc)
+
+    def info(self, what: int) -> int:
+        return int(self._lib.fdtd2d_batch_info(self._h, what))
+
+    @property
+    def resident(self) -> bool:
+        """Whether run() takes the resident path (one launch per run) with the current settings."""
+        return bool(self.info(_abi.BATCH_INFO_RESIDENT))
+
+    @property
+    def step_count(self) -> int:
+        return self.info(_abi.BATCH_INFO_STEP)
+
+    @property
+    def launches(self) -> int:
+        return self.info(_abi.BATCH_INFO_LAUNCHES)
+
+    @property
+    def resident_max_cells(self) -> int:
+        return self.info(_abi.BATCH_INFO_RESIDENT_MAX_CELLS)
+
+    @property
+    def lds_bytes(self) -> int:
+        return self.info(_abi.BATCH_INFO_LDS_BYTES)
+
+    def _shape(self, a, shape, name):
+        if a.shape != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {a.shape}")
+
+    # -- options --------------------------------------------------------------------
+    def set_option(self, resident=None, steps_per_launch=None):
+        """resident: -1 / None = by the capacity rule, 0 / False = never.  steps_per_launch: steps per
+        resident launch, 0 = the whole run.  Results never depend on them."""
+        if resident is not None:
+            v = 0 if resident is False or resident == 0 else -1
+            self._ck(self._lib.fdtd2d_batch_set_option(self._h, _abi.BATCH_OPT_RESIDENT, v))
+        if steps_per_launch is not None:
+            self._ck(self._lib.fdtd2d_batch_set_option(self._h, _abi.BATCH_OPT_STEPS_PER_LAUNCH,
+                                                       int(steps_per_launch)))
+        return self
+
+    def set_stream(self, hip_stream: int | None):
+        self._ck(self._lib.fdtd2d_batch_set_stream(self._h, hip_stream))
+
+    # -- materials ------------------------------------------------------------------
+    def set_materials(self, eps=None, mu=None):
+        """eps, mu: (B, R, C) arrays, scalars, or None for vacuum (material_init(None, ...))."""
+        from .api import EPS0, MU0
+        eps = EPS0 if eps is None else eps
+        mu = MU0 if mu is None else mu
+        if np.isscalar(eps) and np.isscalar(mu):
+            self._ck(self._lib.fdtd2d_batch_set_materials_uniform(self._h, float(eps), float(mu)))
+            return self
+        shape = (self.count, self.rows, self.cols)
+        e = _host(np.broadcast_to(eps, shape) if np.isscalar(eps) else eps, "eps")
+        m = _host(np.broadcast_to(mu, shape) if np.isscalar(mu) else mu, "mu")
+        self._shape(e, shape, "eps")
+        self._shape(m, shape, "mu")
+        if e.dtype != m.dtype:
+            m = m.astype(e.dtype)
+        self._ck(self._lib.fdtd2d_batch_set_materials(self._h, e.ctypes.data, m.ctypes.data, _code(e.dtype)))
+        return self
+
+    def courant(self) -> np.ndarray:
+        out = np.empty(self.count, np.float64)
+        self._ck(self._lib.fdtd2d_batch_courant(self._h, _dptr(out)))
+        return out
+
+    # -- field transfer -------------------------------------------------------------
+    def _field_shapes(self):
+        B, R, Cc = self.count, self.rows, self.cols
+        return (B, R, Cc), (B, R, Cc - 1), (B, R - 1, Cc)
+
+    def upload(self, Ez=None, Hx=None, Hy=None):
+        """Host -> device, any float dtype; a field given as None is left as is."""
+        arrs, code = [], None
+        for a, shp, nm in zip((Ez, Hx, Hy), self._field_shapes(), ("Ez", "Hx", "Hy")):
+            if a is None:
+                arrs.append(None)
+                continue
+            a = _host(a, nm)
+            self._shape(a, shp, nm)
+            if code is None:
+                code = _code(a.dtype)
+            elif _code(a.dtype) != code:
+                a = a.astype(np.float64 if code == _abi.F64 else np.float32)
+            arrs.append(a)
+        if code is None:
+            return self
+        ptr = [None if a is None else a.ctypes.data for a in arrs]
+        self._ck(self._lib.fdtd2d_batch_upload(self._h, ptr[0], ptr[1], ptr[2], code))
+        return self
+
+    def download(self, dtype=None):
+        """Device -> host: new arrays (Ez, Hx, Hy) of the engine dtype (or `dtype`)."""
+        dt = self.dtype if dtype is None else np.dtype(dtype)
+        out = [np.empty(s, dt) for s in self._field_shapes()]
+        self._ck(self._lib.fdtd2d_batch_download(self._h, *(a.ctypes.data for a in out), _code(dt)))
+        return tuple(out)
+
+    def reset(self):
+        self._ck(self._lib.fdtd2d_batch_reset(self._h))
+        return self
+
+    # -- sources and the loop ---------------------------------------------------------
+    def set_sources(self, rects):
+        """rects: (B, 2) {row, col} one-cell sources or (B, 4) {row, col, nrows, ncols} rectangles
+        (0 x 0 = no source for that member)."""
+        r = np.asarray(rects)
+        if r.ndim != 2 or r.shape[0] != self.count or r.shape[1] not in (2, 4):
+            raise ValueError(f"rects must have shape ({self.count}, 2) or ({self.count}, 4), got {r.shape}")
+        if r.shape[1] == 2:
+            r = np.concatenate([r, np.ones_like(r)], axis=1)
+        r = np.ascontiguousarray(r, dtype=np.int32)
+        self._ck(self._lib.fdtd2d_batch_set_sources(self._h, r.ctypes.data_as(C.POINTER(C.c_int))))
+        return self
+
+    def run(self, nsteps, amps=None):
+        """nsteps of H -> E -> source for every member.  amps: (B, nsteps) float64 (None = no source)."""
+        nsteps = int(nsteps)
+        if amps is None:
+            self._ck(self._lib.fdtd2d_batch_run(self._h, nsteps, None))
+            return self
+        a = np.asarray(amps, dtype=np.float64)
+        if a.ndim != 2 or a.shape[0] != self.count or a.shape[1] < nsteps:
+            raise ValueError(f"amps must have shape ({self.count}, {nsteps}), got {a.shape}")
+        a = np.ascontiguousarray(a[:, :nsteps])
+        self._ck(self._lib.fdtd2d_batch_run(self._h, nsteps, _dptr(a)))
+        return self
+
+    def run_waveform(self, nsteps, kind="ricker", fc=30e9, step0=0):
+        """run() with the waveform evaluated by the library at t = (step0 + n) * dt; fc scalar or (B,)."""
+        f = np.ascontiguousarray(np.broadcast_to(np.asarray(fc, dtype=np.float64), (self.count,)))
+        self._ck(self._lib.fdtd2d_batch_run_waveform(self._h, int(nsteps), _KIND[kind], _dptr(f), int(step0)))
+        return self
+
+    def set_dft(self, omega, every=1):
+        """Running Fourier transform of the whole grid at one angular frequency per member (scalar or (B,));
+        None removes it."""
+        if omega is None:
+            self._ck(self._lib.fdtd2d_batch_set_dft(self._h, None, 0))
+            return self
+        w = np.ascontiguousarray(np.broadcast_to(np.asarray(omega, dtype=np.float64), (self.count,)))
+        self._ck(self._lib.fdtd2d_batch_set_dft(self._h, _dptr(w), int(every)))
+        return self
+
+    def read_dft(self) -> np.ndarray:
+        """complex128 (B, R, C): sum of Ez * exp(-i omega n dt) over the sampled steps."""
+        shape = (self.count, self.rows, self.cols)
+        re, im = np.empty(shape), np.empty(shape)
+        self._ck(self._lib.fdtd2d_batch_read_dft(self._h, _dptr(re), _dptr(im)))
+        return re + 1j * im
+
+    def sync(self):
+        self._ck(self._lib.fdtd2d_batch_sync(self._h))
+        return self
+
+
+def _waveform_amps(kind, fc, nsteps, dt):
+    """(B, nsteps) amplitudes evaluated step by step as run_fdtd does (one row per distinct fc)."""
+    from .api import ricker_amplitude, sinusoidal_amplitude
+    f = {"ricker": ricker_amplitude, "sinusoidal": sinusoidal_amplitude}[kind]
+    rows = {}
+    out = np.empty((len(fc), nsteps), np.float64)
+    for b, v in enumerate(fc):
+        v = float(v)
+        if v not in rows:
+            rows[v] = np.array([f(i * dt, v) for i in range(nsteps)], dtype=np.float64)
+        out[b] = rows[v]
+    return out
+
+
+def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker", dt=5e-14, dx=1e-4,
+                   dtype=np.float64, boundary="mur", omega=None, dft_every=1, device=0):
+    """run_fdtd for B members of one shape at once: zero fields, Courant check per member, nsteps of
+    H -> E -> source with t = i*dt.
+
+    eps: (B, R, C); mu: None (vacuum), a scalar or (B, R, C).  sources: (B, 2) or (B, 4) rectangles
+    (BatchEngine.set_sources); fc: scalar or (B,); waveform "ricker", "sinusoidal" or None.  omega: None,
+    or the angular frequency per member (scalar or (B,)) of a running DFT of Ez sampled every `dft_every`
+    steps.  Returns (Ez, Hx, Hy), plus the complex (B, R, C) DFT when omega is given.
+    """
+    from .api import MU0
+    eps = np.asarray(eps)
+    if eps.ndim != 3:
+        raise ValueError(f"eps must have shape (B, R, C), got {eps.shape}")
+    B, R, Cc = eps.shape
+    mu = MU0 if mu is None else mu
+    mu_arr = np.asarray(mu)
+    if mu_arr.ndim not in (0, 3) or (mu_arr.ndim == 3 and mu_arr.shape != eps.shape):
+        raise ValueError(f"mu must be a scalar or have shape {eps.shape}, got {mu_arr.shape}")
+    mu_min = mu_arr.reshape(B, -1).min(axis=1) if mu_arr.ndim == 3 else np.full(B, float(mu_arr))
+    courant = (1 / np.sqrt(eps.reshape(B, -1).min(axis=1) * mu_min) * dt) / dx
+    assert np.all(courant <= 1.0), \
+        f"Courant stability condition not met: members {np.nonzero(~(courant <= 1.0))[0].tolist()} > 1.0"
+    fcs = np.broadcast_to(np.asarray(fc, dtype=np.float64), (B,))
+    with BatchEngine(B, R, Cc, dt, dx, dtype=dtype, boundary=boundary, device=device) as eng:
+        eng.set_materials(eps, mu)
+        eng.set_sources(sources)
+        if omega is not None:
+            eng.set_dft(omega, dft_every)
+        eng.run(nsteps, None if waveform is None else _waveform_amps(waveform, fcs, nsteps, dt))
+        fields = eng.download()
+        if omega is None:
+            return fields
+        return fields + (eng.read_dft(),)

@@ -1,0 +1,667 @@
+// fdtd2d_batch_* -- host side of the batched engine (include/fdtd2d.h, "batched grids").
+// B independent members of one shape, advanced together: members whose fields fit in one workgroup's
+// LDS run a whole fdtd2d_batch_run in one resident launch (k_batch_resident), the others one launch per
+// half-step for the whole batch (k_batch_h / k_batch_e).  Results never depend on the path.
+#include "../../include/fdtd2d.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "kernels_batch.hpp"
+
+struct fdtd2d_batch {
+    int count = 0, rows = 0, cols = 0, dtype = FDTD2D_F32, boundary = FDTD2D_BOUNDARY_MUR5, device = 0;
+    double dt = 0, dx = 0;
+    long long pitch = 0;          // elements per stored row
+    size_t esz = 4;               // element size
+    size_t mstride = 0;           // elements per member (rows * pitch)
+    size_t field_bytes = 0;       // bytes of one field of the whole batch
+
+    void *ez[2] = {nullptr, nullptr};
+    int cur = 0;                  // ez[cur] is the current Ez (the streamed path ping-pongs)
+    void *hx = nullptr, *hy = nullptr;
+    void *ce = nullptr, *ch = nullptr;    // coefficient arrays (nullptr with uniform materials)
+    void *kmur = nullptr;                 // Mur factor per member, in T
+    bool have_mat = false, uniform = true;
+    double ce_u = 0, ch_u = 0;            // uniform coefficients, already rounded to T
+    std::vector<double> courant;          // per member (fdtd.py:25-26)
+
+    int *rect = nullptr;                  // device copy of the source rectangles (4 per member)
+    bool have_src = false;                // some member has a non-empty rectangle
+    double *amps = nullptr;               // device amplitudes of the current run
+    size_t amps_cap = 0;
+
+    double *dft = nullptr;                // per member re[R*C], im[R*C]
+    double *omega = nullptr;
+    int dft_every = 0;
+    long long dft_step0 = 0;
+
+    long long step = 0, launches = 0;
+    int resident_opt = -1;                // -1: by the capacity rule, 0: never
+    int steps_per_launch = 0;             // resident path: 0 = the whole run in one launch
+
+    hipStream_t own_stream = nullptr, stream = nullptr;
+    std::string err;
+};
+
+namespace {
+
+thread_local std::string g_batch_create_error = "";
+
+int bfail(fdtd2d_batch *b, int code, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (b) b->err = buf;
+    else g_batch_create_error = buf;
+    return code;
+}
+
+#define BCHK(b, expr)                                                                                      \
+    do {                                                                                                   \
+        hipError_t e_ = (expr);                                                                            \
+        if (e_ != hipSuccess) return bfail((b), -(1000 + (int)e_), "%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+int use_device(fdtd2d_batch *b)
+{
+    hipError_t e = hipSetDevice(b->device);
+    if (e != hipSuccess)
+        return bfail(b, FDTD2D_E_NODEVICE, "hipSetDevice(%d): %s", b->device, hipGetErrorString(e));
+    return 0;
+}
+
+// dt/(x*dx) in T, as main.py:27,70,74 evaluate it for arrays of type T (same rounding as k_coef)
+template <class T> double coef_of(double x, double dt, double dx)
+{
+    const T xt = (T)x, dtt = (T)dt, dxt = (T)dx;
+    volatile T prod = xt * dxt;
+    volatile T q = dtt / prod;
+    return (double)q;
+}
+
+// (c*dt - dx)/(c*dt + dx), c = 1/sqrt(mu00*eps00), every operation in T (main.py:30-31)
+template <class T> double mur_of(double eps00, double mu00, double dt, double dx)
+{
+    const T e = (T)eps00, m = (T)mu00, dtt = (T)dt, dxt = (T)dx;
+    volatile T prod = m * e;
+    volatile T s = std::sqrt((T)prod);
+    volatile T c = (T)1 / s;
+    volatile T cdt = c * dtt;
+    volatile T num = cdt - dxt, den = cdt + dxt;
+    volatile T k = num / den;
+    return (double)k;
+}
+
+double courant_of(double eps_min, double mu_min, double dt, double dx)
+{
+    const double c = 1 / std::sqrt(eps_min * mu_min);
+    return (c * dt) / dx;
+}
+
+double get_elem(const void *p, int dt, size_t i)
+{
+    return dt == FDTD2D_F64 ? ((const double *)p)[i] : (double)((const float *)p)[i];
+}
+
+// a host value as the engine's type T stores it (NumPy astype: round to nearest)
+double as_engine(const fdtd2d_batch *b, double x) { return b->dtype == FDTD2D_F32 ? (double)(float)x : x; }
+
+// Host arrays (count x nrows x ncols of host_dtype) <-> the padded device layout of one field.
+// The element type changes on the host, one rounding per element like a NumPy astype.
+int copy_in(fdtd2d_batch *b, void *dev, const void *host, int host_dtype, int nrows, int ncols)
+{
+    std::vector<unsigned char> stage(b->field_bytes, 0);
+    for (int m = 0; m < b->count; ++m)
+        for (int i = 0; i < nrows; ++i) {
+            const size_t src = ((size_t)m * nrows + i) * ncols, dst = (size_t)m * b->mstride + (size_t)i * b->pitch;
+            if (b->dtype == FDTD2D_F32) {
+                float *d = (float *)stage.data() + dst;
+                for (int j = 0; j < ncols; ++j) d[j] = (float)get_elem(host, host_dtype, src + j);
+            } else {
+                double *d = (double *)stage.data() + dst;
+                for (int j = 0; j < ncols; ++j) d[j] = get_elem(host, host_dtype, src + j);
+            }
+        }
+    BCHK(b, hipStreamSynchronize(b->stream));
+    BCHK(b, hipMemcpy(dev, stage.data(), b->field_bytes, hipMemcpyHostToDevice));
+    return 0;
+}
+
+int copy_out(fdtd2d_batch *b, const void *dev, void *host, int host_dtype, int nrows, int ncols)
+{
+    std::vector<unsigned char> stage(b->field_bytes);
+    BCHK(b, hipStreamSynchronize(b->stream));
+    BCHK(b, hipMemcpy(stage.data(), dev, b->field_bytes, hipMemcpyDeviceToHost));
+    for (int m = 0; m < b->count; ++m)
+        for (int i = 0; i < nrows; ++i) {
+            const size_t dst = ((size_t)m * nrows + i) * ncols, src = (size_t)m * b->mstride + (size_t)i * b->pitch;
+            for (int j = 0; j < ncols; ++j) {
+                const double v = b->dtype == FDTD2D_F32 ? (double)((const float *)stage.data())[src + j]
+                                                        : ((const double *)stage.data())[src + j];
+                if (host_dtype == FDTD2D_F32) ((float *)host)[dst + j] = (float)v;
+                else ((double *)host)[dst + j] = v;
+            }
+        }
+    return 0;
+}
+
+int zero_fields(fdtd2d_batch *b)
+{
+    for (void *p : {b->ez[0], b->ez[1], b->hx, b->hy}) BCHK(b, hipMemsetAsync(p, 0, b->field_bytes, b->stream));
+    b->cur = 0;
+    b->step = 0;
+    return 0;
+}
+
+// ---- the capacity rule of the resident path ------------------------------------------------------------
+int lds_arrays(const fdtd2d_batch *b) { return (b->have_mat && b->uniform) ? 3 : 5; }
+
+size_t lds_bytes(const fdtd2d_batch *b)
+{
+    const int cells = b->rows * b->cols;
+    return (size_t)lds_arrays(b) * (b->dtype == FDTD2D_F32 ? fdtd::batch_lds_seg<float>(cells) * 4
+                                                           : fdtd::batch_lds_seg<double>(cells) * 8);
+}
+
+// largest R*C whose arrays fit in one workgroup's LDS (materials as currently set; arrays before any call)
+long long resident_max_cells(const fdtd2d_batch *b)
+{
+    const size_t per_array = fdtd::BATCH_LDS_LIMIT / (size_t)lds_arrays(b) / 16 * 16;
+    return (long long)(per_array / b->esz);
+}
+
+bool use_resident(const fdtd2d_batch *b)
+{
+    return b->resident_opt != 0 && (long long)b->rows * b->cols <= resident_max_cells(b);
+}
+
+// threads of a resident workgroup: a wave multiple, at least a quarter of the cells, at most 1024
+int resident_threads(int cells)
+{
+    const int want = ((cells + 3) / 4 + 63) / 64 * 64;
+    return want < fdtd::BATCH_RES_THREADS ? want : fdtd::BATCH_RES_THREADS;
+}
+
+template <class T> fdtd::BatchView<T> view(fdtd2d_batch *b, const double *amps, long long amp_stride)
+{
+    fdtd::BatchView<T> v;
+    v.ez = (T *)b->ez[b->cur];
+    v.hx = (T *)b->hx;
+    v.hy = (T *)b->hy;
+    v.ce = (const T *)b->ce;
+    v.ch = (const T *)b->ch;
+    v.ce_u = (T)b->ce_u;
+    v.ch_u = (T)b->ch_u;
+    v.kmur = (const T *)b->kmur;
+    v.B = b->count;
+    v.R = b->rows;
+    v.C = b->cols;
+    v.mur = b->boundary == FDTD2D_BOUNDARY_MUR5;
+    v.pitch = b->pitch;
+    v.mstride = b->mstride;
+    v.rect = b->rect;
+    v.amps = (b->have_src && amps) ? amps : nullptr;
+    v.amp_stride = amp_stride;
+    v.dft = b->dft;
+    v.omega = b->omega;
+    v.every = b->dft_every > 0 ? b->dft_every : 1;
+    v.dft_step0 = b->dft_step0;
+    v.dt = b->dt;
+    return v;
+}
+
+template <class T, bool ARR, int MAXC>
+int launch_resident(fdtd2d_batch *b, const fdtd::BatchView<T> &v, int n0, int nt, int threads)
+{
+    auto kern = &fdtd::k_batch_resident<T, ARR, MAXC>;
+    const size_t lds = lds_bytes(b);
+    BCHK(b, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds));
+    int per_cu = 0, cus = 0;
+    BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds));
+    BCHK(b, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
+    if (per_cu < 1) return bfail(b, FDTD2D_E_STATE, "resident kernel does not fit a CU (%zu B of LDS)", lds);
+    const long long round = (long long)per_cu * cus;
+    const int blocks = (int)(b->count < round ? b->count : round);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, b->stream, v, n0, nt, b->step);
+    BCHK(b, hipGetLastError());
+    b->launches++;
+    return 0;
+}
+
+template <class T, bool ARR> int run_resident(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride)
+{
+    const int cells = b->rows * b->cols, threads = resident_threads(cells);
+    const int per_thread = (cells + threads - 1) / threads;
+    const int chunk = b->steps_per_launch > 0 ? b->steps_per_launch : nsteps;
+    for (int n = 0; n < nsteps; n += chunk) {
+        const int nt = nsteps - n < chunk ? nsteps - n : chunk;
+        const fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+        int rc;
+        if (per_thread <= 4) rc = launch_resident<T, ARR, 4>(b, v, n, nt, threads);
+        else if (per_thread <= 8) rc = launch_resident<T, ARR, 8>(b, v, n, nt, threads);
+        else if (per_thread <= 16) rc = launch_resident<T, ARR, 16>(b, v, n, nt, threads);
+        else rc = bfail(b, FDTD2D_E_STATE, "%d cells per thread exceed the resident kernel's 16", per_thread);
+        if (rc) return rc;
+        b->step += nt;
+    }
+    return 0;
+}
+
+template <class T, bool ARR> int run_streamed(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride)
+{
+    const int cells = b->rows * b->cols;
+    const dim3 grid((cells + 255) / 256, b->count < 65535 ? b->count : 65535);
+    for (int n = 0; n < nsteps; ++n) {
+        const fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+        hipLaunchKernelGGL((fdtd::k_batch_h<T, ARR>), grid, dim3(256), 0, b->stream, v);
+        BCHK(b, hipGetLastError());
+        hipLaunchKernelGGL((fdtd::k_batch_e<T, ARR>), grid, dim3(256), 0, b->stream, v, (T *)b->ez[b->cur ^ 1], n,
+                           b->step + 1);
+        BCHK(b, hipGetLastError());
+        b->launches += 2;
+        b->cur ^= 1;
+        b->step++;
+    }
+    return 0;
+}
+
+template <class T> int run_impl(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride)
+{
+    const bool arr = !b->uniform;
+    if (use_resident(b))
+        return arr ? run_resident<T, true>(b, nsteps, amps, amp_stride) : run_resident<T, false>(b, nsteps, amps, amp_stride);
+    return arr ? run_streamed<T, true>(b, nsteps, amps, amp_stride) : run_streamed<T, false>(b, nsteps, amps, amp_stride);
+}
+
+int need_ready(fdtd2d_batch *b)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!b->have_mat) return bfail(b, FDTD2D_E_STATE, "materials not set: call fdtd2d_batch_set_materials first");
+    return use_device(b);
+}
+
+int alloc(fdtd2d_batch *b, void **p, size_t bytes)
+{
+    if (hipMalloc(p, bytes) != hipSuccess) {
+        *p = nullptr;
+        return bfail(b, FDTD2D_E_NOMEM, "hipMalloc of %zu bytes failed", bytes);
+    }
+    return 0;
+}
+
+void release(void **p)
+{
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+}
+
+}  // namespace
+
+// ===================================== C ABI ============================================
+
+extern "C" {
+
+int fdtd2d_batch_create(fdtd2d_batch_t **out, int count, int rows, int cols, double dt, double dx, int dtype,
+                        int boundary, int device)
+{
+    if (!out) return bfail(nullptr, FDTD2D_E_ARG, "out is NULL");
+    *out = nullptr;
+    if (count < 1) return bfail(nullptr, FDTD2D_E_ARG, "count must be >= 1, not %d", count);
+    if (rows < 11 || cols < 11)
+        return bfail(nullptr, FDTD2D_E_ARG, "grid %dx%d is below the 11x11 minimum of the 5-px Mur band", rows, cols);
+    if (dtype != FDTD2D_F32 && dtype != FDTD2D_F64)
+        return bfail(nullptr, FDTD2D_E_ARG, "dtype must be FDTD2D_F32 or FDTD2D_F64");
+    if (boundary != FDTD2D_BOUNDARY_NONE && boundary != FDTD2D_BOUNDARY_MUR5)
+        return bfail(nullptr, FDTD2D_E_ARG, "boundary %d: a batch takes FDTD2D_BOUNDARY_NONE or _MUR5", boundary);
+    if (!(dt > 0) || !(dx > 0)) return bfail(nullptr, FDTD2D_E_ARG, "dt and dx must be positive");
+    if (device < 0) return bfail(nullptr, FDTD2D_E_ARG, "device %d out of range", device);
+    if (rows > (1 << 20) || cols > (1 << 20) || (long long)rows * cols > (1LL << 30))
+        return bfail(nullptr, FDTD2D_E_ARG, "member %dx%d is too large", rows, cols);
+
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0)
+        return bfail(nullptr, FDTD2D_E_NODEVICE, "no HIP device available (%s); libfdtd2d has no CPU path",
+                     e == hipSuccess ? "device count is 0" : hipGetErrorString(e));
+    if (device >= ndev) return bfail(nullptr, FDTD2D_E_ARG, "device %d out of range (%d visible)", device, ndev);
+    hipDeviceProp_t prop;
+    e = hipGetDeviceProperties(&prop, device);
+    if (e != hipSuccess)
+        return bfail(nullptr, FDTD2D_E_NODEVICE, "hipGetDeviceProperties: %s", hipGetErrorString(e));
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return bfail(nullptr, FDTD2D_E_NODEVICE, "device %d is %s; this library is built for gfx950", device,
+                     prop.gcnArchName);
+
+    fdtd2d_batch *b = new fdtd2d_batch();
+    b->count = count; b->rows = rows; b->cols = cols;
+    b->dt = dt; b->dx = dx; b->dtype = dtype; b->boundary = boundary; b->device = device;
+    b->esz = dtype == FDTD2D_F32 ? 4 : 8;
+    b->pitch = ((long long)cols + 63) / 64 * 64;
+    b->mstride = (size_t)rows * (size_t)b->pitch;
+    b->field_bytes = (size_t)count * b->mstride * b->esz;
+    b->courant.assign((size_t)count, 0.0);
+    auto bail = [&](int code) {
+        g_batch_create_error = b->err;
+        fdtd2d_batch_destroy(b);
+        return code;
+    };
+    int rc = use_device(b);
+    if (rc) return bail(rc);
+    if (hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking) != hipSuccess)
+        return bail(bfail(b, FDTD2D_E_NODEVICE, "hipStreamCreate failed"));
+    b->stream = b->own_stream;
+    for (void **p : {&b->ez[0], &b->ez[1], &b->hx, &b->hy})
+        if ((rc = alloc(b, p, b->field_bytes))) return bail(rc);
+    if ((rc = alloc(b, &b->kmur, (size_t)count * b->esz))) return bail(rc);
+    if ((rc = alloc(b, (void **)&b->rect, (size_t)count * 4 * sizeof(int)))) return bail(rc);
+    if (hipMemsetAsync(b->rect, 0, (size_t)count * 4 * sizeof(int), b->stream) != hipSuccess)
+        return bail(bfail(b, FDTD2D_E_NODEVICE, "hipMemset of the source rectangles failed"));
+    if ((rc = zero_fields(b))) return bail(rc);
+    if (hipStreamSynchronize(b->stream) != hipSuccess)
+        return bail(bfail(b, FDTD2D_E_NODEVICE, "device sync failed after allocation"));
+    *out = b;
+    return 0;
+}
+
+void fdtd2d_batch_destroy(fdtd2d_batch_t *b)
+{
+    if (!b) return;
+    (void)hipSetDevice(b->device);
+    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    for (void **p : {&b->ez[0], &b->ez[1], &b->hx, &b->hy, &b->ce, &b->ch, &b->kmur, (void **)&b->rect,
+                     (void **)&b->amps, (void **)&b->dft, (void **)&b->omega})
+        release(p);
+    if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
+    delete b;
+}
+
+const char *fdtd2d_batch_last_error(const fdtd2d_batch_t *b)
+{
+    return b ? b->err.c_str() : g_batch_create_error.c_str();
+}
+
+long long fdtd2d_batch_info(const fdtd2d_batch_t *b, int what)
+{
+    if (!b) return FDTD2D_E_ARG;
+    switch (what) {
+    case FDTD2D_BATCH_INFO_COUNT: return b->count;
+    case FDTD2D_BATCH_INFO_ROWS: return b->rows;
+    case FDTD2D_BATCH_INFO_COLS: return b->cols;
+    case FDTD2D_BATCH_INFO_DTYPE: return b->dtype;
+    case FDTD2D_BATCH_INFO_STEP: return b->step;
+    case FDTD2D_BATCH_INFO_RESIDENT: return use_resident(b) ? 1 : 0;
+    case FDTD2D_BATCH_INFO_LAUNCHES: return b->launches;
+    case FDTD2D_BATCH_INFO_RESIDENT_MAX_CELLS: return resident_max_cells(b);
+    case FDTD2D_BATCH_INFO_LDS_BYTES: return (long long)lds_bytes(b);
+    case FDTD2D_BATCH_INFO_PITCH: return b->pitch;
+    default: return FDTD2D_E_ARG;
+    }
+}
+
+int fdtd2d_batch_set_option(fdtd2d_batch_t *b, int option, long long value)
+{
+    if (!b) return FDTD2D_E_ARG;
+    switch (option) {
+    case FDTD2D_BATCH_OPT_RESIDENT:
+        if (value != -1 && value != 0) return bfail(b, FDTD2D_E_ARG, "resident must be -1 (auto) or 0 (never)");
+        b->resident_opt = (int)value;
+        return 0;
+    case FDTD2D_BATCH_OPT_STEPS_PER_LAUNCH:
+        if (value < 0 || value > (1 << 30)) return bfail(b, FDTD2D_E_ARG, "steps per launch must be >= 0");
+        b->steps_per_launch = (int)value;
+        return 0;
+    default: return bfail(b, FDTD2D_E_ARG, "unknown option %d", option);
+    }
+}
+
+int fdtd2d_batch_set_stream(fdtd2d_batch_t *b, void *hip_stream)
+{
+    if (!b) return FDTD2D_E_ARG;
+    b->stream = hip_stream ? (hipStream_t)hip_stream : b->own_stream;
+    return 0;
+}
+
+int fdtd2d_batch_set_materials(fdtd2d_batch_t *b, const void *eps, const void *mu, int host_dtype)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!eps || !mu) return bfail(b, FDTD2D_E_ARG, "eps and mu must not be NULL");
+    if (host_dtype != FDTD2D_F32 && host_dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad host_dtype");
+    const size_t per = (size_t)b->rows * b->cols;
+    std::vector<double> emin((size_t)b->count, 1e300), mmin((size_t)b->count, 1e300), kmur((size_t)b->count);
+    for (int m = 0; m < b->count; ++m) {
+        for (size_t t = 0; t < per; ++t) {
+            const double e = as_engine(b, get_elem(eps, host_dtype, m * per + t));
+            const double u = as_engine(b, get_elem(mu, host_dtype, m * per + t));
+            if (!(e > 0) || !(u > 0))
+                return bfail(b, FDTD2D_E_ARG, "eps and mu must be positive (member %d, cell %zu)", m, t);
+            emin[m] = e < emin[m] ? e : emin[m];
+            mmin[m] = u < mmin[m] ? u : mmin[m];
+        }
+        const double e00 = get_elem(eps, host_dtype, m * per), u00 = get_elem(mu, host_dtype, m * per);
+        kmur[m] = b->dtype == FDTD2D_F32 ? mur_of<float>(e00, u00, b->dt, b->dx) : mur_of<double>(e00, u00, b->dt, b->dx);
+    }
+    int rc = use_device(b);
+    if (rc) return rc;
+    b->have_mat = false;
+    for (void **p : {&b->ce, &b->ch})
+        if (!*p && (rc = alloc(b, p, b->field_bytes))) return rc;
+    // the arrays are uploaded as eps / mu in T, then turned into dt/(x*dx) in place (padding stays 0)
+    if ((rc = copy_in(b, b->ce, eps, host_dtype, b->rows, b->cols))) return rc;
+    if ((rc = copy_in(b, b->ch, mu, host_dtype, b->rows, b->cols))) return rc;
+    const size_t n = (size_t)b->count * b->mstride;
+    for (void *p : {b->ce, b->ch}) {
+        if (b->dtype == FDTD2D_F32)
+            hipLaunchKernelGGL((fdtd::k_coef<float>), dim3(2048), dim3(256), 0, b->stream, (float *)p, n, (float)b->dt,
+                               (float)b->dx);
+        else
+            hipLaunchKernelGGL((fdtd::k_coef<double>), dim3(2048), dim3(256), 0, b->stream, (double *)p, n, b->dt, b->dx);
+        BCHK(b, hipGetLastError());
+    }
+    std::vector<unsigned char> kt((size_t)b->count * b->esz);
+    for (int m = 0; m < b->count; ++m) {
+        if (b->dtype == FDTD2D_F32) ((float *)kt.data())[m] = (float)kmur[m];
+        else ((double *)kt.data())[m] = kmur[m];
+        b->courant[m] = courant_of(emin[m], mmin[m], b->dt, b->dx);
+    }
+    BCHK(b, hipMemcpyAsync(b->kmur, kt.data(), kt.size(), hipMemcpyHostToDevice, b->stream));
+    BCHK(b, hipStreamSynchronize(b->stream));
+    b->uniform = false;
+    b->have_mat = true;
+    return 0;
+}
+
+int fdtd2d_batch_set_materials_uniform(fdtd2d_batch_t *b, double eps, double mu)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!(eps > 0) || !(mu > 0)) return bfail(b, FDTD2D_E_ARG, "eps and mu must be positive");
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    release(&b->ce);
+    release(&b->ch);
+    double k;
+    if (b->dtype == FDTD2D_F32) {
+        b->ce_u = coef_of<float>(eps, b->dt, b->dx);
+        b->ch_u = coef_of<float>(mu, b->dt, b->dx);
+        k = mur_of<float>(eps, mu, b->dt, b->dx);
+    } else {
+        b->ce_u = coef_of<double>(eps, b->dt, b->dx);
+        b->ch_u = coef_of<double>(mu, b->dt, b->dx);
+        k = mur_of<double>(eps, mu, b->dt, b->dx);
+    }
+    std::vector<unsigned char> kt((size_t)b->count * b->esz);
+    for (int m = 0; m < b->count; ++m) {
+        if (b->dtype == FDTD2D_F32) ((float *)kt.data())[m] = (float)k;
+        else ((double *)kt.data())[m] = k;
+    }
+    BCHK(b, hipMemcpy(b->kmur, kt.data(), kt.size(), hipMemcpyHostToDevice));
+    b->courant.assign((size_t)b->count, courant_of(eps, mu, b->dt, b->dx));
+    b->uniform = true;
+    b->have_mat = true;
+    return 0;
+}
+
+int fdtd2d_batch_courant(const fdtd2d_batch_t *b, double *out)
+{
+    if (!b || !out) return FDTD2D_E_ARG;
+    if (!b->have_mat) return FDTD2D_E_STATE;
+    for (int m = 0; m < b->count; ++m) out[m] = b->courant[m];
+    return 0;
+}
+
+int fdtd2d_batch_upload(fdtd2d_batch_t *b, const void *Ez, const void *Hx, const void *Hy, int host_dtype)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (host_dtype != FDTD2D_F32 && host_dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad host_dtype");
+    int rc = use_device(b);
+    if (rc) return rc;
+    if (Ez && (rc = copy_in(b, b->ez[b->cur], Ez, host_dtype, b->rows, b->cols))) return rc;
+    if (Hx && (rc = copy_in(b, b->hx, Hx, host_dtype, b->rows, b->cols - 1))) return rc;
+    if (Hy && (rc = copy_in(b, b->hy, Hy, host_dtype, b->rows - 1, b->cols))) return rc;
+    return 0;
+}
+
+int fdtd2d_batch_download(fdtd2d_batch_t *b, void *Ez, void *Hx, void *Hy, int host_dtype)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (host_dtype != FDTD2D_F32 && host_dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad host_dtype");
+    int rc = use_device(b);
+    if (rc) return rc;
+    if (Ez && (rc = copy_out(b, b->ez[b->cur], Ez, host_dtype, b->rows, b->cols))) return rc;
+    if (Hx && (rc = copy_out(b, b->hx, Hx, host_dtype, b->rows, b->cols - 1))) return rc;
+    if (Hy && (rc = copy_out(b, b->hy, Hy, host_dtype, b->rows - 1, b->cols))) return rc;
+    return 0;
+}
+
+int fdtd2d_batch_reset(fdtd2d_batch_t *b)
+{
+    if (!b) return FDTD2D_E_ARG;
+    int rc = use_device(b);
+    if (rc) return rc;
+    return zero_fields(b);
+}
+
+int fdtd2d_batch_set_sources(fdtd2d_batch_t *b, const int *rect)
+{
+    if (!b || !rect) return FDTD2D_E_ARG;
+    bool any = false;
+    for (int m = 0; m < b->count; ++m) {
+        const int r = rect[4 * m], c = rect[4 * m + 1], nr = rect[4 * m + 2], nc = rect[4 * m + 3];
+        if (nr < 0 || nc < 0 || ((nr == 0) != (nc == 0)))
+            return bfail(b, FDTD2D_E_ARG, "member %d: source extent %dx%d (0 x 0 means none)", m, nr, nc);
+        if (nr == 0) continue;
+        if (r < 0 || c < 0 || r + nr > b->rows || c + nc > b->cols)
+            return bfail(b, FDTD2D_E_ARG, "member %d: source (%d,%d)+%dx%d outside the %dx%d grid", m, r, c, nr, nc,
+                         b->rows, b->cols);
+        any = true;
+    }
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));   // a running launch may still read the old rectangles
+    BCHK(b, hipMemcpy(b->rect, rect, (size_t)b->count * 4 * sizeof(int), hipMemcpyHostToDevice));
+    b->have_src = any;
+    return 0;
+}
+
+int fdtd2d_batch_run(fdtd2d_batch_t *b, int nsteps, const double *amps)
+{
+    int rc = need_ready(b);
+    if (rc) return rc;
+    if (nsteps < 0) return bfail(b, FDTD2D_E_ARG, "nsteps < 0");
+    for (int m = 0; m < b->count; ++m)
+        if (b->courant[m] > 1.0)
+            return bfail(b, FDTD2D_E_COURANT, "Courant stability condition not met for member %d: %.17g > 1.0", m,
+                         b->courant[m]);
+    if (nsteps == 0) return 0;
+    const double *dev_amps = nullptr;
+    if (amps && b->have_src) {
+        const size_t bytes = (size_t)b->count * nsteps * sizeof(double);
+        BCHK(b, hipStreamSynchronize(b->stream));   // earlier launches may still read the buffer
+        if (bytes > b->amps_cap) {
+            release((void **)&b->amps);
+            b->amps_cap = 0;
+            if ((rc = alloc(b, (void **)&b->amps, bytes))) return rc;
+            b->amps_cap = bytes;
+        }
+        BCHK(b, hipMemcpy(b->amps, amps, bytes, hipMemcpyHostToDevice));
+        dev_amps = b->amps;
+    }
+    return b->dtype == FDTD2D_F32 ? run_impl<float>(b, nsteps, dev_amps, nsteps)
+                                  : run_impl<double>(b, nsteps, dev_amps, nsteps);
+}
+
+int fdtd2d_batch_run_waveform(fdtd2d_batch_t *b, int nsteps, int src_kind, const double *fc, long long step0)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (nsteps < 0) return bfail(b, FDTD2D_E_ARG, "nsteps < 0");
+    if (src_kind == FDTD2D_SRC_NONE) return fdtd2d_batch_run(b, nsteps, nullptr);
+    if (src_kind != FDTD2D_SRC_RICKER && src_kind != FDTD2D_SRC_SINUSOIDAL)
+        return bfail(b, FDTD2D_E_ARG, "unknown source kind %d", src_kind);
+    if (!fc) return bfail(b, FDTD2D_E_ARG, "fc must not be NULL");
+    std::vector<double> amps((size_t)b->count * nsteps);
+    for (int m = 0; m < b->count; ++m)
+        for (int n = 0; n < nsteps; ++n)
+            amps[(size_t)m * nsteps + n] = fdtd2d_source_amplitude(src_kind, (double)(step0 + n) * b->dt, fc[m]);
+    return fdtd2d_batch_run(b, nsteps, amps.data());
+}
+
+int fdtd2d_batch_set_dft(fdtd2d_batch_t *b, const double *omega, int every)
+{
+    if (!b) return FDTD2D_E_ARG;
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    release((void **)&b->dft);
+    release((void **)&b->omega);
+    b->dft_every = 0;
+    if (!omega) return 0;
+    if (every < 1) return bfail(b, FDTD2D_E_ARG, "every must be >= 1");
+    const size_t bytes = (size_t)b->count * 2 * b->rows * b->cols * sizeof(double);
+    if ((rc = alloc(b, (void **)&b->dft, bytes))) return rc;
+    if ((rc = alloc(b, (void **)&b->omega, (size_t)b->count * sizeof(double)))) return rc;
+    BCHK(b, hipMemsetAsync(b->dft, 0, bytes, b->stream));
+    BCHK(b, hipStreamSynchronize(b->stream));
+    BCHK(b, hipMemcpy(b->omega, omega, (size_t)b->count * sizeof(double), hipMemcpyHostToDevice));
+    b->dft_every = every;
+    b->dft_step0 = b->step;
+    return 0;
+}
+
+int fdtd2d_batch_read_dft(fdtd2d_batch_t *b, double *re, double *im)
+{
+    if (!b || !re || !im) return FDTD2D_E_ARG;
+    if (!b->dft) return bfail(b, FDTD2D_E_STATE, "no transform is set");
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    const size_t per = (size_t)b->rows * b->cols;
+    std::vector<double> acc((size_t)b->count * 2 * per);
+    BCHK(b, hipMemcpy(acc.data(), b->dft, acc.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int m = 0; m < b->count; ++m) {
+        std::memcpy(re + m * per, acc.data() + 2 * m * per, per * sizeof(double));
+        std::memcpy(im + m * per, acc.data() + (2 * m + 1) * per, per * sizeof(double));
+    }
+    return 0;
+}
+
+int fdtd2d_batch_sync(fdtd2d_batch_t *b)
+{
+    if (!b) return FDTD2D_E_ARG;
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+}  // extern "C"

@@ -375,6 +375,69 @@ int fdtd2d_bytes_per_cell_step(const fdtd2d_t *h);
  * stored row = global row row0-halo) for zero-copy interop.  NULL on error. */
 void *fdtd2d_device_ptr(fdtd2d_t *h, int field);
 
+/* ---- batched grids ------------------------------------------------------------------
+ * `count` independent members of one rows x cols shape on one device, each with its own materials,
+ * Mur factor (from its own eps[0,0], mu[0,0]), source rectangle, amplitudes and DFT frequency, advanced
+ * together: many small simulations (design sweeps, training data) in one launch instead of one handle
+ * each.  Every member is value-identical to an fdtd2d_t run on it.  Members whose fields fit in one
+ * workgroup's LDS run a whole fdtd2d_batch_run in one resident launch (FDTD2D_BATCH_INFO_RESIDENT = 1):
+ * Ez, Hx, Hy (+ the two coefficient arrays with material arrays) take rows*cols elements each, 16-byte
+ * aligned, within 160 KiB; the others run one launch per half-step for the whole batch.
+ * Host arrays are member-major: Ez count x R x C, Hx count x R x (C-1), Hy count x (R-1) x C,
+ * eps / mu count x R x C.  Boundary NONE or MUR5 (no PML), no probes, snapshots or slabs. */
+typedef struct fdtd2d_batch fdtd2d_batch_t;
+
+#define FDTD2D_BATCH_INFO_COUNT              0
+#define FDTD2D_BATCH_INFO_ROWS               1
+#define FDTD2D_BATCH_INFO_COLS               2
+#define FDTD2D_BATCH_INFO_DTYPE              3
+#define FDTD2D_BATCH_INFO_STEP               4  /* completed steps since create / reset */
+#define FDTD2D_BATCH_INFO_RESIDENT           5  /* 1 if fdtd2d_batch_run takes the resident path now */
+#define FDTD2D_BATCH_INFO_LAUNCHES           6  /* step kernels launched so far */
+#define FDTD2D_BATCH_INFO_RESIDENT_MAX_CELLS 7  /* largest rows*cols of the resident path (materials as set) */
+#define FDTD2D_BATCH_INFO_LDS_BYTES          8  /* LDS bytes of one resident member (materials as set) */
+#define FDTD2D_BATCH_INFO_PITCH              9  /* elements per stored row */
+
+#define FDTD2D_BATCH_OPT_RESIDENT         0  /* -1 (default): by the capacity rule; 0: never */
+#define FDTD2D_BATCH_OPT_STEPS_PER_LAUNCH 1  /* resident path: steps per launch, 0 (default) = the whole run */
+
+/* Checks its arguments before it touches a device: count >= 1, rows, cols >= 11, a known dtype,
+ * boundary NONE or MUR5 (PML: FDTD2D_E_ARG).  Fields start at zero. */
+int fdtd2d_batch_create(fdtd2d_batch_t **out, int count, int rows, int cols, double dt, double dx,
+                        int dtype, int boundary, int device);
+void fdtd2d_batch_destroy(fdtd2d_batch_t *b);
+/* Never NULL; with b NULL the message of the last failed create. */
+const char *fdtd2d_batch_last_error(const fdtd2d_batch_t *b);
+long long fdtd2d_batch_info(const fdtd2d_batch_t *b, int what);
+/* Speed only: results never depend on the options. */
+int fdtd2d_batch_set_option(fdtd2d_batch_t *b, int option, long long value);
+int fdtd2d_batch_set_stream(fdtd2d_batch_t *b, void *hip_stream);
+/* eps, mu: count x R x C each.  Coefficients are formed once in the engine's type, as
+ * fdtd2d_set_materials does. */
+int fdtd2d_batch_set_materials(fdtd2d_batch_t *b, const void *eps, const void *mu, int host_dtype);
+int fdtd2d_batch_set_materials_uniform(fdtd2d_batch_t *b, double eps, double mu);
+/* count Courant numbers, fdtd.py:25-26 per member. */
+int fdtd2d_batch_courant(const fdtd2d_batch_t *b, double *out);
+/* Synchronous.  Any pointer may be NULL (field left as is). */
+int fdtd2d_batch_upload(fdtd2d_batch_t *b, const void *Ez, const void *Hx, const void *Hy, int host_dtype);
+int fdtd2d_batch_download(fdtd2d_batch_t *b, void *Ez, void *Hx, void *Hy, int host_dtype);
+int fdtd2d_batch_reset(fdtd2d_batch_t *b);
+/* count x {row, col, nrows, ncols}: every cell of the rectangle gets the member's amplitude, rounded per
+ * cell like fdtd2d_add_point; 0 x 0 = no source.  A rectangle that leaves the grid is FDTD2D_E_ARG. */
+int fdtd2d_batch_set_sources(fdtd2d_batch_t *b, const int *rect);
+/* nsteps of H -> E -> source for every member.  amps: count x nsteps float64, member-major, or NULL
+ * for no source.  FDTD2D_E_COURANT (nothing launched) if any member's Courant number exceeds 1.
+ * Asynchronous, except that given amplitudes wait for the earlier work of the stream. */
+int fdtd2d_batch_run(fdtd2d_batch_t *b, int nsteps, const double *amps);
+/* The same with the waveform evaluated by the library at t = (step0 + n) * dt, fc = count values. */
+int fdtd2d_batch_run_waveform(fdtd2d_batch_t *b, int nsteps, int src_kind, const double *fc, long long step0);
+/* Running Fourier transform over the whole grid, one omega per member: after every `every`-th completed
+ * step n (counted by FDTD2D_BATCH_INFO_STEP from this call on) adds Ez * exp(-i omega n dt) in float64,
+ * as fdtd2d_set_dft.  omega NULL removes it.  fdtd2d_batch_read_dft: re, im count x R x C; synchronous. */
+int fdtd2d_batch_set_dft(fdtd2d_batch_t *b, const double *omega, int every);
+int fdtd2d_batch_read_dft(fdtd2d_batch_t *b, double *re, double *im);
+int fdtd2d_batch_sync(fdtd2d_batch_t *b);
+
 /* Names the build: libfdtd2d.so = "... one rounding per operation: value-identical build" (-ffp-contract=off),
  * libfdtd2d_fused.so = "... fused multiply-add: tolerance build" (the same sources with a*b+c contracted into FMA:
  * 8 instead of 11 operations per cell-step, results within rounding of the exact build -- SURVEY.md M3's fp32

@@ -1,0 +1,119 @@
+"""Batched engine: throughput of BatchEngine.run against the same members run one Engine at a time.
+
+One JSON line per configuration (default: 1024 members of 60 x 60 and 64 members of 256 x 256, float32,
+array eps with random binary permittivity, a ricker line source per member):
+  ms / mcell_steps_per_s      one run(steps) of the whole batch, host call to stream sync (amplitude upload
+                              included), median of --reps
+  path, launches_per_run      resident (one launch per run) or streamed (two per step)
+  lds_bytes_per_member        LDS a resident workgroup declares
+  lds_bound_mcell_steps_per_s the resident kernel's LDS-traffic bound from its own access count per interior
+                              cell-step (H: 5 reads + ch, 2 writes; E: 5 reads + ce, 1 write) at the per-CU
+                              peaks of MI355X_MICROARCH.md section LDS (ds_read_b32 128 B/clk, ds_read_b64 256,
+                              ds_write_b32 64, ds_write_b64 85) x 256 CUs x --clock-ghz; lds_bound_fraction =
+                              achieved / bound
+  loop_*                      the yardstick: --loop-members of the same members, each through its own Engine
+                              (create, materials, run, download), timed alternately with the batch in this
+                              process; loop_ms_extrapolated = per member x count
+Usage: python tools/bench_batch.py [--count 1024 --rows 60 --cols 60 --steps 1000] [--reps 5] [--loop-members 16]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import fdtd2d_amd as fd  # noqa: E402
+
+DT, DX, FC = 5e-14, 1e-4, 30e9
+CUS = 256
+LDS_READ = {4: 128, 8: 256}     # B/clk/CU
+LDS_WRITE = {4: 64, 8: 85}
+
+
+def lds_bound(esz, arrays, clock_ghz):
+    """Cell-steps per second the resident kernel's LDS traffic allows (interior cells)."""
+    reads = 10 + (2 if arrays else 0)
+    writes = 3
+    per_clk_read = LDS_READ[esz] * CUS * clock_ghz * 1e9
+    per_clk_write = LDS_WRITE[esz] * CUS * clock_ghz * 1e9
+    return 1.0 / (reads * esz / per_clk_read + writes * esz / per_clk_write)
+
+
+def members(count, rows, cols, steps, seed=0):
+    rng = np.random.default_rng(seed)
+    eps = np.where(rng.random((count, rows, cols)) < 0.5, fd.EPS0, 5 * fd.EPS0)
+    rr = rng.integers(6, rows - 6, count)
+    rects = np.stack([rr, np.full(count, 5), np.ones(count, int), np.full(count, cols - 10)], axis=1)
+    amps = np.array([fd.ricker_amplitude(i * DT, FC) for i in range(steps)])
+    return eps, rects, np.ascontiguousarray(np.broadcast_to(amps, (count, steps)))
+
+
+def bench(count, rows, cols, steps, dtype, reps, loop_members, clock_ghz):
+    eps, rects, amps = members(count, rows, cols, steps)
+    with fd.BatchEngine(count, rows, cols, DT, DX, dtype=dtype) as b:
+        b.set_materials(eps.astype(dtype), fd.MU0).set_sources(rects)
+        b.run(steps, amps).sync()                      # warm-up: code objects, clocks
+        l0 = b.launches
+        b.reset().run(steps, amps).sync()
+        launches = b.launches - l0
+        batch_ms, loop_ms = [], []
+        for _ in range(reps):
+            b.reset().sync()
+            t0 = time.perf_counter()
+            b.run(steps, amps).sync()
+            batch_ms.append((time.perf_counter() - t0) * 1e3)
+            if loop_members:
+                t0 = time.perf_counter()
+                for m in range(loop_members):
+                    with fd.Engine(rows, cols, DT, DX, dtype=dtype) as e:
+                        e.set_materials(eps[m].astype(dtype), np.full((rows, cols), fd.MU0, dtype))
+                        e.set_source_extent(int(rects[m, 2]), int(rects[m, 3]))
+                        e.run(steps, int(rects[m, 0]), int(rects[m, 1]), amps[m])
+                        e.download()
+                loop_ms.append((time.perf_counter() - t0) * 1e3 / loop_members)
+        resident = b.resident
+        lds = b.lds_bytes
+    ms = float(np.median(batch_ms))
+    rate = count * rows * cols * steps / (ms * 1e-3)
+    esz = np.dtype(dtype).itemsize
+    bound = lds_bound(esz, True, clock_ghz) if resident else None
+    out = {"count": count, "rows": rows, "cols": cols, "steps": steps, "dtype": np.dtype(dtype).name,
+           "materials": "arrays", "path": "resident" if resident else "streamed", "reps": reps,
+           "ms": round(ms, 4), "ms_min": round(min(batch_ms), 4), "mcell_steps_per_s": round(rate / 1e6, 1),
+           "launches_per_run": launches, "lds_bytes_per_member": lds if resident else None,
+           "lds_bound_mcell_steps_per_s": round(bound / 1e6, 1) if bound else None,
+           "lds_bound_fraction": round(rate / bound, 4) if bound else None, "clock_ghz_assumed": clock_ghz}
+    if loop_members:
+        per = float(np.median(loop_ms))
+        out.update({"loop_members_timed": loop_members, "loop_ms_per_member": round(per, 4),
+                    "loop_ms_extrapolated": round(per * count, 2),
+                    "loop_mcell_steps_per_s": round(rows * cols * steps / (per * 1e-3) / 1e6, 2),
+                    "speedup_vs_loop": round(per * count / ms, 1)})
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--count", type=int)
+    ap.add_argument("--rows", type=int)
+    ap.add_argument("--cols", type=int)
+    ap.add_argument("--steps", type=int)
+    ap.add_argument("--dtype", default="float32", choices=["float32", "float64"])
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--loop-members", type=int, default=16, help="members timed one Engine at a time (0: none)")
+    ap.add_argument("--clock-ghz", type=float, default=2.4, help="shader clock of the LDS bound")
+    a = ap.parse_args()
+    if a.count or a.rows or a.cols or a.steps:
+        configs = [(a.count or 1024, a.rows or 60, a.cols or a.rows or 60, a.steps or 1000)]
+    else:
+        configs = [(1024, 60, 60, 1000), (64, 256, 256, 500)]
+    for count, rows, cols, steps in configs:
+        print(json.dumps(bench(count, rows, cols, steps, np.dtype(a.dtype), a.reps,
+                               min(a.loop_members, count), a.clock_ghz)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
