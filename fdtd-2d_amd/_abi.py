@@ -117,6 +117,12 @@ SIGNATURES = {
     "fdtd2d_batch_sync": (_i, [_vp]),
 }
 
+# every symbol include/fdtd2d_batch_pml.h declares (the batch's PML, a companion of fdtd2d.h)
+BATCH_PML_SIGNATURES = {
+    "fdtd2d_batch_set_pml": (_i, [_vp, _vp, _vp, _i, _i]),
+    "fdtd2d_batch_transfer_ezx": (_i, [_vp, _vp, _i, _i]),
+}
+
 # transport callback of fdtd2d_slab_attach
 EXCHANGE_FN = C.CFUNCTYPE(_i, _vp, _vp, _vp, _vp, _vp, _ll, _vp)
 
@@ -164,7 +170,7 @@ def load():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
                 "g.build()'` (or `make -C fdtd-2d_amd/csrc`). There is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **BATCH_PML_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

@@ -4,6 +4,7 @@
 source rectangle, amplitudes and DFT frequency.  Members small enough for one workgroup's LDS run a whole
 ``run(n)`` in one resident launch; larger ones run one launch per half-step for the whole batch.  Every
 member is value-identical to an ``Engine`` run on it.  A thin wrapper over the C ABI, like ``Engine``.
+``boundary="pml"`` gives every member the split-field layer of ``Engine(boundary="pml")`` (``set_pml``).
 """
 from __future__ import annotations
 
@@ -15,17 +16,43 @@ from . import _abi
 from .engine import _BOUNDARY, _code, _host
 
 _KIND = {"none": _abi.SRC_NONE, "ricker": _abi.SRC_RICKER, "sinusoidal": _abi.SRC_SINUSOIDAL}
+_ROW_KEYS, _COL_KEYS = ("ahr", "bhr", "aer", "ber"), ("ahc", "bhc", "aec", "bec")
 
 
 def _dptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def pml_fits(rows, cols, L):
+    """Whether an L-cell layer fits a rows x cols member (the rule of fdtd2d_set_pml / fdtd2d_batch_set_pml)."""
+    return L >= 1 and 2 * L + 3 <= min(rows, cols)
+
+
+def batch_pml_profiles(count, rows, cols, courant00, L=40, m=3, R0=1e-6, dtype=np.float64):
+    """Per-member PML factors as fdtd2d_batch_set_pml takes them: (row_factors (B, 4R) = {ahr, bhr, aer, ber},
+    col_factors (B, 4C) = {ahc, bhc, aec, bec}), member b's from pml_profiles(rows, cols, courant00[b], ...).
+    courant00: scalar or (B,); members with equal values share one pml_profiles call.  Host only."""
+    from .api import pml_profiles
+    c = np.broadcast_to(np.asarray(courant00, dtype=np.float64), (count,))
+    rowf = np.empty((count, 4 * rows), dtype)
+    colf = np.empty((count, 4 * cols), dtype)
+    done = {}
+    for b, v in enumerate(c):
+        v = float(v)
+        if v not in done:
+            P = pml_profiles(rows, cols, v, L, m, R0, dtype)
+            done[v] = (np.concatenate([P[k] for k in _ROW_KEYS]), np.concatenate([P[k] for k in _COL_KEYS]))
+        rowf[b], colf[b] = done[v]
+    return rowf, colf
+
+
 class BatchEngine:
     """``count`` grids of rows x cols resident on one MI355X.
 
     Host arrays are member-major: Ez (B, R, C), Hx (B, R, C-1), Hy (B, R-1, C), eps / mu (B, R, C).
-    boundary: "mur" (reference, main.py:29-61) or "none".
+    boundary: "mur" (reference, main.py:29-61), "none", or "pml": the split-field layer of Engine(boundary="pml")
+    on every member, set with set_pml() before the first run (the handle is a NONE batch: the layer's outer
+    edge is PEC).
     """
 
     def __init__(self, count, rows, cols, dt=5e-14, dx=1e-4, dtype=np.float32, boundary="mur", device=0):
@@ -37,8 +64,11 @@ class BatchEngine:
         self.boundary = boundary
         if boundary not in _BOUNDARY:
             raise ValueError(f"unknown boundary {boundary!r}")
+        self._pml_on = False          # a layer is set
+        self._pml_chosen = False      # set_pml (or clear_pml) has been called: a "pml" batch may run
+        code = _abi.BOUNDARY_NONE if boundary == "pml" else _BOUNDARY[boundary]
         rc = self._lib.fdtd2d_batch_create(C.byref(self._h), self.count, self.rows, self.cols, self.dt, self.dx,
-                                           _code(dtype), _BOUNDARY[boundary], int(device))
+                                           _code(dtype), code, int(device))
         if rc != 0:
             msg = self._lib.fdtd2d_batch_last_error(None).decode()
             self._h = C.c_void_p()
@@ -123,6 +153,67 @@ class BatchEngine:
         self._ck(self._lib.fdtd2d_batch_set_materials(self._h, e.ctypes.data, m.ctypes.data, _code(e.dtype)))
         return self
 
+    # -- the PML (boundary="pml") ------------------------------------------------------
+    def set_pml(self, L=40, m=3, R0=1e-6, courant00=None, profiles=None):
+        """Give every member the split-field PML (Engine.set_pml per member).  courant00: the Courant number of
+        each member's [0,0] material cell, scalar or (B,) (default: vacuum).  profiles: the eight factor arrays
+        themselves (ahr bhr aer ber of length rows, ahc bhc aec bec of length cols), each (n,) for every member
+        or (B, n), instead of the graded ones.  Ezx starts at zero."""
+        if self.boundary != "pml":
+            raise _abi.Fdtd2dError(_abi.E_STATE, f'set_pml needs boundary="pml", not {self.boundary!r}')
+        if not pml_fits(self.rows, self.cols, int(L)):      # as the library refuses it, before grading anything
+            raise _abi.Fdtd2dError(_abi.E_ARG, f"a {int(L)}-cell layer does not fit a {self.rows}x{self.cols} member")
+        if profiles is None:
+            if courant00 is None:
+                from .api import EPS0, MU0
+                courant00 = (1 / np.sqrt(EPS0 * MU0) * self.dt) / self.dx
+            rowf, colf = batch_pml_profiles(self.count, self.rows, self.cols, courant00, L, m, R0, self.dtype)
+        else:
+            def stack(keys, n):
+                out = []
+                for k in keys:
+                    a = np.asarray(profiles[k], dtype=self.dtype)
+                    if a.shape not in ((n,), (self.count, n)):
+                        raise ValueError(f"PML factor {k} must have shape ({n},) or ({self.count}, {n}), got {a.shape}")
+                    out.append(np.broadcast_to(a, (self.count, n)))
+                return np.concatenate(out, axis=1)
+            rowf, colf = stack(_ROW_KEYS, self.rows), stack(_COL_KEYS, self.cols)
+        rowf, colf = np.ascontiguousarray(rowf), np.ascontiguousarray(colf)
+        self._ck(self._lib.fdtd2d_batch_set_pml(self._h, rowf.ctypes.data, colf.ctypes.data, _code(self.dtype),
+                                                int(L)))
+        self._pml_on = self._pml_chosen = True
+        return self
+
+    def clear_pml(self):
+        """Remove the layer (and Ezx): the batch then runs as boundary="none"."""
+        if self.boundary != "pml":
+            raise _abi.Fdtd2dError(_abi.E_STATE, f'clear_pml needs boundary="pml", not {self.boundary!r}')
+        self._ck(self._lib.fdtd2d_batch_set_pml(self._h, None, None, _code(self.dtype), 0))
+        self._pml_on, self._pml_chosen = False, True
+        return self
+
+    @property
+    def pml(self) -> bool:
+        """Whether a layer is set."""
+        return self._pml_on
+
+    def upload_ezx(self, Ezx):
+        """(B, R, C) split field, host -> device (needs a layer)."""
+        a = np.ascontiguousarray(Ezx, dtype=self.dtype)
+        self._shape(a, (self.count, self.rows, self.cols), "Ezx")
+        self._ck(self._lib.fdtd2d_batch_transfer_ezx(self._h, a.ctypes.data, _code(a.dtype), 1))
+        return self
+
+    def download_ezx(self):
+        """(B, R, C) split field, device -> host (needs a layer)."""
+        a = np.empty((self.count, self.rows, self.cols), self.dtype)
+        self._ck(self._lib.fdtd2d_batch_transfer_ezx(self._h, a.ctypes.data, _code(a.dtype), 0))
+        return a
+
+    def _need_pml(self):
+        if self.boundary == "pml" and not self._pml_chosen:
+            raise _abi.Fdtd2dError(_abi.E_STATE, 'boundary="pml": call set_pml() before running')
+
     def courant(self) -> np.ndarray:
         out = np.empty(self.count, np.float64)
         self._ck(self._lib.fdtd2d_batch_courant(self._h, _dptr(out)))
@@ -180,6 +271,7 @@ class BatchEngine:
     def run(self, nsteps, amps=None):
         """nsteps of H -> E -> source for every member.  amps: (B, nsteps) float64 (None = no source)."""
         nsteps = int(nsteps)
+        self._need_pml()
         if amps is None:
             self._ck(self._lib.fdtd2d_batch_run(self._h, nsteps, None))
             return self
@@ -192,6 +284,7 @@ class BatchEngine:
 
     def run_waveform(self, nsteps, kind="ricker", fc=30e9, step0=0):
         """run() with the waveform evaluated by the library at t = (step0 + n) * dt; fc scalar or (B,)."""
+        self._need_pml()
         f = np.ascontiguousarray(np.broadcast_to(np.asarray(fc, dtype=np.float64), (self.count,)))
         self._ck(self._lib.fdtd2d_batch_run_waveform(self._h, int(nsteps), _KIND[kind], _dptr(f), int(step0)))
         return self
@@ -233,14 +326,16 @@ def _waveform_amps(kind, fc, nsteps, dt):
 
 
 def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker", dt=5e-14, dx=1e-4,
-                   dtype=np.float64, boundary="mur", omega=None, dft_every=1, device=0):
+                   dtype=np.float64, boundary="mur", omega=None, dft_every=1, device=0, pml_cells=40):
     """run_fdtd for B members of one shape at once: zero fields, Courant check per member, nsteps of
     H -> E -> source with t = i*dt.
 
     eps: (B, R, C); mu: None (vacuum), a scalar or (B, R, C).  sources: (B, 2) or (B, 4) rectangles
     (BatchEngine.set_sources); fc: scalar or (B,); waveform "ricker", "sinusoidal" or None.  omega: None,
     or the angular frequency per member (scalar or (B,)) of a running DFT of Ez sampled every `dft_every`
-    steps.  Returns (Ez, Hx, Hy), plus the complex (B, R, C) DFT when omega is given.
+    steps.  boundary "mur", "none" or "pml": a pml_cells-deep layer on every member, graded with the Courant number
+    of the member's own eps[0,0], mu[0,0] (as run_fdtd does).  Returns (Ez, Hx, Hy), plus the complex (B, R, C)
+    DFT when omega is given.
     """
     from .api import MU0
     eps = np.asarray(eps)
@@ -256,8 +351,17 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
     assert np.all(courant <= 1.0), \
         f"Courant stability condition not met: members {np.nonzero(~(courant <= 1.0))[0].tolist()} > 1.0"
     fcs = np.broadcast_to(np.asarray(fc, dtype=np.float64), (B,))
+    if boundary == "pml":
+        L = int(pml_cells)
+        if not pml_fits(R, Cc, L):
+            raise ValueError(f"a {L}-cell PML does not fit {R}x{Cc} members (2L + 3 <= min(rows, cols)): the largest "
+                             f"that does is {(min(R, Cc) - 3) // 2}")
+        m00 = mu_arr[:, 0, 0] if mu_arr.ndim == 3 else np.full(B, float(mu_arr))
+        courant00 = np.array([(1 / np.sqrt(float(e) * float(u)) * dt) / dx for e, u in zip(eps[:, 0, 0], m00)])
     with BatchEngine(B, R, Cc, dt, dx, dtype=dtype, boundary=boundary, device=device) as eng:
         eng.set_materials(eps, mu)
+        if boundary == "pml":
+            eng.set_pml(L, courant00=courant00)
         eng.set_sources(sources)
         if omega is not None:
             eng.set_dft(omega, dft_every)

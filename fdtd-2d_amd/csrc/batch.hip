@@ -2,7 +2,10 @@
 // B independent members of one shape, advanced together: members whose fields fit in one workgroup's
 // LDS run a whole fdtd2d_batch_run in one resident launch (k_batch_resident), the others one launch per
 // half-step for the whole batch (k_batch_h / k_batch_e).  Results never depend on the path.
+// fdtd2d_batch_set_pml gives a NONE batch the split-field PML: the same two paths with k_batch_resident_pml and
+// k_batch_h_pml / k_batch_e_pml (kernels_batch_pml.hpp).
 #include "../../include/fdtd2d.h"
+#include "../../include/fdtd2d_batch_pml.h"
 
 #include <hip/hip_runtime.h>
 
@@ -14,6 +17,7 @@
 #include <vector>
 
 #include "kernels_batch.hpp"
+#include "kernels_batch_pml.hpp"
 
 struct fdtd2d_batch {
     int count = 0, rows = 0, cols = 0, dtype = FDTD2D_F32, boundary = FDTD2D_BOUNDARY_MUR5, device = 0;
@@ -36,6 +40,10 @@ struct fdtd2d_batch {
     bool have_src = false;                // some member has a non-empty rectangle
     double *amps = nullptr;               // device amplitudes of the current run
     size_t amps_cap = 0;
+
+    void *ezx = nullptr;                  // PML: x-part of Ez (nullptr = no layer)
+    void *pml_row = nullptr, *pml_col = nullptr;   // PML: per member 4R / 4C factors, in T
+    int pml_L = 0;
 
     double *dft = nullptr;                // per member re[R*C], im[R*C]
     double *omega = nullptr;
@@ -158,25 +166,39 @@ int copy_out(fdtd2d_batch *b, const void *dev, void *host, int host_dtype, int n
 int zero_fields(fdtd2d_batch *b)
 {
     for (void *p : {b->ez[0], b->ez[1], b->hx, b->hy}) BCHK(b, hipMemsetAsync(p, 0, b->field_bytes, b->stream));
+    if (b->ezx) BCHK(b, hipMemsetAsync(b->ezx, 0, b->field_bytes, b->stream));
     b->cur = 0;
     b->step = 0;
     return 0;
 }
 
 // ---- the capacity rule of the resident path ------------------------------------------------------------
-int lds_arrays(const fdtd2d_batch *b) { return (b->have_mat && b->uniform) ? 3 : 5; }
+// Mur / none: Ez, Hx, Hy (+ ce, ch); PML: Ez, Hx, Hy, Ezx (+ ce, ch) and the 4R + 4C factors
+int lds_arrays(const fdtd2d_batch *b) { return (b->have_mat && b->uniform) ? (b->ezx ? 4 : 3) : (b->ezx ? 6 : 5); }
+
+// bytes of the PML factors in LDS (0 without a layer)
+size_t lds_factor_bytes(const fdtd2d_batch *b)
+{
+    if (!b->ezx) return 0;
+    return b->dtype == FDTD2D_F32 ? fdtd::batch_pml_lds_elems<float>(0, b->rows, b->cols) * 4
+                                  : fdtd::batch_pml_lds_elems<double>(0, b->rows, b->cols) * 8;
+}
 
 size_t lds_bytes(const fdtd2d_batch *b)
 {
     const int cells = b->rows * b->cols;
     return (size_t)lds_arrays(b) * (b->dtype == FDTD2D_F32 ? fdtd::batch_lds_seg<float>(cells) * 4
-                                                           : fdtd::batch_lds_seg<double>(cells) * 8);
+                                                           : fdtd::batch_lds_seg<double>(cells) * 8) +
+           lds_factor_bytes(b);
 }
 
-// largest R*C whose arrays fit in one workgroup's LDS (materials as currently set; arrays before any call)
+// largest R*C whose arrays fit in one workgroup's LDS (materials as currently set; arrays before any call;
+// with a layer, beside this batch's own 4R + 4C factors): R*C <= this  <=>  lds_bytes <= BATCH_LDS_LIMIT
 long long resident_max_cells(const fdtd2d_batch *b)
 {
-    const size_t per_array = fdtd::BATCH_LDS_LIMIT / (size_t)lds_arrays(b) / 16 * 16;
+    const size_t fac = lds_factor_bytes(b);
+    if (fac >= fdtd::BATCH_LDS_LIMIT) return 0;
+    const size_t per_array = (fdtd::BATCH_LDS_LIMIT - fac) / (size_t)lds_arrays(b) / 16 * 16;
     return (long long)(per_array / b->esz);
 }
 
@@ -276,9 +298,80 @@ template <class T, bool ARR> int run_streamed(fdtd2d_batch *b, int nsteps, const
     return 0;
 }
 
+// ---- the PML mode (kernels_batch_pml.hpp) ---------------------------------------------------------------
+template <class T> fdtd::BatchPml<T> pml_view(const fdtd2d_batch *b)
+{
+    return fdtd::BatchPml<T>{(T *)b->ezx, (const T *)b->pml_row, (const T *)b->pml_col, b->pml_L};
+}
+
+template <class T, bool ARR, int MAXC>
+int launch_resident_pml(fdtd2d_batch *b, const fdtd::BatchView<T> &v, int n0, int nt, int threads)
+{
+    auto kern = &fdtd::k_batch_resident_pml<T, ARR, MAXC>;
+    const size_t lds = lds_bytes(b);
+    BCHK(b, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds));
+    int per_cu = 0, cus = 0;
+    BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds));
+    BCHK(b, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
+    if (per_cu < 1) return bfail(b, FDTD2D_E_STATE, "resident PML kernel does not fit a CU (%zu B of LDS)", lds);
+    const long long round = (long long)per_cu * cus;
+    const int blocks = (int)(b->count < round ? b->count : round);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), lds, b->stream, v, pml_view<T>(b), n0, nt, b->step);
+    BCHK(b, hipGetLastError());
+    b->launches++;
+    return 0;
+}
+
+template <class T, bool ARR>
+int run_resident_pml(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride)
+{
+    const int cells = b->rows * b->cols, threads = resident_threads(cells);
+    const int per_thread = (cells + threads - 1) / threads;
+    const int chunk = b->steps_per_launch > 0 ? b->steps_per_launch : nsteps;
+    for (int n = 0; n < nsteps; n += chunk) {
+        const int nt = nsteps - n < chunk ? nsteps - n : chunk;
+        const fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+        int rc;
+        if (per_thread <= 4) rc = launch_resident_pml<T, ARR, 4>(b, v, n, nt, threads);
+        else if (per_thread <= 8) rc = launch_resident_pml<T, ARR, 8>(b, v, n, nt, threads);
+        else if (per_thread <= 16) rc = launch_resident_pml<T, ARR, 16>(b, v, n, nt, threads);
+        else rc = bfail(b, FDTD2D_E_STATE, "%d cells per thread exceed the resident kernel's 16", per_thread);
+        if (rc) return rc;
+        b->step += nt;
+    }
+    return 0;
+}
+
+// Ez and Ezx are updated in place (a new Ez reads no neighbour's Ez), so there is no ping-pong
+template <class T, bool ARR>
+int run_streamed_pml(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride)
+{
+    const int cells = b->rows * b->cols;
+    const dim3 grid((cells + 255) / 256, b->count < 65535 ? b->count : 65535);
+    const fdtd::BatchPml<T> p = pml_view<T>(b);
+    for (int n = 0; n < nsteps; ++n) {
+        const fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+        hipLaunchKernelGGL((fdtd::k_batch_h_pml<T, ARR>), grid, dim3(256), 0, b->stream, v, p);
+        BCHK(b, hipGetLastError());
+        hipLaunchKernelGGL((fdtd::k_batch_e_pml<T, ARR>), grid, dim3(256), 0, b->stream, v, p, n, b->step + 1);
+        BCHK(b, hipGetLastError());
+        b->launches += 2;
+        b->step++;
+    }
+    return 0;
+}
+
 template <class T> int run_impl(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride)
 {
     const bool arr = !b->uniform;
+    if (b->ezx) {
+        if (use_resident(b))
+            return arr ? run_resident_pml<T, true>(b, nsteps, amps, amp_stride)
+                       : run_resident_pml<T, false>(b, nsteps, amps, amp_stride);
+        return arr ? run_streamed_pml<T, true>(b, nsteps, amps, amp_stride)
+                   : run_streamed_pml<T, false>(b, nsteps, amps, amp_stride);
+    }
     if (use_resident(b))
         return arr ? run_resident<T, true>(b, nsteps, amps, amp_stride) : run_resident<T, false>(b, nsteps, amps, amp_stride);
     return arr ? run_streamed<T, true>(b, nsteps, amps, amp_stride) : run_streamed<T, false>(b, nsteps, amps, amp_stride);
@@ -380,7 +473,7 @@ void fdtd2d_batch_destroy(fdtd2d_batch_t *b)
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     for (void **p : {&b->ez[0], &b->ez[1], &b->hx, &b->hy, &b->ce, &b->ch, &b->kmur, (void **)&b->rect,
-                     (void **)&b->amps, (void **)&b->dft, (void **)&b->omega})
+                     (void **)&b->amps, &b->ezx, &b->pml_row, &b->pml_col, (void **)&b->dft, (void **)&b->omega})
         release(p);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -510,6 +603,54 @@ int fdtd2d_batch_set_materials_uniform(fdtd2d_batch_t *b, double eps, double mu)
     b->uniform = true;
     b->have_mat = true;
     return 0;
+}
+
+int fdtd2d_batch_set_pml(fdtd2d_batch_t *b, const void *row_factors, const void *col_factors, int host_dtype,
+                         int layer_cells)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (b->boundary != FDTD2D_BOUNDARY_NONE)
+        return bfail(b, FDTD2D_E_STATE, "the PML needs a batch created with FDTD2D_BOUNDARY_NONE (its outer edge is PEC)");
+    int rc = use_device(b);
+    if (rc) return rc;
+    if (!row_factors && !col_factors) {     // remove the layer: a plain NONE batch again
+        BCHK(b, hipStreamSynchronize(b->stream));
+        for (void **p : {&b->ezx, &b->pml_row, &b->pml_col}) release(p);
+        b->pml_L = 0;
+        return 0;
+    }
+    if (!row_factors || !col_factors) return bfail(b, FDTD2D_E_ARG, "factor arrays must both be given (or both NULL)");
+    if (host_dtype != b->dtype) return bfail(b, FDTD2D_E_ARG, "PML factors must have the batch's dtype");
+    if (layer_cells < 1 || 2 * layer_cells + 3 > (b->rows < b->cols ? b->rows : b->cols))
+        return bfail(b, FDTD2D_E_ARG, "a %d-cell layer does not fit a %dx%d member", layer_cells, b->rows, b->cols);
+    const size_t rbytes = (size_t)b->count * 4 * b->rows * b->esz, cbytes = (size_t)b->count * 4 * b->cols * b->esz;
+    BCHK(b, hipStreamSynchronize(b->stream));   // a running launch may still read the old factors
+    if (!b->ezx) {
+        for (void **p : {&b->ezx, &b->pml_row, &b->pml_col}) {
+            const size_t bytes = p == &b->ezx ? b->field_bytes : p == &b->pml_row ? rbytes : cbytes;
+            if ((rc = alloc(b, p, bytes))) {
+                for (void **q : {&b->ezx, &b->pml_row, &b->pml_col}) release(q);
+                return rc;
+            }
+        }
+    }
+    BCHK(b, hipMemcpy(b->pml_row, row_factors, rbytes, hipMemcpyHostToDevice));
+    BCHK(b, hipMemcpy(b->pml_col, col_factors, cbytes, hipMemcpyHostToDevice));
+    BCHK(b, hipMemsetAsync(b->ezx, 0, b->field_bytes, b->stream));
+    BCHK(b, hipStreamSynchronize(b->stream));
+    b->pml_L = layer_cells;
+    return 0;
+}
+
+int fdtd2d_batch_transfer_ezx(fdtd2d_batch_t *b, void *host, int host_dtype, int to_device)
+{
+    if (!b || !host) return FDTD2D_E_ARG;
+    if (!b->ezx) return bfail(b, FDTD2D_E_STATE, "no PML layer is set: call fdtd2d_batch_set_pml first");
+    if (host_dtype != FDTD2D_F32 && host_dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad host_dtype");
+    int rc = use_device(b);
+    if (rc) return rc;
+    return to_device ? copy_in(b, b->ezx, host, host_dtype, b->rows, b->cols)
+                     : copy_out(b, b->ezx, host, host_dtype, b->rows, b->cols);
 }
 
 int fdtd2d_batch_courant(const fdtd2d_batch_t *b, double *out)

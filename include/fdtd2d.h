@@ -384,7 +384,8 @@ void *fdtd2d_device_ptr(fdtd2d_t *h, int field);
  * Ez, Hx, Hy (+ the two coefficient arrays with material arrays) take rows*cols elements each, 16-byte
  * aligned, within 160 KiB; the others run one launch per half-step for the whole batch.
  * Host arrays are member-major: Ez count x R x C, Hx count x R x (C-1), Hy count x (R-1) x C,
- * eps / mu count x R x C.  Boundary NONE or MUR5 (no PML), no probes, snapshots or slabs. */
+ * eps / mu count x R x C.  Boundary NONE or MUR5; a NONE batch takes the split-field PML after creation
+ * (fdtd2d_batch_set_pml, declared in fdtd2d_batch_pml.h).  No probes, snapshots or slabs. */
 typedef struct fdtd2d_batch fdtd2d_batch_t;
 
 #define FDTD2D_BATCH_INFO_COUNT              0
@@ -394,15 +395,15 @@ typedef struct fdtd2d_batch fdtd2d_batch_t;
 #define FDTD2D_BATCH_INFO_STEP               4  /* completed steps since create / reset */
 #define FDTD2D_BATCH_INFO_RESIDENT           5  /* 1 if fdtd2d_batch_run takes the resident path now */
 #define FDTD2D_BATCH_INFO_LAUNCHES           6  /* step kernels launched so far */
-#define FDTD2D_BATCH_INFO_RESIDENT_MAX_CELLS 7  /* largest rows*cols of the resident path (materials as set) */
-#define FDTD2D_BATCH_INFO_LDS_BYTES          8  /* LDS bytes of one resident member (materials as set) */
+#define FDTD2D_BATCH_INFO_RESIDENT_MAX_CELLS 7  /* largest rows*cols of the resident path (materials, PML as set) */
+#define FDTD2D_BATCH_INFO_LDS_BYTES          8  /* LDS bytes of one resident member (materials, PML as set) */
 #define FDTD2D_BATCH_INFO_PITCH              9  /* elements per stored row */
 
 #define FDTD2D_BATCH_OPT_RESIDENT         0  /* -1 (default): by the capacity rule; 0: never */
 #define FDTD2D_BATCH_OPT_STEPS_PER_LAUNCH 1  /* resident path: steps per launch, 0 (default) = the whole run */
 
 /* Checks its arguments before it touches a device: count >= 1, rows, cols >= 11, a known dtype,
- * boundary NONE or MUR5 (PML: FDTD2D_E_ARG).  Fields start at zero. */
+ * boundary NONE or MUR5 (PML: FDTD2D_E_ARG; create NONE and call fdtd2d_batch_set_pml).  Fields start at zero. */
 int fdtd2d_batch_create(fdtd2d_batch_t **out, int count, int rows, int cols, double dt, double dx,
                         int dtype, int boundary, int device);
 void fdtd2d_batch_destroy(fdtd2d_batch_t *b);

@@ -14,7 +14,11 @@ array eps with random binary permittivity, a ricker line source per member):
   loop_*                      the yardstick: --loop-members of the same members, each through its own Engine
                               (create, materials, run, download), timed alternately with the batch in this
                               process; loop_ms_extrapolated = per member x count
+  --boundary pml              every member with a --pml-cells split-field layer (BatchEngine.set_pml); the loop
+                              yardstick is then Engine(boundary="pml"), and the line adds mur_ms / pml_over_mur:
+                              the same members as a Mur batch, timed alternately in this process
 Usage: python tools/bench_batch.py [--count 1024 --rows 60 --cols 60 --steps 1000] [--reps 5] [--loop-members 16]
+                                   [--boundary {mur,pml} --pml-cells 10]
 """
 import argparse
 import json
@@ -33,9 +37,10 @@ LDS_READ = {4: 128, 8: 256}     # B/clk/CU
 LDS_WRITE = {4: 64, 8: 85}
 
 
-def lds_bound(esz, arrays, clock_ghz):
-    """Cell-steps per second the resident kernel's LDS traffic allows (interior cells)."""
-    reads = 10 + (2 if arrays else 0)
+def lds_bound(esz, arrays, clock_ghz, pml=False):
+    """Cell-steps per second the resident kernel's LDS traffic allows (interior cells; the PML kernel reads the
+    four H factors of its row and column in every H update)."""
+    reads = 10 + (4 if pml else 0) + (2 if arrays else 0)
     writes = 3
     per_clk_read = LDS_READ[esz] * CUS * clock_ghz * 1e9
     per_clk_write = LDS_WRITE[esz] * CUS * clock_ghz * 1e9
@@ -51,41 +56,70 @@ def members(count, rows, cols, steps, seed=0):
     return eps, rects, np.ascontiguousarray(np.broadcast_to(amps, (count, steps)))
 
 
-def bench(count, rows, cols, steps, dtype, reps, loop_members, clock_ghz):
+def courant00(eps, dtype):
+    """Each member's Courant number at its [0,0] cell, as run_fdtd(boundary="pml") grades the layer."""
+    return (1 / np.sqrt(eps[:, 0, 0].astype(dtype).astype(np.float64) * fd.MU0) * DT) / DX
+
+
+def bench(count, rows, cols, steps, dtype, reps, loop_members, clock_ghz, boundary="mur", pml_cells=10):
     eps, rects, amps = members(count, rows, cols, steps)
-    with fd.BatchEngine(count, rows, cols, DT, DX, dtype=dtype) as b:
+    pml = boundary == "pml"
+    c00 = courant00(eps, dtype)
+
+    def batch(kind):
+        b = fd.BatchEngine(count, rows, cols, DT, DX, dtype=dtype, boundary=kind)
         b.set_materials(eps.astype(dtype), fd.MU0).set_sources(rects)
+        if kind == "pml":
+            b.set_pml(pml_cells, courant00=c00)
         b.run(steps, amps).sync()                      # warm-up: code objects, clocks
+        return b
+
+    def timed(b):
+        b.reset().sync()
+        t0 = time.perf_counter()
+        b.run(steps, amps).sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    with batch(boundary) as b:
+        mur = batch("mur") if pml else None
         l0 = b.launches
         b.reset().run(steps, amps).sync()
         launches = b.launches - l0
-        batch_ms, loop_ms = [], []
+        batch_ms, loop_ms, mur_ms = [], [], []
         for _ in range(reps):
-            b.reset().sync()
-            t0 = time.perf_counter()
-            b.run(steps, amps).sync()
-            batch_ms.append((time.perf_counter() - t0) * 1e3)
+            batch_ms.append(timed(b))
+            if mur is not None:
+                mur_ms.append(timed(mur))
             if loop_members:
                 t0 = time.perf_counter()
                 for m in range(loop_members):
-                    with fd.Engine(rows, cols, DT, DX, dtype=dtype) as e:
+                    with fd.Engine(rows, cols, DT, DX, dtype=dtype, boundary=boundary) as e:
                         e.set_materials(eps[m].astype(dtype), np.full((rows, cols), fd.MU0, dtype))
+                        if pml:
+                            e.set_pml(pml_cells, courant00=c00[m])
                         e.set_source_extent(int(rects[m, 2]), int(rects[m, 3]))
                         e.run(steps, int(rects[m, 0]), int(rects[m, 1]), amps[m])
                         e.download()
                 loop_ms.append((time.perf_counter() - t0) * 1e3 / loop_members)
         resident = b.resident
         lds = b.lds_bytes
+        mur_resident = mur.resident if mur is not None else None
+        if mur is not None:
+            mur.close()
     ms = float(np.median(batch_ms))
     rate = count * rows * cols * steps / (ms * 1e-3)
     esz = np.dtype(dtype).itemsize
-    bound = lds_bound(esz, True, clock_ghz) if resident else None
+    bound = lds_bound(esz, True, clock_ghz, pml) if resident else None
     out = {"count": count, "rows": rows, "cols": cols, "steps": steps, "dtype": np.dtype(dtype).name,
-           "materials": "arrays", "path": "resident" if resident else "streamed", "reps": reps,
+           "materials": "arrays", "boundary": boundary, "pml_cells": pml_cells if pml else None,
+           "path": "resident" if resident else "streamed", "reps": reps,
            "ms": round(ms, 4), "ms_min": round(min(batch_ms), 4), "mcell_steps_per_s": round(rate / 1e6, 1),
            "launches_per_run": launches, "lds_bytes_per_member": lds if resident else None,
            "lds_bound_mcell_steps_per_s": round(bound / 1e6, 1) if bound else None,
            "lds_bound_fraction": round(rate / bound, 4) if bound else None, "clock_ghz_assumed": clock_ghz}
+    if mur_ms:
+        out.update({"mur_path": "resident" if mur_resident else "streamed", "mur_ms": round(float(np.median(mur_ms)), 4),
+                    "pml_over_mur": round(ms / float(np.median(mur_ms)), 3)})
     if loop_members:
         per = float(np.median(loop_ms))
         out.update({"loop_members_timed": loop_members, "loop_ms_per_member": round(per, 4),
@@ -105,6 +139,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--loop-members", type=int, default=16, help="members timed one Engine at a time (0: none)")
     ap.add_argument("--clock-ghz", type=float, default=2.4, help="shader clock of the LDS bound")
+    ap.add_argument("--boundary", default="mur", choices=["mur", "pml"])
+    ap.add_argument("--pml-cells", type=int, default=10, help="layer depth with --boundary pml")
     a = ap.parse_args()
     if a.count or a.rows or a.cols or a.steps:
         configs = [(a.count or 1024, a.rows or 60, a.cols or a.rows or 60, a.steps or 1000)]
@@ -112,7 +148,7 @@ def main():
         configs = [(1024, 60, 60, 1000), (64, 256, 256, 500)]
     for count, rows, cols, steps in configs:
         print(json.dumps(bench(count, rows, cols, steps, np.dtype(a.dtype), a.reps,
-                               min(a.loop_members, count), a.clock_ghz)), flush=True)
+                               min(a.loop_members, count), a.clock_ghz, a.boundary, a.pml_cells)), flush=True)
 
 
 if __name__ == "__main__":
