@@ -37,6 +37,10 @@ E_ARG, E_NODEVICE, E_NOMEM, E_STATE, E_COURANT = -1, -2, -3, -4, -5
 (BATCH_INFO_COUNT, BATCH_INFO_ROWS, BATCH_INFO_COLS, BATCH_INFO_DTYPE, BATCH_INFO_STEP, BATCH_INFO_RESIDENT,
  BATCH_INFO_LAUNCHES, BATCH_INFO_RESIDENT_MAX_CELLS, BATCH_INFO_LDS_BYTES, BATCH_INFO_PITCH) = range(10)
 BATCH_OPT_RESIDENT, BATCH_OPT_STEPS_PER_LAUNCH = 0, 1
+# include/fdtd2d_batch_monitor.h
+BATCH_INFO_DFT_WINDOW_LDS, BATCH_INFO_PROBE_SAMPLES = 10, 11
+BATCH_OPT_DFT_WINDOW_LDS = 2
+BATCH_MAX_DFT_FREQS, BATCH_MAX_PROBES = 16, 64
 
 _vp, _i, _d, _ll = C.c_void_p, C.c_int, C.c_double, C.c_longlong
 
@@ -123,6 +127,14 @@ BATCH_PML_SIGNATURES = {
     "fdtd2d_batch_transfer_ezx": (_i, [_vp, _vp, _i, _i]),
 }
 
+# every symbol include/fdtd2d_batch_monitor.h declares (window DFT and probes of a batch, a companion of fdtd2d.h)
+BATCH_MONITOR_SIGNATURES = {
+    "fdtd2d_batch_set_dft_window": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(_d), _i]),
+    "fdtd2d_batch_read_dft_window": (_i, [_vp, C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_set_probes": (_i, [_vp, _i, C.POINTER(_i), _ll]),
+    "fdtd2d_batch_read_probes": (_i, [_vp, C.POINTER(_d), _ll, _ll]),
+}
+
 # transport callback of fdtd2d_slab_attach
 EXCHANGE_FN = C.CFUNCTYPE(_i, _vp, _vp, _vp, _vp, _vp, _ll, _vp)
 
@@ -170,7 +182,7 @@ def load():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
                 "g.build()'` (or `make -C fdtd-2d_amd/csrc`). There is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**SIGNATURES, **BATCH_PML_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **BATCH_PML_SIGNATURES, **BATCH_MONITOR_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

@@ -5,6 +5,8 @@ source rectangle, amplitudes and DFT frequency.  Members small enough for one wo
 ``run(n)`` in one resident launch; larger ones run one launch per half-step for the whole batch.  Every
 member is value-identical to an ``Engine`` run on it.  A thin wrapper over the C ABI, like ``Engine``.
 ``boundary="pml"`` gives every member the split-field layer of ``Engine(boundary="pml")`` (``set_pml``).
+Monitors (``set_dft_window``, ``set_probes``) record a window DFT at up to 16 frequencies and up to 64 point probes
+per member inside the step kernels.
 """
 from __future__ import annotations
 
@@ -21,6 +23,28 @@ _ROW_KEYS, _COL_KEYS = ("ahr", "bhr", "aer", "ber"), ("ahc", "bhc", "aec", "bec"
 
 def _dptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _window_omegas(omegas, count):
+    """(B, F) float64 from (F,) for every member or (B, F)."""
+    w = np.asarray(omegas, dtype=np.float64)
+    if w.ndim == 1:
+        w = np.broadcast_to(w, (count, w.size))
+    elif w.ndim != 2 or w.shape[0] != count:
+        raise ValueError(f"omegas must have shape (F,) or ({count}, F), got {w.shape}")
+    return np.ascontiguousarray(w)
+
+
+def _probe_cells(cells, count):
+    """(B, P, 2) int32 from (P, 2) for every member or (B, P, 2)."""
+    c = np.asarray(cells)
+    if c.ndim == 2 and c.shape[1] == 2:
+        c = np.broadcast_to(c, (count,) + c.shape)
+    elif c.ndim != 3 or c.shape[0] != count or c.shape[2] != 2:
+        raise ValueError(f"probe cells must have shape (P, 2) or ({count}, P, 2), got {c.shape}")
+    if c.size and not np.issubdtype(c.dtype, np.integer):
+        raise ValueError(f"probe cells must be integers, got {c.dtype}")
+    return np.ascontiguousarray(c, dtype=np.int32)
 
 
 def pml_fits(rows, cols, L):
@@ -66,6 +90,8 @@ class BatchEngine:
             raise ValueError(f"unknown boundary {boundary!r}")
         self._pml_on = False          # a layer is set
         self._pml_chosen = False      # set_pml (or clear_pml) has been called: a "pml" batch may run
+        self._win = None              # (F, nrows, ncols) of the window DFT
+        self._nprobe = 0
         code = _abi.BOUNDARY_NONE if boundary == "pml" else _BOUNDARY[boundary]
         rc = self._lib.fdtd2d_batch_create(C.byref(self._h), self.count, self.rows, self.cols, self.dt, self.dx,
                                            _code(dtype), code, int(device))
@@ -306,6 +332,71 @@ class BatchEngine:
         self._ck(self._lib.fdtd2d_batch_read_dft(self._h, _dptr(re), _dptr(im)))
         return re + 1j * im
 
+    # -- monitors (fdtd2d_batch_monitor.h) ----------------------------------------------------------
+    def set_dft_window(self, window, omegas, every=1):
+        """Running Fourier transform of Ez over window = (row0, col0, nrows, ncols), shared by all members, at up to
+        16 angular frequencies per member: omegas (F,) for every member or (B, F).  After every `every`-th step n
+        (counted from this call) adds Ez * exp(-1j * omega * n * dt) in float64, as set_dft does.  omegas None or
+        empty removes the window.  Beside set_dft, not instead of it."""
+        if omegas is None or np.size(omegas) == 0:
+            self._ck(self._lib.fdtd2d_batch_set_dft_window(self._h, 0, 0, 0, 0, 0, None, 1))
+            self._win = None
+            return self
+        w = _window_omegas(omegas, self.count)
+        r0, c0, nr, nc = (int(v) for v in window)
+        self._ck(self._lib.fdtd2d_batch_set_dft_window(self._h, r0, c0, nr, nc, int(w.shape[1]), _dptr(w), int(every)))
+        self._win = (int(w.shape[1]), nr, nc)
+        return self
+
+    def read_dft_window(self) -> np.ndarray:
+        """complex128 (B, F, nrows, ncols) of the window DFT."""
+        f, nr, nc = self._win or (0, 0, 0)
+        shape = (self.count, f, nr, nc)
+        re, im = np.empty(shape), np.empty(shape)
+        if self._win is None:     # the library refuses (no window): keep the buffers valid
+            re = im = np.empty(1)
+        self._ck(self._lib.fdtd2d_batch_read_dft_window(self._h, _dptr(re), _dptr(im)))
+        return re + 1j * im
+
+    @property
+    def window_in_lds(self) -> bool:
+        """Whether the window accumulators live in LDS on the resident path now."""
+        return bool(self.info(_abi.BATCH_INFO_DFT_WINDOW_LDS))
+
+    def set_window_lds(self, allow=True):
+        """allow False keeps the window accumulators in global memory (results never depend on it)."""
+        self._ck(self._lib.fdtd2d_batch_set_option(self._h, _abi.BATCH_OPT_DFT_WINDOW_LDS, -1 if allow else 0))
+        return self
+
+    def set_probes(self, cells, capacity):
+        """Record Ez after the source of every following step at up to 64 cells per member: cells (P, 2) {row, col}
+        for every member or (B, P, 2); `capacity` float64 samples per probe, sample 0 = the next step.  None (or no
+        cells) removes the probes."""
+        if cells is None:
+            self._ck(self._lib.fdtd2d_batch_set_probes(self._h, 0, None, 0))
+            self._nprobe = 0
+            return self
+        c = _probe_cells(cells, self.count)
+        self._ck(self._lib.fdtd2d_batch_set_probes(self._h, int(c.shape[1]), c.ctypes.data_as(C.POINTER(C.c_int)),
+                                                   int(capacity)))
+        self._nprobe = int(c.shape[1])
+        return self
+
+    @property
+    def probe_samples(self) -> int:
+        """Samples recorded so far per probe."""
+        return self.info(_abi.BATCH_INFO_PROBE_SAMPLES)
+
+    def read_probes(self, first=0, count=None) -> np.ndarray:
+        """float64 (B, P, count): samples [first, first + count) of every probe; count None = up to the samples
+        recorded so far."""
+        if count is None:
+            count = max(0, self.probe_samples - int(first))
+        out = np.empty((self.count, self._nprobe, max(0, int(count))))
+        buf = out if out.size else np.empty(1)     # a refused or empty read still passes a valid pointer
+        self._ck(self._lib.fdtd2d_batch_read_probes(self._h, _dptr(buf), int(first), int(count)))
+        return out
+
     def sync(self):
         self._ck(self._lib.fdtd2d_batch_sync(self._h))
         return self
@@ -326,7 +417,8 @@ def _waveform_amps(kind, fc, nsteps, dt):
 
 
 def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker", dt=5e-14, dx=1e-4,
-                   dtype=np.float64, boundary="mur", omega=None, dft_every=1, device=0, pml_cells=40):
+                   dtype=np.float64, boundary="mur", omega=None, dft_every=1, device=0, pml_cells=40,
+                   dft_window=None, window_omegas=None, probes=None):
     """run_fdtd for B members of one shape at once: zero fields, Courant check per member, nsteps of
     H -> E -> source with t = i*dt.
 
@@ -334,8 +426,11 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
     (BatchEngine.set_sources); fc: scalar or (B,); waveform "ricker", "sinusoidal" or None.  omega: None,
     or the angular frequency per member (scalar or (B,)) of a running DFT of Ez sampled every `dft_every`
     steps.  boundary "mur", "none" or "pml": a pml_cells-deep layer on every member, graded with the Courant number
-    of the member's own eps[0,0], mu[0,0] (as run_fdtd does).  Returns (Ez, Hx, Hy), plus the complex (B, R, C)
-    DFT when omega is given.
+    of the member's own eps[0,0], mu[0,0] (as run_fdtd does).  dft_window = (row0, col0, nrows, ncols) with
+    window_omegas (F,) or (B, F), F <= 16: a window DFT sampled every `dft_every` steps (set_dft_window).  probes:
+    (P, 2) or (B, P, 2) cells, P <= 64, recorded at every step (set_probes).  Returns (Ez, Hx, Hy), plus the complex
+    (B, R, C) DFT when omega is given, then the complex (B, F, nrows, ncols) window DFT when dft_window is given, then
+    the float64 (B, P, nsteps) probe traces when probes are given.
     """
     from .api import MU0
     eps = np.asarray(eps)
@@ -358,6 +453,7 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
                              f"that does is {(min(R, Cc) - 3) // 2}")
         m00 = mu_arr[:, 0, 0] if mu_arr.ndim == 3 else np.full(B, float(mu_arr))
         courant00 = np.array([(1 / np.sqrt(float(e) * float(u)) * dt) / dx for e, u in zip(eps[:, 0, 0], m00)])
+    win, wom, cells = _check_monitors(B, R, Cc, dft_window, window_omegas, probes, dft_every)
     with BatchEngine(B, R, Cc, dt, dx, dtype=dtype, boundary=boundary, device=device) as eng:
         eng.set_materials(eps, mu)
         if boundary == "pml":
@@ -365,8 +461,47 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
         eng.set_sources(sources)
         if omega is not None:
             eng.set_dft(omega, dft_every)
+        if win is not None:
+            eng.set_dft_window(win, wom, dft_every)
+        if cells is not None:
+            eng.set_probes(cells, max(1, int(nsteps)))
         eng.run(nsteps, None if waveform is None else _waveform_amps(waveform, fcs, nsteps, dt))
-        fields = eng.download()
-        if omega is None:
-            return fields
-        return fields + (eng.read_dft(),)
+        out = eng.download()
+        if omega is not None:
+            out += (eng.read_dft(),)
+        if win is not None:
+            out += (eng.read_dft_window(),)
+        if cells is not None:
+            out += (eng.read_probes(0, int(nsteps)),)
+        return out
+
+
+def _check_monitors(B, R, Cc, dft_window, window_omegas, probes, every):
+    """run_fdtd_batch's monitor arguments, checked on the host as the library would refuse them: (window, (B, F)
+    omegas, (B, P, 2) cells), None where not given."""
+    win = wom = cells = None
+    if (dft_window is None) != (window_omegas is None):
+        raise ValueError("dft_window and window_omegas must be given together")
+    if dft_window is not None:
+        w = np.asarray(dft_window)
+        if w.shape != (4,) or not np.issubdtype(w.dtype, np.integer):
+            raise ValueError(f"dft_window must be 4 integers (row0, col0, nrows, ncols), got {dft_window!r}")
+        r0, c0, nr, nc = (int(v) for v in w)
+        if nr < 1 or nc < 1 or r0 < 0 or c0 < 0 or r0 + nr > R or c0 + nc > Cc:
+            raise ValueError(f"dft_window {(r0, c0, nr, nc)} is empty or leaves the {R}x{Cc} grid")
+        wom = _window_omegas(window_omegas, B)
+        if not 1 <= wom.shape[1] <= _abi.BATCH_MAX_DFT_FREQS:
+            raise ValueError(f"window_omegas must hold 1..{_abi.BATCH_MAX_DFT_FREQS} frequencies, got {wom.shape[1]}")
+        if not np.all(np.isfinite(wom)):
+            raise ValueError("window_omegas must be finite")
+        if int(every) < 1:
+            raise ValueError(f"dft_every must be >= 1, got {every}")
+        win = (r0, c0, nr, nc)
+    if probes is not None:
+        cells = _probe_cells(probes, B)
+        if not 1 <= cells.shape[1] <= _abi.BATCH_MAX_PROBES:
+            raise ValueError(f"probes must hold 1..{_abi.BATCH_MAX_PROBES} cells per member, got {cells.shape[1]}")
+        r, c = cells[..., 0], cells[..., 1]
+        if np.any(r < 0) or np.any(r >= R) or np.any(c < 0) or np.any(c >= Cc):
+            raise ValueError(f"probe cells must lie in the {R}x{Cc} grid")
+    return win, wom, cells

@@ -4,7 +4,10 @@
 // half-step for the whole batch (k_batch_h / k_batch_e).  Results never depend on the path.
 // fdtd2d_batch_set_pml gives a NONE batch the split-field PML: the same two paths with k_batch_resident_pml and
 // k_batch_h_pml / k_batch_e_pml (kernels_batch_pml.hpp).
+// With a window DFT or probes set (fdtd2d_batch_monitor.h) every path takes the monitored instance of its kernels
+// (kernels_batch_monitor.hpp, instantiated in batch_monitor.hip).
 #include "../../include/fdtd2d.h"
+#include "../../include/fdtd2d_batch_monitor.h"
 #include "../../include/fdtd2d_batch_pml.h"
 
 #include <hip/hip_runtime.h>
@@ -17,6 +20,7 @@
 #include <vector>
 
 #include "kernels_batch.hpp"
+#include "kernels_batch_monitor.hpp"
 #include "kernels_batch_pml.hpp"
 
 struct fdtd2d_batch {
@@ -49,6 +53,18 @@ struct fdtd2d_batch {
     double *omega = nullptr;
     int dft_every = 0;
     long long dft_step0 = 0;
+
+    // window DFT (fdtd2d_batch_set_dft_window): per member re[nf][W], im[nf][W], W = win_nr * win_nc
+    int win_r0 = 0, win_c0 = 0, win_nr = 0, win_nc = 0, win_nf = 0, win_every = 1;
+    long long win_step0 = 0;
+    double *win_acc = nullptr, *win_omega = nullptr;
+    double *win_ph = nullptr;             // streamed path: count x nf phasors of the step being completed
+    int win_lds_opt = -1;                 // -1: accumulators in LDS when they fit, 0: never
+    // probes (fdtd2d_batch_set_probes): [member][probe][probe_cap]
+    int nprobe = 0;
+    int *probe_cells = nullptr;           // count x nprobe, row * C + col
+    double *probe_trace = nullptr;
+    long long probe_cap = 0, probe_step0 = 0;
 
     long long step = 0, launches = 0;
     int resident_opt = -1;                // -1: by the capacity rule, 0: never
@@ -184,7 +200,8 @@ size_t lds_factor_bytes(const fdtd2d_batch *b)
                                   : fdtd::batch_pml_lds_elems<double>(0, b->rows, b->cols) * 8;
 }
 
-size_t lds_bytes(const fdtd2d_batch *b)
+// the member's arrays (and PML factors): the offset of the monitors' LDS in the resident kernels
+size_t lds_field_bytes(const fdtd2d_batch *b)
 {
     const int cells = b->rows * b->cols;
     return (size_t)lds_arrays(b) * (b->dtype == FDTD2D_F32 ? fdtd::batch_lds_seg<float>(cells) * 4
@@ -192,11 +209,26 @@ size_t lds_bytes(const fdtd2d_batch *b)
            lds_factor_bytes(b);
 }
 
+// window DFT: the phasor table (part of the capacity rule) and the accumulators (in LDS only when they fit too)
+size_t lds_table_bytes(const fdtd2d_batch *b) { return 16 * (size_t)b->win_nf; }
+size_t win_acc_bytes(const fdtd2d_batch *b) { return 16 * (size_t)b->win_nf * b->win_nr * b->win_nc; }
+bool win_acc_in_lds(const fdtd2d_batch *b)
+{
+    return b->win_nf && b->win_lds_opt != 0 &&
+           lds_field_bytes(b) + lds_table_bytes(b) + win_acc_bytes(b) <= fdtd::BATCH_LDS_LIMIT;
+}
+
+size_t lds_bytes(const fdtd2d_batch *b)
+{
+    return lds_field_bytes(b) + lds_table_bytes(b) + (win_acc_in_lds(b) ? win_acc_bytes(b) : 0);
+}
+
 // largest R*C whose arrays fit in one workgroup's LDS (materials as currently set; arrays before any call;
-// with a layer, beside this batch's own 4R + 4C factors): R*C <= this  <=>  lds_bytes <= BATCH_LDS_LIMIT
+// with a layer, beside this batch's own 4R + 4C factors; with a window, beside its phasor table):
+// R*C <= this  <=>  lds_field_bytes + lds_table_bytes <= BATCH_LDS_LIMIT
 long long resident_max_cells(const fdtd2d_batch *b)
 {
-    const size_t fac = lds_factor_bytes(b);
+    const size_t fac = lds_factor_bytes(b) + lds_table_bytes(b);
     if (fac >= fdtd::BATCH_LDS_LIMIT) return 0;
     const size_t per_array = (fdtd::BATCH_LDS_LIMIT - fac) / (size_t)lds_arrays(b) / 16 * 16;
     return (long long)(per_array / b->esz);
@@ -362,8 +394,96 @@ int run_streamed_pml(fdtd2d_batch *b, int nsteps, const double *amps, long long 
     return 0;
 }
 
+// ---- monitored runs (fdtd2d_batch_monitor.h): the same paths with the kernels of batch_monitor.hip ----------------
+fdtd::BatchMon mon_view(const fdtd2d_batch *b)
+{
+    fdtd::BatchMon m;
+    m.acc = b->win_acc;
+    m.omega = b->win_omega;
+    m.ph = b->win_ph;
+    m.r0 = b->win_r0; m.c0 = b->win_c0; m.nr = b->win_nr; m.nc = b->win_nc;
+    m.nf = b->win_nf;
+    m.every = b->win_every;
+    m.step0 = b->win_step0;
+    m.lds_acc = win_acc_in_lds(b) ? 1 : 0;
+    m.cells = b->probe_cells;
+    m.trace = b->probe_trace;
+    m.np = b->nprobe;
+    m.cap = b->probe_cap;
+    m.pstep0 = b->probe_step0;
+    return m;
+}
+
+int launch_ptr(fdtd2d_batch *b, const void *kern, dim3 grid, dim3 block, void **args, size_t lds)
+{
+    BCHK(b, hipLaunchKernel(kern, grid, block, args, lds, b->stream));
+    BCHK(b, hipGetLastError());
+    return 0;
+}
+
+template <class T> int run_monitored(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride)
+{
+    const fdtd::BatchMonKernels &K = fdtd::batch_mon_kernels<T>();
+    const int arr = b->uniform ? 0 : 1;
+    const bool pml = b->ezx != nullptr;
+    fdtd::BatchPml<T> p = pml_view<T>(b);
+    fdtd::BatchMon m = mon_view(b);
+    if (use_resident(b)) {
+        const int cells = b->rows * b->cols, threads = resident_threads(cells);
+        const int per_thread = (cells + threads - 1) / threads;
+        const int mi = per_thread <= 4 ? 0 : per_thread <= 8 ? 1 : per_thread <= 16 ? 2 : -1;
+        if (mi < 0) return bfail(b, FDTD2D_E_STATE, "%d cells per thread exceed the resident kernel's 16", per_thread);
+        const void *kern = pml ? K.resident_pml[arr][mi] : K.resident[arr][mi];
+        const size_t lds = lds_bytes(b);
+        BCHK(b, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        int per_cu = 0, cus = 0;
+        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds));
+        BCHK(b, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
+        if (per_cu < 1) return bfail(b, FDTD2D_E_STATE, "monitored resident kernel does not fit a CU (%zu B of LDS)", lds);
+        const long long round = (long long)per_cu * cus;
+        const int blocks = (int)(b->count < round ? b->count : round);
+        const int chunk = b->steps_per_launch > 0 ? b->steps_per_launch : nsteps;
+        for (int n = 0; n < nsteps; n += chunk) {
+            int n0 = n, nt = nsteps - n < chunk ? nsteps - n : chunk;
+            long long step_base = b->step;
+            fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+            void *mur_args[] = {&v, &m, &n0, &nt, &step_base};
+            void *pml_args[] = {&v, &p, &m, &n0, &nt, &step_base};
+            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads), pml ? pml_args : mur_args, lds);
+            if (rc) return rc;
+            b->launches++;
+            b->step += nt;
+        }
+        return 0;
+    }
+    const int cells = b->rows * b->cols;
+    const dim3 grid((cells + 255) / 256, b->count < 65535 ? b->count : 65535);
+    for (int n = 0; n < nsteps; ++n) {
+        fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+        long long step = b->step + 1;
+        T *ez_new = (T *)b->ez[b->cur ^ 1];
+        int rc;
+        if (pml) {
+            void *h_args[] = {&v, &p, &m, &step};
+            void *e_args[] = {&v, &p, &m, &n, &step};
+            if ((rc = launch_ptr(b, K.h_pml[arr], grid, dim3(256), h_args, 0))) return rc;
+            if ((rc = launch_ptr(b, K.e_pml[arr], grid, dim3(256), e_args, 0))) return rc;
+        } else {
+            void *h_args[] = {&v, &m, &step};
+            void *e_args[] = {&v, &m, &ez_new, &n, &step};
+            if ((rc = launch_ptr(b, K.h[arr], grid, dim3(256), h_args, 0))) return rc;
+            if ((rc = launch_ptr(b, K.e[arr], grid, dim3(256), e_args, 0))) return rc;
+            b->cur ^= 1;
+        }
+        b->launches += 2;
+        b->step++;
+    }
+    return 0;
+}
+
 template <class T> int run_impl(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride)
 {
+    if (b->win_nf || b->nprobe) return run_monitored<T>(b, nsteps, amps, amp_stride);
     const bool arr = !b->uniform;
     if (b->ezx) {
         if (use_resident(b))
@@ -473,7 +593,9 @@ void fdtd2d_batch_destroy(fdtd2d_batch_t *b)
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     for (void **p : {&b->ez[0], &b->ez[1], &b->hx, &b->hy, &b->ce, &b->ch, &b->kmur, (void **)&b->rect,
-                     (void **)&b->amps, &b->ezx, &b->pml_row, &b->pml_col, (void **)&b->dft, (void **)&b->omega})
+                     (void **)&b->amps, &b->ezx, &b->pml_row, &b->pml_col, (void **)&b->dft, (void **)&b->omega,
+                     (void **)&b->win_acc, (void **)&b->win_omega, (void **)&b->win_ph, (void **)&b->probe_cells,
+                     (void **)&b->probe_trace})
         release(p);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -498,6 +620,12 @@ long long fdtd2d_batch_info(const fdtd2d_batch_t *b, int what)
     case FDTD2D_BATCH_INFO_RESIDENT_MAX_CELLS: return resident_max_cells(b);
     case FDTD2D_BATCH_INFO_LDS_BYTES: return (long long)lds_bytes(b);
     case FDTD2D_BATCH_INFO_PITCH: return b->pitch;
+    case FDTD2D_BATCH_INFO_DFT_WINDOW_LDS: return use_resident(b) && win_acc_in_lds(b) ? 1 : 0;
+    case FDTD2D_BATCH_INFO_PROBE_SAMPLES: {
+        if (!b->nprobe) return 0;
+        const long long n = b->step - b->probe_step0;
+        return n < b->probe_cap ? n : b->probe_cap;
+    }
     default: return FDTD2D_E_ARG;
     }
 }
@@ -513,6 +641,10 @@ int fdtd2d_batch_set_option(fdtd2d_batch_t *b, int option, long long value)
     case FDTD2D_BATCH_OPT_STEPS_PER_LAUNCH:
         if (value < 0 || value > (1 << 30)) return bfail(b, FDTD2D_E_ARG, "steps per launch must be >= 0");
         b->steps_per_launch = (int)value;
+        return 0;
+    case FDTD2D_BATCH_OPT_DFT_WINDOW_LDS:
+        if (value != -1 && value != 0) return bfail(b, FDTD2D_E_ARG, "window LDS must be -1 (auto) or 0 (never)");
+        b->win_lds_opt = (int)value;
         return 0;
     default: return bfail(b, FDTD2D_E_ARG, "unknown option %d", option);
     }
@@ -690,7 +822,15 @@ int fdtd2d_batch_reset(fdtd2d_batch_t *b)
     if (!b) return FDTD2D_E_ARG;
     int rc = use_device(b);
     if (rc) return rc;
-    return zero_fields(b);
+    if ((rc = zero_fields(b))) return rc;
+    // the monitors restart at step 0 (the whole-grid DFT keeps its accumulators and its step0)
+    if (b->win_nf) BCHK(b, hipMemsetAsync(b->win_acc, 0, (size_t)b->count * win_acc_bytes(b), b->stream));
+    if (b->nprobe)
+        BCHK(b, hipMemsetAsync(b->probe_trace, 0, (size_t)b->count * b->nprobe * b->probe_cap * sizeof(double),
+                               b->stream));
+    b->win_step0 = 0;
+    b->probe_step0 = 0;
+    return 0;
 }
 
 int fdtd2d_batch_set_sources(fdtd2d_batch_t *b, const int *rect)
@@ -793,6 +933,119 @@ int fdtd2d_batch_read_dft(fdtd2d_batch_t *b, double *re, double *im)
         std::memcpy(re + m * per, acc.data() + 2 * m * per, per * sizeof(double));
         std::memcpy(im + m * per, acc.data() + (2 * m + 1) * per, per * sizeof(double));
     }
+    return 0;
+}
+
+int fdtd2d_batch_set_dft_window(fdtd2d_batch_t *b, int row0, int col0, int nrows, int ncols, int nfreq,
+                                const double *omega, int every)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (nfreq < 0 || nfreq > FDTD2D_BATCH_MAX_DFT_FREQS)
+        return bfail(b, FDTD2D_E_ARG, "nfreq %d outside 0..%d", nfreq, FDTD2D_BATCH_MAX_DFT_FREQS);
+    if (nfreq > 0) {
+        if (!omega) return bfail(b, FDTD2D_E_ARG, "omega must not be NULL");
+        if (every < 1) return bfail(b, FDTD2D_E_ARG, "every must be >= 1");
+        if (nrows < 1 || ncols < 1 || row0 < 0 || col0 < 0 || (long long)row0 + nrows > b->rows ||
+            (long long)col0 + ncols > b->cols)
+            return bfail(b, FDTD2D_E_ARG, "window (%d,%d)+%dx%d is empty or outside the %dx%d grid", row0, col0, nrows,
+                         ncols, b->rows, b->cols);
+    }
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));   // a running launch may still use the old window
+    for (void **p : {(void **)&b->win_acc, (void **)&b->win_omega, (void **)&b->win_ph}) release(p);
+    b->win_nf = 0;
+    if (nfreq == 0) return 0;
+    const size_t acc = (size_t)b->count * 16 * nfreq * (size_t)nrows * ncols, om = (size_t)b->count * nfreq * sizeof(double);
+    if ((rc = alloc(b, (void **)&b->win_acc, acc)) || (rc = alloc(b, (void **)&b->win_omega, om)) ||
+        (rc = alloc(b, (void **)&b->win_ph, 2 * om))) {
+        for (void **p : {(void **)&b->win_acc, (void **)&b->win_omega, (void **)&b->win_ph}) release(p);
+        return rc;
+    }
+    BCHK(b, hipMemsetAsync(b->win_acc, 0, acc, b->stream));
+    BCHK(b, hipStreamSynchronize(b->stream));
+    BCHK(b, hipMemcpy(b->win_omega, omega, om, hipMemcpyHostToDevice));
+    b->win_r0 = row0; b->win_c0 = col0; b->win_nr = nrows; b->win_nc = ncols;
+    b->win_every = every;
+    b->win_step0 = b->step;
+    b->win_nf = nfreq;
+    return 0;
+}
+
+int fdtd2d_batch_read_dft_window(fdtd2d_batch_t *b, double *re, double *im)
+{
+    if (!b || !re || !im) return FDTD2D_E_ARG;
+    if (!b->win_nf) return bfail(b, FDTD2D_E_STATE, "no window DFT is set");
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    const size_t per = (size_t)b->win_nf * b->win_nr * b->win_nc;   // one member's re (or im)
+    std::vector<double> acc((size_t)b->count * 2 * per);
+    BCHK(b, hipMemcpy(acc.data(), b->win_acc, acc.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int m = 0; m < b->count; ++m) {
+        std::memcpy(re + m * per, acc.data() + 2 * m * per, per * sizeof(double));
+        std::memcpy(im + m * per, acc.data() + (2 * m + 1) * per, per * sizeof(double));
+    }
+    return 0;
+}
+
+int fdtd2d_batch_set_probes(fdtd2d_batch_t *b, int nprobe, const int *cells, long long capacity)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (nprobe < 0 || nprobe > FDTD2D_BATCH_MAX_PROBES)
+        return bfail(b, FDTD2D_E_ARG, "nprobe %d outside 0..%d", nprobe, FDTD2D_BATCH_MAX_PROBES);
+    std::vector<int> lin;
+    if (nprobe > 0) {
+        if (!cells) return bfail(b, FDTD2D_E_ARG, "cells must not be NULL");
+        if (capacity < 1) return bfail(b, FDTD2D_E_ARG, "capacity must be >= 1, not %lld", capacity);
+        if (capacity > (1LL << 40) / ((long long)b->count * nprobe))
+            return bfail(b, FDTD2D_E_ARG, "capacity %lld is too large for %d x %d probes", capacity, b->count, nprobe);
+        lin.resize((size_t)b->count * nprobe);
+        for (size_t k = 0; k < lin.size(); ++k) {
+            const int r = cells[2 * k], c = cells[2 * k + 1];
+            if (r < 0 || r >= b->rows || c < 0 || c >= b->cols)
+                return bfail(b, FDTD2D_E_ARG, "member %d probe %d: cell (%d,%d) outside the %dx%d grid",
+                             (int)(k / nprobe), (int)(k % nprobe), r, c, b->rows, b->cols);
+            lin[k] = r * b->cols + c;
+        }
+    }
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));   // a running launch may still record into the old buffer
+    release((void **)&b->probe_cells);
+    release((void **)&b->probe_trace);
+    b->nprobe = 0;
+    if (nprobe == 0) return 0;
+    const size_t trace = lin.size() * (size_t)capacity * sizeof(double);
+    if ((rc = alloc(b, (void **)&b->probe_cells, lin.size() * sizeof(int))) ||
+        (rc = alloc(b, (void **)&b->probe_trace, trace))) {
+        release((void **)&b->probe_cells);
+        release((void **)&b->probe_trace);
+        return rc;
+    }
+    BCHK(b, hipMemsetAsync(b->probe_trace, 0, trace, b->stream));
+    BCHK(b, hipStreamSynchronize(b->stream));
+    BCHK(b, hipMemcpy(b->probe_cells, lin.data(), lin.size() * sizeof(int), hipMemcpyHostToDevice));
+    b->probe_cap = capacity;
+    b->probe_step0 = b->step;
+    b->nprobe = nprobe;
+    return 0;
+}
+
+int fdtd2d_batch_read_probes(fdtd2d_batch_t *b, double *out, long long first, long long count_samples)
+{
+    if (!b || !out) return FDTD2D_E_ARG;
+    if (!b->nprobe) return bfail(b, FDTD2D_E_STATE, "no probes are set");
+    if (first < 0 || count_samples < 0 || first + count_samples > b->probe_cap)
+        return bfail(b, FDTD2D_E_ARG, "samples [%lld, %lld) outside the capacity %lld", first, first + count_samples,
+                     b->probe_cap);
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    if (count_samples == 0) return 0;
+    const size_t w = (size_t)count_samples * sizeof(double);
+    BCHK(b, hipMemcpy2D(out, w, b->probe_trace + first, (size_t)b->probe_cap * sizeof(double), w,
+                        (size_t)b->count * b->nprobe, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -385,7 +385,8 @@ void *fdtd2d_device_ptr(fdtd2d_t *h, int field);
  * aligned, within 160 KiB; the others run one launch per half-step for the whole batch.
  * Host arrays are member-major: Ez count x R x C, Hx count x R x (C-1), Hy count x (R-1) x C,
  * eps / mu count x R x C.  Boundary NONE or MUR5; a NONE batch takes the split-field PML after creation
- * (fdtd2d_batch_set_pml, declared in fdtd2d_batch_pml.h).  No probes, snapshots or slabs. */
+ * (fdtd2d_batch_set_pml, declared in fdtd2d_batch_pml.h).  Window DFTs and point probes per member are declared in
+ * fdtd2d_batch_monitor.h.  No snapshots or slabs. */
 typedef struct fdtd2d_batch fdtd2d_batch_t;
 
 #define FDTD2D_BATCH_INFO_COUNT              0

@@ -17,8 +17,13 @@ array eps with random binary permittivity, a ricker line source per member):
   --boundary pml              every member with a --pml-cells split-field layer (BatchEngine.set_pml); the loop
                               yardstick is then Engine(boundary="pml"), and the line adds mur_ms / pml_over_mur:
                               the same members as a Mur batch, timed alternately in this process
+  --monitors                  instead: a window DFT (30 x 1 cells, 10 frequencies, every step) and 4 probes per
+                              member (BatchEngine.set_dft_window / set_probes): mon_ms and plain_ms (the same batch
+                              without monitors) timed alternately, mon_over_plain, launches_per_run, and
+                              dft_runs_ms = the same 10 frequencies as 10 runs with the whole-grid set_dft, one
+                              omega each (reset, set_dft, run, read_dft), dft_runs_over_mon
 Usage: python tools/bench_batch.py [--count 1024 --rows 60 --cols 60 --steps 1000] [--reps 5] [--loop-members 16]
-                                   [--boundary {mur,pml} --pml-cells 10]
+                                   [--boundary {mur,pml} --pml-cells 10] [--monitors]
 """
 import argparse
 import json
@@ -129,6 +134,60 @@ def bench(count, rows, cols, steps, dtype, reps, loop_members, clock_ghz, bounda
     return out
 
 
+def bench_monitors(count, rows, cols, steps, dtype, reps, boundary="mur", pml_cells=10):
+    eps, rects, amps = members(count, rows, cols, steps)
+    c00 = courant00(eps, dtype)
+    omegas = 2 * np.pi * np.linspace(10e9, 100e9, 10)
+    window = ((rows - 30) // 2, (3 * cols) // 4, 30, 1)
+    cells = [[rows // 2, cols // 2], [rows // 4, cols // 4], [3 * rows // 4, cols // 2], [rows // 2, 3 * cols // 4]]
+
+    def batch():
+        b = fd.BatchEngine(count, rows, cols, DT, DX, dtype=dtype, boundary=boundary)
+        b.set_materials(eps.astype(dtype), fd.MU0).set_sources(rects)
+        if boundary == "pml":
+            b.set_pml(pml_cells, courant00=c00)
+        return b
+
+    def timed(b, *reads):
+        b.reset().sync()
+        t0 = time.perf_counter()
+        b.run(steps, amps).sync()
+        for r in reads:
+            r()
+        return (time.perf_counter() - t0) * 1e3
+
+    with batch() as plain, batch() as mon, batch() as dft:
+        mon.set_dft_window(window, omegas, 1).set_probes(cells, steps)
+        for b in (plain, mon, dft):
+            b.run(steps, amps).sync()                 # warm-up: code objects, clocks
+        l0 = mon.launches
+        mon.reset().run(steps, amps).sync()
+        launches = mon.launches - l0
+        plain_ms, mon_ms, dft_ms = [], [], []
+        for _ in range(reps):
+            plain_ms.append(timed(plain))
+            mon_ms.append(timed(mon))
+            total = 0.0
+            for w in omegas:
+                dft.set_dft(w, 1)
+                total += timed(dft, dft.read_dft)
+            dft_ms.append(total)
+        mon_read_ms = timed(mon, mon.read_dft_window, mon.read_probes)
+        resident, in_lds, lds = mon.resident, mon.window_in_lds, mon.lds_bytes
+    med = {k: float(np.median(v)) for k, v in (("plain", plain_ms), ("mon", mon_ms), ("dft", dft_ms))}
+    return {"count": count, "rows": rows, "cols": cols, "steps": steps, "dtype": np.dtype(dtype).name,
+            "materials": "arrays", "boundary": boundary, "pml_cells": pml_cells if boundary == "pml" else None,
+            "monitors": {"window": list(window), "freqs": len(omegas), "every": 1, "probes": len(cells)},
+            "path": "resident" if resident else "streamed", "window_in_lds": in_lds,
+            "lds_bytes_per_member": lds if resident else None, "reps": reps,
+            "mon_ms": round(med["mon"], 4), "mon_ms_min": round(min(mon_ms), 4),
+            "plain_ms": round(med["plain"], 4), "plain_ms_min": round(min(plain_ms), 4),
+            "mon_over_plain": round(med["mon"] / med["plain"], 3),
+            "mon_with_reads_ms": round(mon_read_ms, 4),
+            "dft_runs_ms": round(med["dft"], 4), "dft_runs_over_mon": round(med["dft"] / med["mon"], 2),
+            "launches_per_run": launches}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--count", type=int)
@@ -141,12 +200,19 @@ def main():
     ap.add_argument("--clock-ghz", type=float, default=2.4, help="shader clock of the LDS bound")
     ap.add_argument("--boundary", default="mur", choices=["mur", "pml"])
     ap.add_argument("--pml-cells", type=int, default=10, help="layer depth with --boundary pml")
+    ap.add_argument("--monitors", action="store_true", help="time the window DFT and probes (see above)")
     a = ap.parse_args()
     if a.count or a.rows or a.cols or a.steps:
         configs = [(a.count or 1024, a.rows or 60, a.cols or a.rows or 60, a.steps or 1000)]
     else:
         configs = [(1024, 60, 60, 1000), (64, 256, 256, 500)]
+    if a.monitors:
+        configs = [(a.count or 1024, a.rows or 60, a.cols or a.rows or 60, a.steps or 1000)]
     for count, rows, cols, steps in configs:
+        if a.monitors:
+            print(json.dumps(bench_monitors(count, rows, cols, steps, np.dtype(a.dtype), a.reps, a.boundary,
+                                            a.pml_cells)), flush=True)
+            continue
         print(json.dumps(bench(count, rows, cols, steps, np.dtype(a.dtype), a.reps,
                                min(a.loop_members, count), a.clock_ghz, a.boundary, a.pml_cells)), flush=True)
 
