@@ -41,6 +41,9 @@ BATCH_OPT_RESIDENT, BATCH_OPT_STEPS_PER_LAUNCH = 0, 1
 BATCH_INFO_DFT_WINDOW_LDS, BATCH_INFO_PROBE_SAMPLES = 10, 11
 BATCH_OPT_DFT_WINDOW_LDS = 2
 BATCH_MAX_DFT_FREQS, BATCH_MAX_PROBES = 16, 64
+# include/fdtd2d_batch_adjoint.h
+BATCH_INFO_POINT_SOURCES, BATCH_INFO_HELD_WINDOW = 12, 13
+BATCH_MAX_POINT_SOURCES, BATCH_MAX_CHANNELS = 64, 32
 
 _vp, _i, _d, _ll = C.c_void_p, C.c_int, C.c_double, C.c_longlong
 
@@ -135,6 +138,14 @@ BATCH_MONITOR_SIGNATURES = {
     "fdtd2d_batch_read_probes": (_i, [_vp, C.POINTER(_d), _ll, _ll]),
 }
 
+# every symbol include/fdtd2d_batch_adjoint.h declares (point sources with channels, the held window and its product)
+BATCH_ADJOINT_SIGNATURES = {
+    "fdtd2d_batch_set_point_sources": (_i, [_vp, _i, C.POINTER(_i), _i, C.POINTER(_d)]),
+    "fdtd2d_batch_run_channels": (_i, [_vp, _i, C.POINTER(_d), C.POINTER(_d), _i]),
+    "fdtd2d_batch_hold_dft_window": (_i, [_vp]),
+    "fdtd2d_batch_dft_window_product": (_i, [_vp, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]),
+}
+
 # transport callback of fdtd2d_slab_attach
 EXCHANGE_FN = C.CFUNCTYPE(_i, _vp, _vp, _vp, _vp, _vp, _ll, _vp)
 
@@ -182,7 +193,8 @@ def load():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; "
                 "g.build()'` (or `make -C fdtd-2d_amd/csrc`). There is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**SIGNATURES, **BATCH_PML_SIGNATURES, **BATCH_MONITOR_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **BATCH_PML_SIGNATURES, **BATCH_MONITOR_SIGNATURES,
+                                   **BATCH_ADJOINT_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

@@ -6,7 +6,8 @@ source rectangle, amplitudes and DFT frequency.  Members small enough for one wo
 member is value-identical to an ``Engine`` run on it.  A thin wrapper over the C ABI, like ``Engine``.
 ``boundary="pml"`` gives every member the split-field layer of ``Engine(boundary="pml")`` (``set_pml``).
 Monitors (``set_dft_window``, ``set_probes``) record a window DFT at up to 16 frequencies and up to 64 point probes
-per member inside the step kernels.
+per member inside the step kernels.  Point sources with channels (``set_point_sources``, ``run(channels=...)``) and the
+held window (``hold_dft_window``, ``dft_window_product``) are what an adjoint run needs (``adjoint.py``).
 """
 from __future__ import annotations
 
@@ -92,6 +93,7 @@ class BatchEngine:
         self._pml_chosen = False      # set_pml (or clear_pml) has been called: a "pml" batch may run
         self._win = None              # (F, nrows, ncols) of the window DFT
         self._nprobe = 0
+        self._npoint = (0, 0)         # (P, K) of the point sources
         code = _abi.BOUNDARY_NONE if boundary == "pml" else _BOUNDARY[boundary]
         rc = self._lib.fdtd2d_batch_create(C.byref(self._h), self.count, self.rows, self.cols, self.dt, self.dx,
                                            _code(dtype), code, int(device))
@@ -294,19 +296,73 @@ class BatchEngine:
         self._ck(self._lib.fdtd2d_batch_set_sources(self._h, r.ctypes.data_as(C.POINTER(C.c_int))))
         return self
 
-    def run(self, nsteps, amps=None):
-        """nsteps of H -> E -> source for every member.  amps: (B, nsteps) float64 (None = no source)."""
+    def run(self, nsteps, amps=None, channels=None):
+        """nsteps of H -> E -> source for every member.  amps: (B, nsteps) float64 (None = no source).
+        channels: (K, nsteps) for every member or (B, K, nsteps) float64, the time series of set_point_sources;
+        without them the point sources stay silent."""
         nsteps = int(nsteps)
         self._need_pml()
-        if amps is None:
-            self._ck(self._lib.fdtd2d_batch_run(self._h, nsteps, None))
+        a = None
+        if amps is not None:
+            a = np.asarray(amps, dtype=np.float64)
+            if a.ndim != 2 or a.shape[0] != self.count or a.shape[1] < nsteps:
+                raise ValueError(f"amps must have shape ({self.count}, {nsteps}), got {a.shape}")
+            a = np.ascontiguousarray(a[:, :nsteps])
+        if channels is None:
+            self._ck(self._lib.fdtd2d_batch_run(self._h, nsteps, None if a is None else _dptr(a)))
             return self
-        a = np.asarray(amps, dtype=np.float64)
-        if a.ndim != 2 or a.shape[0] != self.count or a.shape[1] < nsteps:
-            raise ValueError(f"amps must have shape ({self.count}, {nsteps}), got {a.shape}")
-        a = np.ascontiguousarray(a[:, :nsteps])
-        self._ck(self._lib.fdtd2d_batch_run(self._h, nsteps, _dptr(a)))
+        ch = np.asarray(channels, dtype=np.float64)
+        K = self._npoint[1]
+        if ch.shape[-1:] != () and ch.shape[-1] >= nsteps:
+            ch = ch[..., :nsteps]
+        if ch.shape not in ((K, nsteps), (self.count, K, nsteps)):
+            raise ValueError(f"channels must have shape ({K}, {nsteps}) or ({self.count}, {K}, {nsteps}), "
+                             f"got {ch.shape}")
+        ch = np.ascontiguousarray(ch)
+        self._ck(self._lib.fdtd2d_batch_run_channels(self._h, nsteps, None if a is None else _dptr(a), _dptr(ch),
+                                                     int(ch.ndim == 3)))
         return self
+
+    # -- point sources and the held window (fdtd2d_batch_adjoint.h) ---------------------------------
+    def set_point_sources(self, cells, weights=None):
+        """Up to 64 point cells per member, each adding sum_c weights[p, c] * channels[c, n] to Ez after the
+        rectangle source of step n of a run(channels=...): cells (P, 2) {row, col} for every member or (B, P, 2),
+        weights (P, K) or (B, P, K) float64, K <= 32.  cells None removes them."""
+        if cells is None:
+            self._ck(self._lib.fdtd2d_batch_set_point_sources(self._h, 0, None, 0, None))
+            self._npoint = (0, 0)
+            return self
+        c = _probe_cells(cells, self.count)
+        w = np.asarray(weights, dtype=np.float64)
+        if w.ndim == 2:
+            w = np.broadcast_to(w, (self.count,) + w.shape)
+        if w.ndim != 3 or w.shape[:2] != c.shape[:2]:
+            raise ValueError(f"weights must have shape ({c.shape[1]}, K) or ({self.count}, {c.shape[1]}, K), "
+                             f"got {np.shape(weights)}")
+        w = np.ascontiguousarray(w)
+        self._ck(self._lib.fdtd2d_batch_set_point_sources(self._h, int(c.shape[1]), c.ctypes.data_as(C.POINTER(C.c_int)),
+                                                          int(w.shape[2]), _dptr(w)))
+        self._npoint = (int(c.shape[1]), int(w.shape[2]))
+        return self
+
+    def hold_dft_window(self):
+        """Keep a device copy of the window DFT as it is now; it survives reset() and further runs."""
+        self._ck(self._lib.fdtd2d_batch_hold_dft_window(self._h))
+        return self
+
+    def dft_window_product(self, coef) -> np.ndarray:
+        """float64 (B, nrows, ncols): sum_k Re(coef[b, k] * held[b, k] * current[b, k]) over the window, on the device.
+        coef: complex (F,) for every member or (B, F)."""
+        f, nr, nc = self._win or (0, 1, 1)
+        k = np.asarray(coef, dtype=np.complex128)
+        if k.ndim == 1:
+            k = np.broadcast_to(k, (self.count, k.size))
+        if self._win is not None and k.shape != (self.count, f):
+            raise ValueError(f"coef must have shape ({f},) or ({self.count}, {f}), got {np.shape(coef)}")
+        re, im = np.ascontiguousarray(k.real), np.ascontiguousarray(k.imag)
+        out = np.empty((self.count, nr, nc))
+        self._ck(self._lib.fdtd2d_batch_dft_window_product(self._h, _dptr(re), _dptr(im), _dptr(out)))
+        return out
 
     def run_waveform(self, nsteps, kind="ricker", fc=30e9, step0=0):
         """run() with the waveform evaluated by the library at t = (step0 + n) * dt; fc scalar or (B,)."""

@@ -6,20 +6,26 @@
 // k_batch_h_pml / k_batch_e_pml (kernels_batch_pml.hpp).
 // With a window DFT or probes set (fdtd2d_batch_monitor.h) every path takes the monitored instance of its kernels
 // (kernels_batch_monitor.hpp, instantiated in batch_monitor.hip).
+// fdtd2d_batch_run_channels (fdtd2d_batch_adjoint.h) takes the point-source instances of those kernels
+// (batch_adjoint.hip), which also holds the window product kernel.
 #include "../../include/fdtd2d.h"
+#include "../../include/fdtd2d_batch_adjoint.h"
 #include "../../include/fdtd2d_batch_monitor.h"
 #include "../../include/fdtd2d_batch_pml.h"
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <numeric>
 #include <string>
 #include <vector>
 
 #include "kernels_batch.hpp"
+#include "kernels_batch_adjoint.hpp"
 #include "kernels_batch_monitor.hpp"
 #include "kernels_batch_pml.hpp"
 
@@ -65,6 +71,14 @@ struct fdtd2d_batch {
     int *probe_cells = nullptr;           // count x nprobe, row * C + col
     double *probe_trace = nullptr;
     long long probe_cap = 0, probe_step0 = 0;
+    double *win_held = nullptr;           // fdtd2d_batch_hold_dft_window: a copy of win_acc
+    // point sources (fdtd2d_batch_set_point_sources), every table in the resident owners' order
+    int npts = 0, pts_nchan = 0;
+    int *pts_cells = nullptr, *pts_own = nullptr;   // count x npts: row * C + col; owner thread * 16 + slot
+    double *pts_w = nullptr;              // count x nchan x npts
+    double *pts_tab = nullptr;            // streamed path: count x npts sums of a step
+    double *chan = nullptr;               // device channels of the current run
+    size_t chan_cap = 0;
 
     long long step = 0, launches = 0;
     int resident_opt = -1;                // -1: by the capacity rule, 0: never
@@ -209,8 +223,9 @@ size_t lds_field_bytes(const fdtd2d_batch *b)
            lds_factor_bytes(b);
 }
 
-// window DFT: the phasor table (part of the capacity rule) and the accumulators (in LDS only when they fit too)
-size_t lds_table_bytes(const fdtd2d_batch *b) { return 16 * (size_t)b->win_nf; }
+// window DFT: the phasor table (part of the capacity rule) and the accumulators (in LDS only when they fit too);
+// point sources: the sums of a step, behind the phasor table
+size_t lds_table_bytes(const fdtd2d_batch *b) { return 16 * (size_t)b->win_nf + 8 * (size_t)b->npts; }
 size_t win_acc_bytes(const fdtd2d_batch *b) { return 16 * (size_t)b->win_nf * b->win_nr * b->win_nc; }
 bool win_acc_in_lds(const fdtd2d_batch *b)
 {
@@ -224,7 +239,8 @@ size_t lds_bytes(const fdtd2d_batch *b)
 }
 
 // largest R*C whose arrays fit in one workgroup's LDS (materials as currently set; arrays before any call;
-// with a layer, beside this batch's own 4R + 4C factors; with a window, beside its phasor table):
+// with a layer, beside this batch's own 4R + 4C factors; with a window, beside its phasor table; with point sources,
+// beside their sums):
 // R*C <= this  <=>  lds_field_bytes + lds_table_bytes <= BATCH_LDS_LIMIT
 long long resident_max_cells(const fdtd2d_batch *b)
 {
@@ -421,9 +437,11 @@ int launch_ptr(fdtd2d_batch *b, const void *kern, dim3 grid, dim3 block, void **
     return 0;
 }
 
-template <class T> int run_monitored(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride)
+// pts: the point sources of fdtd2d_batch_run_channels (nullptr: none); the *_pts kernels take them behind the monitors
+template <class T>
+int run_monitored(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts)
 {
-    const fdtd::BatchMonKernels &K = fdtd::batch_mon_kernels<T>();
+    const fdtd::BatchMonKernels &K = pts ? fdtd::batch_pts_kernels<T>() : fdtd::batch_mon_kernels<T>();
     const int arr = b->uniform ? 0 : 1;
     const bool pml = b->ezx != nullptr;
     fdtd::BatchPml<T> p = pml_view<T>(b);
@@ -449,7 +467,10 @@ template <class T> int run_monitored(fdtd2d_batch *b, int nsteps, const double *
             fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
             void *mur_args[] = {&v, &m, &n0, &nt, &step_base};
             void *pml_args[] = {&v, &p, &m, &n0, &nt, &step_base};
-            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads), pml ? pml_args : mur_args, lds);
+            void *mur_pts[] = {&v, &m, pts, &n0, &nt, &step_base};
+            void *pml_pts[] = {&v, &p, &m, pts, &n0, &nt, &step_base};
+            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads),
+                                pts ? (pml ? pml_pts : mur_pts) : (pml ? pml_args : mur_args), lds);
             if (rc) return rc;
             b->launches++;
             b->step += nt;
@@ -466,13 +487,17 @@ template <class T> int run_monitored(fdtd2d_batch *b, int nsteps, const double *
         if (pml) {
             void *h_args[] = {&v, &p, &m, &step};
             void *e_args[] = {&v, &p, &m, &n, &step};
-            if ((rc = launch_ptr(b, K.h_pml[arr], grid, dim3(256), h_args, 0))) return rc;
-            if ((rc = launch_ptr(b, K.e_pml[arr], grid, dim3(256), e_args, 0))) return rc;
+            void *h_pts[] = {&v, &p, &m, pts, &n, &step};
+            void *e_pts[] = {&v, &p, &m, pts, &n, &step};
+            if ((rc = launch_ptr(b, K.h_pml[arr], grid, dim3(256), pts ? h_pts : h_args, 0))) return rc;
+            if ((rc = launch_ptr(b, K.e_pml[arr], grid, dim3(256), pts ? e_pts : e_args, 0))) return rc;
         } else {
             void *h_args[] = {&v, &m, &step};
             void *e_args[] = {&v, &m, &ez_new, &n, &step};
-            if ((rc = launch_ptr(b, K.h[arr], grid, dim3(256), h_args, 0))) return rc;
-            if ((rc = launch_ptr(b, K.e[arr], grid, dim3(256), e_args, 0))) return rc;
+            void *h_pts[] = {&v, &m, pts, &n, &step};
+            void *e_pts[] = {&v, &m, pts, &ez_new, &n, &step};
+            if ((rc = launch_ptr(b, K.h[arr], grid, dim3(256), pts ? h_pts : h_args, 0))) return rc;
+            if ((rc = launch_ptr(b, K.e[arr], grid, dim3(256), pts ? e_pts : e_args, 0))) return rc;
             b->cur ^= 1;
         }
         b->launches += 2;
@@ -481,9 +506,10 @@ template <class T> int run_monitored(fdtd2d_batch *b, int nsteps, const double *
     return 0;
 }
 
-template <class T> int run_impl(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride)
+template <class T>
+int run_impl(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts = nullptr)
 {
-    if (b->win_nf || b->nprobe) return run_monitored<T>(b, nsteps, amps, amp_stride);
+    if (b->win_nf || b->nprobe || pts) return run_monitored<T>(b, nsteps, amps, amp_stride, pts);
     const bool arr = !b->uniform;
     if (b->ezx) {
         if (use_resident(b))
@@ -517,6 +543,21 @@ void release(void **p)
 {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
+}
+
+// host values of a run (amplitudes, channels) into a device buffer that grows as needed
+int stage(fdtd2d_batch *b, double **dev, size_t *cap, const double *host, size_t bytes)
+{
+    BCHK(b, hipStreamSynchronize(b->stream));   // earlier launches may still read the buffer
+    if (bytes > *cap) {
+        release((void **)dev);
+        *cap = 0;
+        int rc = alloc(b, (void **)dev, bytes);
+        if (rc) return rc;
+        *cap = bytes;
+    }
+    BCHK(b, hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
+    return 0;
 }
 
 }  // namespace
@@ -595,7 +636,8 @@ void fdtd2d_batch_destroy(fdtd2d_batch_t *b)
     for (void **p : {&b->ez[0], &b->ez[1], &b->hx, &b->hy, &b->ce, &b->ch, &b->kmur, (void **)&b->rect,
                      (void **)&b->amps, &b->ezx, &b->pml_row, &b->pml_col, (void **)&b->dft, (void **)&b->omega,
                      (void **)&b->win_acc, (void **)&b->win_omega, (void **)&b->win_ph, (void **)&b->probe_cells,
-                     (void **)&b->probe_trace})
+                     (void **)&b->probe_trace, (void **)&b->win_held, (void **)&b->pts_cells, (void **)&b->pts_own,
+                     (void **)&b->pts_w, (void **)&b->pts_tab, (void **)&b->chan})
         release(p);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -626,6 +668,8 @@ long long fdtd2d_batch_info(const fdtd2d_batch_t *b, int what)
         const long long n = b->step - b->probe_step0;
         return n < b->probe_cap ? n : b->probe_cap;
     }
+    case FDTD2D_BATCH_INFO_POINT_SOURCES: return b->npts;
+    case FDTD2D_BATCH_INFO_HELD_WINDOW: return b->win_held ? 1 : 0;
     default: return FDTD2D_E_ARG;
     }
 }
@@ -867,15 +911,7 @@ int fdtd2d_batch_run(fdtd2d_batch_t *b, int nsteps, const double *amps)
     if (nsteps == 0) return 0;
     const double *dev_amps = nullptr;
     if (amps && b->have_src) {
-        const size_t bytes = (size_t)b->count * nsteps * sizeof(double);
-        BCHK(b, hipStreamSynchronize(b->stream));   // earlier launches may still read the buffer
-        if (bytes > b->amps_cap) {
-            release((void **)&b->amps);
-            b->amps_cap = 0;
-            if ((rc = alloc(b, (void **)&b->amps, bytes))) return rc;
-            b->amps_cap = bytes;
-        }
-        BCHK(b, hipMemcpy(b->amps, amps, bytes, hipMemcpyHostToDevice));
+        if ((rc = stage(b, &b->amps, &b->amps_cap, amps, (size_t)b->count * nsteps * sizeof(double)))) return rc;
         dev_amps = b->amps;
     }
     return b->dtype == FDTD2D_F32 ? run_impl<float>(b, nsteps, dev_amps, nsteps)
@@ -953,7 +989,8 @@ int fdtd2d_batch_set_dft_window(fdtd2d_batch_t *b, int row0, int col0, int nrows
     int rc = use_device(b);
     if (rc) return rc;
     BCHK(b, hipStreamSynchronize(b->stream));   // a running launch may still use the old window
-    for (void **p : {(void **)&b->win_acc, (void **)&b->win_omega, (void **)&b->win_ph}) release(p);
+    for (void **p : {(void **)&b->win_acc, (void **)&b->win_omega, (void **)&b->win_ph, (void **)&b->win_held})
+        release(p);
     b->win_nf = 0;
     if (nfreq == 0) return 0;
     const size_t acc = (size_t)b->count * 16 * nfreq * (size_t)nrows * ncols, om = (size_t)b->count * nfreq * sizeof(double);
@@ -1046,6 +1083,158 @@ int fdtd2d_batch_read_probes(fdtd2d_batch_t *b, double *out, long long first, lo
     const size_t w = (size_t)count_samples * sizeof(double);
     BCHK(b, hipMemcpy2D(out, w, b->probe_trace + first, (size_t)b->probe_cap * sizeof(double), w,
                         (size_t)b->count * b->nprobe, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- fdtd2d_batch_adjoint.h ------------------------------------------------------------------------------------
+
+int fdtd2d_batch_set_point_sources(fdtd2d_batch_t *b, int ncell, const int *cells, int nchan, const double *weights)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (ncell < 0 || ncell > FDTD2D_BATCH_MAX_POINT_SOURCES)
+        return bfail(b, FDTD2D_E_ARG, "ncell %d outside 0..%d", ncell, FDTD2D_BATCH_MAX_POINT_SOURCES);
+    std::vector<int> lin, own;
+    std::vector<double> w;
+    if (ncell > 0) {
+        if (nchan < 1 || nchan > FDTD2D_BATCH_MAX_CHANNELS)
+            return bfail(b, FDTD2D_E_ARG, "nchan %d outside 1..%d", nchan, FDTD2D_BATCH_MAX_CHANNELS);
+        if (!cells || !weights) return bfail(b, FDTD2D_E_ARG, "cells and weights must not be NULL");
+        // every table in the order of the resident cell walk's owners: thread l % nthr, slot l / nthr
+        const int nthr = resident_threads(b->rows * b->cols);
+        lin.resize((size_t)b->count * ncell);
+        own.resize(lin.size());
+        w.resize(lin.size() * nchan);
+        std::vector<int> cell((size_t)ncell), order((size_t)ncell);
+        for (int m = 0; m < b->count; ++m) {
+            for (int p = 0; p < ncell; ++p) {
+                const int r = cells[2 * ((size_t)m * ncell + p)], c = cells[2 * ((size_t)m * ncell + p) + 1];
+                if (r < 0 || r >= b->rows || c < 0 || c >= b->cols)
+                    return bfail(b, FDTD2D_E_ARG, "member %d point source %d: cell (%d,%d) outside the %dx%d grid", m, p,
+                                 r, c, b->rows, b->cols);
+                cell[p] = r * b->cols + c;
+                for (int q = 0; q < nchan; ++q)
+                    if (!std::isfinite(weights[((size_t)m * ncell + p) * nchan + q]))
+                        return bfail(b, FDTD2D_E_ARG, "member %d point source %d: weight %d is not finite", m, p, q);
+            }
+            std::iota(order.begin(), order.end(), 0);
+            auto key = [&](int p) { return (long long)(cell[p] % nthr) * 16 + cell[p] / nthr; };
+            std::sort(order.begin(), order.end(), [&](int x, int y) { return key(x) < key(y); });
+            for (int k = 0; k < ncell; ++k) {
+                const int p = order[k];
+                if (k && cell[order[k - 1]] == cell[p])
+                    return bfail(b, FDTD2D_E_ARG, "member %d: cell (%d,%d) is listed twice", m, cell[p] / b->cols,
+                                 cell[p] % b->cols);
+                lin[(size_t)m * ncell + k] = cell[p];
+                // slots past 15 belong to members that never run resident (16 cells per thread at most)
+                own[(size_t)m * ncell + k] = (cell[p] % nthr) * 16 + (cell[p] / nthr < 16 ? cell[p] / nthr : 15);
+                for (int q = 0; q < nchan; ++q)
+                    w[((size_t)m * nchan + q) * ncell + k] = weights[((size_t)m * ncell + p) * nchan + q];
+            }
+        }
+    }
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));   // a running launch may still read the old tables
+    void **bufs[] = {(void **)&b->pts_cells, (void **)&b->pts_own, (void **)&b->pts_w, (void **)&b->pts_tab};
+    for (void **p : bufs) release(p);
+    b->npts = b->pts_nchan = 0;
+    if (ncell == 0) return 0;
+    if ((rc = alloc(b, (void **)&b->pts_cells, lin.size() * sizeof(int))) ||
+        (rc = alloc(b, (void **)&b->pts_own, own.size() * sizeof(int))) ||
+        (rc = alloc(b, (void **)&b->pts_w, w.size() * sizeof(double))) ||
+        (rc = alloc(b, (void **)&b->pts_tab, lin.size() * sizeof(double)))) {
+        for (void **p : bufs) release(p);
+        return rc;
+    }
+    BCHK(b, hipMemcpy(b->pts_cells, lin.data(), lin.size() * sizeof(int), hipMemcpyHostToDevice));
+    BCHK(b, hipMemcpy(b->pts_own, own.data(), own.size() * sizeof(int), hipMemcpyHostToDevice));
+    BCHK(b, hipMemcpy(b->pts_w, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
+    BCHK(b, hipMemset(b->pts_tab, 0, lin.size() * sizeof(double)));
+    b->npts = ncell;
+    b->pts_nchan = nchan;
+    return 0;
+}
+
+int fdtd2d_batch_run_channels(fdtd2d_batch_t *b, int nsteps, const double *amps, const double *chan,
+                              int chan_per_member)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (nsteps < 0) return bfail(b, FDTD2D_E_ARG, "nsteps < 0");
+    if (!chan) return bfail(b, FDTD2D_E_ARG, "chan must not be NULL");
+    if (!b->npts) return bfail(b, FDTD2D_E_STATE, "no point sources are set: call fdtd2d_batch_set_point_sources first");
+    int rc = need_ready(b);
+    if (rc) return rc;
+    for (int m = 0; m < b->count; ++m)
+        if (b->courant[m] > 1.0)
+            return bfail(b, FDTD2D_E_COURANT, "Courant stability condition not met for member %d: %.17g > 1.0", m,
+                         b->courant[m]);
+    if (nsteps == 0) return 0;
+    const double *dev_amps = nullptr;
+    if (amps && b->have_src) {
+        if ((rc = stage(b, &b->amps, &b->amps_cap, amps, (size_t)b->count * nsteps * sizeof(double)))) return rc;
+        dev_amps = b->amps;
+    }
+    const size_t per = (size_t)b->pts_nchan * nsteps;
+    if ((rc = stage(b, &b->chan, &b->chan_cap, chan, (chan_per_member ? b->count : 1) * per * sizeof(double))))
+        return rc;
+    fdtd::BatchPts P;
+    P.cells = b->pts_cells;
+    P.own = b->pts_own;
+    P.w = b->pts_w;
+    P.chan = b->chan;
+    P.tab = b->pts_tab;
+    P.chan_mstride = chan_per_member ? (long long)per : 0;
+    P.chan_stride = nsteps;
+    P.nc = b->npts;
+    P.nchan = b->pts_nchan;
+    return b->dtype == FDTD2D_F32 ? run_impl<float>(b, nsteps, dev_amps, nsteps, &P)
+                                  : run_impl<double>(b, nsteps, dev_amps, nsteps, &P);
+}
+
+int fdtd2d_batch_hold_dft_window(fdtd2d_batch_t *b)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!b->win_nf) return bfail(b, FDTD2D_E_STATE, "no window DFT is set");
+    int rc = use_device(b);
+    if (rc) return rc;
+    const size_t bytes = (size_t)b->count * win_acc_bytes(b);
+    if (!b->win_held && (rc = alloc(b, (void **)&b->win_held, bytes))) return rc;
+    BCHK(b, hipMemcpyAsync(b->win_held, b->win_acc, bytes, hipMemcpyDeviceToDevice, b->stream));
+    BCHK(b, hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+int fdtd2d_batch_dft_window_product(fdtd2d_batch_t *b, const double *coef_re, const double *coef_im, double *out)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!coef_re || !coef_im || !out) return bfail(b, FDTD2D_E_ARG, "coef_re, coef_im and out must not be NULL");
+    if (!b->win_nf) return bfail(b, FDTD2D_E_STATE, "no window DFT is set");
+    if (!b->win_held) return bfail(b, FDTD2D_E_STATE, "no held window: call fdtd2d_batch_hold_dft_window first");
+    int rc = use_device(b);
+    if (rc) return rc;
+    const size_t W = (size_t)b->win_nr * b->win_nc, nk = (size_t)b->count * b->win_nf;
+    std::vector<double> coef(2 * nk);
+    for (size_t k = 0; k < nk; ++k) {
+        coef[2 * k] = coef_re[k];
+        coef[2 * k + 1] = coef_im[k];
+    }
+    double *dcoef = nullptr, *dout = nullptr;
+    if ((rc = alloc(b, (void **)&dcoef, coef.size() * sizeof(double)))) return rc;
+    if ((rc = alloc(b, (void **)&dout, (size_t)b->count * W * sizeof(double)))) {
+        release((void **)&dcoef);
+        return rc;
+    }
+    hipError_t e = hipMemcpyAsync(dcoef, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice, b->stream);
+    if (e == hipSuccess) {
+        fdtd::batch_window_product_launch(b->win_held, b->win_acc, dcoef, dout, b->count, b->win_nf, W, b->stream);
+        e = hipGetLastError();
+        b->launches++;
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)b->count * W * sizeof(double), hipMemcpyDeviceToHost);
+    release((void **)&dcoef);
+    release((void **)&dout);
+    if (e != hipSuccess) return bfail(b, -(1000 + (int)e), "window product failed: %s", hipGetErrorString(e));
     return 0;
 }
 

@@ -22,8 +22,16 @@ array eps with random binary permittivity, a ricker line source per member):
                               without monitors) timed alternately, mon_over_plain, launches_per_run, and
                               dft_runs_ms = the same 10 frequencies as 10 runs with the whole-grid set_dft, one
                               omega each (reset, set_dft, run, read_dft), dft_runs_over_mon
+  --adjoint                   instead: one batch_eps_gradient (PML, 10 frequencies, 30 probes, a design window of
+                              100 cells in 60 x 60 members or 100 x 100 cells in 250 x 250 ones, dt = 2e-13) against
+                              two monitored runs of the same length with a rectangle source, timed alternately:
+                              grad_ms (the whole helper: engine, both runs, probe reads, host algebra), two_runs_ms,
+                              device_ms (forward run, hold, reset, adjoint run with channels, product, on a standing
+                              engine) and device_over_two_runs = the cost of the channels and the product;
+                              product_ms (dft_window_product) against download_ms (both windows read back and
+                              multiplied in NumPy).  Default: 1024 members of 60 x 60 and 64 of 250 x 250.
 Usage: python tools/bench_batch.py [--count 1024 --rows 60 --cols 60 --steps 1000] [--reps 5] [--loop-members 16]
-                                   [--boundary {mur,pml} --pml-cells 10] [--monitors]
+                                   [--boundary {mur,pml} --pml-cells 10] [--monitors] [--adjoint]
 """
 import argparse
 import json
@@ -188,6 +196,93 @@ def bench_monitors(count, rows, cols, steps, dtype, reps, boundary="mur", pml_ce
             "launches_per_run": launches}
 
 
+def bench_adjoint(count, rows, cols, steps, dtype, reps, pml_cells):
+    from fdtd2d_amd.adjoint import channel_system, gradient_coefficients
+    dt = 2e-13                                   # the Gaussian envelope of the channels (t0 = 4.5 / fc) ends by step 1200
+    rng = np.random.default_rng(0)
+    eps = np.where(rng.random((count, rows, cols)) < 0.5, fd.EPS0, 5 * fd.EPS0)
+    side = 10 if min(rows, cols) < 200 else 100
+    design = ((rows - side) // 2, (cols - side) // 2, side, side)
+    rects = np.tile([rows // 2, design[1] - 8, 1, 1], (count, 1))
+    probes = np.array([[rows // 2 - 15 + k, design[1] + side + 8] for k in range(30)])
+    omegas = 2 * np.pi * np.linspace(10e9, 100e9, 10)
+    amps = np.tile(np.array([fd.ricker_amplitude(i * dt, FC) for i in range(steps)]), (count, 1))
+    c00 = (1 / np.sqrt(eps[:, 0, 0].astype(dtype).astype(np.float64) * fd.MU0) * dt) / DX
+
+    def objective(spectra):
+        mag = np.abs(spectra)
+        return mag.mean(axis=1).sum(axis=1), spectra / np.maximum(mag, 1e-300) / spectra.shape[1]
+
+    info = {}
+
+    def gradient():
+        t0 = time.perf_counter()
+        out = fd.batch_eps_gradient(eps, nsteps=steps, sources=rects, probes=probes, omegas=omegas, design=design,
+                                    objective=objective, fc=FC, dt=dt, dx=DX, dtype=dtype, boundary="pml",
+                                    pml_cells=pml_cells)
+        info.update(out[3])
+        return (time.perf_counter() - t0) * 1e3
+
+    chan, _ = channel_system(omegas, steps, dt, FC)
+    weights = rng.standard_normal((count, 30, 20))
+    coef = gradient_coefficients(omegas, dt)
+    with fd.BatchEngine(count, rows, cols, dt, DX, dtype=dtype, boundary="pml") as b:
+        b.set_materials(eps.astype(dtype), fd.MU0).set_sources(rects).set_pml(pml_cells, courant00=c00)
+        b.set_dft_window(design, omegas).set_probes(probes, steps).set_point_sources(probes, weights)
+
+        def two_runs():
+            t0 = time.perf_counter()
+            for _ in range(2):
+                b.reset().run(steps, amps)
+            b.sync()
+            return (time.perf_counter() - t0) * 1e3
+
+        def device():
+            t0 = time.perf_counter()
+            b.reset().run(steps, amps).hold_dft_window().reset().run(steps, None, chan)
+            b.dft_window_product(coef)
+            return (time.perf_counter() - t0) * 1e3
+
+        def product():
+            t0 = time.perf_counter()
+            b.dft_window_product(coef)
+            return (time.perf_counter() - t0) * 1e3
+
+        def download():
+            t0 = time.perf_counter()
+            held, cur = b.read_dft_window(), b.read_dft_window()
+            (coef[None, :, None, None] * held * cur).real.sum(axis=1)
+            return (time.perf_counter() - t0) * 1e3
+
+        two_runs(), device(), gradient()                 # warm-up: code objects, clocks
+        l0 = b.launches
+        device()
+        launches = b.launches - l0
+        t = {k: [] for k in ("grad", "two", "device", "product", "download")}
+        for _ in range(reps):
+            t["two"].append(two_runs())
+            t["device"].append(device())
+            t["grad"].append(gradient())
+            t["product"].append(product())
+            t["download"].append(download())
+        resident, in_lds, lds = b.resident, b.window_in_lds, b.lds_bytes
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    return {"count": count, "rows": rows, "cols": cols, "steps": steps, "dtype": np.dtype(dtype).name, "dt": dt,
+            "boundary": "pml", "pml_cells": pml_cells, "design": list(design), "freqs": 10, "probes": 30, "channels": 20,
+            "path": "resident" if resident else "streamed", "window_in_lds": in_lds,
+            "lds_bytes_per_member": lds if resident else None, "reps": reps,
+            "grad_ms": round(med["grad"], 3), "grad_ms_min": round(min(t["grad"]), 3),
+            "two_runs_ms": round(med["two"], 3), "two_runs_ms_min": round(min(t["two"]), 3),
+            "device_ms": round(med["device"], 3), "device_ms_min": round(min(t["device"]), 3),
+            "grad_over_two_runs": round(med["grad"] / med["two"], 3),
+            "device_over_two_runs": round(med["device"] / med["two"], 3), "launches_per_gradient": launches,
+            "product_ms": round(med["product"], 3), "download_ms": round(med["download"], 3),
+            "download_over_product": round(med["download"] / med["product"], 2),
+            "condition": round(float(info["condition"]), 2),
+            "residual_forward_max": float(np.max(info["residual_forward"])),
+            "residual_adjoint_max": float(np.max(info["residual_adjoint"]))}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--count", type=int)
@@ -201,7 +296,16 @@ def main():
     ap.add_argument("--boundary", default="mur", choices=["mur", "pml"])
     ap.add_argument("--pml-cells", type=int, default=10, help="layer depth with --boundary pml")
     ap.add_argument("--monitors", action="store_true", help="time the window DFT and probes (see above)")
+    ap.add_argument("--adjoint", action="store_true", help="time batch_eps_gradient (see above)")
     a = ap.parse_args()
+    if a.adjoint:
+        if a.count or a.rows or a.cols or a.steps:
+            configs = [(a.count or 1024, a.rows or 60, a.cols or a.rows or 60, a.steps or 1500, a.pml_cells)]
+        else:
+            configs = [(1024, 60, 60, 1500, 10), (64, 250, 250, 1500, 40)]
+        for count, rows, cols, steps, layer in configs:
+            print(json.dumps(bench_adjoint(count, rows, cols, steps, np.dtype(a.dtype), a.reps, layer)), flush=True)
+        return
     if a.count or a.rows or a.cols or a.steps:
         configs = [(a.count or 1024, a.rows or 60, a.cols or a.rows or 60, a.steps or 1000)]
     else:
