@@ -146,6 +146,13 @@ BATCH_ADJOINT_SIGNATURES = {
     "fdtd2d_batch_dft_window_product": (_i, [_vp, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]),
 }
 
+# every symbol include/fdtd2d_batch_design.h declares (probe spectra, field maxima and a permittivity window on the device)
+BATCH_DESIGN_SIGNATURES = {
+    "fdtd2d_batch_probe_spectra": (_i, [_vp, _i, C.POINTER(_d), _ll, _ll, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_field_absmax": (_i, [_vp, _i, C.POINTER(_d)]),
+    "fdtd2d_batch_set_eps_window": (_i, [_vp, _i, _i, _i, _i, _vp, _i]),
+}
+
 # transport callback of fdtd2d_slab_attach
 EXCHANGE_FN = C.CFUNCTYPE(_i, _vp, _vp, _vp, _vp, _vp, _ll, _vp)
 
@@ -194,7 +201,7 @@ def load():
                 "g.build()'` (or `make -C fdtd-2d_amd/csrc`). There is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in {**SIGNATURES, **BATCH_PML_SIGNATURES, **BATCH_MONITOR_SIGNATURES,
-                                   **BATCH_ADJOINT_SIGNATURES}.items():
+                                   **BATCH_ADJOINT_SIGNATURES, **BATCH_DESIGN_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

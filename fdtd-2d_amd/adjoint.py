@@ -82,28 +82,15 @@ def _check_design(design, rects, R, Cc, margin, why):
     return r0, c0, nr, nc
 
 
-def batch_eps_gradient(eps, mu=None, *, nsteps, sources, probes, omegas, design, objective, fc=30e9,
-                       waveform="ricker", dt=5e-14, dx=1e-4, dtype=np.float64, boundary="pml", pml_cells=40, device=0,
-                       engine=None):
-    """Gradient of an objective on probe spectra with respect to eps over a design window, for B members at once.
+class _Plan:
+    """What batch_eps_gradient and AdjointSession work out on the host before any device work: the checked arguments,
+    the channel systems and the forward amplitudes."""
 
-    eps: (B, R, C); mu: None (vacuum), a scalar or (B, R, C).  sources: (B, 2) or (B, 4) rectangles of the forward
-    run, driven by `waveform` ("ricker" or "sinusoidal") at fc (scalar or (B,)) with t = n * dt.  probes: (P, 2) or
-    (B, P, 2) observation cells, P <= 64.  omegas: (F,) or (B, F) angular frequencies, F <= 16.  design = (row0, col0,
-    nrows, ncols), shared by all members.  objective(spectra) takes the complex (B, P, F) spectra
-    Eobs[b, p, k] = sum_n Ez[p](after step n) exp(-i omega_k (n + 1) dt) and returns (J (B,), g (B, P, F)) with
-    g = dJ/dRe(Eobs) + i dJ/dIm(Eobs).  boundary "pml" (a pml_cells-deep layer) or "mur"; a closed box never rings
-    down, so "none" is refused.  engine: the engine class (BatchEngine by default).
 
-    Conditions, checked on the host before any device work (ValueError): the design window holds no cell of a member's
-    forward source, lies outside the PML layer and at least 6 cells from every edge; the channel system's condition
-    number is at most 1e8.  The fields must have died away by the end of both runs: info["residual_forward"] and
-    info["residual_adjoint"] give, per member, the end-of-run max|Ez| of each run divided by its largest probe sample.
-
-    Returns (J (B,), grad (B, nrows, ncols) float64, spectra (B, P, F) complex128, info)."""
+def _plan(eps, mu, nsteps, sources, probes, omegas, design, fc, waveform, dt, dx, boundary, pml_cells):
+    """The host checks of batch_eps_gradient (ValueError), then the channel systems and the amplitudes."""
     from .api import MU0
-    if engine is None:
-        from .batch import BatchEngine as engine
+    p = _Plan()
     if boundary not in ("pml", "mur"):
         raise ValueError(f'boundary must be "pml" or "mur" (a closed box never rings down), not {boundary!r}')
     eps = np.asarray(eps)
@@ -163,54 +150,228 @@ def batch_eps_gradient(eps, mu=None, *, nsteps, sources, probes, omegas, design,
                                  f"{MAX_CONDITION:g}: {nsteps} steps cannot tell these frequencies apart")
             systems[key] = (chan, A, cond)
         which.append(key)
-    shared = len(systems) == 1
+    p.eps, p.mu, p.mu_arr, p.mu_min = eps, mu, mu_arr, mu_min
+    p.B, p.R, p.Cc, p.nsteps, p.dt, p.dx, p.boundary = B, R, Cc, nsteps, dt, dx, boundary
+    p.rects, p.L, p.win, p.cells, p.P, p.om, p.F = rects, L, win, cells, P, om, F
+    p.systems, p.which, p.shared = systems, which, len(systems) == 1
+    p.channels = systems[which[0]][0] if p.shared else np.stack([systems[k][0] for k in which])
+    p.amps = _waveform_amps(waveform, fcs, nsteps, dt)
+    p.coef = np.stack([gradient_coefficients(w, dt) for w in om])
+    return p
 
-    amps = _waveform_amps(waveform, fcs, nsteps, dt)
-    with engine(B, R, Cc, dt, dx, dtype=dtype, boundary=boundary, device=device) as eng:
-        eng.set_materials(eps, mu)
-        if boundary == "pml":
-            m00 = mu_arr[:, 0, 0] if mu_arr.ndim == 3 else np.full(B, float(mu_arr))
-            eng.set_pml(L, courant00=np.array([(1 / np.sqrt(float(e) * float(u)) * dt) / dx
-                                               for e, u in zip(eps[:, 0, 0], m00)]))
+
+def _setup(eng, p):
+    """Materials, PML, the forward source, the window DFT over the design region and the probes."""
+    eng.set_materials(p.eps, p.mu)
+    if p.boundary == "pml":
+        m00 = p.mu_arr[:, 0, 0] if p.mu_arr.ndim == 3 else np.full(p.B, float(p.mu_arr))
+        eng.set_pml(p.L, courant00=np.array([(1 / np.sqrt(float(e) * float(u)) * p.dt) / p.dx
+                                             for e, u in zip(p.eps[:, 0, 0], m00)]))
+    eng.set_sources(p.rects)
+    eng.set_dft_window(p.win, p.om).set_probes(p.cells, p.nsteps)
+
+
+def _cotangent(p, objective, spectra):
+    J, g = objective(spectra)
+    J = np.asarray(J, dtype=np.float64)
+    g = np.asarray(g, dtype=np.complex128)
+    if J.shape != (p.B,) or g.shape != (p.B, p.P, p.F):
+        raise ValueError(f"objective must return J of shape ({p.B},) and g of shape ({p.B}, {p.P}, {p.F}), got {J.shape} "
+                         f"and {g.shape}")
+    return J, g
+
+
+def _injections(p, g, eps, dtype):
+    """conj(g) / D at the probe cells, D = eps dx / dt with eps as the engine stores it."""
+    D = np.asarray(eps, dtype=dtype).astype(np.float64)[np.arange(p.B)[:, None], p.cells[..., 0], p.cells[..., 1]]
+    return np.conj(g) / (D * p.dx / p.dt)[:, :, None]
+
+
+def _residual(end, peak):
+    return np.divide(end, peak, out=np.full(end.shape, np.inf), where=peak > 0)
+
+
+def batch_eps_gradient(eps, mu=None, *, nsteps, sources, probes, omegas, design, objective, fc=30e9,
+                       waveform="ricker", dt=5e-14, dx=1e-4, dtype=np.float64, boundary="pml", pml_cells=40, device=0,
+                       engine=None):
+    """Gradient of an objective on probe spectra with respect to eps over a design window, for B members at once.
+
+    eps: (B, R, C); mu: None (vacuum), a scalar or (B, R, C).  sources: (B, 2) or (B, 4) rectangles of the forward
+    run, driven by `waveform` ("ricker" or "sinusoidal") at fc (scalar or (B,)) with t = n * dt.  probes: (P, 2) or
+    (B, P, 2) observation cells, P <= 64.  omegas: (F,) or (B, F) angular frequencies, F <= 16.  design = (row0, col0,
+    nrows, ncols), shared by all members.  objective(spectra) takes the complex (B, P, F) spectra
+    Eobs[b, p, k] = sum_n Ez[p](after step n) exp(-i omega_k (n + 1) dt) and returns (J (B,), g (B, P, F)) with
+    g = dJ/dRe(Eobs) + i dJ/dIm(Eobs).  boundary "pml" (a pml_cells-deep layer) or "mur"; a closed box never rings
+    down, so "none" is refused.  engine: the engine class (BatchEngine by default).
+
+    Conditions, checked on the host before any device work (ValueError): the design window holds no cell of a member's
+    forward source, lies outside the PML layer and at least 6 cells from every edge; the channel system's condition
+    number is at most 1e8.  The fields must have died away by the end of both runs: info["residual_forward"] and
+    info["residual_adjoint"] give, per member, the end-of-run max|Ez| of each run divided by its largest probe sample.
+
+    One call builds its engine and reads every probe trace back; a loop that calls it again and again is what
+    AdjointSession is for.
+
+    Returns (J (B,), grad (B, nrows, ncols) float64, spectra (B, P, F) complex128, info)."""
+    if engine is None:
+        from .batch import BatchEngine as engine
+    p = _plan(eps, mu, nsteps, sources, probes, omegas, design, fc, waveform, dt, dx, boundary, pml_cells)
+    B, nsteps = p.B, p.nsteps
+    with engine(B, p.R, p.Cc, dt, dx, dtype=dtype, boundary=boundary, device=device) as eng:
         # 1. forward: the member's own source; window DFT over the design region, probes at the observation cells
-        eng.set_sources(rects)
-        eng.set_dft_window(win, om).set_probes(cells, nsteps)
-        eng.run(nsteps, amps)
+        _setup(eng, p)
+        eng.run(nsteps, p.amps)
         traces = eng.read_probes(0, nsteps)
         end_fwd = np.abs(eng.download()[0].astype(np.float64)).reshape(B, -1).max(axis=1)
         eng.hold_dft_window()
-        spectra = probe_spectra(traces, om, dt)
+        spectra = probe_spectra(traces, p.om, dt)
 
         # 2. the cotangent
-        J, g = objective(spectra)
-        J = np.asarray(J, dtype=np.float64)
-        g = np.asarray(g, dtype=np.complex128)
-        if J.shape != (B,) or g.shape != (B, P, F):
-            raise ValueError(f"objective must return J of shape ({B},) and g of shape ({B}, {P}, {F}), got {J.shape} "
-                             f"and {g.shape}")
+        J, g = _cotangent(p, objective, spectra)
 
         # 3. adjoint: same materials, fields zero, step 0; the probe cells inject conj(g) / D at every frequency
-        D = np.asarray(eps, dtype=dtype).astype(np.float64)[np.arange(B)[:, None], cells[..., 0], cells[..., 1]] * dx / dt
-        c = np.conj(g) / D[:, :, None]
-        weights = np.empty((B, P, 2 * F))
+        c = _injections(p, g, p.eps, dtype)
+        weights = np.empty((B, p.P, 2 * p.F))
         for b in range(B):
-            weights[b] = np.linalg.solve(systems[which[b]][1], np.concatenate([c[b].real, c[b].imag], axis=1).T).T
+            weights[b] = np.linalg.solve(p.systems[p.which[b]][1], np.concatenate([c[b].real, c[b].imag], axis=1).T).T
         eng.reset()
-        eng.set_point_sources(cells, weights)
-        channels = systems[which[0]][0] if shared else np.stack([systems[k][0] for k in which])
-        eng.run(nsteps, None, channels)      # amps None: no rectangle source
+        eng.set_point_sources(p.cells, weights)
+        eng.run(nsteps, None, p.channels)      # amps None: no rectangle source
         adj_traces = eng.read_probes(0, nsteps)
         end_adj = np.abs(eng.download()[0].astype(np.float64)).reshape(B, -1).max(axis=1)
 
         # 4. the gradient, formed on the device from the two windows
-        coef = np.stack([gradient_coefficients(w, dt) for w in om])
-        grad = eng.dft_window_product(coef) * (dx / dt)
+        grad = eng.dft_window_product(p.coef) * (dx / dt)
 
-    def ratio(end, tr):
+    def peak(tr):
         flat = tr.reshape(B, -1)
-        peak = np.maximum(flat.max(axis=1), -flat.min(axis=1))
-        return np.divide(end, peak, out=np.full(B, np.inf), where=peak > 0)
-    info = {"condition": max(s[2] for s in systems.values()),
-            "residual_forward": ratio(end_fwd, traces), "residual_adjoint": ratio(end_adj, adj_traces),
-            "channels_shared": shared}
+        return np.maximum(flat.max(axis=1), -flat.min(axis=1))
+    info = {"condition": max(s[2] for s in p.systems.values()),
+            "residual_forward": _residual(end_fwd, peak(traces)), "residual_adjoint": _residual(end_adj, peak(adj_traces)),
+            "channels_shared": p.shared}
     return J, grad, spectra, info
+
+
+class AdjointSession:
+    """batch_eps_gradient as a loop: the engine stands between iterations, and an iteration moves only what it needs.
+
+    The constructor takes batch_eps_gradient's arguments (without the objective), makes its host checks with its
+    messages and does once what the helper does per call: the channel systems, the amplitudes, the engine with its
+    materials, PML, source rectangles, window DFT and probes.  value_and_grad(objective) returns what the helper
+    returns; it transforms the probe traces and takes the fields' maxima on the device (BatchEngine.probe_spectra,
+    field_absmax), so B * P * F spectra and B * nrows * ncols gradients come down and B * P * 2F weights go up, and no
+    trace, field or window is read back.  set_design_eps(eps_window) replaces the permittivity of the design window
+    (BatchEngine.set_eps_window).  The spectra are summed in ascending step order, where the helper's host transform
+    sums as its matrix product does: they agree to rounding (1e-14 of their maximum), not bit for bit.
+
+        with AdjointSession(eps, nsteps=..., sources=..., probes=..., omegas=..., design=win) as s:
+            for it in range(100):
+                J, grad, spectra, info = s.value_and_grad(objective)
+                s.set_design_eps(np.clip(s.eps[:, r0:r0 + nr, c0:c0 + nc] + step * grad, lo, hi))
+    """
+
+    def __init__(self, eps, mu=None, *, nsteps, sources, probes, omegas, design, fc=30e9, waveform="ricker", dt=5e-14,
+                 dx=1e-4, dtype=np.float64, boundary="pml", pml_cells=40, device=0, engine=None):
+        if engine is None:
+            from .batch import BatchEngine as engine
+        self._eng = None
+        p = self._p = _plan(eps, mu, nsteps, sources, probes, omegas, design, fc, waveform, dt, dx, boundary, pml_cells)
+        p.eps = np.array(p.eps)                 # the session's own copy: set_design_eps keeps it current
+        self._dtype = dtype
+        # one solve per distinct channel system, for all of its members' probes at once
+        self._groups = [(A, np.array([b for b, k in enumerate(p.which) if k == key]))
+                        for key, (_, A, _) in p.systems.items()]
+        self._condition = max(s[2] for s in p.systems.values())
+        r0, c0, nr, nc = p.win
+        outside = p.eps.astype(np.float64)
+        outside[:, r0:r0 + nr, c0:c0 + nc] = np.inf
+        self._eps_min_outside = outside.reshape(p.B, -1).min(axis=1)
+        eng = engine(p.B, p.R, p.Cc, dt, dx, dtype=dtype, boundary=boundary, device=device)
+        try:
+            _setup(eng, p)
+        except BaseException:
+            eng.__exit__(None, None, None)
+            raise
+        self._eng = eng
+
+    # -- lifetime -------------------------------------------------------------------
+    def close(self):
+        eng, self._eng = self._eng, None
+        if eng is not None:
+            eng.__exit__(None, None, None)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def engine(self):
+        """The standing engine (None once closed)."""
+        return self._eng
+
+    @property
+    def eps(self):
+        """The members' permittivity as the session holds it, (B, R, C), read-only."""
+        v = self._p.eps.view()
+        v.flags.writeable = False
+        return v
+
+    # -- one iteration ----------------------------------------------------------------
+    def value_and_grad(self, objective):
+        """(J (B,), grad (B, nrows, ncols) float64, spectra (B, P, F) complex128, info) of the current permittivity,
+        as batch_eps_gradient returns them."""
+        p, eng = self._p, self._eng
+        if eng is None:
+            raise RuntimeError("the session is closed")
+        none = np.empty((p.B, 0))
+        # 1. forward
+        eng.reset()
+        eng.run(p.nsteps, p.amps)
+        spectra, peak_fwd = eng.probe_spectra(p.om, 0, p.nsteps, peak=True)
+        end_fwd = eng.field_absmax("Ez")
+        eng.hold_dft_window()
+        # 2. the cotangent
+        J, g = _cotangent(p, objective, spectra)
+        # 3. adjoint
+        c = _injections(p, g, p.eps, self._dtype)
+        rhs = np.concatenate([c.real, c.imag], axis=2)              # (B, P, 2F)
+        weights = np.empty((p.B, p.P, 2 * p.F))
+        for A, members in self._groups:
+            w = np.linalg.solve(A, rhs[members].reshape(-1, 2 * p.F).T)
+            weights[members] = w.T.reshape(len(members), p.P, 2 * p.F)
+        eng.reset()
+        eng.set_point_sources(p.cells, weights)
+        eng.run(p.nsteps, None, p.channels)
+        _, peak_adj = eng.probe_spectra(none, 0, p.nsteps, peak=True)
+        end_adj = eng.field_absmax("Ez")
+        # 4. the gradient
+        grad = eng.dft_window_product(p.coef) * (p.dx / p.dt)
+        info = {"condition": self._condition, "residual_forward": _residual(end_fwd, peak_fwd),
+                "residual_adjoint": _residual(end_adj, peak_adj), "channels_shared": p.shared}
+        return J, grad, spectra, info
+
+    def set_design_eps(self, eps_window):
+        """New permittivity of the design window for every member: (B, nrows, ncols).  Checked on the host
+        (ValueError, nothing changed): the shape, positive finite values, the Courant condition of the updated
+        members."""
+        p = self._p
+        if self._eng is None:
+            raise RuntimeError("the session is closed")
+        r0, c0, nr, nc = p.win
+        new = np.asarray(eps_window)
+        if new.shape != (p.B, nr, nc):
+            raise ValueError(f"eps_window must have shape ({p.B}, {nr}, {nc}), got {new.shape}")
+        new = new.astype(p.eps.dtype)
+        ok = np.isfinite(new) & (new > 0)
+        if not np.all(ok):
+            raise ValueError(f"eps_window must be positive and finite: members "
+                             f"{np.nonzero(~ok.reshape(p.B, -1).all(axis=1))[0].tolist()}")
+        eps_min = np.minimum(self._eps_min_outside, new.reshape(p.B, -1).min(axis=1))
+        courant = (1 / np.sqrt(eps_min * p.mu_min) * p.dt) / p.dx
+        if not np.all(courant <= 1.0):
+            raise ValueError(f"Courant stability condition not met: members {np.nonzero(~(courant <= 1.0))[0].tolist()}")
+        self._eng.set_eps_window(p.win, new)
+        p.eps[:, r0:r0 + nr, c0:c0 + nc] = new
+        return self

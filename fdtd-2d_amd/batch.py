@@ -8,6 +8,8 @@ member is value-identical to an ``Engine`` run on it.  A thin wrapper over the C
 Monitors (``set_dft_window``, ``set_probes``) record a window DFT at up to 16 frequencies and up to 64 point probes
 per member inside the step kernels.  Point sources with channels (``set_point_sources``, ``run(channels=...)``) and the
 held window (``hold_dft_window``, ``dft_window_product``) are what an adjoint run needs (``adjoint.py``).
+``probe_spectra``, ``field_absmax`` and ``set_eps_window`` keep a design loop's traffic on the device
+(``AdjointSession``).
 """
 from __future__ import annotations
 
@@ -452,6 +454,44 @@ class BatchEngine:
         buf = out if out.size else np.empty(1)     # a refused or empty read still passes a valid pointer
         self._ck(self._lib.fdtd2d_batch_read_probes(self._h, _dptr(buf), int(first), int(count)))
         return out
+
+    # -- the design loop (fdtd2d_batch_design.h) ---------------------------------------------------------------
+    def probe_spectra(self, omegas, first=0, count=None, peak=False):
+        """complex128 (B, P, F): sum over the samples n in [first, first + count) of trace[b, p, n] *
+        exp(-1j * omegas[b, k] * s * dt), s the step after which sample n was recorded, formed on the device with the
+        window DFT's arithmetic in ascending n.  omegas (F,) for every member or (B, F), F <= 16; count None = up to
+        the samples recorded so far.  peak True: also float64 (B,), the largest |sample| of each member in the range."""
+        w = _window_omegas(omegas, self.count)
+        if count is None:
+            count = max(0, self.probe_samples - int(first))
+        F = int(w.shape[1])
+        re, im = np.empty((self.count, self._nprobe, F)), np.empty((self.count, self._nprobe, F))
+        pk = np.empty(self.count) if peak else None
+        buf = (re, im) if re.size else (np.empty(1), np.empty(1))    # a refused call still passes valid pointers
+        self._ck(self._lib.fdtd2d_batch_probe_spectra(self._h, F, _dptr(w) if F else None, int(first), int(count),
+                                                      _dptr(buf[0]) if F else None, _dptr(buf[1]) if F else None,
+                                                      None if pk is None else _dptr(pk)))
+        out = re + 1j * im
+        return (out, pk) if peak else out
+
+    def field_absmax(self, field="Ez"):
+        """float64 (B,): max |field| over each member's cells, reduced on the device.  field "Ez", "Hx" or "Hy"."""
+        codes = {"Ez": _abi.FIELD_EZ, "Hx": _abi.FIELD_HX, "Hy": _abi.FIELD_HY}
+        if field not in codes:
+            raise ValueError(f'field must be "Ez", "Hx" or "Hy", not {field!r}')
+        out = np.empty(self.count)
+        self._ck(self._lib.fdtd2d_batch_field_absmax(self._h, codes[field], _dptr(out)))
+        return out
+
+    def set_eps_window(self, window, eps):
+        """New permittivity for window = (row0, col0, nrows, ncols) of every member: eps (B, nrows, ncols).  The
+        engine is then as set_materials with the full updated arrays would leave it; fields, monitors, sources and the
+        PML stay.  Needs material arrays (not a uniform batch); the window must not hold cell [0, 0]."""
+        r0, c0, nr, nc = (int(v) for v in window)
+        e = _host(eps, "eps")
+        self._shape(e, (self.count, nr, nc), "eps")
+        self._ck(self._lib.fdtd2d_batch_set_eps_window(self._h, r0, c0, nr, nc, e.ctypes.data, _code(e.dtype)))
+        return self
 
     def sync(self):
         self._ck(self._lib.fdtd2d_batch_sync(self._h))

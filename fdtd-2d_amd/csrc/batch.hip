@@ -8,8 +8,10 @@
 // (kernels_batch_monitor.hpp, instantiated in batch_monitor.hip).
 // fdtd2d_batch_run_channels (fdtd2d_batch_adjoint.h) takes the point-source instances of those kernels
 // (batch_adjoint.hip), which also holds the window product kernel.
+// The design-loop entry points (fdtd2d_batch_design.h) launch the post-run kernels of batch_design.hip.
 #include "../../include/fdtd2d.h"
 #include "../../include/fdtd2d_batch_adjoint.h"
+#include "../../include/fdtd2d_batch_design.h"
 #include "../../include/fdtd2d_batch_monitor.h"
 #include "../../include/fdtd2d_batch_pml.h"
 
@@ -26,6 +28,7 @@
 
 #include "kernels_batch.hpp"
 #include "kernels_batch_adjoint.hpp"
+#include "kernels_batch_design.hpp"
 #include "kernels_batch_monitor.hpp"
 #include "kernels_batch_pml.hpp"
 
@@ -45,6 +48,12 @@ struct fdtd2d_batch {
     bool have_mat = false, uniform = true;
     double ce_u = 0, ch_u = 0;            // uniform coefficients, already rounded to T
     std::vector<double> courant;          // per member (fdtd.py:25-26)
+    // fdtd2d_batch_set_eps_window: eps as the engine stores it (count x rows x cols) and mu's minimum per member,
+    // kept from fdtd2d_batch_set_materials on; eps' minimum outside the last window, while that window stays
+    std::vector<double> eps_host, mu_min, eps_out_min;
+    int out_win[4] = {0, 0, 0, 0};
+    void *dsg = nullptr;                  // device scratch of the design-loop entry points
+    size_t dsg_cap = 0;
 
     int *rect = nullptr;                  // device copy of the source rectangles (4 per member)
     bool have_src = false;                // some member has a non-empty rectangle
@@ -560,6 +569,20 @@ int stage(fdtd2d_batch *b, double **dev, size_t *cap, const double *host, size_t
     return 0;
 }
 
+// the device scratch of the design-loop entry points, at least `bytes` large; waits for the stream first
+int scratch(fdtd2d_batch *b, size_t bytes)
+{
+    BCHK(b, hipStreamSynchronize(b->stream));
+    if (bytes > b->dsg_cap) {
+        release(&b->dsg);
+        b->dsg_cap = 0;
+        int rc = alloc(b, &b->dsg, bytes);
+        if (rc) return rc;
+        b->dsg_cap = bytes;
+    }
+    return 0;
+}
+
 }  // namespace
 
 // ===================================== C ABI ============================================
@@ -637,7 +660,7 @@ void fdtd2d_batch_destroy(fdtd2d_batch_t *b)
                      (void **)&b->amps, &b->ezx, &b->pml_row, &b->pml_col, (void **)&b->dft, (void **)&b->omega,
                      (void **)&b->win_acc, (void **)&b->win_omega, (void **)&b->win_ph, (void **)&b->probe_cells,
                      (void **)&b->probe_trace, (void **)&b->win_held, (void **)&b->pts_cells, (void **)&b->pts_own,
-                     (void **)&b->pts_w, (void **)&b->pts_tab, (void **)&b->chan})
+                     (void **)&b->pts_w, (void **)&b->pts_tab, (void **)&b->chan, &b->dsg})
         release(p);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -708,9 +731,10 @@ int fdtd2d_batch_set_materials(fdtd2d_batch_t *b, const void *eps, const void *m
     if (host_dtype != FDTD2D_F32 && host_dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad host_dtype");
     const size_t per = (size_t)b->rows * b->cols;
     std::vector<double> emin((size_t)b->count, 1e300), mmin((size_t)b->count, 1e300), kmur((size_t)b->count);
+    std::vector<double> eps_host((size_t)b->count * per);
     for (int m = 0; m < b->count; ++m) {
         for (size_t t = 0; t < per; ++t) {
-            const double e = as_engine(b, get_elem(eps, host_dtype, m * per + t));
+            const double e = eps_host[m * per + t] = as_engine(b, get_elem(eps, host_dtype, m * per + t));
             const double u = as_engine(b, get_elem(mu, host_dtype, m * per + t));
             if (!(e > 0) || !(u > 0))
                 return bfail(b, FDTD2D_E_ARG, "eps and mu must be positive (member %d, cell %zu)", m, t);
@@ -745,6 +769,9 @@ int fdtd2d_batch_set_materials(fdtd2d_batch_t *b, const void *eps, const void *m
     }
     BCHK(b, hipMemcpyAsync(b->kmur, kt.data(), kt.size(), hipMemcpyHostToDevice, b->stream));
     BCHK(b, hipStreamSynchronize(b->stream));
+    b->eps_host.swap(eps_host);
+    b->mu_min.swap(mmin);
+    b->eps_out_min.clear();
     b->uniform = false;
     b->have_mat = true;
     return 0;
@@ -1235,6 +1262,134 @@ int fdtd2d_batch_dft_window_product(fdtd2d_batch_t *b, const double *coef_re, co
     release((void **)&dcoef);
     release((void **)&dout);
     if (e != hipSuccess) return bfail(b, -(1000 + (int)e), "window product failed: %s", hipGetErrorString(e));
+    return 0;
+}
+
+// ---- fdtd2d_batch_design.h -------------------------------------------------------------------------------------
+
+int fdtd2d_batch_probe_spectra(fdtd2d_batch_t *b, int nfreq, const double *omega, long long first,
+                               long long count_samples, double *re, double *im, double *peak)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!b->nprobe) return bfail(b, FDTD2D_E_STATE, "no probes are set");
+    if (nfreq < 0 || nfreq > FDTD2D_BATCH_MAX_DFT_FREQS)
+        return bfail(b, FDTD2D_E_ARG, "nfreq %d outside 0..%d", nfreq, FDTD2D_BATCH_MAX_DFT_FREQS);
+    if (nfreq > 0 && (!omega || !re || !im)) return bfail(b, FDTD2D_E_ARG, "omega, re and im must not be NULL");
+    if (nfreq == 0 && !peak) return bfail(b, FDTD2D_E_ARG, "nfreq 0 asks for the peak alone: peak must not be NULL");
+    for (size_t k = 0; k < (size_t)b->count * nfreq; ++k)
+        if (!std::isfinite(omega[k]))
+            return bfail(b, FDTD2D_E_ARG, "member %d: frequency %d is not finite", (int)(k / nfreq), (int)(k % nfreq));
+    const long long recorded = fdtd2d_batch_info(b, FDTD2D_BATCH_INFO_PROBE_SAMPLES);
+    if (first < 0 || count_samples < 0 || first > recorded || count_samples > recorded - first)
+        return bfail(b, FDTD2D_E_ARG, "samples [%lld, %lld) outside the %lld recorded so far", first, first + count_samples,
+                     recorded);
+    int rc = use_device(b);
+    if (rc) return rc;
+    // scratch: omega (count x nfreq), re, im (count x nprobe x nfreq each), peak (count)
+    const size_t nom = (size_t)b->count * nfreq, nsp = nom * b->nprobe;
+    if ((rc = scratch(b, (nom + 2 * nsp + b->count) * sizeof(double)))) return rc;
+    double *d = (double *)b->dsg;
+    if (nom) BCHK(b, hipMemcpyAsync(d, omega, nom * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    fdtd::BatchSpectra a;
+    a.trace = b->probe_trace;
+    a.omega = d;
+    a.re = d + nom;
+    a.im = d + nom + nsp;
+    a.peak = peak ? d + nom + 2 * nsp : nullptr;
+    a.B = b->count; a.np = b->nprobe; a.nf = nfreq;
+    a.cap = b->probe_cap; a.first = first; a.count = count_samples;
+    a.step0 = b->probe_step0;
+    a.dt = b->dt;
+    fdtd::batch_probe_spectra_launch(a, b->stream);
+    BCHK(b, hipGetLastError());
+    b->launches++;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    if (nsp) {
+        BCHK(b, hipMemcpy(re, a.re, nsp * sizeof(double), hipMemcpyDeviceToHost));
+        BCHK(b, hipMemcpy(im, a.im, nsp * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    if (peak) BCHK(b, hipMemcpy(peak, a.peak, (size_t)b->count * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int fdtd2d_batch_field_absmax(fdtd2d_batch_t *b, int field, double *out)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!out) return bfail(b, FDTD2D_E_ARG, "out must not be NULL");
+    if (field != FDTD2D_FIELD_EZ && field != FDTD2D_FIELD_HX && field != FDTD2D_FIELD_HY)
+        return bfail(b, FDTD2D_E_ARG, "field %d: FDTD2D_FIELD_EZ, _HX or _HY", field);
+    int rc = use_device(b);
+    if (rc) return rc;
+    if ((rc = scratch(b, (size_t)b->count * sizeof(double)))) return rc;
+    const void *f = field == FDTD2D_FIELD_EZ ? b->ez[b->cur] : field == FDTD2D_FIELD_HX ? b->hx : b->hy;
+    fdtd::batch_field_absmax_launch(f, b->dtype == FDTD2D_F64, (double *)b->dsg, b->count,
+                                    b->rows - (field == FDTD2D_FIELD_HY), b->cols - (field == FDTD2D_FIELD_HX), b->pitch,
+                                    b->mstride, b->stream);
+    BCHK(b, hipGetLastError());
+    b->launches++;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    BCHK(b, hipMemcpy(out, b->dsg, (size_t)b->count * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int fdtd2d_batch_set_eps_window(fdtd2d_batch_t *b, int row0, int col0, int nrows, int ncols, const void *eps,
+                                int host_dtype)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!b->have_mat || b->uniform)
+        return bfail(b, FDTD2D_E_STATE, "no material arrays to patch: call fdtd2d_batch_set_materials first");
+    if (!eps) return bfail(b, FDTD2D_E_ARG, "eps must not be NULL");
+    if (host_dtype != FDTD2D_F32 && host_dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad host_dtype");
+    if (nrows < 1 || ncols < 1 || row0 < 0 || col0 < 0 || (long long)row0 + nrows > b->rows ||
+        (long long)col0 + ncols > b->cols)
+        return bfail(b, FDTD2D_E_ARG, "window (%d,%d)+%dx%d is empty or outside the %dx%d grid", row0, col0, nrows, ncols,
+                     b->rows, b->cols);
+    if (row0 == 0 && col0 == 0)
+        return bfail(b, FDTD2D_E_ARG, "the window holds cell [0, 0], which sets the Mur factor and the PML grading");
+    const size_t W = (size_t)nrows * ncols, per = (size_t)b->rows * b->cols;
+    std::vector<unsigned char> stage_w((size_t)b->count * W * b->esz);
+    std::vector<double> wmin((size_t)b->count, 1e300);
+    for (int m = 0; m < b->count; ++m)
+        for (size_t t = 0; t < W; ++t) {
+            const double e = as_engine(b, get_elem(eps, host_dtype, m * W + t));
+            if (!(e > 0) || !std::isfinite(e))
+                return bfail(b, FDTD2D_E_ARG, "eps must be positive and finite (member %d, window cell %zu)", m, t);
+            if (b->dtype == FDTD2D_F32) ((float *)stage_w.data())[m * W + t] = (float)e;
+            else ((double *)stage_w.data())[m * W + t] = e;
+            wmin[m] = e < wmin[m] ? e : wmin[m];
+        }
+    int rc = use_device(b);
+    if (rc) return rc;
+    if ((rc = scratch(b, stage_w.size()))) return rc;      // waits for launches that still read the coefficients
+    BCHK(b, hipMemcpyAsync(b->dsg, stage_w.data(), stage_w.size(), hipMemcpyHostToDevice, b->stream));
+    fdtd::batch_eps_window_launch(b->ce, b->dsg, b->dtype == FDTD2D_F64, b->count, row0, col0, nrows, ncols, b->pitch,
+                                  b->mstride, b->dt, b->dx, b->stream);
+    BCHK(b, hipGetLastError());
+    b->launches++;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    // the host copy and the Courant number of the full updated member
+    const int win[4] = {row0, col0, nrows, ncols};
+    if (b->eps_out_min.empty() || std::memcmp(win, b->out_win, sizeof win) != 0) {
+        b->eps_out_min.assign((size_t)b->count, 1e300);
+        for (int m = 0; m < b->count; ++m)
+            for (int i = 0; i < b->rows; ++i) {
+                const bool in_rows = i >= row0 && i < row0 + nrows;
+                const double *row = b->eps_host.data() + m * per + (size_t)i * b->cols;
+                for (int j = 0; j < b->cols; ++j) {
+                    if (in_rows && j >= col0 && j < col0 + ncols) continue;
+                    b->eps_out_min[m] = row[j] < b->eps_out_min[m] ? row[j] : b->eps_out_min[m];
+                }
+            }
+        std::memcpy(b->out_win, win, sizeof win);
+    }
+    for (int m = 0; m < b->count; ++m) {
+        for (int i = 0; i < nrows; ++i)
+            for (int j = 0; j < ncols; ++j)
+                b->eps_host[m * per + (size_t)(row0 + i) * b->cols + (col0 + j)] =
+                    as_engine(b, get_elem(eps, host_dtype, m * W + (size_t)i * ncols + j));
+        const double emin = wmin[m] < b->eps_out_min[m] ? wmin[m] : b->eps_out_min[m];
+        b->courant[m] = courant_of(emin, b->mu_min[m], b->dt, b->dx);
+    }
     return 0;
 }
 

@@ -30,6 +30,13 @@ array eps with random binary permittivity, a ricker line source per member):
                               engine) and device_over_two_runs = the cost of the channels and the product;
                               product_ms (dft_window_product) against download_ms (both windows read back and
                               multiplied in NumPy).  Default: 1024 members of 60 x 60 and 64 of 250 x 250.
+                              Timed alternately with those, in the same process: session_ms (one value_and_grad of a
+                              standing AdjointSession, the same objective) and session_over_two_runs / _over_device /
+                              grad_over_session; spectra_device_ms (one BatchEngine.probe_spectra of all members with
+                              the peaks; spectra_trace_bytes = B * P * n * 8 is what its kernel reads) against
+                              spectra_host_ms (read_probes + adjoint.probe_spectra, the helper's way); eps_window_ms
+                              (set_eps_window of the design window) against set_materials_ms (the full arrays);
+                              launches_per_session_iteration.
 Usage: python tools/bench_batch.py [--count 1024 --rows 60 --cols 60 --steps 1000] [--reps 5] [--loop-members 16]
                                    [--boundary {mur,pml} --pml-cells 10] [--monitors] [--adjoint]
 """
@@ -223,7 +230,12 @@ def bench_adjoint(count, rows, cols, steps, dtype, reps, pml_cells):
         info.update(out[3])
         return (time.perf_counter() - t0) * 1e3
 
+    from fdtd2d_amd.adjoint import probe_spectra as host_spectra
     chan, _ = channel_system(omegas, steps, dt, FC)
+    session = fd.AdjointSession(eps, nsteps=steps, sources=rects, probes=probes, omegas=omegas, design=design, fc=FC,
+                                dt=dt, dx=DX, dtype=dtype, boundary="pml", pml_cells=pml_cells)
+    om = np.tile(omegas, (count, 1))
+    new_window = np.where(rng.random((count, side, side)) < 0.5, fd.EPS0, 5 * fd.EPS0)
     weights = rng.standard_normal((count, 30, 20))
     coef = gradient_coefficients(omegas, dt)
     with fd.BatchEngine(count, rows, cols, dt, DX, dtype=dtype, boundary="pml") as b:
@@ -254,18 +266,53 @@ def bench_adjoint(count, rows, cols, steps, dtype, reps, pml_cells):
             (coef[None, :, None, None] * held * cur).real.sum(axis=1)
             return (time.perf_counter() - t0) * 1e3
 
-        two_runs(), device(), gradient()                 # warm-up: code objects, clocks
+        def iteration():
+            t0 = time.perf_counter()
+            session.value_and_grad(objective)
+            return (time.perf_counter() - t0) * 1e3
+
+        def spectra_device():
+            t0 = time.perf_counter()
+            b.probe_spectra(om, 0, steps, peak=True)
+            return (time.perf_counter() - t0) * 1e3
+
+        def spectra_host():
+            t0 = time.perf_counter()
+            host_spectra(b.read_probes(0, steps), om, dt)
+            return (time.perf_counter() - t0) * 1e3
+
+        def eps_window():
+            t0 = time.perf_counter()
+            session.engine.set_eps_window(design, new_window)
+            return (time.perf_counter() - t0) * 1e3
+
+        def materials():
+            t0 = time.perf_counter()
+            b.set_materials(eps.astype(dtype), fd.MU0)
+            return (time.perf_counter() - t0) * 1e3
+
+        two_runs(), device(), gradient(), iteration()    # warm-up: code objects, clocks
         l0 = b.launches
         device()
         launches = b.launches - l0
-        t = {k: [] for k in ("grad", "two", "device", "product", "download")}
+        l0 = session.engine.launches
+        iteration()
+        session_launches = session.engine.launches - l0
+        t = {k: [] for k in ("grad", "two", "device", "product", "download", "session", "spectra_device",
+                             "spectra_host", "eps_window", "materials")}
         for _ in range(reps):
             t["two"].append(two_runs())
             t["device"].append(device())
             t["grad"].append(gradient())
+            t["session"].append(iteration())
             t["product"].append(product())
             t["download"].append(download())
+            t["spectra_device"].append(spectra_device())
+            t["spectra_host"].append(spectra_host())
+            t["eps_window"].append(eps_window())
+            t["materials"].append(materials())
         resident, in_lds, lds = b.resident, b.window_in_lds, b.lds_bytes
+    session.close()
     med = {k: float(np.median(v)) for k, v in t.items()}
     return {"count": count, "rows": rows, "cols": cols, "steps": steps, "dtype": np.dtype(dtype).name, "dt": dt,
             "boundary": "pml", "pml_cells": pml_cells, "design": list(design), "freqs": 10, "probes": 30, "channels": 20,
@@ -278,6 +325,14 @@ def bench_adjoint(count, rows, cols, steps, dtype, reps, pml_cells):
             "device_over_two_runs": round(med["device"] / med["two"], 3), "launches_per_gradient": launches,
             "product_ms": round(med["product"], 3), "download_ms": round(med["download"], 3),
             "download_over_product": round(med["download"] / med["product"], 2),
+            "session_ms": round(med["session"], 3), "session_ms_min": round(min(t["session"]), 3),
+            "session_over_two_runs": round(med["session"] / med["two"], 3),
+            "session_over_device": round(med["session"] / med["device"], 3),
+            "grad_over_session": round(med["grad"] / med["session"], 2),
+            "launches_per_session_iteration": session_launches,
+            "spectra_device_ms": round(med["spectra_device"], 3), "spectra_host_ms": round(med["spectra_host"], 3),
+            "spectra_trace_bytes": count * 30 * steps * 8,
+            "eps_window_ms": round(med["eps_window"], 3), "set_materials_ms": round(med["materials"], 3),
             "condition": round(float(info["condition"]), 2),
             "residual_forward_max": float(np.max(info["residual_forward"])),
             "residual_adjoint_max": float(np.max(info["residual_adjoint"]))}
