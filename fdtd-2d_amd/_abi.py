@@ -44,6 +44,8 @@ BATCH_MAX_DFT_FREQS, BATCH_MAX_PROBES = 16, 64
 # include/fdtd2d_batch_adjoint.h
 BATCH_INFO_POINT_SOURCES, BATCH_INFO_HELD_WINDOW = 12, 13
 BATCH_MAX_POINT_SOURCES, BATCH_MAX_CHANNELS = 64, 32
+# include/fdtd2d_batch_lossy.h
+BATCH_INFO_LOSSY = 14
 
 _vp, _i, _d, _ll = C.c_void_p, C.c_int, C.c_double, C.c_longlong
 
@@ -153,6 +155,12 @@ BATCH_DESIGN_SIGNATURES = {
     "fdtd2d_batch_set_eps_window": (_i, [_vp, _i, _i, _i, _i, _vp, _i]),
 }
 
+# every symbol include/fdtd2d_batch_lossy.h declares (an electric conductivity per cell of a batch)
+BATCH_LOSSY_SIGNATURES = {
+    "fdtd2d_batch_set_conductivity": (_i, [_vp, _vp, _i]),
+    "fdtd2d_batch_set_conductivity_window": (_i, [_vp, C.POINTER(_i), _vp, _i]),
+}
+
 # transport callback of fdtd2d_slab_attach
 EXCHANGE_FN = C.CFUNCTYPE(_i, _vp, _vp, _vp, _vp, _vp, _ll, _vp)
 
@@ -201,7 +209,8 @@ def load():
                 "g.build()'` (or `make -C fdtd-2d_amd/csrc`). There is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in {**SIGNATURES, **BATCH_PML_SIGNATURES, **BATCH_MONITOR_SIGNATURES,
-                                   **BATCH_ADJOINT_SIGNATURES, **BATCH_DESIGN_SIGNATURES}.items():
+                                   **BATCH_ADJOINT_SIGNATURES, **BATCH_DESIGN_SIGNATURES,
+                                   **BATCH_LOSSY_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

@@ -14,6 +14,14 @@ where E_k, Eadj_k are the window DFTs of the two runs over the design window.  N
 transposed kernel exists: the forward run records a window DFT and the probes, ``hold_dft_window`` keeps the window on
 the device, the adjoint run injects at every probe cell a time series whose DFT at omega_k is conj(g[p, k]) / D[p]
 through ``set_point_sources`` / ``run(channels=...)``, and ``dft_window_product`` forms the sum above on the device.
+
+With an electric conductivity sigma per cell (``BatchEngine.set_conductivity``) the one-step operator becomes
+D (z - 2 + 1/z) + G (z - 1/z) - L with G = sigma dx / 2.  It is still symmetric and eps still enters through D alone,
+so dJ/d eps keeps its formula, and ``batch_material_gradient`` adds
+
+    dJ/d sigma[i] = (dx / 2) * sum_k Re( -(z_k + 1) / z_k * E_k[i] * Eadj_k[i] )
+
+from the same two windows: one more product, no new run.
 """
 from __future__ import annotations
 
@@ -63,6 +71,48 @@ def gradient_coefficients(omegas, dt):
     """-(z - 2 + 1/z) / (z - 1) for z = exp(i omega dt): the factor of E_k * Eadj_k in the gradient."""
     z = np.exp(1j * np.asarray(omegas, dtype=np.float64) * dt)
     return -(z - 2 + 1 / z) / (z - 1)
+
+
+def sigma_coefficients(omegas, dt):
+    """-(z + 1) / z for z = exp(i omega dt): the factor of E_k * Eadj_k in the conductivity gradient."""
+    z = np.exp(1j * np.asarray(omegas, dtype=np.float64) * dt)
+    return -(z + 1) / z
+
+
+def _check_sigma(p, sigma, window=None):
+    """The host checks of a conductivity (ValueError naming the first offending member): (B, R, C), or (B, nrows, ncols)
+    for window = (row0, col0, nrows, ncols); >= 0 and finite; zero in the boundary frame or the PML layer and at every
+    probe cell.  Returns it as a float64 array."""
+    r0, c0, nr, nc = (0, 0, p.R, p.Cc) if window is None else window
+    s = np.asarray(sigma, dtype=np.float64)
+    if s.ndim == 0 and window is None:
+        full = np.zeros((p.B, p.R, p.Cc))
+        full[:, p.margin:p.R - p.margin, p.margin:p.Cc - p.margin] = s
+        if not s >= 0:
+            full[...] = s
+        s = full
+    if s.shape != (p.B, nr, nc):
+        raise ValueError(f"sigma must have shape ({p.B}, {nr}, {nc}), got {s.shape}")
+    bad = ~(np.isfinite(s) & (s >= 0))
+    if bad.any():
+        raise ValueError(f"member {int(np.nonzero(bad.reshape(p.B, -1).any(axis=1))[0][0])}: sigma must be >= 0 and "
+                         f"finite")
+    rows, cols = np.arange(r0, r0 + nr), np.arange(c0, c0 + nc)
+    edge = ((rows < p.margin) | (rows > p.R - 1 - p.margin))[:, None] | \
+        ((cols < p.margin) | (cols > p.Cc - 1 - p.margin))[None, :]
+    out = (s != 0) & edge[None]
+    if out.any():
+        b = int(np.nonzero(out.reshape(p.B, -1).any(axis=1))[0][0])
+        i, j = (int(v[0]) for v in np.nonzero(out[b]))
+        raise ValueError(f"member {b}: sigma is non-zero at cell ({r0 + i}, {c0 + j}), within {p.margin} cells of an "
+                         f"edge ({p.margin_why}): only cells that take the plain update may conduct")
+    for b in range(p.B):
+        for r, c in p.cells[b]:
+            r, c = int(r) - r0, int(c) - c0
+            if 0 <= r < nr and 0 <= c < nc and s[b, r, c] != 0:
+                raise ValueError(f"member {b}: sigma is non-zero at the probe cell ({r + r0}, {c + c0}); the adjoint "
+                                 f"injection there would be conj(g) / (D + G), which is not implemented")
+    return s
 
 
 def _check_design(design, rects, R, Cc, margin, why):
@@ -118,8 +168,9 @@ def _plan(eps, mu, nsteps, sources, probes, omegas, design, fc, waveform, dt, dx
     if boundary == "pml" and not pml_fits(R, Cc, L):
         raise ValueError(f"a {L}-cell PML does not fit {R}x{Cc} members (2L + 3 <= min(rows, cols))")
     margin = max(EDGE_MARGIN, L) if boundary == "pml" else EDGE_MARGIN
-    win = _check_design(design, rects, R, Cc, margin,
-                        f"the {L}-cell PML layer" if margin > EDGE_MARGIN else "the boundary frame and cell [0, 0]")
+    p.margin = margin
+    p.margin_why = f"the {L}-cell PML layer" if margin > EDGE_MARGIN else "the boundary frame and cell [0, 0]"
+    win = _check_design(design, rects, R, Cc, margin, p.margin_why)
 
     cells = _probe_cells(probes, B)
     P = cells.shape[1]
@@ -157,6 +208,7 @@ def _plan(eps, mu, nsteps, sources, probes, omegas, design, fc, waveform, dt, dx
     p.channels = systems[which[0]][0] if p.shared else np.stack([systems[k][0] for k in which])
     p.amps = _waveform_amps(waveform, fcs, nsteps, dt)
     p.coef = np.stack([gradient_coefficients(w, dt) for w in om])
+    p.coef_sigma = np.stack([sigma_coefficients(w, dt) for w in om])
     return p
 
 
@@ -213,13 +265,22 @@ def batch_eps_gradient(eps, mu=None, *, nsteps, sources, probes, omegas, design,
     AdjointSession is for.
 
     Returns (J (B,), grad (B, nrows, ncols) float64, spectra (B, P, F) complex128, info)."""
+    p = _plan(eps, mu, nsteps, sources, probes, omegas, design, fc, waveform, dt, dx, boundary, pml_cells)
+    J, grad, _, spectra, info = _two_runs(p, None, objective, dtype, device, engine)
+    return J, grad, spectra, info
+
+
+def _two_runs(p, sigma, objective, dtype, device, engine):
+    """The forward and the adjoint run of batch_eps_gradient and batch_material_gradient on a fresh engine; sigma: the
+    checked conductivity, or None for a lossless batch.  Returns (J, grad_eps, grad_sigma or None, spectra, info)."""
     if engine is None:
         from .batch import BatchEngine as engine
-    p = _plan(eps, mu, nsteps, sources, probes, omegas, design, fc, waveform, dt, dx, boundary, pml_cells)
-    B, nsteps = p.B, p.nsteps
+    B, nsteps, dt, dx, boundary = p.B, p.nsteps, p.dt, p.dx, p.boundary
     with engine(B, p.R, p.Cc, dt, dx, dtype=dtype, boundary=boundary, device=device) as eng:
         # 1. forward: the member's own source; window DFT over the design region, probes at the observation cells
         _setup(eng, p)
+        if sigma is not None:
+            eng.set_conductivity(sigma)
         eng.run(nsteps, p.amps)
         traces = eng.read_probes(0, nsteps)
         end_fwd = np.abs(eng.download()[0].astype(np.float64)).reshape(B, -1).max(axis=1)
@@ -240,8 +301,9 @@ def batch_eps_gradient(eps, mu=None, *, nsteps, sources, probes, omegas, design,
         adj_traces = eng.read_probes(0, nsteps)
         end_adj = np.abs(eng.download()[0].astype(np.float64)).reshape(B, -1).max(axis=1)
 
-        # 4. the gradient, formed on the device from the two windows
+        # 4. the gradients, formed on the device from the two windows
         grad = eng.dft_window_product(p.coef) * (dx / dt)
+        grad_sigma = None if sigma is None else eng.dft_window_product(p.coef_sigma) * (dx / 2)
 
     def peak(tr):
         flat = tr.reshape(B, -1)
@@ -249,7 +311,26 @@ def batch_eps_gradient(eps, mu=None, *, nsteps, sources, probes, omegas, design,
     info = {"condition": max(s[2] for s in p.systems.values()),
             "residual_forward": _residual(end_fwd, peak(traces)), "residual_adjoint": _residual(end_adj, peak(adj_traces)),
             "channels_shared": p.shared}
-    return J, grad, spectra, info
+    return J, grad, grad_sigma, spectra, info
+
+
+def batch_material_gradient(eps, sigma, mu=None, *, nsteps, sources, probes, omegas, design, objective, fc=30e9,
+                            waveform="ricker", dt=5e-14, dx=1e-4, dtype=np.float64, boundary="pml", pml_cells=40,
+                            device=0, engine=None):
+    """batch_eps_gradient for lossy members: the gradients of the objective with respect to eps and to the electric
+    conductivity sigma over the design window, from the same two runs.
+
+    sigma: (B, R, C) in S/m (BatchEngine.set_conductivity), a scalar for every cell that may conduct, or None for
+    zero.  The other arguments, the conditions and their checks are batch_eps_gradient's.  In addition, checked on the
+    host with a ValueError that names the member: sigma is >= 0 and finite, zero within 6 cells of every edge and
+    inside the PML layer (only cells that take the plain update may conduct), and zero at every probe cell (the
+    injection there would be conj(g) / (D + G); only the sigma = 0 case is implemented).
+
+    Returns (J (B,), grad_eps (B, nrows, ncols), grad_sigma (B, nrows, ncols) float64, spectra (B, P, F) complex128,
+    info)."""
+    p = _plan(eps, mu, nsteps, sources, probes, omegas, design, fc, waveform, dt, dx, boundary, pml_cells)
+    s = _check_sigma(p, 0.0 if sigma is None else sigma)
+    return _two_runs(p, s, objective, dtype, device, engine)
 
 
 class AdjointSession:
@@ -286,6 +367,8 @@ class AdjointSession:
         outside = p.eps.astype(np.float64)
         outside[:, r0:r0 + nr, c0:c0 + nc] = np.inf
         self._eps_min_outside = outside.reshape(p.B, -1).min(axis=1)
+        self._sigma = None                      # the conductivity as the session holds it (None: lossless)
+        self._ran = False                       # the windows of a value_and_grad are on the device
         eng = engine(p.B, p.R, p.Cc, dt, dx, dtype=dtype, boundary=boundary, device=device)
         try:
             _setup(eng, p)
@@ -348,9 +431,58 @@ class AdjointSession:
         end_adj = eng.field_absmax("Ez")
         # 4. the gradient
         grad = eng.dft_window_product(p.coef) * (p.dx / p.dt)
+        self._ran = True
         info = {"condition": self._condition, "residual_forward": _residual(end_fwd, peak_fwd),
                 "residual_adjoint": _residual(end_adj, peak_adj), "channels_shared": p.shared}
         return J, grad, spectra, info
+
+    # -- lossy members ------------------------------------------------------------------
+    @property
+    def sigma(self):
+        """The members' conductivity as the session holds it, (B, R, C) float64, read-only (None: lossless)."""
+        if self._sigma is None:
+            return None
+        v = self._sigma.view()
+        v.flags.writeable = False
+        return v
+
+    def set_conductivity(self, sigma):
+        """The conductivity of every member, (B, R, C) in S/m (a scalar: every cell that may conduct; None removes
+        it), before the first iteration or between iterations.  Checked on the host as batch_material_gradient checks
+        it (ValueError, nothing changed)."""
+        if self._eng is None:
+            raise RuntimeError("the session is closed")
+        if sigma is None:
+            self._eng.set_conductivity(None)
+            self._sigma = None
+            return self
+        s = _check_sigma(self._p, sigma)
+        self._eng.set_conductivity(s)
+        self._sigma = s.copy()
+        return self
+
+    def set_design_sigma(self, sigma_window):
+        """New conductivity of the design window for every member: (B, nrows, ncols).  Checked on the host
+        (ValueError, nothing changed): the shape, values >= 0 and finite, zero at probe cells."""
+        p = self._p
+        if self._eng is None:
+            raise RuntimeError("the session is closed")
+        r0, c0, nr, nc = p.win
+        s = _check_sigma(p, sigma_window, p.win)
+        self._eng.set_conductivity_window(p.win, s)
+        if self._sigma is None:
+            self._sigma = np.zeros((p.B, p.R, p.Cc))
+        self._sigma[:, r0:r0 + nr, c0:c0 + nc] = s
+        return self
+
+    def sigma_gradient(self):
+        """dJ/d sigma over the design window, (B, nrows, ncols) float64, for the latest value_and_grad: one more
+        product of the two windows that are still on the device, and one read-back."""
+        if self._eng is None:
+            raise RuntimeError("the session is closed")
+        if not self._ran:
+            raise RuntimeError("no gradient yet: call value_and_grad first")
+        return self._eng.dft_window_product(self._p.coef_sigma) * (self._p.dx / 2)
 
     def set_design_eps(self, eps_window):
         """New permittivity of the design window for every member: (B, nrows, ncols).  Checked on the host

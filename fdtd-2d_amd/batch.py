@@ -9,7 +9,8 @@ Monitors (``set_dft_window``, ``set_probes``) record a window DFT at up to 16 fr
 per member inside the step kernels.  Point sources with channels (``set_point_sources``, ``run(channels=...)``) and the
 held window (``hold_dft_window``, ``dft_window_product``) are what an adjoint run needs (``adjoint.py``).
 ``probe_spectra``, ``field_absmax`` and ``set_eps_window`` keep a design loop's traffic on the device
-(``AdjointSession``).
+(``AdjointSession``).  ``set_conductivity`` gives every member an electric conductivity per cell (lossy dielectrics,
+absorbers, resistive sheets); the batch then runs on the lossy step kernels.
 """
 from __future__ import annotations
 
@@ -93,6 +94,7 @@ class BatchEngine:
             raise ValueError(f"unknown boundary {boundary!r}")
         self._pml_on = False          # a layer is set
         self._pml_chosen = False      # set_pml (or clear_pml) has been called: a "pml" batch may run
+        self._pml_L = 0               # the layer's depth
         self._win = None              # (F, nrows, ncols) of the window DFT
         self._nprobe = 0
         self._npoint = (0, 0)         # (P, K) of the point sources
@@ -212,6 +214,7 @@ class BatchEngine:
         self._ck(self._lib.fdtd2d_batch_set_pml(self._h, rowf.ctypes.data, colf.ctypes.data, _code(self.dtype),
                                                 int(L)))
         self._pml_on = self._pml_chosen = True
+        self._pml_L = int(L)
         return self
 
     def clear_pml(self):
@@ -219,7 +222,7 @@ class BatchEngine:
         if self.boundary != "pml":
             raise _abi.Fdtd2dError(_abi.E_STATE, f'clear_pml needs boundary="pml", not {self.boundary!r}')
         self._ck(self._lib.fdtd2d_batch_set_pml(self._h, None, None, _code(self.dtype), 0))
-        self._pml_on, self._pml_chosen = False, True
+        self._pml_on, self._pml_chosen, self._pml_L = False, True, 0
         return self
 
     @property
@@ -492,6 +495,55 @@ class BatchEngine:
         self._shape(e, (self.count, nr, nc), "eps")
         self._ck(self._lib.fdtd2d_batch_set_eps_window(self._h, r0, c0, nr, nc, e.ctypes.data, _code(e.dtype)))
         return self
+
+    # -- lossy materials (fdtd2d_batch_lossy.h) ------------------------------------------------------------------
+    @property
+    def conductivity_margin(self) -> int:
+        """Cells next to every edge that may not conduct with the current boundary: the 5-cell Mur frame and cell
+        [0, 0] (6), the PML layer (its depth, at least 6), or the edge cells of a closed box (1)."""
+        if self.boundary == "mur":
+            return 6
+        return max(6, self._pml_L) if self._pml_on else 1
+
+    def set_conductivity(self, sigma):
+        """Electric conductivity in S/m, >= 0: (B, R, C), or a scalar for every cell that may conduct (zero in the
+        margin of conductivity_margin), or None to remove it.  The cells that take the plain E update then take
+        e = ca * e + (dhy - dhx) * cb with s = sigma dt / (2 eps), ca = (1 - s) / (1 + s), cb = ce / (1 + s); it
+        persists across set_materials and set_eps_window.  Needs materials (a uniform batch gets coefficient arrays).
+        The library refuses (E_ARG) a value that is negative, not finite, or non-zero inside the margin."""
+        if sigma is None:
+            self._ck(self._lib.fdtd2d_batch_set_conductivity(self._h, None, _code(self.dtype)))
+            return self
+        shape = (self.count, self.rows, self.cols)
+        if np.isscalar(sigma):
+            g = self.conductivity_margin
+            s = np.zeros(shape, np.float64)
+            s[:, g:self.rows - g, g:self.cols - g] = float(sigma)
+            if not float(sigma) >= 0:             # negative or NaN: let the library name it even where s is empty
+                s[...] = float(sigma)
+        else:
+            s = _host(sigma, "sigma")
+        self._shape(s, shape, "sigma")
+        self._ck(self._lib.fdtd2d_batch_set_conductivity(self._h, s.ctypes.data, _code(s.dtype)))
+        return self
+
+    def set_conductivity_window(self, window, sigma):
+        """New conductivity for window = (row0, col0, nrows, ncols) of every member: sigma (B, nrows, ncols).  The
+        engine is then as set_conductivity with the full updated array would leave it (a batch without conductivity
+        starts from zero)."""
+        w = np.ascontiguousarray([int(v) for v in window], dtype=np.int32)
+        if w.shape != (4,):
+            raise ValueError(f"window must be 4 integers (row0, col0, nrows, ncols), got {window!r}")
+        s = _host(sigma, "sigma")
+        self._shape(s, (self.count, int(w[2]), int(w[3])), "sigma")
+        self._ck(self._lib.fdtd2d_batch_set_conductivity_window(self._h, w.ctypes.data_as(C.POINTER(C.c_int)),
+                                                                s.ctypes.data, _code(s.dtype)))
+        return self
+
+    @property
+    def lossy(self) -> bool:
+        """Whether a conductivity is set (the batch runs on the lossy kernels)."""
+        return bool(self.info(_abi.BATCH_INFO_LOSSY))
 
     def sync(self):
         self._ck(self._lib.fdtd2d_batch_sync(self._h))

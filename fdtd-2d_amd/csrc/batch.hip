@@ -9,9 +9,11 @@
 // fdtd2d_batch_run_channels (fdtd2d_batch_adjoint.h) takes the point-source instances of those kernels
 // (batch_adjoint.hip), which also holds the window product kernel.
 // The design-loop entry points (fdtd2d_batch_design.h) launch the post-run kernels of batch_design.hip.
+// With a conductivity set (fdtd2d_batch_lossy.h) every run takes the lossy kernels of batch_lossy.hip.
 #include "../../include/fdtd2d.h"
 #include "../../include/fdtd2d_batch_adjoint.h"
 #include "../../include/fdtd2d_batch_design.h"
+#include "../../include/fdtd2d_batch_lossy.h"
 #include "../../include/fdtd2d_batch_monitor.h"
 #include "../../include/fdtd2d_batch_pml.h"
 
@@ -29,6 +31,7 @@
 #include "kernels_batch.hpp"
 #include "kernels_batch_adjoint.hpp"
 #include "kernels_batch_design.hpp"
+#include "kernels_batch_lossy.hpp"
 #include "kernels_batch_monitor.hpp"
 #include "kernels_batch_pml.hpp"
 
@@ -52,6 +55,10 @@ struct fdtd2d_batch {
     // kept from fdtd2d_batch_set_materials on; eps' minimum outside the last window, while that window stays
     std::vector<double> eps_host, mu_min, eps_out_min;
     int out_win[4] = {0, 0, 0, 0};
+    // fdtd2d_batch_set_conductivity: ca and cb = ce / (1 + s) beside ce (nullptr = lossless), sigma as given
+    void *ca = nullptr, *cb = nullptr;
+    std::vector<double> sigma_host;
+    double eps_u = 0, mu_u = 0;           // uniform materials as given (a conductivity materialises them)
     void *dsg = nullptr;                  // device scratch of the design-loop entry points
     size_t dsg_cap = 0;
 
@@ -212,8 +219,13 @@ int zero_fields(fdtd2d_batch *b)
 }
 
 // ---- the capacity rule of the resident path ------------------------------------------------------------
-// Mur / none: Ez, Hx, Hy (+ ce, ch); PML: Ez, Hx, Hy, Ezx (+ ce, ch) and the 4R + 4C factors
-int lds_arrays(const fdtd2d_batch *b) { return (b->have_mat && b->uniform) ? (b->ezx ? 4 : 3) : (b->ezx ? 6 : 5); }
+// Mur / none: Ez, Hx, Hy (+ ce, ch); PML: Ez, Hx, Hy, Ezx (+ ce, ch) and the 4R + 4C factors; with a conductivity
+// cb stands in ce's place and ca is one more array
+int lds_arrays(const fdtd2d_batch *b)
+{
+    if (b->ca) return b->ezx ? 7 : 6;
+    return (b->have_mat && b->uniform) ? (b->ezx ? 4 : 3) : (b->ezx ? 6 : 5);
+}
 
 // bytes of the PML factors in LDS (0 without a layer)
 size_t lds_factor_bytes(const fdtd2d_batch *b)
@@ -515,9 +527,78 @@ int run_monitored(fdtd2d_batch *b, int nsteps, const double *amps, long long amp
     return 0;
 }
 
+// ---- lossy runs (fdtd2d_batch_lossy.h): the point-source paths with the kernels of batch_lossy.hip -----------------
+// v.ce carries cb; without point sources the table is empty and the kernels' point-source code stays silent
+template <class T>
+int run_lossy(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts)
+{
+    const fdtd::BatchLossyKernels &K = fdtd::batch_lossy_kernels<T>();
+    const fdtd::BatchMonKernels &H = fdtd::batch_pts_kernels<T>();   // the streamed H launches: H sees no conductivity
+    const bool pml = b->ezx != nullptr;
+    fdtd::BatchPml<T> p = pml_view<T>(b);
+    fdtd::BatchMon m = mon_view(b);
+    fdtd::BatchPts silent{};
+    if (!pts) pts = &silent;
+    const T *ca = (const T *)b->ca;
+    if (use_resident(b)) {
+        const int cells = b->rows * b->cols, threads = resident_threads(cells);
+        const int per_thread = (cells + threads - 1) / threads;
+        const int mi = per_thread <= 4 ? 0 : per_thread <= 8 ? 1 : per_thread <= 16 ? 2 : -1;
+        if (mi < 0) return bfail(b, FDTD2D_E_STATE, "%d cells per thread exceed the resident kernel's 16", per_thread);
+        const void *kern = pml ? K.resident_pml[mi] : K.resident[mi];
+        const size_t lds = lds_bytes(b);
+        BCHK(b, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        int per_cu = 0, cus = 0;
+        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds));
+        BCHK(b, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
+        if (per_cu < 1) return bfail(b, FDTD2D_E_STATE, "lossy resident kernel does not fit a CU (%zu B of LDS)", lds);
+        const long long round = (long long)per_cu * cus;
+        const int blocks = (int)(b->count < round ? b->count : round);
+        const int chunk = b->steps_per_launch > 0 ? b->steps_per_launch : nsteps;
+        for (int n = 0; n < nsteps; n += chunk) {
+            int n0 = n, nt = nsteps - n < chunk ? nsteps - n : chunk;
+            long long step_base = b->step;
+            fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+            v.ce = (const T *)b->cb;
+            void *mur_args[] = {&v, &m, pts, &ca, &n0, &nt, &step_base};
+            void *pml_args[] = {&v, &p, &m, pts, &ca, &n0, &nt, &step_base};
+            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads), pml ? pml_args : mur_args, lds);
+            if (rc) return rc;
+            b->launches++;
+            b->step += nt;
+        }
+        return 0;
+    }
+    const int cells = b->rows * b->cols;
+    const dim3 grid((cells + 255) / 256, b->count < 65535 ? b->count : 65535);
+    for (int n = 0; n < nsteps; ++n) {
+        fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+        v.ce = (const T *)b->cb;
+        long long step = b->step + 1;
+        T *ez_new = (T *)b->ez[b->cur ^ 1];
+        int rc;
+        if (pml) {
+            void *h_args[] = {&v, &p, &m, pts, &n, &step};
+            void *e_args[] = {&v, &p, &m, pts, &ca, &n, &step};
+            if ((rc = launch_ptr(b, H.h_pml[1], grid, dim3(256), h_args, 0))) return rc;
+            if ((rc = launch_ptr(b, K.e_pml, grid, dim3(256), e_args, 0))) return rc;
+        } else {
+            void *h_args[] = {&v, &m, pts, &n, &step};
+            void *e_args[] = {&v, &m, pts, &ca, &ez_new, &n, &step};
+            if ((rc = launch_ptr(b, H.h[1], grid, dim3(256), h_args, 0))) return rc;
+            if ((rc = launch_ptr(b, K.e, grid, dim3(256), e_args, 0))) return rc;
+            b->cur ^= 1;
+        }
+        b->launches += 2;
+        b->step++;
+    }
+    return 0;
+}
+
 template <class T>
 int run_impl(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts = nullptr)
 {
+    if (b->ca) return run_lossy<T>(b, nsteps, amps, amp_stride, pts);
     if (b->win_nf || b->nprobe || pts) return run_monitored<T>(b, nsteps, amps, amp_stride, pts);
     const bool arr = !b->uniform;
     if (b->ezx) {
@@ -581,6 +662,109 @@ int scratch(fdtd2d_batch *b, size_t bytes)
         b->dsg_cap = bytes;
     }
     return 0;
+}
+
+// ---- fdtd2d_batch_lossy.h --------------------------------------------------------------------------------------
+// cells nearer than this to an edge take no plain update (or, like [0, 0], set the Mur factor and the PML grading)
+int sigma_margin(const fdtd2d_batch *b, int layer) { return b->boundary == FDTD2D_BOUNDARY_MUR5 ? 6 : layer > 0 ? (layer > 6 ? layer : 6) : 1; }
+
+// the first cell of sigma_host that is non-zero within `margin` cells of an edge: member * cells + cell, or -1
+long long sigma_outside(const fdtd2d_batch *b, int margin)
+{
+    const size_t per = (size_t)b->rows * b->cols;
+    for (size_t t = 0; t < b->sigma_host.size(); ++t) {
+        const int i = (int)(t % per / b->cols), j = (int)(t % per % b->cols);
+        if (b->sigma_host[t] != 0 && (i < margin || i > b->rows - 1 - margin || j < margin || j > b->cols - 1 - margin))
+            return (long long)t;
+    }
+    return -1;
+}
+
+// ca and cb of a window from sigma_host and eps_host: one upload, one launch (k_batch_sigma_window)
+int lossy_reform(fdtd2d_batch *b, int r0, int c0, int nr, int nc)
+{
+    const size_t W = (size_t)nr * nc, n = (size_t)b->count * W, per = (size_t)b->rows * b->cols;
+    std::vector<double> w(2 * n);
+    for (int m = 0; m < b->count; ++m)
+        for (int i = 0; i < nr; ++i)
+            for (int j = 0; j < nc; ++j) {
+                const size_t src = m * per + (size_t)(r0 + i) * b->cols + (c0 + j), dst = m * W + (size_t)i * nc + j;
+                w[dst] = b->sigma_host[src];
+                w[n + dst] = b->eps_host[src];
+            }
+    int rc = scratch(b, w.size() * sizeof(double));      // waits for launches that still read the coefficients
+    if (rc) return rc;
+    BCHK(b, hipMemcpyAsync(b->dsg, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    fdtd::batch_sigma_window_launch(b->ca, b->cb, b->ce, (const double *)b->dsg, b->dtype == FDTD2D_F64, b->count, r0, c0,
+                                    nr, nc, b->pitch, b->mstride, b->dt, b->stream);
+    BCHK(b, hipGetLastError());
+    b->launches++;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+// the coefficient arrays of a uniform batch (there is no uniform lossy kernel)
+int materialise_uniform(fdtd2d_batch *b)
+{
+    const std::vector<double> e((size_t)b->count * b->rows * b->cols, b->eps_u), u(e.size(), b->mu_u);
+    return fdtd2d_batch_set_materials(b, e.data(), u.data(), FDTD2D_F64);
+}
+
+// sets (or patches, window != nullptr) the conductivity after the checks that need no device
+int set_sigma(fdtd2d_batch *b, const int *window, const void *sigma, int dtype)
+{
+    if (!sigma) return bfail(b, FDTD2D_E_ARG, "sigma must not be NULL");
+    if (dtype != FDTD2D_F32 && dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad dtype");
+    if (!b->have_mat) return bfail(b, FDTD2D_E_STATE, "materials not set: call fdtd2d_batch_set_materials first");
+    const int r0 = window ? window[0] : 0, c0 = window ? window[1] : 0;
+    const int nr = window ? window[2] : b->rows, nc = window ? window[3] : b->cols;
+    if (nr < 1 || nc < 1 || r0 < 0 || c0 < 0 || (long long)r0 + nr > b->rows || (long long)c0 + nc > b->cols)
+        return bfail(b, FDTD2D_E_ARG, "window (%d,%d)+%dx%d is empty or outside the %dx%d grid", r0, c0, nr, nc, b->rows,
+                     b->cols);
+    const int mg = sigma_margin(b, b->ezx ? b->pml_L : 0);
+    const size_t W = (size_t)nr * nc, per = (size_t)b->rows * b->cols;
+    for (int m = 0; m < b->count; ++m)
+        for (size_t t = 0; t < W; ++t) {
+            const double s = get_elem(sigma, dtype, m * W + t);
+            const int i = r0 + (int)(t / nc), j = c0 + (int)(t % nc);
+            if (!(s >= 0) || !std::isfinite(s))
+                return bfail(b, FDTD2D_E_ARG, "member %d: sigma must be >= 0 and finite (cell (%d,%d))", m, i, j);
+            if (s != 0 && (i < mg || i > b->rows - 1 - mg || j < mg || j > b->cols - 1 - mg))
+                return bfail(b, FDTD2D_E_ARG, "member %d: sigma is non-zero at cell (%d,%d), within %d cells of an edge "
+                             "(%s): only cells that take the plain update may conduct", m, i, j, mg,
+                             b->ezx ? "the PML layer, the frame and cell [0, 0]"
+                                    : b->boundary == FDTD2D_BOUNDARY_MUR5 ? "the Mur frame and cell [0, 0]" : "the edge cells");
+        }
+    int rc = use_device(b);
+    if (rc) return rc;
+    if (b->uniform && (rc = materialise_uniform(b))) return rc;
+    const bool fresh = !b->ca;
+    if (fresh) {
+        if ((rc = alloc(b, &b->ca, b->field_bytes))) return rc;
+        if ((rc = alloc(b, &b->cb, b->field_bytes))) {
+            release(&b->ca);
+            return rc;
+        }
+        b->sigma_host.assign((size_t)b->count * per, 0.0);
+        hipError_t e = hipMemsetAsync(b->ca, 0, b->field_bytes, b->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(b->cb, 0, b->field_bytes, b->stream);
+        if (e != hipSuccess) {
+            release(&b->ca);
+            release(&b->cb);
+            b->sigma_host.clear();
+            return bfail(b, -(1000 + (int)e), "hipMemset of the lossy coefficients failed: %s", hipGetErrorString(e));
+        }
+    }
+    for (int m = 0; m < b->count; ++m)
+        for (size_t t = 0; t < W; ++t)
+            b->sigma_host[m * per + (size_t)(r0 + t / nc) * b->cols + (c0 + t % nc)] = get_elem(sigma, dtype, m * W + t);
+    rc = fresh ? lossy_reform(b, 0, 0, b->rows, b->cols) : lossy_reform(b, r0, c0, nr, nc);
+    if (rc && fresh) {
+        release(&b->ca);
+        release(&b->cb);
+        b->sigma_host.clear();
+    }
+    return rc;
 }
 
 }  // namespace
@@ -660,7 +844,7 @@ void fdtd2d_batch_destroy(fdtd2d_batch_t *b)
                      (void **)&b->amps, &b->ezx, &b->pml_row, &b->pml_col, (void **)&b->dft, (void **)&b->omega,
                      (void **)&b->win_acc, (void **)&b->win_omega, (void **)&b->win_ph, (void **)&b->probe_cells,
                      (void **)&b->probe_trace, (void **)&b->win_held, (void **)&b->pts_cells, (void **)&b->pts_own,
-                     (void **)&b->pts_w, (void **)&b->pts_tab, (void **)&b->chan, &b->dsg})
+                     (void **)&b->pts_w, (void **)&b->pts_tab, (void **)&b->chan, &b->dsg, &b->ca, &b->cb})
         release(p);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -693,6 +877,7 @@ long long fdtd2d_batch_info(const fdtd2d_batch_t *b, int what)
     }
     case FDTD2D_BATCH_INFO_POINT_SOURCES: return b->npts;
     case FDTD2D_BATCH_INFO_HELD_WINDOW: return b->win_held ? 1 : 0;
+    case FDTD2D_BATCH_INFO_LOSSY: return b->ca ? 1 : 0;
     default: return FDTD2D_E_ARG;
     }
 }
@@ -774,13 +959,16 @@ int fdtd2d_batch_set_materials(fdtd2d_batch_t *b, const void *eps, const void *m
     b->eps_out_min.clear();
     b->uniform = false;
     b->have_mat = true;
-    return 0;
+    return b->ca ? lossy_reform(b, 0, 0, b->rows, b->cols) : 0;
 }
 
 int fdtd2d_batch_set_materials_uniform(fdtd2d_batch_t *b, double eps, double mu)
 {
     if (!b) return FDTD2D_E_ARG;
     if (!(eps > 0) || !(mu > 0)) return bfail(b, FDTD2D_E_ARG, "eps and mu must be positive");
+    b->eps_u = eps;
+    b->mu_u = mu;
+    if (b->ca) return materialise_uniform(b);      // a lossy batch keeps coefficient arrays
     int rc = use_device(b);
     if (rc) return rc;
     BCHK(b, hipStreamSynchronize(b->stream));
@@ -826,6 +1014,13 @@ int fdtd2d_batch_set_pml(fdtd2d_batch_t *b, const void *row_factors, const void 
     if (host_dtype != b->dtype) return bfail(b, FDTD2D_E_ARG, "PML factors must have the batch's dtype");
     if (layer_cells < 1 || 2 * layer_cells + 3 > (b->rows < b->cols ? b->rows : b->cols))
         return bfail(b, FDTD2D_E_ARG, "a %d-cell layer does not fit a %dx%d member", layer_cells, b->rows, b->cols);
+    if (b->ca) {
+        const int mg = sigma_margin(b, layer_cells);
+        const long long t = sigma_outside(b, mg);
+        if (t >= 0)
+            return bfail(b, FDTD2D_E_ARG, "member %d: sigma is non-zero within %d cells of an edge (the PML layer, the "
+                         "frame and cell [0, 0])", (int)(t / ((long long)b->rows * b->cols)), mg);
+    }
     const size_t rbytes = (size_t)b->count * 4 * b->rows * b->esz, cbytes = (size_t)b->count * 4 * b->cols * b->esz;
     BCHK(b, hipStreamSynchronize(b->stream));   // a running launch may still read the old factors
     if (!b->ezx) {
@@ -1390,7 +1585,32 @@ int fdtd2d_batch_set_eps_window(fdtd2d_batch_t *b, int row0, int col0, int nrows
         const double emin = wmin[m] < b->eps_out_min[m] ? wmin[m] : b->eps_out_min[m];
         b->courant[m] = courant_of(emin, b->mu_min[m], b->dt, b->dx);
     }
-    return 0;
+    return b->ca ? lossy_reform(b, row0, col0, nrows, ncols) : 0;
+}
+
+// ---- fdtd2d_batch_lossy.h --------------------------------------------------------------------------------------
+
+int fdtd2d_batch_set_conductivity(fdtd2d_batch_t *b, const void *sigma, int dtype)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!sigma) {                           // remove it: the other kernels again
+        if (!b->ca) return 0;
+        int rc = use_device(b);
+        if (rc) return rc;
+        BCHK(b, hipStreamSynchronize(b->stream));
+        release(&b->ca);
+        release(&b->cb);
+        b->sigma_host.clear();
+        return 0;
+    }
+    return set_sigma(b, nullptr, sigma, dtype);
+}
+
+int fdtd2d_batch_set_conductivity_window(fdtd2d_batch_t *b, const int window[4], const void *sigma, int dtype)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!window) return bfail(b, FDTD2D_E_ARG, "window must not be NULL");
+    return set_sigma(b, window, sigma, dtype);
 }
 
 int fdtd2d_batch_sync(fdtd2d_batch_t *b)

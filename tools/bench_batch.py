@@ -37,8 +37,15 @@ array eps with random binary permittivity, a ricker line source per member):
                               spectra_host_ms (read_probes + adjoint.probe_spectra, the helper's way); eps_window_ms
                               (set_eps_window of the design window) against set_materials_ms (the full arrays);
                               launches_per_session_iteration.
+  --lossy                     instead: the lossy step kernels (BatchEngine.set_conductivity, sigma random up to 20 S/m
+                              on the cells that may conduct) against the point-source kernels they were copied from, on
+                              the same members with the same one silent point source (weight 0, a zero channel), timed
+                              alternately: lossy_ms, pts_ms, lossy_over_pts, both paths and LDS sizes, and
+                              workgroups_per_cu of each from its LDS size (160 KiB per CU).  By this script's LDS count
+                              the lossy update adds one read per interior cell-step (lds_reads_per_cell_step).  One
+                              line for Mur and one for the PML.
 Usage: python tools/bench_batch.py [--count 1024 --rows 60 --cols 60 --steps 1000] [--reps 5] [--loop-members 16]
-                                   [--boundary {mur,pml} --pml-cells 10] [--monitors] [--adjoint]
+                                   [--boundary {mur,pml} --pml-cells 10] [--monitors] [--adjoint] [--lossy]
 """
 import argparse
 import json
@@ -203,6 +210,57 @@ def bench_monitors(count, rows, cols, steps, dtype, reps, boundary="mur", pml_ce
             "launches_per_run": launches}
 
 
+def bench_lossy(count, rows, cols, steps, dtype, reps, boundary, pml_cells):
+    eps, rects, amps = members(count, rows, cols, steps)
+    c00 = courant00(eps, dtype)
+    rng = np.random.default_rng(1)
+    g = max(6, pml_cells) if boundary == "pml" else 6
+    sigma = np.zeros((count, rows, cols))
+    sigma[:, g:rows - g, g:cols - g] = 20.0 * rng.random((count, rows - 2 * g, cols - 2 * g))
+    chan = np.zeros((1, steps))
+
+    def batch(lossy):
+        b = fd.BatchEngine(count, rows, cols, DT, DX, dtype=dtype, boundary=boundary)
+        b.set_materials(eps.astype(dtype), fd.MU0).set_sources(rects)
+        if boundary == "pml":
+            b.set_pml(pml_cells, courant00=c00)
+        b.set_point_sources([[rows // 2, cols // 2]], np.zeros((1, 1)))
+        if lossy:
+            b.set_conductivity(sigma)
+        b.run(steps, amps, chan).sync()                # warm-up: code objects, clocks
+        return b
+
+    def timed(b):
+        b.reset().sync()
+        t0 = time.perf_counter()
+        b.run(steps, amps, chan).sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    with batch(False) as pts, batch(True) as lossy:
+        assert lossy.lossy and not pts.lossy
+        l0 = lossy.launches
+        lossy.reset().run(steps, amps, chan).sync()
+        launches = lossy.launches - l0
+        pts_ms, lossy_ms = [], []
+        for _ in range(reps):
+            pts_ms.append(timed(pts))
+            lossy_ms.append(timed(lossy))
+        paths = ["resident" if b.resident else "streamed" for b in (pts, lossy)]
+        lds = [b.lds_bytes for b in (pts, lossy)]
+    med_p, med_l = float(np.median(pts_ms)), float(np.median(lossy_ms))
+    reads = 12 + (4 if boundary == "pml" else 0)
+    return {"count": count, "rows": rows, "cols": cols, "steps": steps, "dtype": np.dtype(dtype).name,
+            "materials": "arrays", "boundary": boundary, "pml_cells": pml_cells if boundary == "pml" else None,
+            "reps": reps, "pts_path": paths[0], "lossy_path": paths[1],
+            "pts_lds_bytes_per_member": lds[0], "lossy_lds_bytes_per_member": lds[1],
+            "pts_workgroups_per_cu": 163840 // lds[0], "lossy_workgroups_per_cu": 163840 // lds[1],
+            "lds_reads_per_cell_step": {"pts": reads, "lossy": reads + 1},
+            "pts_ms": round(med_p, 4), "pts_ms_min": round(min(pts_ms), 4),
+            "lossy_ms": round(med_l, 4), "lossy_ms_min": round(min(lossy_ms), 4),
+            "lossy_over_pts": round(med_l / med_p, 3), "launches_per_run": launches,
+            "lossy_mcell_steps_per_s": round(count * rows * cols * steps / (med_l * 1e-3) / 1e6, 1)}
+
+
 def bench_adjoint(count, rows, cols, steps, dtype, reps, pml_cells):
     from fdtd2d_amd.adjoint import channel_system, gradient_coefficients
     dt = 2e-13                                   # the Gaussian envelope of the channels (t0 = 4.5 / fc) ends by step 1200
@@ -352,7 +410,13 @@ def main():
     ap.add_argument("--pml-cells", type=int, default=10, help="layer depth with --boundary pml")
     ap.add_argument("--monitors", action="store_true", help="time the window DFT and probes (see above)")
     ap.add_argument("--adjoint", action="store_true", help="time batch_eps_gradient (see above)")
+    ap.add_argument("--lossy", action="store_true", help="time the lossy kernels against the point-source ones")
     a = ap.parse_args()
+    if a.lossy:
+        for boundary in ("mur", "pml"):
+            print(json.dumps(bench_lossy(a.count or 1024, a.rows or 60, a.cols or a.rows or 60, a.steps or 1000,
+                                         np.dtype(a.dtype), a.reps, boundary, a.pml_cells)), flush=True)
+        return
     if a.adjoint:
         if a.count or a.rows or a.cols or a.steps:
             configs = [(a.count or 1024, a.rows or 60, a.cols or a.rows or 60, a.steps or 1500, a.pml_cells)]
