@@ -46,6 +46,8 @@ BATCH_INFO_POINT_SOURCES, BATCH_INFO_HELD_WINDOW = 12, 13
 BATCH_MAX_POINT_SOURCES, BATCH_MAX_CHANNELS = 64, 32
 # include/fdtd2d_batch_lossy.h
 BATCH_INFO_LOSSY = 14
+# include/fdtd2d_batch_periodic.h
+BATCH_INFO_PERIODIC = 15
 
 _vp, _i, _d, _ll = C.c_void_p, C.c_int, C.c_double, C.c_longlong
 
@@ -161,6 +163,11 @@ BATCH_LOSSY_SIGNATURES = {
     "fdtd2d_batch_set_conductivity_window": (_i, [_vp, C.POINTER(_i), _vp, _i]),
 }
 
+# every symbol include/fdtd2d_batch_periodic.h declares (periodic columns of a batch)
+BATCH_PERIODIC_SIGNATURES = {
+    "fdtd2d_batch_set_periodic": (_i, [_vp, _i]),
+}
+
 # transport callback of fdtd2d_slab_attach
 EXCHANGE_FN = C.CFUNCTYPE(_i, _vp, _vp, _vp, _vp, _vp, _ll, _vp)
 
@@ -210,7 +217,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in {**SIGNATURES, **BATCH_PML_SIGNATURES, **BATCH_MONITOR_SIGNATURES,
                                    **BATCH_ADJOINT_SIGNATURES, **BATCH_DESIGN_SIGNATURES,
-                                   **BATCH_LOSSY_SIGNATURES}.items():
+                                   **BATCH_LOSSY_SIGNATURES, **BATCH_PERIODIC_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

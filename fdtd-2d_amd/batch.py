@@ -11,6 +11,9 @@ held window (``hold_dft_window``, ``dft_window_product``) are what an adjoint ru
 ``probe_spectra``, ``field_absmax`` and ``set_eps_window`` keep a design loop's traffic on the device
 (``AdjointSession``).  ``set_conductivity`` gives every member an electric conductivity per cell (lossy dielectrics,
 absorbers, resistive sheets); the batch then runs on the lossy step kernels.
+``boundary="periodic"`` makes every member one period of a structure that repeats along its columns (gratings,
+metasurface unit cells, photonic-crystal slabs): column C-1 is the image of column 0, rows end in the PML of ``set_pml``
+or in PEC (fdtd2d_batch_periodic.h).
 """
 from __future__ import annotations
 
@@ -51,8 +54,11 @@ def _probe_cells(cells, count):
     return np.ascontiguousarray(c, dtype=np.int32)
 
 
-def pml_fits(rows, cols, L):
-    """Whether an L-cell layer fits a rows x cols member (the rule of fdtd2d_set_pml / fdtd2d_batch_set_pml)."""
+def pml_fits(rows, cols, L, periodic=False):
+    """Whether an L-cell layer fits a rows x cols member (the rule of fdtd2d_set_pml / fdtd2d_batch_set_pml).
+    periodic: the layer of a batch with periodic columns, which lies on rows alone."""
+    if periodic:
+        return L >= 1 and 2 * L + 3 <= rows and cols >= 3
     return L >= 1 and 2 * L + 3 <= min(rows, cols)
 
 
@@ -80,7 +86,10 @@ class BatchEngine:
     Host arrays are member-major: Ez (B, R, C), Hx (B, R, C-1), Hy (B, R-1, C), eps / mu (B, R, C).
     boundary: "mur" (reference, main.py:29-61), "none", or "pml": the split-field layer of Engine(boundary="pml")
     on every member, set with set_pml() before the first run (the handle is a NONE batch: the layer's outer
-    edge is PEC).
+    edge is PEC).  "periodic": the columns wrap around with the period C - 1 (column C-1 is the image of column 0 and
+    is output only: no source there, materials there are never read, upload() overwrites it with column 0); set_pml()
+    lays the layer on the top and bottom rows alone, clear_pml() leaves PEC there.  There is no Bloch phase and there
+    are no periodic rows.
     """
 
     def __init__(self, count, rows, cols, dt=5e-14, dx=1e-4, dtype=np.float32, boundary="mur", device=0):
@@ -90,7 +99,7 @@ class BatchEngine:
         self.dt, self.dx = float(dt), float(dx)
         self.dtype = np.dtype(dtype)
         self.boundary = boundary
-        if boundary not in _BOUNDARY:
+        if boundary not in _BOUNDARY and boundary != "periodic":
             raise ValueError(f"unknown boundary {boundary!r}")
         self._pml_on = False          # a layer is set
         self._pml_chosen = False      # set_pml (or clear_pml) has been called: a "pml" batch may run
@@ -98,13 +107,20 @@ class BatchEngine:
         self._win = None              # (F, nrows, ncols) of the window DFT
         self._nprobe = 0
         self._npoint = (0, 0)         # (P, K) of the point sources
-        code = _abi.BOUNDARY_NONE if boundary == "pml" else _BOUNDARY[boundary]
+        code = _abi.BOUNDARY_NONE if boundary in ("pml", "periodic") else _BOUNDARY[boundary]
         rc = self._lib.fdtd2d_batch_create(C.byref(self._h), self.count, self.rows, self.cols, self.dt, self.dx,
                                            _code(dtype), code, int(device))
         if rc != 0:
             msg = self._lib.fdtd2d_batch_last_error(None).decode()
             self._h = C.c_void_p()
             raise _abi.Fdtd2dError(rc, msg)
+        if boundary == "periodic":
+            try:
+                self._ck(self._lib.fdtd2d_batch_set_periodic(self._h, 1))
+            except BaseException:
+                self.close()
+                raise
+            self._pml_chosen = True   # without set_pml() the rows end in PEC
 
     # -- lifetime -------------------------------------------------------------------
     def close(self):
@@ -125,6 +141,11 @@ class BatchEngine:
 
     def info(self, what: int) -> int:
         return int(self._lib.fdtd2d_batch_info(self._h, what))
+
+    @property
+    def periodic(self) -> bool:
+        """Whether the columns are periodic (the batch runs on the periodic kernels)."""
+        return bool(self.info(_abi.BATCH_INFO_PERIODIC))
 
     @property
     def resident(self) -> bool:
@@ -190,16 +211,22 @@ class BatchEngine:
         """Give every member the split-field PML (Engine.set_pml per member).  courant00: the Courant number of
         each member's [0,0] material cell, scalar or (B,) (default: vacuum).  profiles: the eight factor arrays
         themselves (ahr bhr aer ber of length rows, ahc bhc aec bec of length cols), each (n,) for every member
-        or (B, n), instead of the graded ones.  Ezx starts at zero."""
-        if self.boundary != "pml":
-            raise _abi.Fdtd2dError(_abi.E_STATE, f'set_pml needs boundary="pml", not {self.boundary!r}')
-        if not pml_fits(self.rows, self.cols, int(L)):      # as the library refuses it, before grading anything
+        or (B, n), instead of the graded ones.  Ezx starts at zero.  boundary="periodic": the layer lies on the top and
+        bottom rows alone (2 L + 3 <= rows), the column factors are exactly 1 (the library refuses others)."""
+        periodic = self.boundary == "periodic"
+        if self.boundary != "pml" and not periodic:
+            raise _abi.Fdtd2dError(_abi.E_STATE, f'set_pml needs boundary="pml" or "periodic", not {self.boundary!r}')
+        if not pml_fits(self.rows, self.cols, int(L), periodic):    # as the library refuses it, before grading anything
             raise _abi.Fdtd2dError(_abi.E_ARG, f"a {int(L)}-cell layer does not fit a {self.rows}x{self.cols} member")
         if profiles is None:
             if courant00 is None:
                 from .api import EPS0, MU0
                 courant00 = (1 / np.sqrt(EPS0 * MU0) * self.dt) / self.dx
-            rowf, colf = batch_pml_profiles(self.count, self.rows, self.cols, courant00, L, m, R0, self.dtype)
+            # periodic: only the rows are graded (columns wide enough for any L give the same row factors)
+            rowf, colf = batch_pml_profiles(self.count, self.rows, 2 * int(L) + 3 if periodic else self.cols, courant00,
+                                            L, m, R0, self.dtype)
+            if periodic:
+                colf = np.ones((self.count, 4 * self.cols), self.dtype)
         else:
             def stack(keys, n):
                 out = []
@@ -218,9 +245,10 @@ class BatchEngine:
         return self
 
     def clear_pml(self):
-        """Remove the layer (and Ezx): the batch then runs as boundary="none"."""
-        if self.boundary != "pml":
-            raise _abi.Fdtd2dError(_abi.E_STATE, f'clear_pml needs boundary="pml", not {self.boundary!r}')
+        """Remove the layer (and Ezx): the batch then runs as boundary="none"; a periodic batch keeps its periodic
+        columns and ends in PEC at the top and bottom rows."""
+        if self.boundary not in ("pml", "periodic"):
+            raise _abi.Fdtd2dError(_abi.E_STATE, f'clear_pml needs boundary="pml" or "periodic", not {self.boundary!r}')
         self._ck(self._lib.fdtd2d_batch_set_pml(self._h, None, None, _code(self.dtype), 0))
         self._pml_on, self._pml_chosen, self._pml_L = False, True, 0
         return self
@@ -500,9 +528,12 @@ class BatchEngine:
     @property
     def conductivity_margin(self) -> int:
         """Cells next to every edge that may not conduct with the current boundary: the 5-cell Mur frame and cell
-        [0, 0] (6), the PML layer (its depth, at least 6), or the edge cells of a closed box (1)."""
+        [0, 0] (6), the PML layer (its depth, at least 6), or the edge cells of a closed box (1).  With periodic columns
+        it counts rows alone (the layer's depth, at least 6): every column of the period may conduct."""
         if self.boundary == "mur":
             return 6
+        if self.boundary == "periodic":
+            return max(6, self._pml_L)
         return max(6, self._pml_L) if self._pml_on else 1
 
     def set_conductivity(self, sigma):
@@ -518,7 +549,10 @@ class BatchEngine:
         if np.isscalar(sigma):
             g = self.conductivity_margin
             s = np.zeros(shape, np.float64)
-            s[:, g:self.rows - g, g:self.cols - g] = float(sigma)
+            if self.boundary == "periodic":
+                s[:, g:self.rows - g, :] = float(sigma)
+            else:
+                s[:, g:self.rows - g, g:self.cols - g] = float(sigma)
             if not float(sigma) >= 0:             # negative or NaN: let the library name it even where s is empty
                 s[...] = float(sigma)
         else:
@@ -574,7 +608,8 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
     (BatchEngine.set_sources); fc: scalar or (B,); waveform "ricker", "sinusoidal" or None.  omega: None,
     or the angular frequency per member (scalar or (B,)) of a running DFT of Ez sampled every `dft_every`
     steps.  boundary "mur", "none" or "pml": a pml_cells-deep layer on every member, graded with the Courant number
-    of the member's own eps[0,0], mu[0,0] (as run_fdtd does).  dft_window = (row0, col0, nrows, ncols) with
+    of the member's own eps[0,0], mu[0,0] (as run_fdtd does); "periodic": periodic columns (period C - 1) with that
+    layer on the top and bottom rows (pml_cells 0 or None: PEC there).  dft_window = (row0, col0, nrows, ncols) with
     window_omegas (F,) or (B, F), F <= 16: a window DFT sampled every `dft_every` steps (set_dft_window).  probes:
     (P, 2) or (B, P, 2) cells, P <= 64, recorded at every step (set_probes).  Returns (Ez, Hx, Hy), plus the complex
     (B, R, C) DFT when omega is given, then the complex (B, F, nrows, ncols) window DFT when dft_window is given, then
@@ -594,17 +629,23 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
     assert np.all(courant <= 1.0), \
         f"Courant stability condition not met: members {np.nonzero(~(courant <= 1.0))[0].tolist()} > 1.0"
     fcs = np.broadcast_to(np.asarray(fc, dtype=np.float64), (B,))
+    layered = boundary == "pml" or (boundary == "periodic" and pml_cells)
+    if boundary == "periodic" and layered and not pml_fits(R, Cc, int(pml_cells), True):
+        raise ValueError(f"a {int(pml_cells)}-cell PML does not fit {R}x{Cc} periodic members (2L + 3 <= rows): the "
+                         f"largest that does is {(R - 3) // 2}")
     if boundary == "pml":
         L = int(pml_cells)
         if not pml_fits(R, Cc, L):
             raise ValueError(f"a {L}-cell PML does not fit {R}x{Cc} members (2L + 3 <= min(rows, cols)): the largest "
                              f"that does is {(min(R, Cc) - 3) // 2}")
+    if layered:
+        L = int(pml_cells)
         m00 = mu_arr[:, 0, 0] if mu_arr.ndim == 3 else np.full(B, float(mu_arr))
         courant00 = np.array([(1 / np.sqrt(float(e) * float(u)) * dt) / dx for e, u in zip(eps[:, 0, 0], m00)])
     win, wom, cells = _check_monitors(B, R, Cc, dft_window, window_omegas, probes, dft_every)
     with BatchEngine(B, R, Cc, dt, dx, dtype=dtype, boundary=boundary, device=device) as eng:
         eng.set_materials(eps, mu)
-        if boundary == "pml":
+        if layered:
             eng.set_pml(L, courant00=courant00)
         eng.set_sources(sources)
         if omega is not None:

@@ -10,11 +10,13 @@
 // (batch_adjoint.hip), which also holds the window product kernel.
 // The design-loop entry points (fdtd2d_batch_design.h) launch the post-run kernels of batch_design.hip.
 // With a conductivity set (fdtd2d_batch_lossy.h) every run takes the lossy kernels of batch_lossy.hip.
+// With periodic columns (fdtd2d_batch_periodic.h) every run takes the periodic kernels of batch_periodic.hip.
 #include "../../include/fdtd2d.h"
 #include "../../include/fdtd2d_batch_adjoint.h"
 #include "../../include/fdtd2d_batch_design.h"
 #include "../../include/fdtd2d_batch_lossy.h"
 #include "../../include/fdtd2d_batch_monitor.h"
+#include "../../include/fdtd2d_batch_periodic.h"
 #include "../../include/fdtd2d_batch_pml.h"
 
 #include <hip/hip_runtime.h>
@@ -33,6 +35,7 @@
 #include "kernels_batch_design.hpp"
 #include "kernels_batch_lossy.hpp"
 #include "kernels_batch_monitor.hpp"
+#include "kernels_batch_periodic.hpp"
 #include "kernels_batch_pml.hpp"
 
 struct fdtd2d_batch {
@@ -61,6 +64,10 @@ struct fdtd2d_batch {
     double eps_u = 0, mu_u = 0;           // uniform materials as given (a conductivity materialises them)
     void *dsg = nullptr;                  // device scratch of the design-loop entry points
     size_t dsg_cap = 0;
+    // fdtd2d_batch_set_periodic: column C-1 is the image of column 0.  The batch then always holds Ezx and the factors
+    // (all exactly 1 and pml_L = 0 without a layer) and ca / cb (sigma_implicit: made by the batch itself, all zero)
+    bool periodic = false, sigma_implicit = false;
+    std::vector<int> rect_host;           // the source rectangles as given (4 per member)
 
     int *rect = nullptr;                  // device copy of the source rectangles (4 per member)
     bool have_src = false;                // some member has a non-empty rectangle
@@ -90,6 +97,7 @@ struct fdtd2d_batch {
     double *win_held = nullptr;           // fdtd2d_batch_hold_dft_window: a copy of win_acc
     // point sources (fdtd2d_batch_set_point_sources), every table in the resident owners' order
     int npts = 0, pts_nchan = 0;
+    int npts_user = 0;                    // npts without the image entries of a periodic batch
     int *pts_cells = nullptr, *pts_own = nullptr;   // count x npts: row * C + col; owner thread * 16 + slot
     double *pts_w = nullptr;              // count x nchan x npts
     double *pts_tab = nullptr;            // streamed path: count x npts sums of a step
@@ -223,6 +231,7 @@ int zero_fields(fdtd2d_batch *b)
 // cb stands in ce's place and ca is one more array
 int lds_arrays(const fdtd2d_batch *b)
 {
+    if (b->periodic) return 7;
     if (b->ca) return b->ezx ? 7 : 6;
     return (b->have_mat && b->uniform) ? (b->ezx ? 4 : 3) : (b->ezx ? 6 : 5);
 }
@@ -230,7 +239,7 @@ int lds_arrays(const fdtd2d_batch *b)
 // bytes of the PML factors in LDS (0 without a layer)
 size_t lds_factor_bytes(const fdtd2d_batch *b)
 {
-    if (!b->ezx) return 0;
+    if (!b->ezx && !b->periodic) return 0;
     return b->dtype == FDTD2D_F32 ? fdtd::batch_pml_lds_elems<float>(0, b->rows, b->cols) * 4
                                   : fdtd::batch_pml_lds_elems<double>(0, b->rows, b->cols) * 8;
 }
@@ -595,9 +604,67 @@ int run_lossy(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_str
     return 0;
 }
 
+// ---- periodic runs (fdtd2d_batch_periodic.h): the lossy PML paths with the kernels of batch_periodic.hip ---------------
+// H needs no wrap of its own: Hy[i, C-2] reads the image column.
+template <class T>
+int run_periodic(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts)
+{
+    if (!b->ca || !b->ezx) return bfail(b, FDTD2D_E_STATE, "periodic batch without its coefficient arrays");
+    const fdtd::BatchPeriodicKernels &K = fdtd::batch_periodic_kernels<T>();
+    fdtd::BatchPml<T> p = pml_view<T>(b);
+    fdtd::BatchMon m = mon_view(b);
+    fdtd::BatchPts silent{};
+    if (!pts) pts = &silent;
+    const T *ca = (const T *)b->ca;
+    if (use_resident(b)) {
+        const int cells = b->rows * b->cols, threads = resident_threads(cells);
+        const int per_thread = (cells + threads - 1) / threads;
+        const int mi = per_thread <= 4 ? 0 : per_thread <= 8 ? 1 : per_thread <= 16 ? 2 : -1;
+        if (mi < 0) return bfail(b, FDTD2D_E_STATE, "%d cells per thread exceed the resident kernel's 16", per_thread);
+        const void *kern = K.resident[mi];
+        const size_t lds = lds_bytes(b);
+        BCHK(b, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        int per_cu = 0, cus = 0;
+        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds));
+        BCHK(b, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
+        if (per_cu < 1) return bfail(b, FDTD2D_E_STATE, "periodic resident kernel does not fit a CU (%zu B of LDS)", lds);
+        const long long round = (long long)per_cu * cus;
+        const int blocks = (int)(b->count < round ? b->count : round);
+        const int chunk = b->steps_per_launch > 0 ? b->steps_per_launch : nsteps;
+        for (int n = 0; n < nsteps; n += chunk) {
+            int n0 = n, nt = nsteps - n < chunk ? nsteps - n : chunk;
+            long long step_base = b->step;
+            fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+            v.ce = (const T *)b->cb;
+            void *args[] = {&v, &p, &m, pts, &ca, &n0, &nt, &step_base};
+            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads), args, lds);
+            if (rc) return rc;
+            b->launches++;
+            b->step += nt;
+        }
+        return 0;
+    }
+    const int cells = b->rows * b->cols;
+    const dim3 grid((cells + 255) / 256, b->count < 65535 ? b->count : 65535);
+    for (int n = 0; n < nsteps; ++n) {
+        fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+        v.ce = (const T *)b->cb;
+        long long step = b->step + 1;
+        int rc;
+        void *h_args[] = {&v, &p, &m, pts, &n, &step};
+        void *e_args[] = {&v, &p, &m, pts, &ca, &n, &step};
+        if ((rc = launch_ptr(b, K.h, grid, dim3(256), h_args, 0))) return rc;
+        if ((rc = launch_ptr(b, K.e, grid, dim3(256), e_args, 0))) return rc;
+        b->launches += 2;
+        b->step++;
+    }
+    return 0;
+}
+
 template <class T>
 int run_impl(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts = nullptr)
 {
+    if (b->periodic) return run_periodic<T>(b, nsteps, amps, amp_stride, pts);
     if (b->ca) return run_lossy<T>(b, nsteps, amps, amp_stride, pts);
     if (b->win_nf || b->nprobe || pts) return run_monitored<T>(b, nsteps, amps, amp_stride, pts);
     const bool arr = !b->uniform;
@@ -666,7 +733,19 @@ int scratch(fdtd2d_batch *b, size_t bytes)
 
 // ---- fdtd2d_batch_lossy.h --------------------------------------------------------------------------------------
 // cells nearer than this to an edge take no plain update (or, like [0, 0], set the Mur factor and the PML grading)
-int sigma_margin(const fdtd2d_batch *b, int layer) { return b->boundary == FDTD2D_BOUNDARY_MUR5 ? 6 : layer > 0 ? (layer > 6 ? layer : 6) : 1; }
+int sigma_margin(const fdtd2d_batch *b, int layer)
+{
+    if (b->periodic) return layer > 6 ? layer : 6;      // rows alone (sigma_barred)
+    return b->boundary == FDTD2D_BOUNDARY_MUR5 ? 6 : layer > 0 ? (layer > 6 ? layer : 6) : 1;
+}
+
+// whether cell (i, j) may not conduct with the margin mg; a periodic batch has no column margin (its image column is
+// never read)
+bool sigma_barred(const fdtd2d_batch *b, int i, int j, int mg)
+{
+    if (b->periodic) return j < b->cols - 1 && (i < mg || i > b->rows - 1 - mg);
+    return i < mg || i > b->rows - 1 - mg || j < mg || j > b->cols - 1 - mg;
+}
 
 // the first cell of sigma_host that is non-zero within `margin` cells of an edge: member * cells + cell, or -1
 long long sigma_outside(const fdtd2d_batch *b, int margin)
@@ -674,7 +753,7 @@ long long sigma_outside(const fdtd2d_batch *b, int margin)
     const size_t per = (size_t)b->rows * b->cols;
     for (size_t t = 0; t < b->sigma_host.size(); ++t) {
         const int i = (int)(t % per / b->cols), j = (int)(t % per % b->cols);
-        if (b->sigma_host[t] != 0 && (i < margin || i > b->rows - 1 - margin || j < margin || j > b->cols - 1 - margin))
+        if (b->sigma_host[t] != 0 && sigma_barred(b, i, j, margin))
             return (long long)t;
     }
     return -1;
@@ -729,10 +808,11 @@ int set_sigma(fdtd2d_batch *b, const int *window, const void *sigma, int dtype)
             const int i = r0 + (int)(t / nc), j = c0 + (int)(t % nc);
             if (!(s >= 0) || !std::isfinite(s))
                 return bfail(b, FDTD2D_E_ARG, "member %d: sigma must be >= 0 and finite (cell (%d,%d))", m, i, j);
-            if (s != 0 && (i < mg || i > b->rows - 1 - mg || j < mg || j > b->cols - 1 - mg))
+            if (s != 0 && sigma_barred(b, i, j, mg))
                 return bfail(b, FDTD2D_E_ARG, "member %d: sigma is non-zero at cell (%d,%d), within %d cells of an edge "
                              "(%s): only cells that take the plain update may conduct", m, i, j, mg,
-                             b->ezx ? "the PML layer, the frame and cell [0, 0]"
+                             b->periodic ? "the PML rows, the PEC rows and cell [0, 0] of a periodic batch"
+                             : b->ezx ? "the PML layer, the frame and cell [0, 0]"
                                     : b->boundary == FDTD2D_BOUNDARY_MUR5 ? "the Mur frame and cell [0, 0]" : "the edge cells");
         }
     int rc = use_device(b);
@@ -764,6 +844,63 @@ int set_sigma(fdtd2d_batch *b, const int *window, const void *sigma, int dtype)
         release(&b->cb);
         b->sigma_host.clear();
     }
+    return rc;
+}
+
+// ---- fdtd2d_batch_periodic.h -----------------------------------------------------------------------------------
+// column 0 of a field over its image column C-1, every row of every member (one strided device copy)
+int copy_image(fdtd2d_batch *b, void *field)
+{
+    BCHK(b, hipStreamSynchronize(b->stream));
+    BCHK(b, hipMemcpy2D((char *)field + (size_t)(b->cols - 1) * b->esz, (size_t)b->pitch * b->esz, field,
+                        (size_t)b->pitch * b->esz, b->esz, (size_t)b->count * b->rows, hipMemcpyDeviceToDevice));
+    return 0;
+}
+
+// no layer on a periodic batch: Ezx and the factor arrays stay (the periodic kernels always take them), every factor
+// exactly 1 and pml_L = 0, so that every row takes the plain update (PEC top and bottom)
+int unit_layer(fdtd2d_batch *b)
+{
+    const size_t rn = (size_t)b->count * 4 * b->rows, cn = (size_t)b->count * 4 * b->cols;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    int rc;
+    if (!b->ezx) {
+        for (void **p : {&b->ezx, &b->pml_row, &b->pml_col}) {
+            const size_t bytes = p == &b->ezx ? b->field_bytes : (p == &b->pml_row ? rn : cn) * b->esz;
+            if ((rc = alloc(b, p, bytes))) {
+                for (void **q : {&b->ezx, &b->pml_row, &b->pml_col}) release(q);
+                return rc;
+            }
+        }
+    }
+    std::vector<unsigned char> ones((rn > cn ? rn : cn) * b->esz);
+    for (size_t k = 0; k < (rn > cn ? rn : cn); ++k) {
+        if (b->dtype == FDTD2D_F32) ((float *)ones.data())[k] = 1.0f;
+        else ((double *)ones.data())[k] = 1.0;
+    }
+    BCHK(b, hipMemcpy(b->pml_row, ones.data(), rn * b->esz, hipMemcpyHostToDevice));
+    BCHK(b, hipMemcpy(b->pml_col, ones.data(), cn * b->esz, hipMemcpyHostToDevice));
+    BCHK(b, hipMemsetAsync(b->ezx, 0, b->field_bytes, b->stream));
+    BCHK(b, hipStreamSynchronize(b->stream));
+    b->pml_L = 0;
+    return 0;
+}
+
+// the first column factor of count x 4C that is not exactly 1: its index, or -1
+long long colf_not_one(const fdtd2d_batch *b, const void *col_factors)
+{
+    for (size_t k = 0; k < (size_t)b->count * 4 * b->cols; ++k)
+        if (get_elem(col_factors, b->dtype, k) != 1.0) return (long long)k;
+    return -1;
+}
+
+// ca and cb of a periodic batch that has materials and no conductivity: all-zero sigma (ca = 1, cb = ce)
+int periodic_coefficients(fdtd2d_batch *b)
+{
+    if (b->uniform) return materialise_uniform(b);      // fdtd2d_batch_set_materials comes back here
+    const std::vector<double> zero((size_t)b->count * b->rows * b->cols, 0.0);
+    int rc = set_sigma(b, nullptr, zero.data(), FDTD2D_F64);
+    if (!rc) b->sigma_implicit = true;
     return rc;
 }
 
@@ -875,9 +1012,10 @@ long long fdtd2d_batch_info(const fdtd2d_batch_t *b, int what)
         const long long n = b->step - b->probe_step0;
         return n < b->probe_cap ? n : b->probe_cap;
     }
-    case FDTD2D_BATCH_INFO_POINT_SOURCES: return b->npts;
+    case FDTD2D_BATCH_INFO_POINT_SOURCES: return b->npts_user;
     case FDTD2D_BATCH_INFO_HELD_WINDOW: return b->win_held ? 1 : 0;
-    case FDTD2D_BATCH_INFO_LOSSY: return b->ca ? 1 : 0;
+    case FDTD2D_BATCH_INFO_LOSSY: return b->ca && !b->sigma_implicit ? 1 : 0;
+    case FDTD2D_BATCH_INFO_PERIODIC: return b->periodic ? 1 : 0;
     default: return FDTD2D_E_ARG;
     }
 }
@@ -959,6 +1097,7 @@ int fdtd2d_batch_set_materials(fdtd2d_batch_t *b, const void *eps, const void *m
     b->eps_out_min.clear();
     b->uniform = false;
     b->have_mat = true;
+    if (b->periodic && !b->ca) return periodic_coefficients(b);
     return b->ca ? lossy_reform(b, 0, 0, b->rows, b->cols) : 0;
 }
 
@@ -993,7 +1132,7 @@ int fdtd2d_batch_set_materials_uniform(fdtd2d_batch_t *b, double eps, double mu)
     b->courant.assign((size_t)b->count, courant_of(eps, mu, b->dt, b->dx));
     b->uniform = true;
     b->have_mat = true;
-    return 0;
+    return b->periodic ? periodic_coefficients(b) : 0;       // a periodic batch keeps coefficient arrays
 }
 
 int fdtd2d_batch_set_pml(fdtd2d_batch_t *b, const void *row_factors, const void *col_factors, int host_dtype,
@@ -1004,6 +1143,7 @@ int fdtd2d_batch_set_pml(fdtd2d_batch_t *b, const void *row_factors, const void 
         return bfail(b, FDTD2D_E_STATE, "the PML needs a batch created with FDTD2D_BOUNDARY_NONE (its outer edge is PEC)");
     int rc = use_device(b);
     if (rc) return rc;
+    if (!row_factors && !col_factors && b->periodic) return unit_layer(b);   // PEC top and bottom
     if (!row_factors && !col_factors) {     // remove the layer: a plain NONE batch again
         BCHK(b, hipStreamSynchronize(b->stream));
         for (void **p : {&b->ezx, &b->pml_row, &b->pml_col}) release(p);
@@ -1012,8 +1152,14 @@ int fdtd2d_batch_set_pml(fdtd2d_batch_t *b, const void *row_factors, const void 
     }
     if (!row_factors || !col_factors) return bfail(b, FDTD2D_E_ARG, "factor arrays must both be given (or both NULL)");
     if (host_dtype != b->dtype) return bfail(b, FDTD2D_E_ARG, "PML factors must have the batch's dtype");
-    if (layer_cells < 1 || 2 * layer_cells + 3 > (b->rows < b->cols ? b->rows : b->cols))
+    if (layer_cells < 1 || 2 * layer_cells + 3 > (b->periodic || b->rows < b->cols ? b->rows : b->cols) || b->cols < 3)
         return bfail(b, FDTD2D_E_ARG, "a %d-cell layer does not fit a %dx%d member", layer_cells, b->rows, b->cols);
+    if (b->periodic) {
+        const long long k = colf_not_one(b, col_factors);
+        if (k >= 0)
+            return bfail(b, FDTD2D_E_ARG, "member %d: column factor %d is not exactly 1: a periodic batch has its layer on "
+                         "rows alone", (int)(k / (4 * b->cols)), (int)(k % (4 * b->cols)));
+    }
     if (b->ca) {
         const int mg = sigma_margin(b, layer_cells);
         const long long t = sigma_outside(b, mg);
@@ -1047,8 +1193,9 @@ int fdtd2d_batch_transfer_ezx(fdtd2d_batch_t *b, void *host, int host_dtype, int
     if (host_dtype != FDTD2D_F32 && host_dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad host_dtype");
     int rc = use_device(b);
     if (rc) return rc;
-    return to_device ? copy_in(b, b->ezx, host, host_dtype, b->rows, b->cols)
-                     : copy_out(b, b->ezx, host, host_dtype, b->rows, b->cols);
+    if (!to_device) return copy_out(b, b->ezx, host, host_dtype, b->rows, b->cols);
+    if ((rc = copy_in(b, b->ezx, host, host_dtype, b->rows, b->cols))) return rc;
+    return b->periodic ? copy_image(b, b->ezx) : 0;
 }
 
 int fdtd2d_batch_courant(const fdtd2d_batch_t *b, double *out)
@@ -1066,6 +1213,7 @@ int fdtd2d_batch_upload(fdtd2d_batch_t *b, const void *Ez, const void *Hx, const
     int rc = use_device(b);
     if (rc) return rc;
     if (Ez && (rc = copy_in(b, b->ez[b->cur], Ez, host_dtype, b->rows, b->cols))) return rc;
+    if (Ez && b->periodic && (rc = copy_image(b, b->ez[b->cur]))) return rc;
     if (Hx && (rc = copy_in(b, b->hx, Hx, host_dtype, b->rows, b->cols - 1))) return rc;
     if (Hy && (rc = copy_in(b, b->hy, Hy, host_dtype, b->rows - 1, b->cols))) return rc;
     return 0;
@@ -1111,6 +1259,9 @@ int fdtd2d_batch_set_sources(fdtd2d_batch_t *b, const int *rect)
         if (r < 0 || c < 0 || r + nr > b->rows || c + nc > b->cols)
             return bfail(b, FDTD2D_E_ARG, "member %d: source (%d,%d)+%dx%d outside the %dx%d grid", m, r, c, nr, nc,
                          b->rows, b->cols);
+        if (b->periodic && c + nc > b->cols - 1)
+            return bfail(b, FDTD2D_E_ARG, "member %d: source (%d,%d)+%dx%d reaches column %d, the image of column 0 of a "
+                         "periodic batch", m, r, c, nr, nc, b->cols - 1);
         any = true;
     }
     int rc = use_device(b);
@@ -1118,6 +1269,7 @@ int fdtd2d_batch_set_sources(fdtd2d_batch_t *b, const int *rect)
     BCHK(b, hipStreamSynchronize(b->stream));   // a running launch may still read the old rectangles
     BCHK(b, hipMemcpy(b->rect, rect, (size_t)b->count * 4 * sizeof(int), hipMemcpyHostToDevice));
     b->have_src = any;
+    b->rect_host.assign(rect, rect + (size_t)b->count * 4);
     return 0;
 }
 
@@ -1317,40 +1469,69 @@ int fdtd2d_batch_set_point_sources(fdtd2d_batch_t *b, int ncell, const int *cell
         return bfail(b, FDTD2D_E_ARG, "ncell %d outside 0..%d", ncell, FDTD2D_BATCH_MAX_POINT_SOURCES);
     std::vector<int> lin, own;
     std::vector<double> w;
+    int ntab = ncell;                       // entries per member: a periodic batch lists column-0 cells at their images too
     if (ncell > 0) {
         if (nchan < 1 || nchan > FDTD2D_BATCH_MAX_CHANNELS)
             return bfail(b, FDTD2D_E_ARG, "nchan %d outside 1..%d", nchan, FDTD2D_BATCH_MAX_CHANNELS);
         if (!cells || !weights) return bfail(b, FDTD2D_E_ARG, "cells and weights must not be NULL");
-        // every table in the order of the resident cell walk's owners: thread l % nthr, slot l / nthr
-        const int nthr = resident_threads(b->rows * b->cols);
-        lin.resize((size_t)b->count * ncell);
-        own.resize(lin.size());
-        w.resize(lin.size() * nchan);
-        std::vector<int> cell((size_t)ncell), order((size_t)ncell);
         for (int m = 0; m < b->count; ++m) {
+            int images = 0;
             for (int p = 0; p < ncell; ++p) {
                 const int r = cells[2 * ((size_t)m * ncell + p)], c = cells[2 * ((size_t)m * ncell + p) + 1];
                 if (r < 0 || r >= b->rows || c < 0 || c >= b->cols)
                     return bfail(b, FDTD2D_E_ARG, "member %d point source %d: cell (%d,%d) outside the %dx%d grid", m, p,
                                  r, c, b->rows, b->cols);
+                if (b->periodic && c == b->cols - 1)
+                    return bfail(b, FDTD2D_E_ARG, "member %d point source %d: cell (%d,%d) is in column %d, the image of "
+                                 "column 0 of a periodic batch", m, p, r, c, b->cols - 1);
+                images += b->periodic && c == 0;
+            }
+            if (ncell + images > FDTD2D_BATCH_MAX_POINT_SOURCES)
+                return bfail(b, FDTD2D_E_ARG, "member %d: %d point sources and the %d images of those in column 0 exceed %d",
+                             m, ncell, images, FDTD2D_BATCH_MAX_POINT_SOURCES);
+            ntab = ncell + images > ntab ? ncell + images : ntab;
+        }
+        // every table in the order of the resident cell walk's owners: thread l % nthr, slot l / nthr.  Entries past a
+        // member's own (fewer images than another member's) are silent: cell -1, no owner thread, zero weights.
+        const int nthr = resident_threads(b->rows * b->cols);
+        lin.resize((size_t)b->count * ntab);
+        own.resize(lin.size());
+        w.assign(lin.size() * nchan, 0.0);
+        std::vector<int> cell((size_t)ntab), from((size_t)ntab), order((size_t)ntab);
+        for (int m = 0; m < b->count; ++m) {
+            int n = ncell;
+            for (int p = 0; p < ncell; ++p) {
+                const int r = cells[2 * ((size_t)m * ncell + p)], c = cells[2 * ((size_t)m * ncell + p) + 1];
                 cell[p] = r * b->cols + c;
+                from[p] = p;
                 for (int q = 0; q < nchan; ++q)
                     if (!std::isfinite(weights[((size_t)m * ncell + p) * nchan + q]))
                         return bfail(b, FDTD2D_E_ARG, "member %d point source %d: weight %d is not finite", m, p, q);
+                if (b->periodic && c == 0) {
+                    cell[n] = r * b->cols + b->cols - 1;
+                    from[n++] = p;
+                }
             }
+            for (; n < ntab; ++n) cell[n] = from[n] = -1;
             std::iota(order.begin(), order.end(), 0);
-            auto key = [&](int p) { return (long long)(cell[p] % nthr) * 16 + cell[p] / nthr; };
+            auto key = [&](int p) {
+                return cell[p] < 0 ? (1LL << 40) + p : (long long)(cell[p] % nthr) * 16 + cell[p] / nthr;
+            };
             std::sort(order.begin(), order.end(), [&](int x, int y) { return key(x) < key(y); });
-            for (int k = 0; k < ncell; ++k) {
+            for (int k = 0; k < ntab; ++k) {
                 const int p = order[k];
+                lin[(size_t)m * ntab + k] = cell[p];
+                if (cell[p] < 0) {
+                    own[(size_t)m * ntab + k] = 4096 * 16;       // past every thread of a workgroup
+                    continue;
+                }
                 if (k && cell[order[k - 1]] == cell[p])
                     return bfail(b, FDTD2D_E_ARG, "member %d: cell (%d,%d) is listed twice", m, cell[p] / b->cols,
                                  cell[p] % b->cols);
-                lin[(size_t)m * ncell + k] = cell[p];
                 // slots past 15 belong to members that never run resident (16 cells per thread at most)
-                own[(size_t)m * ncell + k] = (cell[p] % nthr) * 16 + (cell[p] / nthr < 16 ? cell[p] / nthr : 15);
+                own[(size_t)m * ntab + k] = (cell[p] % nthr) * 16 + (cell[p] / nthr < 16 ? cell[p] / nthr : 15);
                 for (int q = 0; q < nchan; ++q)
-                    w[((size_t)m * nchan + q) * ncell + k] = weights[((size_t)m * ncell + p) * nchan + q];
+                    w[((size_t)m * nchan + q) * ntab + k] = weights[((size_t)m * ncell + from[p]) * nchan + q];
             }
         }
     }
@@ -1359,7 +1540,7 @@ int fdtd2d_batch_set_point_sources(fdtd2d_batch_t *b, int ncell, const int *cell
     BCHK(b, hipStreamSynchronize(b->stream));   // a running launch may still read the old tables
     void **bufs[] = {(void **)&b->pts_cells, (void **)&b->pts_own, (void **)&b->pts_w, (void **)&b->pts_tab};
     for (void **p : bufs) release(p);
-    b->npts = b->pts_nchan = 0;
+    b->npts = b->npts_user = b->pts_nchan = 0;
     if (ncell == 0) return 0;
     if ((rc = alloc(b, (void **)&b->pts_cells, lin.size() * sizeof(int))) ||
         (rc = alloc(b, (void **)&b->pts_own, own.size() * sizeof(int))) ||
@@ -1372,7 +1553,8 @@ int fdtd2d_batch_set_point_sources(fdtd2d_batch_t *b, int ncell, const int *cell
     BCHK(b, hipMemcpy(b->pts_own, own.data(), own.size() * sizeof(int), hipMemcpyHostToDevice));
     BCHK(b, hipMemcpy(b->pts_w, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
     BCHK(b, hipMemset(b->pts_tab, 0, lin.size() * sizeof(double)));
-    b->npts = ncell;
+    b->npts = ntab;
+    b->npts_user = ncell;
     b->pts_nchan = nchan;
     return 0;
 }
@@ -1597,20 +1779,91 @@ int fdtd2d_batch_set_conductivity(fdtd2d_batch_t *b, const void *sigma, int dtyp
         if (!b->ca) return 0;
         int rc = use_device(b);
         if (rc) return rc;
+        if (b->periodic) {                  // a periodic batch keeps its arrays, with ca = 1 and cb = ce
+            std::fill(b->sigma_host.begin(), b->sigma_host.end(), 0.0);
+            b->sigma_implicit = true;
+            return lossy_reform(b, 0, 0, b->rows, b->cols);
+        }
         BCHK(b, hipStreamSynchronize(b->stream));
         release(&b->ca);
         release(&b->cb);
         b->sigma_host.clear();
         return 0;
     }
-    return set_sigma(b, nullptr, sigma, dtype);
+    int rc = set_sigma(b, nullptr, sigma, dtype);
+    if (!rc) b->sigma_implicit = false;
+    return rc;
 }
 
 int fdtd2d_batch_set_conductivity_window(fdtd2d_batch_t *b, const int window[4], const void *sigma, int dtype)
 {
     if (!b) return FDTD2D_E_ARG;
     if (!window) return bfail(b, FDTD2D_E_ARG, "window must not be NULL");
-    return set_sigma(b, window, sigma, dtype);
+    int rc = set_sigma(b, window, sigma, dtype);
+    if (!rc) b->sigma_implicit = false;
+    return rc;
+}
+
+// ---- fdtd2d_batch_periodic.h -----------------------------------------------------------------------------------
+
+int fdtd2d_batch_set_periodic(fdtd2d_batch_t *b, int on)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (b->boundary != FDTD2D_BOUNDARY_NONE)
+        return bfail(b, FDTD2D_E_STATE, "periodic columns need a batch created with FDTD2D_BOUNDARY_NONE: the Mur frame "
+                     "and a periodic boundary exclude each other");
+    if ((on != 0) == b->periodic) return 0;
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    if (!on) {
+        if ((rc = fdtd2d_batch_set_point_sources(b, 0, nullptr, 0, nullptr))) return rc;
+        b->periodic = false;
+        if (b->sigma_implicit) {
+            release(&b->ca);
+            release(&b->cb);
+            b->sigma_host.clear();
+            b->sigma_implicit = false;
+        }
+        if (b->pml_L == 0) {
+            for (void **p : {&b->ezx, &b->pml_row, &b->pml_col}) release(p);
+        }
+        return 0;
+    }
+    // the refusals, before anything changes
+    for (int m = 0; m < b->count && !b->rect_host.empty(); ++m) {
+        const int *r = b->rect_host.data() + 4 * m;
+        if (r[2] > 0 && r[1] + r[3] > b->cols - 1)
+            return bfail(b, FDTD2D_E_ARG, "member %d: source (%d,%d)+%dx%d reaches column %d, the image of column 0 of a "
+                         "periodic batch", m, r[0], r[1], r[2], r[3], b->cols - 1);
+    }
+    if (b->ezx) {
+        std::vector<unsigned char> colf((size_t)b->count * 4 * b->cols * b->esz);
+        BCHK(b, hipMemcpy(colf.data(), b->pml_col, colf.size(), hipMemcpyDeviceToHost));
+        const long long k = colf_not_one(b, colf.data());
+        if (k >= 0)
+            return bfail(b, FDTD2D_E_ARG, "member %d: column factor %d of the layer is not exactly 1: a periodic batch has "
+                         "its layer on rows alone", (int)(k / (4 * b->cols)), (int)(k % (4 * b->cols)));
+    }
+    b->periodic = true;
+    if (b->ca) {
+        const int mg = sigma_margin(b, b->ezx ? b->pml_L : 0);
+        const long long t = sigma_outside(b, mg);
+        if (t >= 0) {
+            b->periodic = false;
+            return bfail(b, FDTD2D_E_ARG, "member %d: sigma is non-zero within %d rows of the top or bottom edge",
+                         (int)(t / ((long long)b->rows * b->cols)), mg);
+        }
+    }
+    auto undo = [&](int code) {
+        b->periodic = false;
+        return code;
+    };
+    if ((rc = fdtd2d_batch_set_point_sources(b, 0, nullptr, 0, nullptr))) return undo(rc);
+    if (!b->ezx && (rc = unit_layer(b))) return undo(rc);
+    if ((rc = copy_image(b, b->ez[b->cur])) || (rc = copy_image(b, b->ezx))) return undo(rc);
+    if (b->have_mat && !b->ca && (rc = periodic_coefficients(b))) return undo(rc);
+    return 0;
 }
 
 int fdtd2d_batch_sync(fdtd2d_batch_t *b)

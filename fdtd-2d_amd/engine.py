@@ -52,6 +52,9 @@ class Engine:
         self.rows, self.cols, self.dt, self.dx = int(rows), int(cols), float(dt), float(dx)
         self.dtype = np.dtype(dtype)
         self.boundary = boundary
+        if boundary == "periodic":
+            raise ValueError('boundary="periodic" exists for BatchEngine alone: the single-grid Engine has no periodic '
+                             'columns')
         code, bcode = _code(dtype), _BOUNDARY[boundary]
         if slab is None:
             self.row0, self.nrows, self.halo = 0, self.rows, 0

@@ -44,8 +44,15 @@ array eps with random binary permittivity, a ricker line source per member):
                               workgroups_per_cu of each from its LDS size (160 KiB per CU).  By this script's LDS count
                               the lossy update adds one read per interior cell-step (lds_reads_per_cell_step).  One
                               line for Mur and one for the PML.
+  --periodic                  instead: the periodic step kernels (boundary="periodic", a layer on the rows) against the
+                              lossy PML kernels they were copied from (boundary="pml", profiles= with the same row
+                              factors and unit column factors), on the same members with the same conductivity and the
+                              same one silent point source, timed alternately in one process: periodic_ms,
+                              lossy_pml_ms, periodic_over_lossy_pml, both paths and LDS sizes.  Default: 1024 members
+                              of 60 rows x 61 columns, a 10-cell layer, 1000 steps.
 Usage: python tools/bench_batch.py [--count 1024 --rows 60 --cols 60 --steps 1000] [--reps 5] [--loop-members 16]
                                    [--boundary {mur,pml} --pml-cells 10] [--monitors] [--adjoint] [--lossy]
+                                   [--periodic]
 """
 import argparse
 import json
@@ -261,6 +268,56 @@ def bench_lossy(count, rows, cols, steps, dtype, reps, boundary, pml_cells):
             "lossy_mcell_steps_per_s": round(count * rows * cols * steps / (med_l * 1e-3) / 1e6, 1)}
 
 
+def bench_periodic(count, rows, cols, steps, dtype, reps, pml_cells):
+    eps, rects, amps = members(count, rows, cols, steps)
+    c00 = courant00(eps, dtype)
+    rng = np.random.default_rng(1)
+    g = max(6, pml_cells)
+    sigma = np.zeros((count, rows, cols))           # inside the PML batch's column margin too: the same for both
+    sigma[:, g:rows - g, g:cols - g] = 20.0 * rng.random((count, rows - 2 * g, cols - 2 * g))
+    chan = np.zeros((1, steps))
+    rowf, _ = fd.batch.batch_pml_profiles(count, rows, 2 * pml_cells + 3, c00, pml_cells, dtype=dtype)
+    prof = {k: rowf[:, i * rows:(i + 1) * rows] for i, k in enumerate(("ahr", "bhr", "aer", "ber"))}
+    prof.update({k: np.ones(cols, dtype) for k in ("ahc", "bhc", "aec", "bec")})
+
+    def batch(boundary):
+        b = fd.BatchEngine(count, rows, cols, DT, DX, dtype=dtype, boundary=boundary)
+        b.set_materials(eps.astype(dtype), fd.MU0).set_sources(rects)
+        b.set_pml(pml_cells, profiles=prof)
+        b.set_point_sources([[rows // 2, cols // 2]], np.zeros((1, 1)))
+        b.set_conductivity(sigma)
+        b.run(steps, amps, chan).sync()                # warm-up: code objects, clocks
+        return b
+
+    def timed(b):
+        b.reset().sync()
+        t0 = time.perf_counter()
+        b.run(steps, amps, chan).sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    with batch("pml") as pml, batch("periodic") as per:
+        assert per.periodic and per.lossy and pml.lossy and not pml.periodic
+        l0 = per.launches
+        per.reset().run(steps, amps, chan).sync()
+        launches = per.launches - l0
+        pml_ms, per_ms = [], []
+        for _ in range(reps):
+            pml_ms.append(timed(pml))
+            per_ms.append(timed(per))
+        paths = ["resident" if b.resident else "streamed" for b in (pml, per)]
+        lds = [b.lds_bytes for b in (pml, per)]
+    med_l, med_p = float(np.median(pml_ms)), float(np.median(per_ms))
+    return {"count": count, "rows": rows, "cols": cols, "steps": steps, "dtype": np.dtype(dtype).name,
+            "materials": "arrays", "pml_cells": pml_cells, "reps": reps, "lossy_pml_path": paths[0],
+            "periodic_path": paths[1], "lossy_pml_lds_bytes_per_member": lds[0], "periodic_lds_bytes_per_member": lds[1],
+            "lossy_pml_ms": round(med_l, 4), "lossy_pml_ms_min": round(min(pml_ms), 4),
+            "lossy_pml_ms_all": [round(v, 4) for v in pml_ms],
+            "periodic_ms": round(med_p, 4), "periodic_ms_min": round(min(per_ms), 4),
+            "periodic_ms_all": [round(v, 4) for v in per_ms],
+            "periodic_over_lossy_pml": round(med_p / med_l, 3), "launches_per_run": launches,
+            "periodic_mcell_steps_per_s": round(count * rows * cols * steps / (med_p * 1e-3) / 1e6, 1)}
+
+
 def bench_adjoint(count, rows, cols, steps, dtype, reps, pml_cells):
     from fdtd2d_amd.adjoint import channel_system, gradient_coefficients
     dt = 2e-13                                   # the Gaussian envelope of the channels (t0 = 4.5 / fc) ends by step 1200
@@ -411,7 +468,12 @@ def main():
     ap.add_argument("--monitors", action="store_true", help="time the window DFT and probes (see above)")
     ap.add_argument("--adjoint", action="store_true", help="time batch_eps_gradient (see above)")
     ap.add_argument("--lossy", action="store_true", help="time the lossy kernels against the point-source ones")
+    ap.add_argument("--periodic", action="store_true", help="time the periodic kernels against the lossy PML ones")
     a = ap.parse_args()
+    if a.periodic:
+        print(json.dumps(bench_periodic(a.count or 1024, a.rows or 60, a.cols or 61, a.steps or 1000, np.dtype(a.dtype),
+                                        a.reps, a.pml_cells)), flush=True)
+        return
     if a.lossy:
         for boundary in ("mur", "pml"):
             print(json.dumps(bench_lossy(a.count or 1024, a.rows or 60, a.cols or a.rows or 60, a.steps or 1000,
