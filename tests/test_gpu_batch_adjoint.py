@@ -43,10 +43,12 @@ def _threads(cells):
     return min(1024, -(-(-(-cells // 4)) // 64) * 64)
 
 
-def _expect_path(b, nf, window_cells, ncell, never=False, lds_allowed=True):
-    """The capacity rule with monitors and point sources, restated; returns whether the run is resident."""
+def _expect_path(b, nf, window_cells, ncell, never=False, lds_allowed=True, uniform=False):
+    """The capacity rule with monitors and point sources, restated; returns whether the run is resident.  uniform: the
+    batch holds no coefficient arrays (two arrays fewer)."""
     esz, R, Cc = b.dtype.itemsize, b.rows, b.cols
-    fields = 6 * _seg(R * Cc, esz) + _seg(4 * R, esz) + _seg(4 * Cc, esz) if b.pml else 5 * _seg(R * Cc, esz)
+    arrays = (6 if b.pml else 5) - 2 * uniform
+    fields = arrays * _seg(R * Cc, esz) + (_seg(4 * R, esz) + _seg(4 * Cc, esz) if b.pml else 0)
     table, acc = 16 * nf + 8 * ncell, 16 * nf * window_cells
     resident = fields + table <= LDS_LIMIT and not never
     in_lds = bool(nf) and lds_allowed and fields + table + acc <= LDS_LIMIT
@@ -62,17 +64,23 @@ def _shape(boundary, dtype, where):
     return (48, 48) if (boundary, dtype) == ("pml", np.float64) else (60, 60)
 
 
-def _setup(fd, rng, B, R, Cc, dtype, K, n):
+def _setup(fd, rng, B, R, Cc, dtype, K, n, cells=None, uniform=False):
     """Members with their own materials, line sources and amplitudes; point cells: two interior cells owned by one
-    thread of the resident walk, a frame / layer cell, an edge cell, the corner and a cell of the rectangle source."""
+    thread of the resident walk, a frame / layer cell, an edge cell, the corner and a cell of the rectangle source.
+    cells: other point cells, (B, P, 2).  uniform: one permittivity for every cell of every member (what a batch with
+    uniform materials holds), for _drive(uniform=True)."""
     eps = (fd.EPS0 * np.where(rng.random((B, R, Cc)) < 0.3, 4.0, 1.0)).astype(dtype)
+    if uniform:
+        eps = np.full((B, R, Cc), fd.EPS0 * (1 + 3 * rng.random())).astype(dtype)
     mu = np.full((B, R, Cc), fd.MU0).astype(dtype)
     rects = np.array([[R // 2 + (m % 3) - 1, 3, 1, Cc - 6] for m in range(B)])
     amps = np.stack([[fd.ricker_amplitude(k * DT, 30e9 * (1 + 0.1 * m)) for k in range(n)] for m in range(B)])
     omegas = OMEGAS[None, :] * (1 + 0.01 * np.arange(B))[:, None]
     twin = divmod(10 * Cc + 10 + _threads(R * Cc), Cc)
-    cells = np.stack([[[10, 10], list(twin), [2 + m % 2, Cc // 3], [R - 1, 5], [0, 0], [int(r[0]), Cc // 2]]
-                      for m, r in enumerate(rects)])
+    if cells is None:
+        cells = np.stack([[[10, 10], list(twin), [2 + m % 2, Cc // 3], [R - 1, 5], [0, 0], [int(r[0]), Cc // 2]]
+                          for m, r in enumerate(rects)])
+    cells = np.asarray(cells)
     weights = rng.standard_normal((B, cells.shape[1], K))
     t = np.arange(n) * DT
     chan = np.stack([np.sin(2 * np.pi * 20e9 * (1 + c) * t + c) * np.exp(-((t - 20 * DT) / (15 * DT)) ** 2)
@@ -82,24 +90,30 @@ def _setup(fd, rng, B, R, Cc, dtype, K, n):
     return eps, mu, rects, amps, omegas, cells, weights, chan
 
 
-def _drive(b, boundary, cfg, window, splits):
+def _drive(b, boundary, cfg, window, splits, uniform=False, layer=LAYER):
     eps, mu, rects, amps, omegas, cells, weights, chan = cfg
-    b.set_materials(eps, mu).set_sources(rects)
+    if uniform:      # scalars: the batch keeps no coefficient arrays
+        assert np.all(eps == eps[0, 0, 0]) and np.all(mu == mu[0, 0, 0])
+        b.set_materials(float(eps[0, 0, 0]), float(mu[0, 0, 0]))
+    else:
+        b.set_materials(eps, mu)
+    b.set_sources(rects)
     if boundary == "pml":
         c00 = [(1 / np.sqrt(float(e) * float(u)) * DT) / DX for e, u in zip(eps[:, 0, 0], mu[:, 0, 0])]
-        b.set_pml(LAYER, courant00=np.array(c00))
+        b.set_pml(layer, courant00=np.array(c00))
     n = sum(splits)
     b.set_dft_window(window, omegas).set_probes(cells, n).set_point_sources(cells, weights)
     return n
 
 
-def _device_run(fd, boundary, dtype, R, Cc, cfg, window, splits, resident=None, spl=None, lds=True):
+def _device_run(fd, boundary, dtype, R, Cc, cfg, window, splits, resident=None, spl=None, lds=True, uniform=False,
+                layer=LAYER):
     B = cfg[0].shape[0]
     with fd.BatchEngine(B, R, Cc, DT, DX, dtype=dtype, boundary=boundary) as b:
-        n = _drive(b, boundary, cfg, window, splits)
+        n = _drive(b, boundary, cfg, window, splits, uniform, layer)
         b.set_option(resident=resident, steps_per_launch=spl).set_window_lds(lds)
         path = _expect_path(b, cfg[4].shape[1], window[2] * window[3], cfg[5].shape[1], never=resident == 0,
-                            lds_allowed=lds)
+                            lds_allowed=lds, uniform=uniform)
         done, launches = 0, b.launches
         for k in splits:
             b.run(k, cfg[3][:, done:done + k], cfg[7][..., done:done + k])
@@ -108,8 +122,8 @@ def _device_run(fd, boundary, dtype, R, Cc, cfg, window, splits, resident=None, 
             assert b.launches - launches == sum(-(-k // spl) if spl else 1 for k in splits)
         else:
             assert b.launches - launches == 2 * n
-        return dict(fields=b.download(), dft=b.read_dft_window(), probes=b.read_probes(), path=path,
-                    in_lds=b.window_in_lds)
+        fields = b.download() + ((b.download_ezx(),) if boundary == "pml" else ())
+        return dict(fields=fields, dft=b.read_dft_window(), probes=b.read_probes(), path=path, in_lds=b.window_in_lds)
 
 
 def _same(a, b):

@@ -85,22 +85,22 @@ def _expect_path(b, nf, window_cells, ncell, lossy, never=False, lds_allowed=Tru
     return resident
 
 
-def _drive(b, boundary, cfg, window, n, monitors=True):
+def _drive(b, boundary, cfg, window, n, monitors=True, layer=LAYER):
     eps, mu, rects, amps, omegas, cells, weights, chan = cfg
     b.set_materials(eps, mu).set_sources(rects)
     if boundary == "pml":
         c00 = [(1 / np.sqrt(float(e) * float(u)) * DT) / DX for e, u in zip(eps[:, 0, 0], mu[:, 0, 0])]
-        b.set_pml(LAYER, courant00=np.array(c00))
+        b.set_pml(layer, courant00=np.array(c00))
     if monitors:
         b.set_dft_window(window, omegas).set_probes(cells, n).set_point_sources(cells, weights)
 
 
 def _device_run(fd, boundary, dtype, R, Cc, cfg, window, splits, sigma, monitors=True, resident=None, spl=None,
-                lds=True):
+                lds=True, layer=LAYER):
     """sigma None: no conductivity.  Returns fields (+ monitors) and the path."""
     B, n = cfg[0].shape[0], sum(splits)
     with fd.BatchEngine(B, R, Cc, DT, DX, dtype=dtype, boundary=boundary) as b:
-        _drive(b, boundary, cfg, window, n, monitors)
+        _drive(b, boundary, cfg, window, n, monitors, layer)
         if sigma is not None:
             b.set_conductivity(sigma)
         b.set_option(resident=resident, steps_per_launch=spl).set_window_lds(lds)

@@ -64,11 +64,11 @@ def _window(R, Cc, dtype):
     return (R // 2 - 6, Cc - 8, 12, 8) if dtype == np.float32 else (R // 2 - 2, Cc - 6, 3, 6)
 
 
-def _cfg(fd, rng, B, R, Cc, dtype, n, K=6):
+def _cfg(fd, rng, B, R, Cc, dtype, n, K=6, points=None, image_row=13):
     """Members with their own materials (the image column's are random too: they are never read), line sources that
     touch column 0, column C-2 or span the whole period, and point cells in columns 0 and C-2, two owned by one thread of
     the resident walk, a layer row, the last row, cell [0, 0] and a cell of the rectangle source.  The probes are the
-    point cells and a cell of the image column."""
+    point cells and a cell of the image column.  points: other point cells, (B, P, 2); image_row: that probe's row."""
     eps = (fd.EPS0 * np.where(rng.random((B, R, Cc)) < 0.3, 4.0, 1.0)).astype(dtype)
     mu = (fd.MU0 * np.where(rng.random((B, R, Cc)) < 0.1, 1.5, 1.0)).astype(dtype)
     spans = [(0, Cc - 1), (0, 5), (Cc - 6, 5), (3, Cc - 7)]
@@ -76,9 +76,11 @@ def _cfg(fd, rng, B, R, Cc, dtype, n, K=6):
     amps = np.stack([[fd.ricker_amplitude(k * DT, 30e9 * (1 + 0.1 * m)) for k in range(n)] for m in range(B)])
     omegas = (2 * np.pi * np.linspace(10e9, 100e9, 10))[None, :] * (1 + 0.01 * np.arange(B))[:, None]
     twin = divmod(12 * Cc + 10 + _threads(R * Cc), Cc)
-    points = np.stack([[[10 + m % 2, 0], [11, Cc - 2], [12, 10], list(twin), [2 + m % 2, Cc // 3], [R - 1, 5], [0, 0],
-                        [int(r[0]), int(r[1]) + 1]] for m, r in enumerate(rects)])
-    probes = np.concatenate([points, np.tile([[[13, Cc - 1]]], (B, 1, 1))], axis=1)
+    if points is None:
+        points = np.stack([[[10 + m % 2, 0], [11, Cc - 2], [12, 10], list(twin), [2 + m % 2, Cc // 3], [R - 1, 5],
+                            [0, 0], [int(r[0]), int(r[1]) + 1]] for m, r in enumerate(rects)])
+    points = np.asarray(points)
+    probes = np.concatenate([points, np.tile([[[image_row, Cc - 1]]], (B, 1, 1))], axis=1)
     weights = rng.standard_normal((B, points.shape[1], K))
     t = np.arange(n) * DT
     chan = np.stack([np.sin(2 * np.pi * 20e9 * (1 + c) * t + c) * np.exp(-((t - 20 * DT) / (15 * DT)) ** 2)
