@@ -48,6 +48,8 @@ BATCH_MAX_POINT_SOURCES, BATCH_MAX_CHANNELS = 64, 32
 BATCH_INFO_LOSSY = 14
 # include/fdtd2d_batch_periodic.h
 BATCH_INFO_PERIODIC = 15
+# include/fdtd2d_batch_bloch.h
+BATCH_INFO_BLOCH = 16
 
 _vp, _i, _d, _ll = C.c_void_p, C.c_int, C.c_double, C.c_longlong
 
@@ -168,6 +170,16 @@ BATCH_PERIODIC_SIGNATURES = {
     "fdtd2d_batch_set_periodic": (_i, [_vp, _i]),
 }
 
+# every symbol include/fdtd2d_batch_bloch.h declares (a Bloch phase for a periodic batch: complex fields)
+BATCH_BLOCH_SIGNATURES = {
+    "fdtd2d_batch_set_bloch": (_i, [_vp, C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_set_bloch_source": (_i, [_vp, C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_run_bloch": (_i, [_vp, _i, C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_transfer_bloch": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i]),
+    "fdtd2d_batch_read_dft_window_bloch": (_i, [_vp, C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_read_probes_bloch": (_i, [_vp, C.POINTER(_d), _ll, _ll]),
+}
+
 # transport callback of fdtd2d_slab_attach
 EXCHANGE_FN = C.CFUNCTYPE(_i, _vp, _vp, _vp, _vp, _vp, _ll, _vp)
 
@@ -217,7 +229,8 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in {**SIGNATURES, **BATCH_PML_SIGNATURES, **BATCH_MONITOR_SIGNATURES,
                                    **BATCH_ADJOINT_SIGNATURES, **BATCH_DESIGN_SIGNATURES,
-                                   **BATCH_LOSSY_SIGNATURES, **BATCH_PERIODIC_SIGNATURES}.items():
+                                   **BATCH_LOSSY_SIGNATURES, **BATCH_PERIODIC_SIGNATURES,
+                                   **BATCH_BLOCH_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

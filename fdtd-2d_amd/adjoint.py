@@ -252,6 +252,14 @@ def _setup(eng, p):
     eng.set_dft_window(p.win, p.om).set_probes(p.cells, p.nsteps)
 
 
+def _refuse_bloch(eng):
+    """The adjoint of complex fields is not implemented: an engine with a Bloch phase (an engine factory that sets one,
+    or set_bloch_phase on a session's engine) is refused before any run."""
+    if getattr(eng, "_bloch", None) is not None:
+        from ._abi import E_STATE, Fdtd2dError
+        raise Fdtd2dError(E_STATE, "adjoint gradients are not available while a Bloch phase is set (complex fields)")
+
+
 def _cotangent(p, objective, spectra):
     J, g = objective(spectra)
     J = np.asarray(J, dtype=np.float64)
@@ -315,6 +323,7 @@ def _two_runs(p, sigma, objective, dtype, device, engine):
         from .batch import BatchEngine as engine
     B, nsteps, dt, dx, boundary = p.B, p.nsteps, p.dt, p.dx, p.boundary
     with engine(B, p.R, p.Cc, dt, dx, dtype=dtype, boundary=boundary, device=device) as eng:
+        _refuse_bloch(eng)
         # 1. forward: the member's own source; window DFT over the design region, probes at the observation cells
         _setup(eng, p)
         if sigma is not None:
@@ -409,6 +418,7 @@ class AdjointSession:
         self._ran = False                       # the windows of a value_and_grad are on the device
         eng = engine(p.B, p.R, p.Cc, dt, dx, dtype=dtype, boundary=boundary, device=device)
         try:
+            _refuse_bloch(eng)
             _setup(eng, p)
         except BaseException:
             eng.__exit__(None, None, None)
@@ -446,6 +456,7 @@ class AdjointSession:
         p, eng = self._p, self._eng
         if eng is None:
             raise RuntimeError("the session is closed")
+        _refuse_bloch(eng)
         none = np.empty((p.B, 0))
         # 1. forward
         eng.reset()

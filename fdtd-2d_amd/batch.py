@@ -13,7 +13,9 @@ held window (``hold_dft_window``, ``dft_window_product``) are what an adjoint ru
 absorbers, resistive sheets); the batch then runs on the lossy step kernels.
 ``boundary="periodic"`` makes every member one period of a structure that repeats along its columns (gratings,
 metasurface unit cells, photonic-crystal slabs): column C-1 is the image of column 0, rows end in the PML of ``set_pml``
-or in PEC (fdtd2d_batch_periodic.h).
+or in PEC (fdtd2d_batch_periodic.h).  ``set_bloch_phase`` gives a periodic batch one Bloch phase per member: the fields
+become complex and repeat as F(x + period) = F(x) e^{i phi} (oblique incidence, angle sweeps, band diagrams;
+fdtd2d_batch_bloch.h).
 """
 from __future__ import annotations
 
@@ -88,8 +90,8 @@ class BatchEngine:
     on every member, set with set_pml() before the first run (the handle is a NONE batch: the layer's outer
     edge is PEC).  "periodic": the columns wrap around with the period C - 1 (column C-1 is the image of column 0 and
     is output only: no source there, materials there are never read, upload() overwrites it with column 0); set_pml()
-    lays the layer on the top and bottom rows alone, clear_pml() leaves PEC there.  There is no Bloch phase and there
-    are no periodic rows.
+    lays the layer on the top and bottom rows alone, clear_pml() leaves PEC there.  set_bloch_phase() makes the fields
+    complex with one Bloch phase per member.  There are no periodic rows.
     """
 
     def __init__(self, count, rows, cols, dt=5e-14, dx=1e-4, dtype=np.float32, boundary="mur", device=0):
@@ -107,6 +109,8 @@ class BatchEngine:
         self._win = None              # (F, nrows, ncols) of the window DFT
         self._nprobe = 0
         self._npoint = (0, 0)         # (P, K) of the point sources
+        self._bloch = None            # (c, s): the (B,) rotations of a Bloch phase
+        self._phi = None              # the phases as given (None with rotation=)
         code = _abi.BOUNDARY_NONE if boundary in ("pml", "periodic") else _BOUNDARY[boundary]
         rc = self._lib.fdtd2d_batch_create(C.byref(self._h), self.count, self.rows, self.cols, self.dt, self.dx,
                                            _code(dtype), code, int(device))
@@ -146,6 +150,82 @@ class BatchEngine:
     def periodic(self) -> bool:
         """Whether the columns are periodic (the batch runs on the periodic kernels)."""
         return bool(self.info(_abi.BATCH_INFO_PERIODIC))
+
+    @property
+    def bloch(self) -> bool:
+        """Whether a Bloch phase is set (complex fields, the batch runs on the Bloch kernels)."""
+        return bool(self.info(_abi.BATCH_INFO_BLOCH))
+
+    def _no_bloch(self, what):
+        """The library's refusal of `what` while a Bloch phase is set, before the call."""
+        if self._bloch is not None:
+            raise _abi.Fdtd2dError(_abi.E_STATE, f"{what} is not available while a Bloch phase is set (complex fields)")
+
+    # -- a Bloch phase (fdtd2d_batch_bloch.h) -------------------------------------------------------------------------
+    def set_bloch_phase(self, phi, rotation=None):
+        """One Bloch phase per member of a periodic batch: F(x + period) = F(x) * exp(1j * phi).  phi: a scalar or (B,)
+        in radians; the library takes cos(phi) and sin(phi), rounded to the batch dtype.  rotation=(c, s), scalars or
+        (B,), gives those pairs directly, so that exact ones such as (-1, 0) and (0, 1) can be set (phi is then not
+        read).  None (and no rotation) turns the phase off: a plain periodic batch again, real parts as they are.
+        While a phase is set the fields, the window DFT and the probes are complex (upload, download, download_ezx,
+        read_dft_window, read_probes), run() takes complex amps, and set_dft, point sources and channels, the held
+        window, probe_spectra, field_absmax and the adjoint helpers are refused, as are windows and probes touching
+        column C-1."""
+        if phi is None and rotation is None:
+            self._ck(self._lib.fdtd2d_batch_set_bloch(self._h, None, None))
+            self._bloch = self._phi = None
+            return self
+        if rotation is not None:
+            if len(rotation) != 2:
+                raise ValueError(f"rotation must be a pair (c, s), got {rotation!r}")
+            c, s = (np.asarray(v, dtype=np.float64) for v in rotation)
+            ph = None
+        else:
+            ph = np.asarray(phi, dtype=np.float64)
+            c, s = np.cos(ph), np.sin(ph)
+        for v, nm in ((c, "c"), (s, "s")) if ph is None else ((ph, "phi"),):
+            if v.shape not in ((), (self.count,)):
+                raise ValueError(f"{nm} must be a scalar or have shape ({self.count},), got {v.shape}")
+        if self.boundary != "periodic":
+            raise _abi.Fdtd2dError(_abi.E_STATE, "a Bloch phase needs periodic columns: call fdtd2d_batch_set_periodic "
+                                   "first")
+        c = np.ascontiguousarray(np.broadcast_to(c, (self.count,)))
+        s = np.ascontiguousarray(np.broadcast_to(s, (self.count,)))
+        self._ck(self._lib.fdtd2d_batch_set_bloch(self._h, _dptr(c), _dptr(s)))
+        self._bloch = (c, s)
+        self._phi = None if ph is None else np.ascontiguousarray(np.broadcast_to(ph, (self.count,)))
+        return self
+
+    def set_bloch_source(self, weights="ramp"):
+        """The complex weight of the rectangle source per column 0..C-2: "ramp" = exp(1j * phi * j / (C - 1)) (a line
+        source across the period then launches the obliquely travelling wave; needs set_bloch_phase(phi), not
+        rotation=), None = ones, or a complex array (C-1,) for every member or (B, C-1)."""
+        Q = self.cols - 1
+        if self._bloch is None:
+            raise _abi.Fdtd2dError(_abi.E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first")
+        if weights is None:
+            self._ck(self._lib.fdtd2d_batch_set_bloch_source(self._h, None, None))
+            return self
+        if isinstance(weights, str):
+            if weights != "ramp":
+                raise ValueError(f'weights must be "ramp", None or an array, not {weights!r}')
+            if self._phi is None:
+                raise ValueError('weights="ramp" needs the phases: call set_bloch_phase(phi) without rotation=')
+            w = np.exp(1j * self._phi[:, None] * np.arange(Q)[None, :] / Q)
+        else:
+            w = np.asarray(weights, dtype=np.complex128)
+            if w.shape not in ((Q,), (self.count, Q)):
+                raise ValueError(f"weights must have shape ({Q},) or ({self.count}, {Q}), got {w.shape}")
+            w = np.broadcast_to(w, (self.count, Q))
+        wr, wi = np.ascontiguousarray(w.real), np.ascontiguousarray(w.imag)
+        self._ck(self._lib.fdtd2d_batch_set_bloch_source(self._h, _dptr(wr), _dptr(wi)))
+        return self
+
+    def _touches_image(self, what, cols):
+        """The library's refusal of a monitor in column C-1 while a Bloch phase is set."""
+        if self._bloch is not None and np.any(np.asarray(cols) >= self.cols - 1):
+            raise _abi.Fdtd2dError(_abi.E_ARG, f"{what} touches column {self.cols - 1}, the image of column 0: not "
+                                   "while a Bloch phase is set")
 
     @property
     def resident(self) -> bool:
@@ -260,15 +340,25 @@ class BatchEngine:
 
     def upload_ezx(self, Ezx):
         """(B, R, C) split field, host -> device (needs a layer)."""
-        a = np.ascontiguousarray(Ezx, dtype=self.dtype)
+        z = np.asarray(Ezx)
+        if np.iscomplexobj(z) and self._bloch is None:
+            raise ValueError("complex fields need a Bloch phase (set_bloch_phase)")
+        a = np.ascontiguousarray(z.real, dtype=self.dtype)
         self._shape(a, (self.count, self.rows, self.cols), "Ezx")
         self._ck(self._lib.fdtd2d_batch_transfer_ezx(self._h, a.ctypes.data, _code(a.dtype), 1))
+        if self._bloch is not None:
+            i = np.ascontiguousarray(z.imag, dtype=self.dtype)
+            self._ck(self._lib.fdtd2d_batch_transfer_bloch(self._h, None, None, None, i.ctypes.data, _code(i.dtype), 1))
         return self
 
     def download_ezx(self):
         """(B, R, C) split field, device -> host (needs a layer)."""
         a = np.empty((self.count, self.rows, self.cols), self.dtype)
         self._ck(self._lib.fdtd2d_batch_transfer_ezx(self._h, a.ctypes.data, _code(a.dtype), 0))
+        if self._bloch is not None:
+            i = np.empty_like(a)
+            self._ck(self._lib.fdtd2d_batch_transfer_bloch(self._h, None, None, None, i.ctypes.data, _code(i.dtype), 0))
+            return a + 1j * i
         return a
 
     def _need_pml(self):
@@ -286,7 +376,20 @@ class BatchEngine:
         return (B, R, Cc), (B, R, Cc - 1), (B, R - 1, Cc)
 
     def upload(self, Ez=None, Hx=None, Hy=None):
-        """Host -> device, any float dtype; a field given as None is left as is."""
+        """Host -> device, any float dtype; a field given as None is left as is.  With a Bloch phase the fields may be
+        complex (a real array has a zero imaginary part)."""
+        if any(a is not None and np.iscomplexobj(a) for a in (Ez, Hx, Hy)) and self._bloch is None:
+            raise ValueError("complex fields need a Bloch phase (set_bloch_phase)")
+        if self._bloch is not None:
+            given = [None if a is None else np.asarray(a) for a in (Ez, Hx, Hy)]
+            for a, shp, nm in zip(given, self._field_shapes(), ("Ez", "Hx", "Hy")):
+                if a is not None:
+                    self._shape(a, shp, nm)
+            im = [None if a is None else np.ascontiguousarray(a.imag, dtype=np.float64) for a in given]
+            Ez, Hx, Hy = (None if a is None else np.ascontiguousarray(a.real) for a in given)
+            if any(a is not None for a in im):
+                ptr = [None if a is None else a.ctypes.data for a in im]
+                self._ck(self._lib.fdtd2d_batch_transfer_bloch(self._h, ptr[0], ptr[1], ptr[2], None, _abi.F64, 1))
         arrs, code = [], None
         for a, shp, nm in zip((Ez, Hx, Hy), self._field_shapes(), ("Ez", "Hx", "Hy")):
             if a is None:
@@ -306,10 +409,15 @@ class BatchEngine:
         return self
 
     def download(self, dtype=None):
-        """Device -> host: new arrays (Ez, Hx, Hy) of the engine dtype (or `dtype`)."""
+        """Device -> host: new arrays (Ez, Hx, Hy) of the engine dtype (or `dtype`); complex ones with a Bloch phase,
+        the image column of Ez then rotated by the member's phase."""
         dt = self.dtype if dtype is None else np.dtype(dtype)
         out = [np.empty(s, dt) for s in self._field_shapes()]
         self._ck(self._lib.fdtd2d_batch_download(self._h, *(a.ctypes.data for a in out), _code(dt)))
+        if self._bloch is not None:
+            im = [np.empty(s, dt) for s in self._field_shapes()]
+            self._ck(self._lib.fdtd2d_batch_transfer_bloch(self._h, *(a.ctypes.data for a in im), None, _code(dt), 0))
+            return tuple(a + 1j * b for a, b in zip(out, im))
         return tuple(out)
 
     def reset(self):
@@ -335,12 +443,23 @@ class BatchEngine:
         without them the point sources stay silent."""
         nsteps = int(nsteps)
         self._need_pml()
-        a = None
+        a = ai = None
+        if amps is not None and np.iscomplexobj(amps):
+            if self._bloch is None:
+                raise ValueError("complex amps need a Bloch phase (set_bloch_phase)")
+            ai = np.asarray(amps).imag
+            amps = np.asarray(amps).real
         if amps is not None:
             a = np.asarray(amps, dtype=np.float64)
             if a.ndim != 2 or a.shape[0] != self.count or a.shape[1] < nsteps:
                 raise ValueError(f"amps must have shape ({self.count}, {nsteps}), got {a.shape}")
             a = np.ascontiguousarray(a[:, :nsteps])
+        if channels is not None:
+            self._no_bloch("a run with channels")
+        if ai is not None:
+            ai = np.ascontiguousarray(ai[:, :nsteps], dtype=np.float64)
+            self._ck(self._lib.fdtd2d_batch_run_bloch(self._h, nsteps, _dptr(a), _dptr(ai)))
+            return self
         if channels is None:
             self._ck(self._lib.fdtd2d_batch_run(self._h, nsteps, None if a is None else _dptr(a)))
             return self
@@ -365,6 +484,7 @@ class BatchEngine:
             self._ck(self._lib.fdtd2d_batch_set_point_sources(self._h, 0, None, 0, None))
             self._npoint = (0, 0)
             return self
+        self._no_bloch("a point source")
         c = _probe_cells(cells, self.count)
         w = np.asarray(weights, dtype=np.float64)
         if w.ndim == 2:
@@ -380,12 +500,14 @@ class BatchEngine:
 
     def hold_dft_window(self):
         """Keep a device copy of the window DFT as it is now; it survives reset() and further runs."""
+        self._no_bloch("the held window")
         self._ck(self._lib.fdtd2d_batch_hold_dft_window(self._h))
         return self
 
     def dft_window_product(self, coef) -> np.ndarray:
         """float64 (B, nrows, ncols): sum_k Re(coef[b, k] * held[b, k] * current[b, k]) over the window, on the device.
         coef: complex (F,) for every member or (B, F)."""
+        self._no_bloch("the window product")
         f, nr, nc = self._win or (0, 1, 1)
         k = np.asarray(coef, dtype=np.complex128)
         if k.ndim == 1:
@@ -410,6 +532,7 @@ class BatchEngine:
         if omega is None:
             self._ck(self._lib.fdtd2d_batch_set_dft(self._h, None, 0))
             return self
+        self._no_bloch("the whole-grid transform (use fdtd2d_batch_set_dft_window)")
         w = np.ascontiguousarray(np.broadcast_to(np.asarray(omega, dtype=np.float64), (self.count,)))
         self._ck(self._lib.fdtd2d_batch_set_dft(self._h, _dptr(w), int(every)))
         return self
@@ -433,18 +556,23 @@ class BatchEngine:
             return self
         w = _window_omegas(omegas, self.count)
         r0, c0, nr, nc = (int(v) for v in window)
+        self._touches_image(f"window ({r0},{c0})+{nr}x{nc}", c0 + nc - 1)
         self._ck(self._lib.fdtd2d_batch_set_dft_window(self._h, r0, c0, nr, nc, int(w.shape[1]), _dptr(w), int(every)))
         self._win = (int(w.shape[1]), nr, nc)
         return self
 
     def read_dft_window(self) -> np.ndarray:
-        """complex128 (B, F, nrows, ncols) of the window DFT."""
+        """complex128 (B, F, nrows, ncols) of the window DFT.  With a Bloch phase: of the complex Ez, W(re) + 1j * W(im)."""
         f, nr, nc = self._win or (0, 0, 0)
         shape = (self.count, f, nr, nc)
         re, im = np.empty(shape), np.empty(shape)
         if self._win is None:     # the library refuses (no window): keep the buffers valid
             re = im = np.empty(1)
         self._ck(self._lib.fdtd2d_batch_read_dft_window(self._h, _dptr(re), _dptr(im)))
+        if self._bloch is not None:
+            re2, im2 = np.empty_like(re), np.empty_like(im)
+            self._ck(self._lib.fdtd2d_batch_read_dft_window_bloch(self._h, _dptr(re2), _dptr(im2)))
+            return (re + 1j * im) + 1j * (re2 + 1j * im2)
         return re + 1j * im
 
     @property
@@ -466,6 +594,7 @@ class BatchEngine:
             self._nprobe = 0
             return self
         c = _probe_cells(cells, self.count)
+        self._touches_image("a probe", c[..., 1])
         self._ck(self._lib.fdtd2d_batch_set_probes(self._h, int(c.shape[1]), c.ctypes.data_as(C.POINTER(C.c_int)),
                                                    int(capacity)))
         self._nprobe = int(c.shape[1])
@@ -478,12 +607,17 @@ class BatchEngine:
 
     def read_probes(self, first=0, count=None) -> np.ndarray:
         """float64 (B, P, count): samples [first, first + count) of every probe; count None = up to the samples
-        recorded so far."""
+        recorded so far.  complex128 with a Bloch phase."""
         if count is None:
             count = max(0, self.probe_samples - int(first))
         out = np.empty((self.count, self._nprobe, max(0, int(count))))
         buf = out if out.size else np.empty(1)     # a refused or empty read still passes a valid pointer
         self._ck(self._lib.fdtd2d_batch_read_probes(self._h, _dptr(buf), int(first), int(count)))
+        if self._bloch is not None:
+            im = np.empty_like(out)
+            buf = im if im.size else np.empty(1)
+            self._ck(self._lib.fdtd2d_batch_read_probes_bloch(self._h, _dptr(buf), int(first), int(count)))
+            return out + 1j * im
         return out
 
     # -- the design loop (fdtd2d_batch_design.h) ---------------------------------------------------------------
@@ -492,6 +626,7 @@ class BatchEngine:
         exp(-1j * omegas[b, k] * s * dt), s the step after which sample n was recorded, formed on the device with the
         window DFT's arithmetic in ascending n.  omegas (F,) for every member or (B, F), F <= 16; count None = up to
         the samples recorded so far.  peak True: also float64 (B,), the largest |sample| of each member in the range."""
+        self._no_bloch("fdtd2d_batch_probe_spectra")
         w = _window_omegas(omegas, self.count)
         if count is None:
             count = max(0, self.probe_samples - int(first))
@@ -510,6 +645,7 @@ class BatchEngine:
         codes = {"Ez": _abi.FIELD_EZ, "Hx": _abi.FIELD_HX, "Hy": _abi.FIELD_HY}
         if field not in codes:
             raise ValueError(f'field must be "Ez", "Hx" or "Hy", not {field!r}')
+        self._no_bloch("fdtd2d_batch_field_absmax")
         out = np.empty(self.count)
         self._ck(self._lib.fdtd2d_batch_field_absmax(self._h, codes[field], _dptr(out)))
         return out
@@ -600,7 +736,7 @@ def _waveform_amps(kind, fc, nsteps, dt):
 
 def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker", dt=5e-14, dx=1e-4,
                    dtype=np.float64, boundary="mur", omega=None, dft_every=1, device=0, pml_cells=40,
-                   dft_window=None, window_omegas=None, probes=None):
+                   dft_window=None, window_omegas=None, probes=None, bloch_phase=None, source_weights=None):
     """run_fdtd for B members of one shape at once: zero fields, Courant check per member, nsteps of
     H -> E -> source with t = i*dt.
 
@@ -613,7 +749,9 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
     window_omegas (F,) or (B, F), F <= 16: a window DFT sampled every `dft_every` steps (set_dft_window).  probes:
     (P, 2) or (B, P, 2) cells, P <= 64, recorded at every step (set_probes).  Returns (Ez, Hx, Hy), plus the complex
     (B, R, C) DFT when omega is given, then the complex (B, F, nrows, ncols) window DFT when dft_window is given, then
-    the float64 (B, P, nsteps) probe traces when probes are given.
+    the float64 (B, P, nsteps) probe traces when probes are given.  bloch_phase (boundary "periodic" alone): a scalar or
+    (B,) in radians, the Bloch phase of set_bloch_phase; every returned array is then complex.  source_weights: "ramp",
+    None or an array as set_bloch_source takes them (needs bloch_phase).
     """
     from .api import MU0
     eps = np.asarray(eps)
@@ -642,12 +780,27 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
         L = int(pml_cells)
         m00 = mu_arr[:, 0, 0] if mu_arr.ndim == 3 else np.full(B, float(mu_arr))
         courant00 = np.array([(1 / np.sqrt(float(e) * float(u)) * dt) / dx for e, u in zip(eps[:, 0, 0], m00)])
+    if bloch_phase is not None and boundary != "periodic":
+        raise ValueError(f'bloch_phase needs boundary="periodic", not {boundary!r}')
+    if source_weights is not None and bloch_phase is None:
+        raise ValueError("source_weights needs bloch_phase")
+    if bloch_phase is not None and omega is not None:
+        raise ValueError("omega (the whole-grid transform) is not available with bloch_phase: use dft_window")
     win, wom, cells = _check_monitors(B, R, Cc, dft_window, window_omegas, probes, dft_every)
+    if bloch_phase is not None:
+        if win is not None and win[1] + win[3] > Cc - 1:
+            raise ValueError(f"dft_window {win} touches column {Cc - 1}, the image of column 0: not with bloch_phase")
+        if cells is not None and np.any(cells[..., 1] >= Cc - 1):
+            raise ValueError(f"a probe lies in column {Cc - 1}, the image of column 0: not with bloch_phase")
     with BatchEngine(B, R, Cc, dt, dx, dtype=dtype, boundary=boundary, device=device) as eng:
         eng.set_materials(eps, mu)
         if layered:
             eng.set_pml(L, courant00=courant00)
         eng.set_sources(sources)
+        if bloch_phase is not None:
+            eng.set_bloch_phase(bloch_phase)
+            if source_weights is not None:
+                eng.set_bloch_source(source_weights)
         if omega is not None:
             eng.set_dft(omega, dft_every)
         if win is not None:

@@ -11,8 +11,10 @@
 // The design-loop entry points (fdtd2d_batch_design.h) launch the post-run kernels of batch_design.hip.
 // With a conductivity set (fdtd2d_batch_lossy.h) every run takes the lossy kernels of batch_lossy.hip.
 // With periodic columns (fdtd2d_batch_periodic.h) every run takes the periodic kernels of batch_periodic.hip.
+// With a Bloch phase (fdtd2d_batch_bloch.h) every run takes the complex-field kernels of batch_bloch.hip.
 #include "../../include/fdtd2d.h"
 #include "../../include/fdtd2d_batch_adjoint.h"
+#include "../../include/fdtd2d_batch_bloch.h"
 #include "../../include/fdtd2d_batch_design.h"
 #include "../../include/fdtd2d_batch_lossy.h"
 #include "../../include/fdtd2d_batch_monitor.h"
@@ -32,6 +34,7 @@
 
 #include "kernels_batch.hpp"
 #include "kernels_batch_adjoint.hpp"
+#include "kernels_batch_bloch.hpp"
 #include "kernels_batch_design.hpp"
 #include "kernels_batch_lossy.hpp"
 #include "kernels_batch_monitor.hpp"
@@ -68,6 +71,16 @@ struct fdtd2d_batch {
     // (all exactly 1 and pml_L = 0 without a layer) and ca / cb (sigma_implicit: made by the batch itself, all zero)
     bool periodic = false, sigma_implicit = false;
     std::vector<int> rect_host;           // the source rectangles as given (4 per member)
+    // fdtd2d_batch_set_bloch: the imaginary parts of Ez, Hx, Hy, Ezx (the periodic kernels never flip `cur`, so one Ez),
+    // rho = count x {c, s} in T, the source weights count x {wr[C-1], wi[C-1]}, the imaginary amplitudes of a run and
+    // the imaginary parts of the monitors (allocated while the monitor is set)
+    bool bloch = false;
+    void *ez_im = nullptr, *hx_im = nullptr, *hy_im = nullptr, *ezx_im = nullptr, *rho = nullptr;
+    std::vector<double> rho_host;         // count x {c, s} as the engine stores them
+    double *bloch_w = nullptr, *amps_im = nullptr, *win_acc_im = nullptr, *probe_trace_im = nullptr;
+    size_t amps_im_cap = 0;
+    const double *run_amps_im = nullptr;  // device imaginary amplitudes of the run in progress (nullptr = zero)
+    std::vector<int> probe_host;          // the probes' cells as the device holds them (row * C + col)
 
     int *rect = nullptr;                  // device copy of the source rectangles (4 per member)
     bool have_src = false;                // some member has a non-empty rectangle
@@ -221,6 +234,8 @@ int zero_fields(fdtd2d_batch *b)
 {
     for (void *p : {b->ez[0], b->ez[1], b->hx, b->hy}) BCHK(b, hipMemsetAsync(p, 0, b->field_bytes, b->stream));
     if (b->ezx) BCHK(b, hipMemsetAsync(b->ezx, 0, b->field_bytes, b->stream));
+    if (b->bloch)
+        for (void *p : {b->ez_im, b->hx_im, b->hy_im, b->ezx_im}) BCHK(b, hipMemsetAsync(p, 0, b->field_bytes, b->stream));
     b->cur = 0;
     b->step = 0;
     return 0;
@@ -228,9 +243,11 @@ int zero_fields(fdtd2d_batch *b)
 
 // ---- the capacity rule of the resident path ------------------------------------------------------------
 // Mur / none: Ez, Hx, Hy (+ ce, ch); PML: Ez, Hx, Hy, Ezx (+ ce, ch) and the 4R + 4C factors; with a conductivity
-// cb stands in ce's place and ca is one more array
+// cb stands in ce's place and ca is one more array; a Bloch phase: the four fields twice and cb, ch, ca, the row
+// factors alone, the source weights with the tables and the accumulators twice
 int lds_arrays(const fdtd2d_batch *b)
 {
+    if (b->bloch) return 11;
     if (b->periodic) return 7;
     if (b->ca) return b->ezx ? 7 : 6;
     return (b->have_mat && b->uniform) ? (b->ezx ? 4 : 3) : (b->ezx ? 6 : 5);
@@ -240,6 +257,9 @@ int lds_arrays(const fdtd2d_batch *b)
 size_t lds_factor_bytes(const fdtd2d_batch *b)
 {
     if (!b->ezx && !b->periodic) return 0;
+    if (b->bloch)                           // the row factors alone
+        return b->dtype == FDTD2D_F32 ? fdtd::batch_lds_seg<float>(4 * b->rows) * 4
+                                      : fdtd::batch_lds_seg<double>(4 * b->rows) * 8;
     return b->dtype == FDTD2D_F32 ? fdtd::batch_pml_lds_elems<float>(0, b->rows, b->cols) * 4
                                   : fdtd::batch_pml_lds_elems<double>(0, b->rows, b->cols) * 8;
 }
@@ -255,17 +275,21 @@ size_t lds_field_bytes(const fdtd2d_batch *b)
 
 // window DFT: the phasor table (part of the capacity rule) and the accumulators (in LDS only when they fit too);
 // point sources: the sums of a step, behind the phasor table
-size_t lds_table_bytes(const fdtd2d_batch *b) { return 16 * (size_t)b->win_nf + 8 * (size_t)b->npts; }
+size_t lds_table_bytes(const fdtd2d_batch *b)
+{
+    return 16 * (size_t)b->win_nf + 8 * (size_t)b->npts + (b->bloch ? 16 * (size_t)(b->cols - 1) : 0);
+}
 size_t win_acc_bytes(const fdtd2d_batch *b) { return 16 * (size_t)b->win_nf * b->win_nr * b->win_nc; }
+size_t lds_acc_bytes(const fdtd2d_batch *b) { return (b->bloch ? 2 : 1) * win_acc_bytes(b); }   // both parts
 bool win_acc_in_lds(const fdtd2d_batch *b)
 {
     return b->win_nf && b->win_lds_opt != 0 &&
-           lds_field_bytes(b) + lds_table_bytes(b) + win_acc_bytes(b) <= fdtd::BATCH_LDS_LIMIT;
+           lds_field_bytes(b) + lds_table_bytes(b) + lds_acc_bytes(b) <= fdtd::BATCH_LDS_LIMIT;
 }
 
 size_t lds_bytes(const fdtd2d_batch *b)
 {
-    return lds_field_bytes(b) + lds_table_bytes(b) + (win_acc_in_lds(b) ? win_acc_bytes(b) : 0);
+    return lds_field_bytes(b) + lds_table_bytes(b) + (win_acc_in_lds(b) ? lds_acc_bytes(b) : 0);
 }
 
 // largest R*C whose arrays fit in one workgroup's LDS (materials as currently set; arrays before any call;
@@ -661,9 +685,69 @@ int run_periodic(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_
     return 0;
 }
 
+// ---- Bloch runs (fdtd2d_batch_bloch.h): the periodic paths with the complex-field kernels of batch_bloch.hip ----------
+template <class T> fdtd::BatchBloch<T> bloch_view(const fdtd2d_batch *b)
+{
+    return fdtd::BatchBloch<T>{(T *)b->ez_im, (T *)b->hx_im, (T *)b->hy_im, (T *)b->ezx_im, (const T *)b->rho,
+                               b->bloch_w, b->have_src ? b->run_amps_im : nullptr, b->win_acc_im, b->probe_trace_im};
+}
+
+template <class T> int run_bloch(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride)
+{
+    if (!b->ca || !b->ezx || !b->ez_im) return bfail(b, FDTD2D_E_STATE, "Bloch batch without its arrays");
+    const fdtd::BatchBlochKernels &K = fdtd::batch_bloch_kernels<T>();
+    fdtd::BatchPml<T> p = pml_view<T>(b);
+    fdtd::BatchMon m = mon_view(b);
+    fdtd::BatchBloch<T> bl = bloch_view<T>(b);
+    const T *ca = (const T *)b->ca;
+    if (use_resident(b)) {
+        const int cells = b->rows * b->cols, threads = resident_threads(cells);
+        const int per_thread = (cells + threads - 1) / threads;
+        if (per_thread > 4) return bfail(b, FDTD2D_E_STATE, "%d cells per thread exceed the Bloch resident kernel's 4", per_thread);
+        const void *kern = K.resident;
+        const size_t lds = lds_bytes(b);
+        BCHK(b, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        int per_cu = 0, cus = 0;
+        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds));
+        BCHK(b, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
+        if (per_cu < 1) return bfail(b, FDTD2D_E_STATE, "Bloch resident kernel does not fit a CU (%zu B of LDS)", lds);
+        const long long round = (long long)per_cu * cus;
+        const int blocks = (int)(b->count < round ? b->count : round);
+        const int chunk = b->steps_per_launch > 0 ? b->steps_per_launch : nsteps;
+        for (int n = 0; n < nsteps; n += chunk) {
+            int n0 = n, nt = nsteps - n < chunk ? nsteps - n : chunk;
+            long long step_base = b->step;
+            fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+            v.ce = (const T *)b->cb;
+            void *args[] = {&v, &p, &m, &bl, &ca, &n0, &nt, &step_base};
+            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads), args, lds);
+            if (rc) return rc;
+            b->launches++;
+            b->step += nt;
+        }
+        return 0;
+    }
+    const int cells = b->rows * b->cols;
+    const dim3 grid((cells + 255) / 256, b->count < 65535 ? b->count : 65535);
+    for (int n = 0; n < nsteps; ++n) {
+        fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+        v.ce = (const T *)b->cb;
+        long long step = b->step + 1;
+        int rc;
+        void *h_args[] = {&v, &p, &m, &bl, &step};
+        void *e_args[] = {&v, &p, &m, &bl, &ca, &n, &step};
+        if ((rc = launch_ptr(b, K.h, grid, dim3(256), h_args, 0))) return rc;
+        if ((rc = launch_ptr(b, K.e, grid, dim3(256), e_args, 0))) return rc;
+        b->launches += 2;
+        b->step++;
+    }
+    return 0;
+}
+
 template <class T>
 int run_impl(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts = nullptr)
 {
+    if (b->bloch) return run_bloch<T>(b, nsteps, amps, amp_stride);
     if (b->periodic) return run_periodic<T>(b, nsteps, amps, amp_stride, pts);
     if (b->ca) return run_lossy<T>(b, nsteps, amps, amp_stride, pts);
     if (b->win_nf || b->nprobe || pts) return run_monitored<T>(b, nsteps, amps, amp_stride, pts);
@@ -881,6 +965,7 @@ int unit_layer(fdtd2d_batch *b)
     BCHK(b, hipMemcpy(b->pml_row, ones.data(), rn * b->esz, hipMemcpyHostToDevice));
     BCHK(b, hipMemcpy(b->pml_col, ones.data(), cn * b->esz, hipMemcpyHostToDevice));
     BCHK(b, hipMemsetAsync(b->ezx, 0, b->field_bytes, b->stream));
+    if (b->bloch) BCHK(b, hipMemsetAsync(b->ezx_im, 0, b->field_bytes, b->stream));
     BCHK(b, hipStreamSynchronize(b->stream));
     b->pml_L = 0;
     return 0;
@@ -902,6 +987,102 @@ int periodic_coefficients(fdtd2d_batch *b)
     int rc = set_sigma(b, nullptr, zero.data(), FDTD2D_F64);
     if (!rc) b->sigma_implicit = true;
     return rc;
+}
+
+// ---- fdtd2d_batch_bloch.h ----------------------------------------------------------------------------------------
+// rho * (re, im) as the kernels form it (batch_bloch_rot), in the engine's type: part 0 = real, 1 = imaginary
+template <class T> double bloch_rot_host(double c, double s, double re, double im, int part)
+{
+    const T ct = (T)c, st = (T)s, rt = (T)re, it = (T)im;
+#ifdef FDTD2D_FUSED
+    return part ? (double)std::fma(st, rt, (T)(ct * it)) : (double)std::fma(ct, rt, (T)-(st * it));
+#else
+    const T x = part ? st * rt : ct * rt, y = part ? ct * it : st * it;
+    return part ? (double)(T)(x + y) : (double)(T)(x - y);
+#endif
+}
+
+// Ez or Ezx of a Bloch batch, device -> host (count x rows x cols): one part, the image column delivered as
+// rho * the image slot (which holds the unrotated copy of column 0)
+int copy_out_bloch(fdtd2d_batch *b, const void *re, const void *im, void *host, int host_dtype, int part)
+{
+    // the wanted part whole; of the other part only the image slots, which the rotation needs: the stored rows of the
+    // batch are count * rows lines of one pitch (mstride = rows * pitch), so that column is one strided copy
+    const int C = b->cols;
+    const size_t lines = (size_t)b->count * b->rows;
+    std::vector<unsigned char> own(b->field_bytes), other(lines * b->esz);
+    BCHK(b, hipStreamSynchronize(b->stream));
+    BCHK(b, hipMemcpy(own.data(), part ? im : re, b->field_bytes, hipMemcpyDeviceToHost));
+    BCHK(b, hipMemcpy2D(other.data(), b->esz, (const unsigned char *)(part ? re : im) + (size_t)(C - 1) * b->esz,
+                        (size_t)b->pitch * b->esz, b->esz, lines, hipMemcpyDeviceToHost));
+    for (int m = 0; m < b->count; ++m)
+        for (int i = 0; i < b->rows; ++i) {
+            const size_t line = (size_t)m * b->rows + i, dst = line * C, src = (size_t)m * b->mstride + (size_t)i * b->pitch;
+            for (int j = 0; j < C; ++j) {
+                double v = get_elem(own.data(), b->dtype, src + j);
+                if (j == C - 1) {
+                    const double o = get_elem(other.data(), b->dtype, line);
+                    const double zr = part ? o : v, zi = part ? v : o;
+                    const double c = b->rho_host[2 * m], s = b->rho_host[2 * m + 1];
+                    v = b->dtype == FDTD2D_F32 ? bloch_rot_host<float>(c, s, zr, zi, part)
+                                               : bloch_rot_host<double>(c, s, zr, zi, part);
+                }
+                if (host_dtype == FDTD2D_F32) ((float *)host)[dst + j] = (float)v;
+                else ((double *)host)[dst + j] = v;
+            }
+        }
+    return 0;
+}
+
+// the imaginary part of the window DFT / of the probe traces: there (zeroed) exactly while a Bloch phase and the
+// monitor are both set.  The caller has waited for the stream.
+int bloch_window(fdtd2d_batch *b)
+{
+    release((void **)&b->win_acc_im);
+    if (!b->bloch || !b->win_nf) return 0;
+    const size_t bytes = (size_t)b->count * win_acc_bytes(b);
+    int rc = alloc(b, (void **)&b->win_acc_im, bytes);
+    if (rc) return rc;
+    BCHK(b, hipMemsetAsync(b->win_acc_im, 0, bytes, b->stream));
+    BCHK(b, hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+int bloch_probes(fdtd2d_batch *b)
+{
+    release((void **)&b->probe_trace_im);
+    if (!b->bloch || !b->nprobe) return 0;
+    const size_t bytes = (size_t)b->count * b->nprobe * (size_t)b->probe_cap * sizeof(double);
+    int rc = alloc(b, (void **)&b->probe_trace_im, bytes);
+    if (rc) return rc;
+    BCHK(b, hipMemsetAsync(b->probe_trace_im, 0, bytes, b->stream));
+    BCHK(b, hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+// the first probe in column C-1 (member * nprobe + probe), or -1
+long long probe_in_image(const fdtd2d_batch *b, const std::vector<int> &lin)
+{
+    for (size_t k = 0; k < lin.size(); ++k)
+        if (lin[k] % b->cols == b->cols - 1) return (long long)k;
+    return -1;
+}
+
+int bloch_off(fdtd2d_batch *b)
+{
+    BCHK(b, hipStreamSynchronize(b->stream));
+    for (void **p : {&b->ez_im, &b->hx_im, &b->hy_im, &b->ezx_im, &b->rho, (void **)&b->bloch_w, (void **)&b->amps_im,
+                     (void **)&b->win_acc_im, (void **)&b->probe_trace_im})
+        release(p);
+    b->amps_im_cap = 0;
+    b->rho_host.clear();
+    b->bloch = false;
+    return 0;
+}
+
+int refuse_bloch(fdtd2d_batch *b, const char *what)
+{
+    return bfail(b, FDTD2D_E_STATE, "%s is not available while a Bloch phase is set (complex fields)", what);
 }
 
 }  // namespace
@@ -981,7 +1162,9 @@ void fdtd2d_batch_destroy(fdtd2d_batch_t *b)
                      (void **)&b->amps, &b->ezx, &b->pml_row, &b->pml_col, (void **)&b->dft, (void **)&b->omega,
                      (void **)&b->win_acc, (void **)&b->win_omega, (void **)&b->win_ph, (void **)&b->probe_cells,
                      (void **)&b->probe_trace, (void **)&b->win_held, (void **)&b->pts_cells, (void **)&b->pts_own,
-                     (void **)&b->pts_w, (void **)&b->pts_tab, (void **)&b->chan, &b->dsg, &b->ca, &b->cb})
+                     (void **)&b->pts_w, (void **)&b->pts_tab, (void **)&b->chan, &b->dsg, &b->ca, &b->cb,
+                     &b->ez_im, &b->hx_im, &b->hy_im, &b->ezx_im, &b->rho, (void **)&b->bloch_w, (void **)&b->amps_im,
+                     (void **)&b->win_acc_im, (void **)&b->probe_trace_im})
         release(p);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -1016,6 +1199,7 @@ long long fdtd2d_batch_info(const fdtd2d_batch_t *b, int what)
     case FDTD2D_BATCH_INFO_HELD_WINDOW: return b->win_held ? 1 : 0;
     case FDTD2D_BATCH_INFO_LOSSY: return b->ca && !b->sigma_implicit ? 1 : 0;
     case FDTD2D_BATCH_INFO_PERIODIC: return b->periodic ? 1 : 0;
+    case FDTD2D_BATCH_INFO_BLOCH: return b->bloch ? 1 : 0;
     default: return FDTD2D_E_ARG;
     }
 }
@@ -1181,6 +1365,7 @@ int fdtd2d_batch_set_pml(fdtd2d_batch_t *b, const void *row_factors, const void 
     BCHK(b, hipMemcpy(b->pml_row, row_factors, rbytes, hipMemcpyHostToDevice));
     BCHK(b, hipMemcpy(b->pml_col, col_factors, cbytes, hipMemcpyHostToDevice));
     BCHK(b, hipMemsetAsync(b->ezx, 0, b->field_bytes, b->stream));
+    if (b->bloch) BCHK(b, hipMemsetAsync(b->ezx_im, 0, b->field_bytes, b->stream));
     BCHK(b, hipStreamSynchronize(b->stream));
     b->pml_L = layer_cells;
     return 0;
@@ -1193,6 +1378,7 @@ int fdtd2d_batch_transfer_ezx(fdtd2d_batch_t *b, void *host, int host_dtype, int
     if (host_dtype != FDTD2D_F32 && host_dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad host_dtype");
     int rc = use_device(b);
     if (rc) return rc;
+    if (!to_device && b->bloch) return copy_out_bloch(b, b->ezx, b->ezx_im, host, host_dtype, 0);
     if (!to_device) return copy_out(b, b->ezx, host, host_dtype, b->rows, b->cols);
     if ((rc = copy_in(b, b->ezx, host, host_dtype, b->rows, b->cols))) return rc;
     return b->periodic ? copy_image(b, b->ezx) : 0;
@@ -1225,7 +1411,8 @@ int fdtd2d_batch_download(fdtd2d_batch_t *b, void *Ez, void *Hx, void *Hy, int h
     if (host_dtype != FDTD2D_F32 && host_dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad host_dtype");
     int rc = use_device(b);
     if (rc) return rc;
-    if (Ez && (rc = copy_out(b, b->ez[b->cur], Ez, host_dtype, b->rows, b->cols))) return rc;
+    if (Ez && b->bloch && (rc = copy_out_bloch(b, b->ez[b->cur], b->ez_im, Ez, host_dtype, 0))) return rc;
+    if (Ez && !b->bloch && (rc = copy_out(b, b->ez[b->cur], Ez, host_dtype, b->rows, b->cols))) return rc;
     if (Hx && (rc = copy_out(b, b->hx, Hx, host_dtype, b->rows, b->cols - 1))) return rc;
     if (Hy && (rc = copy_out(b, b->hy, Hy, host_dtype, b->rows - 1, b->cols))) return rc;
     return 0;
@@ -1241,6 +1428,10 @@ int fdtd2d_batch_reset(fdtd2d_batch_t *b)
     if (b->win_nf) BCHK(b, hipMemsetAsync(b->win_acc, 0, (size_t)b->count * win_acc_bytes(b), b->stream));
     if (b->nprobe)
         BCHK(b, hipMemsetAsync(b->probe_trace, 0, (size_t)b->count * b->nprobe * b->probe_cap * sizeof(double),
+                               b->stream));
+    if (b->win_acc_im) BCHK(b, hipMemsetAsync(b->win_acc_im, 0, (size_t)b->count * win_acc_bytes(b), b->stream));
+    if (b->probe_trace_im)
+        BCHK(b, hipMemsetAsync(b->probe_trace_im, 0, (size_t)b->count * b->nprobe * b->probe_cap * sizeof(double),
                                b->stream));
     b->win_step0 = 0;
     b->probe_step0 = 0;
@@ -1275,6 +1466,7 @@ int fdtd2d_batch_set_sources(fdtd2d_batch_t *b, const int *rect)
 
 int fdtd2d_batch_run(fdtd2d_batch_t *b, int nsteps, const double *amps)
 {
+    if (b && b->bloch) return fdtd2d_batch_run_bloch(b, nsteps, amps, nullptr);
     int rc = need_ready(b);
     if (rc) return rc;
     if (nsteps < 0) return bfail(b, FDTD2D_E_ARG, "nsteps < 0");
@@ -1310,6 +1502,7 @@ int fdtd2d_batch_run_waveform(fdtd2d_batch_t *b, int nsteps, int src_kind, const
 int fdtd2d_batch_set_dft(fdtd2d_batch_t *b, const double *omega, int every)
 {
     if (!b) return FDTD2D_E_ARG;
+    if (omega && b->bloch) return refuse_bloch(b, "the whole-grid transform (use fdtd2d_batch_set_dft_window)");
     int rc = use_device(b);
     if (rc) return rc;
     BCHK(b, hipStreamSynchronize(b->stream));
@@ -1359,6 +1552,9 @@ int fdtd2d_batch_set_dft_window(fdtd2d_batch_t *b, int row0, int col0, int nrows
             (long long)col0 + ncols > b->cols)
             return bfail(b, FDTD2D_E_ARG, "window (%d,%d)+%dx%d is empty or outside the %dx%d grid", row0, col0, nrows,
                          ncols, b->rows, b->cols);
+        if (b->bloch && col0 + ncols > b->cols - 1)
+            return bfail(b, FDTD2D_E_ARG, "window (%d,%d)+%dx%d touches column %d, the image of column 0: not while a "
+                         "Bloch phase is set", row0, col0, nrows, ncols, b->cols - 1);
     }
     int rc = use_device(b);
     if (rc) return rc;
@@ -1366,7 +1562,7 @@ int fdtd2d_batch_set_dft_window(fdtd2d_batch_t *b, int row0, int col0, int nrows
     for (void **p : {(void **)&b->win_acc, (void **)&b->win_omega, (void **)&b->win_ph, (void **)&b->win_held})
         release(p);
     b->win_nf = 0;
-    if (nfreq == 0) return 0;
+    if (nfreq == 0) return bloch_window(b);
     const size_t acc = (size_t)b->count * 16 * nfreq * (size_t)nrows * ncols, om = (size_t)b->count * nfreq * sizeof(double);
     if ((rc = alloc(b, (void **)&b->win_acc, acc)) || (rc = alloc(b, (void **)&b->win_omega, om)) ||
         (rc = alloc(b, (void **)&b->win_ph, 2 * om))) {
@@ -1380,7 +1576,7 @@ int fdtd2d_batch_set_dft_window(fdtd2d_batch_t *b, int row0, int col0, int nrows
     b->win_every = every;
     b->win_step0 = b->step;
     b->win_nf = nfreq;
-    return 0;
+    return bloch_window(b);
 }
 
 int fdtd2d_batch_read_dft_window(fdtd2d_batch_t *b, double *re, double *im)
@@ -1419,6 +1615,10 @@ int fdtd2d_batch_set_probes(fdtd2d_batch_t *b, int nprobe, const int *cells, lon
                              (int)(k / nprobe), (int)(k % nprobe), r, c, b->rows, b->cols);
             lin[k] = r * b->cols + c;
         }
+        const long long k = b->bloch ? probe_in_image(b, lin) : -1;
+        if (k >= 0)
+            return bfail(b, FDTD2D_E_ARG, "member %d probe %d: column %d is the image of column 0: not while a Bloch "
+                         "phase is set", (int)(k / nprobe), (int)(k % nprobe), b->cols - 1);
     }
     int rc = use_device(b);
     if (rc) return rc;
@@ -1426,7 +1626,8 @@ int fdtd2d_batch_set_probes(fdtd2d_batch_t *b, int nprobe, const int *cells, lon
     release((void **)&b->probe_cells);
     release((void **)&b->probe_trace);
     b->nprobe = 0;
-    if (nprobe == 0) return 0;
+    b->probe_host.clear();
+    if (nprobe == 0) return bloch_probes(b);
     const size_t trace = lin.size() * (size_t)capacity * sizeof(double);
     if ((rc = alloc(b, (void **)&b->probe_cells, lin.size() * sizeof(int))) ||
         (rc = alloc(b, (void **)&b->probe_trace, trace))) {
@@ -1440,7 +1641,8 @@ int fdtd2d_batch_set_probes(fdtd2d_batch_t *b, int nprobe, const int *cells, lon
     b->probe_cap = capacity;
     b->probe_step0 = b->step;
     b->nprobe = nprobe;
-    return 0;
+    b->probe_host = lin;
+    return bloch_probes(b);
 }
 
 int fdtd2d_batch_read_probes(fdtd2d_batch_t *b, double *out, long long first, long long count_samples)
@@ -1467,6 +1669,7 @@ int fdtd2d_batch_set_point_sources(fdtd2d_batch_t *b, int ncell, const int *cell
     if (!b) return FDTD2D_E_ARG;
     if (ncell < 0 || ncell > FDTD2D_BATCH_MAX_POINT_SOURCES)
         return bfail(b, FDTD2D_E_ARG, "ncell %d outside 0..%d", ncell, FDTD2D_BATCH_MAX_POINT_SOURCES);
+    if (ncell > 0 && b->bloch) return refuse_bloch(b, "a point source");
     std::vector<int> lin, own;
     std::vector<double> w;
     int ntab = ncell;                       // entries per member: a periodic batch lists column-0 cells at their images too
@@ -1565,6 +1768,7 @@ int fdtd2d_batch_run_channels(fdtd2d_batch_t *b, int nsteps, const double *amps,
     if (!b) return FDTD2D_E_ARG;
     if (nsteps < 0) return bfail(b, FDTD2D_E_ARG, "nsteps < 0");
     if (!chan) return bfail(b, FDTD2D_E_ARG, "chan must not be NULL");
+    if (b->bloch) return refuse_bloch(b, "a run with channels");
     if (!b->npts) return bfail(b, FDTD2D_E_STATE, "no point sources are set: call fdtd2d_batch_set_point_sources first");
     int rc = need_ready(b);
     if (rc) return rc;
@@ -1598,6 +1802,7 @@ int fdtd2d_batch_run_channels(fdtd2d_batch_t *b, int nsteps, const double *amps,
 int fdtd2d_batch_hold_dft_window(fdtd2d_batch_t *b)
 {
     if (!b) return FDTD2D_E_ARG;
+    if (b->bloch) return refuse_bloch(b, "the held window");
     if (!b->win_nf) return bfail(b, FDTD2D_E_STATE, "no window DFT is set");
     int rc = use_device(b);
     if (rc) return rc;
@@ -1612,6 +1817,7 @@ int fdtd2d_batch_dft_window_product(fdtd2d_batch_t *b, const double *coef_re, co
 {
     if (!b) return FDTD2D_E_ARG;
     if (!coef_re || !coef_im || !out) return bfail(b, FDTD2D_E_ARG, "coef_re, coef_im and out must not be NULL");
+    if (b->bloch) return refuse_bloch(b, "the window product");
     if (!b->win_nf) return bfail(b, FDTD2D_E_STATE, "no window DFT is set");
     if (!b->win_held) return bfail(b, FDTD2D_E_STATE, "no held window: call fdtd2d_batch_hold_dft_window first");
     int rc = use_device(b);
@@ -1648,6 +1854,7 @@ int fdtd2d_batch_probe_spectra(fdtd2d_batch_t *b, int nfreq, const double *omega
                                long long count_samples, double *re, double *im, double *peak)
 {
     if (!b) return FDTD2D_E_ARG;
+    if (b->bloch) return refuse_bloch(b, "fdtd2d_batch_probe_spectra");
     if (!b->nprobe) return bfail(b, FDTD2D_E_STATE, "no probes are set");
     if (nfreq < 0 || nfreq > FDTD2D_BATCH_MAX_DFT_FREQS)
         return bfail(b, FDTD2D_E_ARG, "nfreq %d outside 0..%d", nfreq, FDTD2D_BATCH_MAX_DFT_FREQS);
@@ -1693,6 +1900,7 @@ int fdtd2d_batch_field_absmax(fdtd2d_batch_t *b, int field, double *out)
 {
     if (!b) return FDTD2D_E_ARG;
     if (!out) return bfail(b, FDTD2D_E_ARG, "out must not be NULL");
+    if (b->bloch) return refuse_bloch(b, "fdtd2d_batch_field_absmax");
     if (field != FDTD2D_FIELD_EZ && field != FDTD2D_FIELD_HX && field != FDTD2D_FIELD_HY)
         return bfail(b, FDTD2D_E_ARG, "field %d: FDTD2D_FIELD_EZ, _HX or _HY", field);
     int rc = use_device(b);
@@ -1817,6 +2025,7 @@ int fdtd2d_batch_set_periodic(fdtd2d_batch_t *b, int on)
     if (rc) return rc;
     BCHK(b, hipStreamSynchronize(b->stream));
     if (!on) {
+        if (b->bloch && (rc = bloch_off(b))) return rc;
         if ((rc = fdtd2d_batch_set_point_sources(b, 0, nullptr, 0, nullptr))) return rc;
         b->periodic = false;
         if (b->sigma_implicit) {
@@ -1863,6 +2072,174 @@ int fdtd2d_batch_set_periodic(fdtd2d_batch_t *b, int on)
     if (!b->ezx && (rc = unit_layer(b))) return undo(rc);
     if ((rc = copy_image(b, b->ez[b->cur])) || (rc = copy_image(b, b->ezx))) return undo(rc);
     if (b->have_mat && !b->ca && (rc = periodic_coefficients(b))) return undo(rc);
+    return 0;
+}
+
+// ---- fdtd2d_batch_bloch.h ----------------------------------------------------------------------------------------
+
+int fdtd2d_batch_set_bloch(fdtd2d_batch_t *b, const double *cos_phi, const double *sin_phi)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!cos_phi != !sin_phi) return bfail(b, FDTD2D_E_ARG, "cos_phi and sin_phi must both be given (or both NULL)");
+    int rc = use_device(b);
+    if (rc) return rc;
+    if (!cos_phi) return b->bloch ? bloch_off(b) : 0;
+    if (!b->periodic)
+        return bfail(b, FDTD2D_E_STATE, "a Bloch phase needs periodic columns: call fdtd2d_batch_set_periodic first");
+    for (int m = 0; m < b->count; ++m)
+        if (!std::isfinite(cos_phi[m]) || !std::isfinite(sin_phi[m]))
+            return bfail(b, FDTD2D_E_ARG, "member %d: the rotation (%g, %g) is not finite", m, cos_phi[m], sin_phi[m]);
+    if (!b->bloch) {
+        if (b->dft) return refuse_bloch(b, "the whole-grid transform (remove it, use fdtd2d_batch_set_dft_window)");
+        if (b->npts) return refuse_bloch(b, "a point source (remove them)");
+        if (b->win_held) return refuse_bloch(b, "the held window (set the window again)");
+        if (b->win_nf && b->win_c0 + b->win_nc > b->cols - 1)
+            return bfail(b, FDTD2D_E_ARG, "window (%d,%d)+%dx%d touches column %d, the image of column 0: not with a Bloch "
+                         "phase", b->win_r0, b->win_c0, b->win_nr, b->win_nc, b->cols - 1);
+        const long long k = probe_in_image(b, b->probe_host);
+        if (k >= 0)
+            return bfail(b, FDTD2D_E_ARG, "member %d probe %d: column %d is the image of column 0: not with a Bloch "
+                         "phase", (int)(k / b->nprobe), (int)(k % b->nprobe), b->cols - 1);
+    }
+    std::vector<double> rho((size_t)b->count * 2);
+    std::vector<unsigned char> rt(rho.size() * b->esz);
+    for (size_t k = 0; k < rho.size(); ++k) {
+        rho[k] = as_engine(b, k % 2 ? sin_phi[k / 2] : cos_phi[k / 2]);
+        if (b->dtype == FDTD2D_F32) ((float *)rt.data())[k] = (float)rho[k];
+        else ((double *)rt.data())[k] = rho[k];
+    }
+    BCHK(b, hipStreamSynchronize(b->stream));   // a running launch may still read the old rotations
+    if (!b->bloch) {
+        const size_t wn = (size_t)b->count * 2 * (b->cols - 1);
+        auto undo = [&](int code) {
+            bloch_off(b);
+            return code;
+        };
+        for (void **p : {&b->ez_im, &b->hx_im, &b->hy_im, &b->ezx_im}) {
+            if ((rc = alloc(b, p, b->field_bytes))) return undo(rc);
+            if (hipMemsetAsync(*p, 0, b->field_bytes, b->stream) != hipSuccess)
+                return undo(bfail(b, FDTD2D_E_NOMEM, "hipMemset of the imaginary fields failed"));
+        }
+        if (hipStreamSynchronize(b->stream) != hipSuccess)
+            return undo(bfail(b, FDTD2D_E_NOMEM, "hipMemset of the imaginary fields failed"));
+        if ((rc = alloc(b, &b->rho, rt.size())) || (rc = alloc(b, (void **)&b->bloch_w, wn * sizeof(double))))
+            return undo(rc);
+        b->bloch = true;
+        if ((rc = fdtd2d_batch_set_bloch_source(b, nullptr, nullptr)) || (rc = bloch_window(b)) || (rc = bloch_probes(b)))
+            return undo(rc);
+    }
+    BCHK(b, hipMemcpy(b->rho, rt.data(), rt.size(), hipMemcpyHostToDevice));
+    b->rho_host.swap(rho);
+    return 0;
+}
+
+int fdtd2d_batch_set_bloch_source(fdtd2d_batch_t *b, const double *wr, const double *wi)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (!wr != !wi) return bfail(b, FDTD2D_E_ARG, "wr and wi must both be given (or both NULL)");
+    const size_t Q = (size_t)b->cols - 1;
+    std::vector<double> w((size_t)b->count * 2 * Q);
+    for (int m = 0; m < b->count; ++m)
+        for (size_t j = 0; j < Q; ++j) {
+            const double r = wr ? wr[m * Q + j] : 1.0, i = wi ? wi[m * Q + j] : 0.0;
+            if (!std::isfinite(r) || !std::isfinite(i))
+                return bfail(b, FDTD2D_E_ARG, "member %d: the source weight of column %zu is not finite", m, j);
+            w[(size_t)m * 2 * Q + j] = r;
+            w[(size_t)m * 2 * Q + Q + j] = i;
+        }
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));   // a running launch may still read the old weights
+    BCHK(b, hipMemcpy(b->bloch_w, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
+    return 0;
+}
+
+int fdtd2d_batch_run_bloch(fdtd2d_batch_t *b, int nsteps, const double *amps_re, const double *amps_im)
+{
+    int rc = need_ready(b);
+    if (rc) return rc;
+    if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (nsteps < 0) return bfail(b, FDTD2D_E_ARG, "nsteps < 0");
+    if (amps_im && !amps_re) return bfail(b, FDTD2D_E_ARG, "amps_im needs amps_re (zeros for a purely imaginary source)");
+    for (int m = 0; m < b->count; ++m)
+        if (b->courant[m] > 1.0)
+            return bfail(b, FDTD2D_E_COURANT, "Courant stability condition not met for member %d: %.17g > 1.0", m,
+                         b->courant[m]);
+    if (nsteps == 0) return 0;
+    const double *dev_amps = nullptr;
+    b->run_amps_im = nullptr;
+    if (amps_re && b->have_src) {
+        const size_t bytes = (size_t)b->count * nsteps * sizeof(double);
+        if ((rc = stage(b, &b->amps, &b->amps_cap, amps_re, bytes))) return rc;
+        dev_amps = b->amps;
+        if (amps_im) {
+            if ((rc = stage(b, &b->amps_im, &b->amps_im_cap, amps_im, bytes))) return rc;
+            b->run_amps_im = b->amps_im;
+        }
+    }
+    return b->dtype == FDTD2D_F32 ? run_impl<float>(b, nsteps, dev_amps, nsteps)
+                                  : run_impl<double>(b, nsteps, dev_amps, nsteps);
+}
+
+int fdtd2d_batch_transfer_bloch(fdtd2d_batch_t *b, void *Ez_im, void *Hx_im, void *Hy_im, void *Ezx_im, int host_dtype,
+                                int to_device)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (host_dtype != FDTD2D_F32 && host_dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad host_dtype");
+    int rc = use_device(b);
+    if (rc) return rc;
+    if (to_device) {
+        if (Ez_im && ((rc = copy_in(b, b->ez_im, Ez_im, host_dtype, b->rows, b->cols)) || (rc = copy_image(b, b->ez_im))))
+            return rc;
+        if (Hx_im && (rc = copy_in(b, b->hx_im, Hx_im, host_dtype, b->rows, b->cols - 1))) return rc;
+        if (Hy_im && (rc = copy_in(b, b->hy_im, Hy_im, host_dtype, b->rows - 1, b->cols))) return rc;
+        if (Ezx_im && ((rc = copy_in(b, b->ezx_im, Ezx_im, host_dtype, b->rows, b->cols)) ||
+                       (rc = copy_image(b, b->ezx_im))))
+            return rc;
+        return 0;
+    }
+    if (Ez_im && (rc = copy_out_bloch(b, b->ez[b->cur], b->ez_im, Ez_im, host_dtype, 1))) return rc;
+    if (Hx_im && (rc = copy_out(b, b->hx_im, Hx_im, host_dtype, b->rows, b->cols - 1))) return rc;
+    if (Hy_im && (rc = copy_out(b, b->hy_im, Hy_im, host_dtype, b->rows - 1, b->cols))) return rc;
+    if (Ezx_im && (rc = copy_out_bloch(b, b->ezx, b->ezx_im, Ezx_im, host_dtype, 1))) return rc;
+    return 0;
+}
+
+int fdtd2d_batch_read_dft_window_bloch(fdtd2d_batch_t *b, double *re, double *im)
+{
+    if (!b || !re || !im) return FDTD2D_E_ARG;
+    if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (!b->win_nf || !b->win_acc_im) return bfail(b, FDTD2D_E_STATE, "no window DFT is set");
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    const size_t per = (size_t)b->win_nf * b->win_nr * b->win_nc;   // one member's re (or im)
+    std::vector<double> acc((size_t)b->count * 2 * per);
+    BCHK(b, hipMemcpy(acc.data(), b->win_acc_im, acc.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int m = 0; m < b->count; ++m) {
+        std::memcpy(re + m * per, acc.data() + 2 * m * per, per * sizeof(double));
+        std::memcpy(im + m * per, acc.data() + (2 * m + 1) * per, per * sizeof(double));
+    }
+    return 0;
+}
+
+int fdtd2d_batch_read_probes_bloch(fdtd2d_batch_t *b, double *out, long long first, long long count_samples)
+{
+    if (!b || !out) return FDTD2D_E_ARG;
+    if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (!b->nprobe || !b->probe_trace_im) return bfail(b, FDTD2D_E_STATE, "no probes are set");
+    if (first < 0 || count_samples < 0 || first + count_samples > b->probe_cap)
+        return bfail(b, FDTD2D_E_ARG, "samples [%lld, %lld) outside the capacity %lld", first, first + count_samples,
+                     b->probe_cap);
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    if (count_samples == 0) return 0;
+    const size_t w = (size_t)count_samples * sizeof(double);
+    BCHK(b, hipMemcpy2D(out, w, b->probe_trace_im + first, (size_t)b->probe_cap * sizeof(double), w,
+                        (size_t)b->count * b->nprobe, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -26,8 +26,8 @@
  *
  * A periodic batch always runs on the periodic step kernels (the lossy PML family with its monitors and point sources
  * silent when unset); a uniform-material batch gets coefficient arrays.  The capacity rule of the resident path is the
- * lossy PML one (7 arrays and the factors).  Not supported: the Mur frame, a Bloch phase (complex fields), periodic
- * rows, the single-grid engine. */
+ * lossy PML one (7 arrays and the factors).  A Bloch phase (complex fields, one phase per member) is the companion
+ * fdtd2d_batch_bloch.h.  Not supported: the Mur frame, periodic rows, the single-grid engine. */
 #ifndef FDTD2D_BATCH_PERIODIC_H
 #define FDTD2D_BATCH_PERIODIC_H
 

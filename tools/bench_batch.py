@@ -50,9 +50,14 @@ array eps with random binary permittivity, a ricker line source per member):
                               same one silent point source, timed alternately in one process: periodic_ms,
                               lossy_pml_ms, periodic_over_lossy_pml, both paths and LDS sizes.  Default: 1024 members
                               of 60 rows x 61 columns, a 10-cell layer, 1000 steps.
+  --bloch                     instead: a Bloch batch (set_bloch_phase, a phase sweep over the members, ramp weights)
+                              against the plain periodic batch of the same members, layer and conductivity, timed
+                              alternately in one process: bloch_ms, periodic_ms, bloch_over_periodic, both paths and
+                              LDS sizes.  A Bloch member carries two members' fields, so the number to beat is 2.
+                              Default: 1024 members of 60 x 60, a 10-cell layer, 1000 steps.
 Usage: python tools/bench_batch.py [--count 1024 --rows 60 --cols 60 --steps 1000] [--reps 5] [--loop-members 16]
                                    [--boundary {mur,pml} --pml-cells 10] [--monitors] [--adjoint] [--lossy]
-                                   [--periodic]
+                                   [--periodic] [--bloch]
 """
 import argparse
 import json
@@ -318,6 +323,53 @@ def bench_periodic(count, rows, cols, steps, dtype, reps, pml_cells):
             "periodic_mcell_steps_per_s": round(count * rows * cols * steps / (med_p * 1e-3) / 1e6, 1)}
 
 
+def bench_bloch(count, rows, cols, steps, dtype, reps, pml_cells):
+    eps, rects, amps = members(count, rows, cols, steps)
+    c00 = courant00(eps, dtype)
+    rng = np.random.default_rng(1)
+    g = max(6, pml_cells)
+    sigma = np.zeros((count, rows, cols))
+    sigma[:, g:rows - g, :] = 20.0 * rng.random((count, rows - 2 * g, cols))
+    phis = np.linspace(0.0, np.pi, count)
+
+    def batch(bloch):
+        b = fd.BatchEngine(count, rows, cols, DT, DX, dtype=dtype, boundary="periodic")
+        b.set_materials(eps.astype(dtype), fd.MU0).set_sources(rects)
+        b.set_pml(pml_cells, courant00=c00).set_conductivity(sigma)
+        if bloch:
+            b.set_bloch_phase(phis).set_bloch_source("ramp")
+        b.run(steps, amps).sync()                      # warm-up: code objects, clocks
+        return b
+
+    def timed(b):
+        b.reset().sync()
+        t0 = time.perf_counter()
+        b.run(steps, amps).sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    with batch(False) as per, batch(True) as blo:
+        assert blo.bloch and blo.periodic and per.periodic and not per.bloch
+        l0 = blo.launches
+        blo.reset().run(steps, amps).sync()
+        launches = blo.launches - l0
+        per_ms, blo_ms = [], []
+        for _ in range(reps):
+            per_ms.append(timed(per))
+            blo_ms.append(timed(blo))
+        paths = ["resident" if b.resident else "streamed" for b in (per, blo)]
+        lds = [b.lds_bytes for b in (per, blo)]
+    med_p, med_b = float(np.median(per_ms)), float(np.median(blo_ms))
+    return {"count": count, "rows": rows, "cols": cols, "steps": steps, "dtype": np.dtype(dtype).name,
+            "materials": "arrays", "pml_cells": pml_cells, "reps": reps, "periodic_path": paths[0], "bloch_path": paths[1],
+            "periodic_lds_bytes_per_member": lds[0], "bloch_lds_bytes_per_member": lds[1],
+            "periodic_ms": round(med_p, 4), "periodic_ms_min": round(min(per_ms), 4),
+            "periodic_ms_all": [round(v, 4) for v in per_ms],
+            "bloch_ms": round(med_b, 4), "bloch_ms_min": round(min(blo_ms), 4),
+            "bloch_ms_all": [round(v, 4) for v in blo_ms],
+            "bloch_over_periodic": round(med_b / med_p, 3), "launches_per_run": launches,
+            "bloch_mcell_steps_per_s": round(count * rows * cols * steps / (med_b * 1e-3) / 1e6, 1)}
+
+
 def bench_adjoint(count, rows, cols, steps, dtype, reps, pml_cells):
     from fdtd2d_amd.adjoint import channel_system, gradient_coefficients
     dt = 2e-13                                   # the Gaussian envelope of the channels (t0 = 4.5 / fc) ends by step 1200
@@ -469,7 +521,12 @@ def main():
     ap.add_argument("--adjoint", action="store_true", help="time batch_eps_gradient (see above)")
     ap.add_argument("--lossy", action="store_true", help="time the lossy kernels against the point-source ones")
     ap.add_argument("--periodic", action="store_true", help="time the periodic kernels against the lossy PML ones")
+    ap.add_argument("--bloch", action="store_true", help="time a Bloch batch against the plain periodic one")
     a = ap.parse_args()
+    if a.bloch:
+        print(json.dumps(bench_bloch(a.count or 1024, a.rows or 60, a.cols or 60, a.steps or 1000, np.dtype(a.dtype),
+                                     a.reps, a.pml_cells)), flush=True)
+        return
     if a.periodic:
         print(json.dumps(bench_periodic(a.count or 1024, a.rows or 60, a.cols or 61, a.steps or 1000, np.dtype(a.dtype),
                                         a.reps, a.pml_cells)), flush=True)
