@@ -915,13 +915,14 @@ int fdtd2d_set_dft(fdtd2d_t *h, int row0, int col0, int nrows, int ncols, int nf
     int rc = use_device(h);
     if (rc) return rc;
     if (h->pend_nt) return fail(h, FDTD2D_E_STATE, "a partial pass is pending: commit it first");
+    // (a refused call leaves the transform that is set as it is)
+    if (nfreq != 0 && (nfreq < 0 || nfreq > 16 || !omega || every < 1 || nrows < 1 || ncols < 1 || row0 < 0 || col0 < 0 ||
+                       row0 + nrows > h->rows || col0 + ncols > h->cols))
+        return fail(h, FDTD2D_E_ARG, "need 1..16 frequencies, every >= 1 and a window inside the %dx%d grid", h->rows, h->cols);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (h->dft_acc) { (void)hipFree(h->dft_acc); h->dft_acc = nullptr; }
     h->dft_n = 0;
     if (nfreq == 0) return 0;
-    if (nfreq < 0 || nfreq > 16 || !omega || every < 1 || nrows < 1 || ncols < 1 || row0 < 0 || col0 < 0 ||
-        row0 + nrows > h->rows || col0 + ncols > h->cols)
-        return fail(h, FDTD2D_E_ARG, "need 1..16 frequencies, every >= 1 and a window inside the %dx%d grid", h->rows, h->cols);
     h->dft_row0 = row0; h->dft_col0 = col0; h->dft_rows = nrows; h->dft_cols = ncols; h->dft_every = every;
     for (int k = 0; k < nfreq; ++k) h->dft_omega[k] = omega[k];
     h->dft_step0 = h->step;

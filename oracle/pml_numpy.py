@@ -70,9 +70,12 @@ def step(Ez, Ezx, Hx, Hy, eps, mu, dt, dx, P):
     return Ez, Ezx, Hx, Hy
 
 
-def leapfrog(Ez, Ezx, Hx, Hy, eps, mu, dt, dx, nsteps, src_row, src_col, amps, P):
+def leapfrog(Ez, Ezx, Hx, Hy, eps, mu, dt, dx, nsteps, src_row, src_col, amps, P, on_step=None):
+    """on_step(n, Ez, Ezx, Hx, Hy) is called after every step (source added), n counting from 0."""
     for n in range(nsteps):
         step(Ez, Ezx, Hx, Hy, eps, mu, dt, dx, P)
         if amps is not None:
             Ez[src_row, src_col] = Ez.dtype.type(np.float64(Ez[src_row, src_col]) + np.float64(amps[n]))
+        if on_step is not None:
+            on_step(n, Ez, Ezx, Hx, Hy)
     return Ez, Ezx, Hx, Hy
