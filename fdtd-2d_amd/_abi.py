@@ -50,6 +50,8 @@ BATCH_INFO_LOSSY = 14
 BATCH_INFO_PERIODIC = 15
 # include/fdtd2d_batch_bloch.h
 BATCH_INFO_BLOCH = 16
+# include/fdtd2d_batch_bloch_adjoint.h
+BATCH_INFO_BLOCH_POINT_SOURCES, BATCH_INFO_HELD_BLOCH_WINDOW = 17, 18
 
 _vp, _i, _d, _ll = C.c_void_p, C.c_int, C.c_double, C.c_longlong
 
@@ -180,6 +182,18 @@ BATCH_BLOCH_SIGNATURES = {
     "fdtd2d_batch_read_probes_bloch": (_i, [_vp, C.POINTER(_d), _ll, _ll]),
 }
 
+# every symbol include/fdtd2d_batch_bloch_adjoint.h declares (point sources, the held window, its product, probe spectra and
+# field maxima of a Bloch batch: what an adjoint run of complex fields needs)
+BATCH_BLOCH_ADJOINT_SIGNATURES = {
+    "fdtd2d_batch_set_bloch_point_sources": (_i, [_vp, _i, C.POINTER(_i), _i, C.POINTER(_d)]),
+    "fdtd2d_batch_run_bloch_channels": (_i, [_vp, _i, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), _i, _i]),
+    "fdtd2d_batch_hold_bloch_window": (_i, [_vp]),
+    "fdtd2d_batch_bloch_window_product": (_i, [_vp, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_bloch_probe_spectra": (_i, [_vp, _i, C.POINTER(_d), _ll, _ll, C.POINTER(_d), C.POINTER(_d),
+                                              C.POINTER(_d)]),
+    "fdtd2d_batch_bloch_field_absmax": (_i, [_vp, _i, C.POINTER(_d)]),
+}
+
 # transport callback of fdtd2d_slab_attach
 EXCHANGE_FN = C.CFUNCTYPE(_i, _vp, _vp, _vp, _vp, _vp, _ll, _vp)
 
@@ -230,7 +244,7 @@ def load():
         for name, (res, args) in {**SIGNATURES, **BATCH_PML_SIGNATURES, **BATCH_MONITOR_SIGNATURES,
                                    **BATCH_ADJOINT_SIGNATURES, **BATCH_DESIGN_SIGNATURES,
                                    **BATCH_LOSSY_SIGNATURES, **BATCH_PERIODIC_SIGNATURES,
-                                   **BATCH_BLOCH_SIGNATURES}.items():
+                                   **BATCH_BLOCH_SIGNATURES, **BATCH_BLOCH_ADJOINT_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

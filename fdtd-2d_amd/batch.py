@@ -169,10 +169,13 @@ class BatchEngine:
         read).  None (and no rotation) turns the phase off: a plain periodic batch again, real parts as they are.
         While a phase is set the fields, the window DFT and the probes are complex (upload, download, download_ezx,
         read_dft_window, read_probes), run() takes complex amps, and set_dft, point sources and channels, the held
-        window, probe_spectra, field_absmax and the adjoint helpers are refused, as are windows and probes touching
-        column C-1."""
+        window, probe_spectra, field_absmax and the real adjoint helpers are refused, as are windows and probes touching
+        column C-1.  Their complex counterparts are set_bloch_point_sources, run_bloch_channels, hold_bloch_window,
+        bloch_window_product, bloch_probe_spectra and bloch_field_absmax (batch_bloch_gradient, BlochAdjointSession)."""
         if phi is None and rotation is None:
             self._ck(self._lib.fdtd2d_batch_set_bloch(self._h, None, None))
+            if self._bloch is not None:
+                self._npoint = (0, 0)         # the point sources of a Bloch batch go with the phase
             self._bloch = self._phi = None
             return self
         if rotation is not None:
@@ -517,6 +520,118 @@ class BatchEngine:
         re, im = np.ascontiguousarray(k.real), np.ascontiguousarray(k.imag)
         out = np.empty((self.count, nr, nc))
         self._ck(self._lib.fdtd2d_batch_dft_window_product(self._h, _dptr(re), _dptr(im), _dptr(out)))
+        return out
+
+    # -- the same for a Bloch batch (fdtd2d_batch_bloch_adjoint.h) -----------------------------------------------------
+    def _need_bloch(self):
+        """The library's refusal of a Bloch call without a phase, before the call."""
+        if self._bloch is None:
+            raise _abi.Fdtd2dError(_abi.E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first")
+
+    def set_bloch_point_sources(self, cells, weights=None):
+        """set_point_sources for a Bloch batch: each cell adds the real sum_c weights[p, c] * channels[c, n] to the real
+        part of Ez after the rectangle source of step n of a run_bloch_channels (the imaginary part takes nothing; the
+        seam carries the series into it).  Cells lie in columns 0..C-2; cells None removes them, and so does turning
+        the phase off."""
+        self._need_bloch()
+        if cells is None:
+            self._ck(self._lib.fdtd2d_batch_set_bloch_point_sources(self._h, 0, None, 0, None))
+            self._npoint = (0, 0)
+            return self
+        c = _probe_cells(cells, self.count)
+        if np.any(c[..., 1] >= self.cols - 1):
+            b = int(np.nonzero((c[..., 1] >= self.cols - 1).any(axis=1))[0][0])
+            raise _abi.Fdtd2dError(_abi.E_ARG, f"member {b}: a point source lies in column {self.cols - 1}, the image "
+                                   "of column 0 of a periodic batch")
+        w = np.asarray(weights, dtype=np.float64)
+        if w.ndim == 2:
+            w = np.broadcast_to(w, (self.count,) + w.shape)
+        if w.ndim != 3 or w.shape[:2] != c.shape[:2]:
+            raise ValueError(f"weights must have shape ({c.shape[1]}, K) or ({self.count}, {c.shape[1]}, K), "
+                             f"got {np.shape(weights)}")
+        w = np.ascontiguousarray(w)
+        self._ck(self._lib.fdtd2d_batch_set_bloch_point_sources(self._h, int(c.shape[1]),
+                                                                c.ctypes.data_as(C.POINTER(C.c_int)), int(w.shape[2]),
+                                                                _dptr(w)))
+        self._npoint = (int(c.shape[1]), int(w.shape[2]))
+        return self
+
+    def run_bloch_channels(self, nsteps, amps=None, channels=None, conjugate=False):
+        """run() of a Bloch batch with the point sources of set_bloch_point_sources: amps (B, nsteps) real or complex
+        (None = no rectangle source), channels (K, nsteps) for every member or (B, K, nsteps) float64.  conjugate True
+        steps with the rotation conj(rho) = (c, -s): the transpose of the one-step operator, what an adjoint run needs;
+        downloads after it rotate the image column by that rotation."""
+        nsteps = int(nsteps)
+        self._need_bloch()
+        self._need_pml()
+        a = ai = None
+        if amps is not None:
+            z = np.asarray(amps)
+            if z.ndim != 2 or z.shape[0] != self.count or z.shape[1] < nsteps:
+                raise ValueError(f"amps must have shape ({self.count}, {nsteps}), got {z.shape}")
+            a = np.ascontiguousarray(z.real[:, :nsteps], dtype=np.float64)
+            if np.iscomplexobj(z):
+                ai = np.ascontiguousarray(z.imag[:, :nsteps], dtype=np.float64)
+        ch = np.asarray(channels, dtype=np.float64)
+        K = self._npoint[1]
+        if ch.shape[-1:] != () and ch.shape[-1] >= nsteps:
+            ch = ch[..., :nsteps]
+        if ch.shape not in ((K, nsteps), (self.count, K, nsteps)):
+            raise ValueError(f"channels must have shape ({K}, {nsteps}) or ({self.count}, {K}, {nsteps}), "
+                             f"got {ch.shape}")
+        ch = np.ascontiguousarray(ch)
+        self._ck(self._lib.fdtd2d_batch_run_bloch_channels(self._h, nsteps, None if a is None else _dptr(a),
+                                                           None if ai is None else _dptr(ai), _dptr(ch),
+                                                           int(ch.ndim == 3), int(bool(conjugate))))
+        return self
+
+    def hold_bloch_window(self):
+        """hold_dft_window for a Bloch batch: a device copy of both parts of the window DFT."""
+        self._need_bloch()
+        self._ck(self._lib.fdtd2d_batch_hold_bloch_window(self._h))
+        return self
+
+    def bloch_window_product(self, coef) -> np.ndarray:
+        """float64 (B, nrows, ncols): sum_k Re(coef[b, k] * held[b, k] * current[b, k]) of the complex windows
+        W(re) + 1j * W(im), on the device; the plain product, nothing conjugated.  coef: complex (F,) or (B, F)."""
+        self._need_bloch()
+        f, nr, nc = self._win or (0, 1, 1)
+        k = np.asarray(coef, dtype=np.complex128)
+        if k.ndim == 1:
+            k = np.broadcast_to(k, (self.count, k.size))
+        if self._win is not None and k.shape != (self.count, f):
+            raise ValueError(f"coef must have shape ({f},) or ({self.count}, {f}), got {np.shape(coef)}")
+        re, im = np.ascontiguousarray(k.real), np.ascontiguousarray(k.imag)
+        out = np.empty((self.count, nr, nc))
+        self._ck(self._lib.fdtd2d_batch_bloch_window_product(self._h, _dptr(re), _dptr(im), _dptr(out)))
+        return out
+
+    def bloch_probe_spectra(self, omegas, first=0, count=None, peak=False):
+        """probe_spectra of the complex traces of a Bloch batch: complex128 (B, P, F).  peak True: also float64 (B,), the
+        larger of the largest |real sample| and the largest |imaginary sample| of each member in the range."""
+        self._need_bloch()
+        w = _window_omegas(omegas, self.count)
+        if count is None:
+            count = max(0, self.probe_samples - int(first))
+        F = int(w.shape[1])
+        re, im = np.empty((self.count, self._nprobe, F)), np.empty((self.count, self._nprobe, F))
+        pk = np.empty(self.count) if peak else None
+        buf = (re, im) if re.size else (np.empty(1), np.empty(1))    # a refused call still passes valid pointers
+        self._ck(self._lib.fdtd2d_batch_bloch_probe_spectra(self._h, F, _dptr(w) if F else None, int(first), int(count),
+                                                            _dptr(buf[0]) if F else None, _dptr(buf[1]) if F else None,
+                                                            None if pk is None else _dptr(pk)))
+        out = re + 1j * im
+        return (out, pk) if peak else out
+
+    def bloch_field_absmax(self, which="Ez"):
+        """float64 (B,): max(max |Re field|, max |Im field|) over each member's cells, reduced on the device; of Ez over
+        columns 0..C-2 (the image column repeats column 0, rotated).  which "Ez", "Hx" or "Hy"."""
+        codes = {"Ez": _abi.FIELD_EZ, "Hx": _abi.FIELD_HX, "Hy": _abi.FIELD_HY}
+        if which not in codes:
+            raise ValueError(f'which must be "Ez", "Hx" or "Hy", not {which!r}')
+        self._need_bloch()
+        out = np.empty(self.count)
+        self._ck(self._lib.fdtd2d_batch_bloch_field_absmax(self._h, codes[which], _dptr(out)))
         return out
 
     def run_waveform(self, nsteps, kind="ricker", fc=30e9, step0=0):

@@ -12,9 +12,12 @@
 // With a conductivity set (fdtd2d_batch_lossy.h) every run takes the lossy kernels of batch_lossy.hip.
 // With periodic columns (fdtd2d_batch_periodic.h) every run takes the periodic kernels of batch_periodic.hip.
 // With a Bloch phase (fdtd2d_batch_bloch.h) every run takes the complex-field kernels of batch_bloch.hip.
+// fdtd2d_batch_run_bloch_channels (fdtd2d_batch_bloch_adjoint.h) takes their point-source instances
+// (batch_bloch_adjoint.hip), which also holds the product kernel of two complex windows.
 #include "../../include/fdtd2d.h"
 #include "../../include/fdtd2d_batch_adjoint.h"
 #include "../../include/fdtd2d_batch_bloch.h"
+#include "../../include/fdtd2d_batch_bloch_adjoint.h"
 #include "../../include/fdtd2d_batch_design.h"
 #include "../../include/fdtd2d_batch_lossy.h"
 #include "../../include/fdtd2d_batch_monitor.h"
@@ -35,6 +38,7 @@
 #include "kernels_batch.hpp"
 #include "kernels_batch_adjoint.hpp"
 #include "kernels_batch_bloch.hpp"
+#include "kernels_batch_bloch_adjoint.hpp"
 #include "kernels_batch_design.hpp"
 #include "kernels_batch_lossy.hpp"
 #include "kernels_batch_monitor.hpp"
@@ -81,6 +85,11 @@ struct fdtd2d_batch {
     size_t amps_im_cap = 0;
     const double *run_amps_im = nullptr;  // device imaginary amplitudes of the run in progress (nullptr = zero)
     std::vector<int> probe_host;          // the probes' cells as the device holds them (row * C + col)
+    // fdtd2d_batch_bloch_adjoint.h: count x {c, -s} beside rho, whether the last run took it (downloads rotate the image
+    // by the rotation the run used), and the held copy of the imaginary part's window (win_held holds the real part's)
+    void *rho_conj = nullptr;
+    bool run_conj = false;
+    double *win_held_im = nullptr;
 
     int *rect = nullptr;                  // device copy of the source rectangles (4 per member)
     bool have_src = false;                // some member has a non-empty rectangle
@@ -124,6 +133,9 @@ struct fdtd2d_batch {
     hipStream_t own_stream = nullptr, stream = nullptr;
     std::string err;
 };
+
+// the body of fdtd2d_batch_set_point_sources, shared with fdtd2d_batch_set_bloch_point_sources
+static int batch_set_points(fdtd2d_batch *b, int ncell, const int *cells, int nchan, const double *weights);
 
 namespace {
 
@@ -238,6 +250,7 @@ int zero_fields(fdtd2d_batch *b)
         for (void *p : {b->ez_im, b->hx_im, b->hy_im, b->ezx_im}) BCHK(b, hipMemsetAsync(p, 0, b->field_bytes, b->stream));
     b->cur = 0;
     b->step = 0;
+    b->run_conj = false;
     return 0;
 }
 
@@ -686,19 +699,25 @@ int run_periodic(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_
 }
 
 // ---- Bloch runs (fdtd2d_batch_bloch.h): the periodic paths with the complex-field kernels of batch_bloch.hip ----------
-template <class T> fdtd::BatchBloch<T> bloch_view(const fdtd2d_batch *b)
+template <class T> fdtd::BatchBloch<T> bloch_view(const fdtd2d_batch *b, bool conj)
 {
-    return fdtd::BatchBloch<T>{(T *)b->ez_im, (T *)b->hx_im, (T *)b->hy_im, (T *)b->ezx_im, (const T *)b->rho,
+    return fdtd::BatchBloch<T>{(T *)b->ez_im, (T *)b->hx_im, (T *)b->hy_im, (T *)b->ezx_im,
+                               (const T *)(conj ? b->rho_conj : b->rho),
                                b->bloch_w, b->have_src ? b->run_amps_im : nullptr, b->win_acc_im, b->probe_trace_im};
 }
 
-template <class T> int run_bloch(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride)
+// pts: the point sources of fdtd2d_batch_run_bloch_channels (nullptr: none, the kernels of batch_bloch.hip); conj: step
+// with (c, -s)
+template <class T>
+int run_bloch(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts = nullptr,
+              bool conj = false)
 {
-    if (!b->ca || !b->ezx || !b->ez_im) return bfail(b, FDTD2D_E_STATE, "Bloch batch without its arrays");
-    const fdtd::BatchBlochKernels &K = fdtd::batch_bloch_kernels<T>();
+    if (!b->ca || !b->ezx || !b->ez_im || !b->rho_conj) return bfail(b, FDTD2D_E_STATE, "Bloch batch without its arrays");
+    const fdtd::BatchBlochKernels &K = pts ? fdtd::batch_bloch_pts_kernels<T>() : fdtd::batch_bloch_kernels<T>();
     fdtd::BatchPml<T> p = pml_view<T>(b);
     fdtd::BatchMon m = mon_view(b);
-    fdtd::BatchBloch<T> bl = bloch_view<T>(b);
+    fdtd::BatchBloch<T> bl = bloch_view<T>(b, conj);
+    b->run_conj = conj;
     const T *ca = (const T *)b->ca;
     if (use_resident(b)) {
         const int cells = b->rows * b->cols, threads = resident_threads(cells);
@@ -720,7 +739,8 @@ template <class T> int run_bloch(fdtd2d_batch *b, int nsteps, const double *amps
             fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
             v.ce = (const T *)b->cb;
             void *args[] = {&v, &p, &m, &bl, &ca, &n0, &nt, &step_base};
-            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads), args, lds);
+            void *args_pts[] = {&v, &p, &m, &bl, pts, &ca, &n0, &nt, &step_base};
+            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads), pts ? args_pts : args, lds);
             if (rc) return rc;
             b->launches++;
             b->step += nt;
@@ -736,8 +756,10 @@ template <class T> int run_bloch(fdtd2d_batch *b, int nsteps, const double *amps
         int rc;
         void *h_args[] = {&v, &p, &m, &bl, &step};
         void *e_args[] = {&v, &p, &m, &bl, &ca, &n, &step};
-        if ((rc = launch_ptr(b, K.h, grid, dim3(256), h_args, 0))) return rc;
-        if ((rc = launch_ptr(b, K.e, grid, dim3(256), e_args, 0))) return rc;
+        void *h_pts[] = {&v, &p, &m, &bl, pts, &n, &step};
+        void *e_pts[] = {&v, &p, &m, &bl, pts, &ca, &n, &step};
+        if ((rc = launch_ptr(b, K.h, grid, dim3(256), pts ? h_pts : h_args, 0))) return rc;
+        if ((rc = launch_ptr(b, K.e, grid, dim3(256), pts ? e_pts : e_args, 0))) return rc;
         b->launches += 2;
         b->step++;
     }
@@ -1023,7 +1045,7 @@ int copy_out_bloch(fdtd2d_batch *b, const void *re, const void *im, void *host, 
                 if (j == C - 1) {
                     const double o = get_elem(other.data(), b->dtype, line);
                     const double zr = part ? o : v, zi = part ? v : o;
-                    const double c = b->rho_host[2 * m], s = b->rho_host[2 * m + 1];
+                    const double c = b->rho_host[2 * m], s = b->run_conj ? -b->rho_host[2 * m + 1] : b->rho_host[2 * m + 1];
                     v = b->dtype == FDTD2D_F32 ? bloch_rot_host<float>(c, s, zr, zi, part)
                                                : bloch_rot_host<double>(c, s, zr, zi, part);
                 }
@@ -1039,6 +1061,7 @@ int copy_out_bloch(fdtd2d_batch *b, const void *re, const void *im, void *host, 
 int bloch_window(fdtd2d_batch *b)
 {
     release((void **)&b->win_acc_im);
+    release((void **)&b->win_held_im);     // the held Bloch window goes with the window (win_held: the caller's)
     if (!b->bloch || !b->win_nf) return 0;
     const size_t bytes = (size_t)b->count * win_acc_bytes(b);
     int rc = alloc(b, (void **)&b->win_acc_im, bytes);
@@ -1071,13 +1094,14 @@ long long probe_in_image(const fdtd2d_batch *b, const std::vector<int> &lin)
 int bloch_off(fdtd2d_batch *b)
 {
     BCHK(b, hipStreamSynchronize(b->stream));
-    for (void **p : {&b->ez_im, &b->hx_im, &b->hy_im, &b->ezx_im, &b->rho, (void **)&b->bloch_w, (void **)&b->amps_im,
-                     (void **)&b->win_acc_im, (void **)&b->probe_trace_im})
+    for (void **p : {&b->ez_im, &b->hx_im, &b->hy_im, &b->ezx_im, &b->rho, &b->rho_conj, (void **)&b->bloch_w,
+                     (void **)&b->amps_im, (void **)&b->win_acc_im, (void **)&b->probe_trace_im,
+                     (void **)&b->win_held, (void **)&b->win_held_im})     // a held window here is a Bloch one
         release(p);
     b->amps_im_cap = 0;
     b->rho_host.clear();
-    b->bloch = false;
-    return 0;
+    b->bloch = b->run_conj = false;
+    return batch_set_points(b, 0, nullptr, 0, nullptr);      // the point sources of a Bloch batch go with the phase
 }
 
 int refuse_bloch(fdtd2d_batch *b, const char *what)
@@ -1164,7 +1188,7 @@ void fdtd2d_batch_destroy(fdtd2d_batch_t *b)
                      (void **)&b->probe_trace, (void **)&b->win_held, (void **)&b->pts_cells, (void **)&b->pts_own,
                      (void **)&b->pts_w, (void **)&b->pts_tab, (void **)&b->chan, &b->dsg, &b->ca, &b->cb,
                      &b->ez_im, &b->hx_im, &b->hy_im, &b->ezx_im, &b->rho, (void **)&b->bloch_w, (void **)&b->amps_im,
-                     (void **)&b->win_acc_im, (void **)&b->probe_trace_im})
+                     (void **)&b->win_acc_im, (void **)&b->probe_trace_im, &b->rho_conj, (void **)&b->win_held_im})
         release(p);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -1195,8 +1219,10 @@ long long fdtd2d_batch_info(const fdtd2d_batch_t *b, int what)
         const long long n = b->step - b->probe_step0;
         return n < b->probe_cap ? n : b->probe_cap;
     }
-    case FDTD2D_BATCH_INFO_POINT_SOURCES: return b->npts_user;
-    case FDTD2D_BATCH_INFO_HELD_WINDOW: return b->win_held ? 1 : 0;
+    case FDTD2D_BATCH_INFO_POINT_SOURCES: return b->bloch ? 0 : b->npts_user;
+    case FDTD2D_BATCH_INFO_HELD_WINDOW: return b->win_held && !b->bloch ? 1 : 0;
+    case FDTD2D_BATCH_INFO_BLOCH_POINT_SOURCES: return b->bloch ? b->npts_user : 0;
+    case FDTD2D_BATCH_INFO_HELD_BLOCH_WINDOW: return b->win_held && b->win_held_im && b->bloch ? 1 : 0;
     case FDTD2D_BATCH_INFO_LOSSY: return b->ca && !b->sigma_implicit ? 1 : 0;
     case FDTD2D_BATCH_INFO_PERIODIC: return b->periodic ? 1 : 0;
     case FDTD2D_BATCH_INFO_BLOCH: return b->bloch ? 1 : 0;
@@ -1670,6 +1696,15 @@ int fdtd2d_batch_set_point_sources(fdtd2d_batch_t *b, int ncell, const int *cell
     if (ncell < 0 || ncell > FDTD2D_BATCH_MAX_POINT_SOURCES)
         return bfail(b, FDTD2D_E_ARG, "ncell %d outside 0..%d", ncell, FDTD2D_BATCH_MAX_POINT_SOURCES);
     if (ncell > 0 && b->bloch) return refuse_bloch(b, "a point source");
+    return batch_set_points(b, ncell, cells, nchan, weights);
+}
+
+}  // extern "C"
+
+static int batch_set_points(fdtd2d_batch *b, int ncell, const int *cells, int nchan, const double *weights)
+{
+    if (ncell < 0 || ncell > FDTD2D_BATCH_MAX_POINT_SOURCES)
+        return bfail(b, FDTD2D_E_ARG, "ncell %d outside 0..%d", ncell, FDTD2D_BATCH_MAX_POINT_SOURCES);
     std::vector<int> lin, own;
     std::vector<double> w;
     int ntab = ncell;                       // entries per member: a periodic batch lists column-0 cells at their images too
@@ -1761,6 +1796,8 @@ int fdtd2d_batch_set_point_sources(fdtd2d_batch_t *b, int ncell, const int *cell
     b->pts_nchan = nchan;
     return 0;
 }
+
+extern "C" {
 
 int fdtd2d_batch_run_channels(fdtd2d_batch_t *b, int nsteps, const double *amps, const double *chan,
                               int chan_per_member)
@@ -2102,11 +2139,17 @@ int fdtd2d_batch_set_bloch(fdtd2d_batch_t *b, const double *cos_phi, const doubl
                          "phase", (int)(k / b->nprobe), (int)(k % b->nprobe), b->cols - 1);
     }
     std::vector<double> rho((size_t)b->count * 2);
-    std::vector<unsigned char> rt(rho.size() * b->esz);
+    std::vector<unsigned char> rt(rho.size() * b->esz), rtc(rt.size());     // (c, s) and (c, -s): negation is exact
     for (size_t k = 0; k < rho.size(); ++k) {
         rho[k] = as_engine(b, k % 2 ? sin_phi[k / 2] : cos_phi[k / 2]);
-        if (b->dtype == FDTD2D_F32) ((float *)rt.data())[k] = (float)rho[k];
-        else ((double *)rt.data())[k] = rho[k];
+        const double conj = k % 2 ? -rho[k] : rho[k];
+        if (b->dtype == FDTD2D_F32) {
+            ((float *)rt.data())[k] = (float)rho[k];
+            ((float *)rtc.data())[k] = (float)conj;
+        } else {
+            ((double *)rt.data())[k] = rho[k];
+            ((double *)rtc.data())[k] = conj;
+        }
     }
     BCHK(b, hipStreamSynchronize(b->stream));   // a running launch may still read the old rotations
     if (!b->bloch) {
@@ -2122,14 +2165,17 @@ int fdtd2d_batch_set_bloch(fdtd2d_batch_t *b, const double *cos_phi, const doubl
         }
         if (hipStreamSynchronize(b->stream) != hipSuccess)
             return undo(bfail(b, FDTD2D_E_NOMEM, "hipMemset of the imaginary fields failed"));
-        if ((rc = alloc(b, &b->rho, rt.size())) || (rc = alloc(b, (void **)&b->bloch_w, wn * sizeof(double))))
+        if ((rc = alloc(b, &b->rho, rt.size())) || (rc = alloc(b, &b->rho_conj, rt.size())) ||
+            (rc = alloc(b, (void **)&b->bloch_w, wn * sizeof(double))))
             return undo(rc);
         b->bloch = true;
         if ((rc = fdtd2d_batch_set_bloch_source(b, nullptr, nullptr)) || (rc = bloch_window(b)) || (rc = bloch_probes(b)))
             return undo(rc);
     }
     BCHK(b, hipMemcpy(b->rho, rt.data(), rt.size(), hipMemcpyHostToDevice));
+    BCHK(b, hipMemcpy(b->rho_conj, rtc.data(), rtc.size(), hipMemcpyHostToDevice));
     b->rho_host.swap(rho);
+    b->run_conj = false;
     return 0;
 }
 
@@ -2240,6 +2286,184 @@ int fdtd2d_batch_read_probes_bloch(fdtd2d_batch_t *b, double *out, long long fir
     const size_t w = (size_t)count_samples * sizeof(double);
     BCHK(b, hipMemcpy2D(out, w, b->probe_trace_im + first, (size_t)b->probe_cap * sizeof(double), w,
                         (size_t)b->count * b->nprobe, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- fdtd2d_batch_bloch_adjoint.h ----------------------------------------------------------------------------------
+
+int fdtd2d_batch_set_bloch_point_sources(fdtd2d_batch_t *b, int ncell, const int *cells, int nchan,
+                                         const double *weights)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    return batch_set_points(b, ncell, cells, nchan, weights);     // a periodic batch: column C-1 is refused there
+}
+
+int fdtd2d_batch_run_bloch_channels(fdtd2d_batch_t *b, int nsteps, const double *amps_re, const double *amps_im,
+                                    const double *chan, int chan_per_member, int conjugate)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (nsteps < 0) return bfail(b, FDTD2D_E_ARG, "nsteps < 0");
+    if (!chan) return bfail(b, FDTD2D_E_ARG, "chan must not be NULL");
+    if (amps_im && !amps_re) return bfail(b, FDTD2D_E_ARG, "amps_im needs amps_re (zeros for a purely imaginary source)");
+    if (!b->npts)
+        return bfail(b, FDTD2D_E_STATE, "no point sources are set: call fdtd2d_batch_set_bloch_point_sources first");
+    int rc = need_ready(b);
+    if (rc) return rc;
+    for (int m = 0; m < b->count; ++m)
+        if (b->courant[m] > 1.0)
+            return bfail(b, FDTD2D_E_COURANT, "Courant stability condition not met for member %d: %.17g > 1.0", m,
+                         b->courant[m]);
+    if (nsteps == 0) return 0;
+    const double *dev_amps = nullptr;
+    b->run_amps_im = nullptr;
+    if (amps_re && b->have_src) {
+        const size_t bytes = (size_t)b->count * nsteps * sizeof(double);
+        if ((rc = stage(b, &b->amps, &b->amps_cap, amps_re, bytes))) return rc;
+        dev_amps = b->amps;
+        if (amps_im) {
+            if ((rc = stage(b, &b->amps_im, &b->amps_im_cap, amps_im, bytes))) return rc;
+            b->run_amps_im = b->amps_im;
+        }
+    }
+    const size_t per = (size_t)b->pts_nchan * nsteps;
+    if ((rc = stage(b, &b->chan, &b->chan_cap, chan, (chan_per_member ? b->count : 1) * per * sizeof(double))))
+        return rc;
+    fdtd::BatchPts P;
+    P.cells = b->pts_cells;
+    P.own = b->pts_own;
+    P.w = b->pts_w;
+    P.chan = b->chan;
+    P.tab = b->pts_tab;
+    P.chan_mstride = chan_per_member ? (long long)per : 0;
+    P.chan_stride = nsteps;
+    P.nc = b->npts;
+    P.nchan = b->pts_nchan;
+    return b->dtype == FDTD2D_F32 ? run_bloch<float>(b, nsteps, dev_amps, nsteps, &P, conjugate != 0)
+                                  : run_bloch<double>(b, nsteps, dev_amps, nsteps, &P, conjugate != 0);
+}
+
+int fdtd2d_batch_hold_bloch_window(fdtd2d_batch_t *b)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (!b->win_nf || !b->win_acc_im) return bfail(b, FDTD2D_E_STATE, "no window DFT is set");
+    int rc = use_device(b);
+    if (rc) return rc;
+    const size_t bytes = (size_t)b->count * win_acc_bytes(b);
+    if (!b->win_held && (rc = alloc(b, (void **)&b->win_held, bytes))) return rc;
+    if (!b->win_held_im && (rc = alloc(b, (void **)&b->win_held_im, bytes))) return rc;
+    BCHK(b, hipMemcpyAsync(b->win_held, b->win_acc, bytes, hipMemcpyDeviceToDevice, b->stream));
+    BCHK(b, hipMemcpyAsync(b->win_held_im, b->win_acc_im, bytes, hipMemcpyDeviceToDevice, b->stream));
+    BCHK(b, hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+int fdtd2d_batch_bloch_window_product(fdtd2d_batch_t *b, const double *coef_re, const double *coef_im, double *out)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!coef_re || !coef_im || !out) return bfail(b, FDTD2D_E_ARG, "coef_re, coef_im and out must not be NULL");
+    if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (!b->win_nf || !b->win_acc_im) return bfail(b, FDTD2D_E_STATE, "no window DFT is set");
+    if (!b->win_held || !b->win_held_im)
+        return bfail(b, FDTD2D_E_STATE, "no held window: call fdtd2d_batch_hold_bloch_window first");
+    int rc = use_device(b);
+    if (rc) return rc;
+    const size_t W = (size_t)b->win_nr * b->win_nc, nk = (size_t)b->count * b->win_nf;
+    std::vector<double> coef(2 * nk);
+    for (size_t k = 0; k < nk; ++k) {
+        coef[2 * k] = coef_re[k];
+        coef[2 * k + 1] = coef_im[k];
+    }
+    // scratch: coef (count x nf x 2), out (count x W)
+    if ((rc = scratch(b, (coef.size() + (size_t)b->count * W) * sizeof(double)))) return rc;
+    double *dcoef = (double *)b->dsg, *dout = dcoef + coef.size();
+    BCHK(b, hipMemcpyAsync(dcoef, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    fdtd::batch_bloch_window_product_launch(b->win_held, b->win_held_im, b->win_acc, b->win_acc_im, dcoef, dout, b->count,
+                                            b->win_nf, W, b->stream);
+    BCHK(b, hipGetLastError());
+    b->launches++;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    BCHK(b, hipMemcpy(out, dout, (size_t)b->count * W * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int fdtd2d_batch_bloch_probe_spectra(fdtd2d_batch_t *b, int nfreq, const double *omega, long long first,
+                                     long long count_samples, double *re, double *im, double *peak)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (!b->nprobe || !b->probe_trace_im) return bfail(b, FDTD2D_E_STATE, "no probes are set");
+    if (nfreq < 0 || nfreq > FDTD2D_BATCH_MAX_DFT_FREQS)
+        return bfail(b, FDTD2D_E_ARG, "nfreq %d outside 0..%d", nfreq, FDTD2D_BATCH_MAX_DFT_FREQS);
+    if (nfreq > 0 && (!omega || !re || !im)) return bfail(b, FDTD2D_E_ARG, "omega, re and im must not be NULL");
+    if (nfreq == 0 && !peak) return bfail(b, FDTD2D_E_ARG, "nfreq 0 asks for the peak alone: peak must not be NULL");
+    for (size_t k = 0; k < (size_t)b->count * nfreq; ++k)
+        if (!std::isfinite(omega[k]))
+            return bfail(b, FDTD2D_E_ARG, "member %d: frequency %d is not finite", (int)(k / nfreq), (int)(k % nfreq));
+    const long long recorded = fdtd2d_batch_info(b, FDTD2D_BATCH_INFO_PROBE_SAMPLES);
+    if (first < 0 || count_samples < 0 || first > recorded || count_samples > recorded - first)
+        return bfail(b, FDTD2D_E_ARG, "samples [%lld, %lld) outside the %lld recorded so far", first, first + count_samples,
+                     recorded);
+    int rc = use_device(b);
+    if (rc) return rc;
+    // scratch: omega (count x nfreq), then per part re, im (count x nprobe x nfreq each) and peak (count)
+    const size_t nom = (size_t)b->count * nfreq, nsp = nom * b->nprobe, part = 2 * nsp + b->count;
+    if ((rc = scratch(b, (nom + 2 * part) * sizeof(double)))) return rc;
+    double *d = (double *)b->dsg;
+    if (nom) BCHK(b, hipMemcpyAsync(d, omega, nom * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    for (int q = 0; q < 2; ++q) {
+        fdtd::BatchSpectra a;
+        a.trace = q ? b->probe_trace_im : b->probe_trace;
+        a.omega = d;
+        a.re = d + nom + q * part;
+        a.im = a.re + nsp;
+        a.peak = peak ? a.im + nsp : nullptr;
+        a.B = b->count; a.np = b->nprobe; a.nf = nfreq;
+        a.cap = b->probe_cap; a.first = first; a.count = count_samples;
+        a.step0 = b->probe_step0;
+        a.dt = b->dt;
+        fdtd::batch_probe_spectra_launch(a, b->stream);
+        BCHK(b, hipGetLastError());
+        b->launches++;
+    }
+    BCHK(b, hipStreamSynchronize(b->stream));
+    std::vector<double> h(2 * part);
+    BCHK(b, hipMemcpy(h.data(), d + nom, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const double *sr = h.data(), *si = h.data() + part;      // S(re) and S(im): re[nsp], im[nsp], peak[count]
+    for (size_t k = 0; k < nsp; ++k) {
+        re[k] = sr[k] - si[nsp + k];
+        im[k] = sr[nsp + k] + si[k];
+    }
+    for (int m = 0; peak && m < b->count; ++m) peak[m] = std::max(sr[2 * nsp + m], si[2 * nsp + m]);
+    return 0;
+}
+
+int fdtd2d_batch_bloch_field_absmax(fdtd2d_batch_t *b, int field, double *out)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!out) return bfail(b, FDTD2D_E_ARG, "out must not be NULL");
+    if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (field != FDTD2D_FIELD_EZ && field != FDTD2D_FIELD_HX && field != FDTD2D_FIELD_HY)
+        return bfail(b, FDTD2D_E_ARG, "field %d: FDTD2D_FIELD_EZ, _HX or _HY", field);
+    int rc = use_device(b);
+    if (rc) return rc;
+    if ((rc = scratch(b, 2 * (size_t)b->count * sizeof(double)))) return rc;
+    const void *re = field == FDTD2D_FIELD_EZ ? b->ez[b->cur] : field == FDTD2D_FIELD_HX ? b->hx : b->hy;
+    const void *im = field == FDTD2D_FIELD_EZ ? b->ez_im : field == FDTD2D_FIELD_HX ? b->hx_im : b->hy_im;
+    for (int q = 0; q < 2; ++q) {
+        // Ez: columns 0..C-2 (the image slot holds a copy of column 0); Hx has C-1 columns, Hy has R-1 rows
+        fdtd::batch_field_absmax_launch(q ? im : re, b->dtype == FDTD2D_F64, (double *)b->dsg + (size_t)q * b->count,
+                                        b->count, b->rows - (field == FDTD2D_FIELD_HY),
+                                        b->cols - (field != FDTD2D_FIELD_HY), b->pitch, b->mstride, b->stream);
+        BCHK(b, hipGetLastError());
+        b->launches++;
+    }
+    BCHK(b, hipStreamSynchronize(b->stream));
+    std::vector<double> h(2 * (size_t)b->count);
+    BCHK(b, hipMemcpy(h.data(), b->dsg, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int m = 0; m < b->count; ++m) out[m] = std::max(h[m], h[(size_t)b->count + m]);
     return 0;
 }
 

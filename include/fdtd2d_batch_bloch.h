@@ -41,8 +41,8 @@
  * naming the member for a probe: the rotation would have to be applied there too); the whole-grid fdtd2d_batch_set_dft
  * (use a window), fdtd2d_batch_set_point_sources and fdtd2d_batch_run_channels, fdtd2d_batch_hold_dft_window and
  * fdtd2d_batch_dft_window_product, fdtd2d_batch_probe_spectra and fdtd2d_batch_field_absmax (all FDTD2D_E_STATE).
- * Adjoint gradients of complex fields are not part of this interface yet.  fdtd2d_batch_set_conductivity,
- * _set_conductivity_window, _set_eps_window, _set_pml, _set_option keep working. */
+ * Their complex counterparts, which an adjoint run of complex fields needs, are in fdtd2d_batch_bloch_adjoint.h.
+ * fdtd2d_batch_set_conductivity, _set_conductivity_window, _set_eps_window, _set_pml, _set_option keep working. */
 #ifndef FDTD2D_BATCH_BLOCH_H
 #define FDTD2D_BATCH_BLOCH_H
 

@@ -55,9 +55,17 @@ array eps with random binary permittivity, a ricker line source per member):
                               alternately in one process: bloch_ms, periodic_ms, bloch_over_periodic, both paths and
                               LDS sizes.  A Bloch member carries two members' fields, so the number to beat is 2.
                               Default: 1024 members of 60 x 60, a 10-cell layer, 1000 steps.
+  --bloch-adjoint             instead: the adjoint gradient of a Bloch batch (a phase sweep over the members, a
+                              conductivity, ramp weights, 10 frequencies, 30 probes, 20 channels, a design window of 100
+                              cells, dt = 2e-13), the columns of --adjoint: device_ms (forward run, hold_bloch_window,
+                              reset, adjoint run with channels and the conjugate rotation, bloch_window_product, on a
+                              standing engine) against two_runs_ms (two monitored Bloch runs of that length with the
+                              rectangle source) and session_ms (one value_and_grad of a standing BlochAdjointSession),
+                              timed alternately in one process: device_over_two_runs, session_over_two_runs, the path
+                              and the LDS size.  Default: 1024 members of 60 x 60, a 10-cell layer, 1500 steps.
 Usage: python tools/bench_batch.py [--count 1024 --rows 60 --cols 60 --steps 1000] [--reps 5] [--loop-members 16]
                                    [--boundary {mur,pml} --pml-cells 10] [--monitors] [--adjoint] [--lossy]
-                                   [--periodic] [--bloch]
+                                   [--periodic] [--bloch] [--bloch-adjoint]
 """
 import argparse
 import json
@@ -505,6 +513,91 @@ def bench_adjoint(count, rows, cols, steps, dtype, reps, pml_cells):
             "residual_adjoint_max": float(np.max(info["residual_adjoint"]))}
 
 
+def bench_bloch_adjoint(count, rows, cols, steps, dtype, reps, pml_cells):
+    from fdtd2d_amd.adjoint import channel_system, gradient_coefficients
+    dt = 2e-13                                   # as --adjoint: the channels' envelope ends by step 1200
+    rng = np.random.default_rng(0)
+    eps = np.where(rng.random((count, rows, cols)) < 0.5, fd.EPS0, 5 * fd.EPS0)
+    eps[:, :, -1] = eps[:, :, 0]
+    side, g = 10, max(6, pml_cells)
+    design = ((rows - side) // 2, (cols - side) // 2, side, side)
+    rects = np.tile([g + 2, 0, 1, cols - 1], (count, 1))
+    probes = np.array([[rows // 2 - 15 + k, design[1] + side + 8] for k in range(30)])
+    sigma = np.zeros((count, rows, cols))
+    sigma[:, g:rows - g, :] = 2.0 * rng.random((count, rows - 2 * g, cols))
+    sigma[:, probes[:, 0], probes[:, 1]] = 0     # the probe cells do not conduct
+    omegas = 2 * np.pi * np.linspace(10e9, 100e9, 10)
+    phis = np.linspace(0.0, np.pi, count)
+    amps = np.tile(np.array([fd.ricker_amplitude(i * dt, FC) for i in range(steps)]), (count, 1))
+    c00 = (1 / np.sqrt(eps[:, 0, 0].astype(dtype).astype(np.float64) * fd.MU0) * dt) / DX
+
+    def objective(spectra):
+        mag = np.abs(spectra)
+        return mag.mean(axis=1).sum(axis=1), spectra / np.maximum(mag, 1e-300) / spectra.shape[1]
+
+    chan, _ = channel_system(omegas, steps, dt, FC)
+    session = fd.BlochAdjointSession(eps, bloch_phase=phis, source_weights="ramp", nsteps=steps, sources=rects,
+                                     probes=probes, omegas=omegas, design=design, fc=FC, dt=dt, dx=DX, dtype=dtype,
+                                     pml_cells=pml_cells)
+    session.set_conductivity(sigma)
+    weights = rng.standard_normal((count, 30, 20))
+    coef = gradient_coefficients(omegas, dt)
+    info = {}
+    with fd.BatchEngine(count, rows, cols, dt, DX, dtype=dtype, boundary="periodic") as b:
+        b.set_materials(eps.astype(dtype), fd.MU0).set_sources(rects).set_pml(pml_cells, courant00=c00)
+        b.set_conductivity(sigma).set_bloch_phase(phis).set_bloch_source("ramp")
+        b.set_dft_window(design, omegas).set_probes(probes, steps).set_bloch_point_sources(probes, weights)
+
+        def two_runs():
+            t0 = time.perf_counter()
+            for _ in range(2):
+                b.reset().run(steps, amps)
+            b.sync()
+            return (time.perf_counter() - t0) * 1e3
+
+        def device():
+            t0 = time.perf_counter()
+            b.reset().run(steps, amps).hold_bloch_window().reset().run_bloch_channels(steps, None, chan, conjugate=True)
+            b.bloch_window_product(coef)
+            return (time.perf_counter() - t0) * 1e3
+
+        def iteration():
+            t0 = time.perf_counter()
+            info.update(session.value_and_grad(objective)[3])
+            return (time.perf_counter() - t0) * 1e3
+
+        two_runs(), device(), iteration()            # warm-up: code objects, clocks
+        l0 = b.launches
+        device()
+        launches = b.launches - l0
+        l0 = session.engine.launches
+        iteration()
+        session_launches = session.engine.launches - l0
+        t = {k: [] for k in ("two", "device", "session")}
+        for _ in range(reps):
+            t["two"].append(two_runs())
+            t["device"].append(device())
+            t["session"].append(iteration())
+        resident, in_lds, lds = b.resident, b.window_in_lds, b.lds_bytes
+    session.close()
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    return {"count": count, "rows": rows, "cols": cols, "steps": steps, "dtype": np.dtype(dtype).name, "dt": dt,
+            "boundary": "periodic+bloch", "pml_cells": pml_cells, "design": list(design), "freqs": 10, "probes": 30,
+            "channels": 20, "path": "resident" if resident else "streamed", "window_in_lds": in_lds,
+            "lds_bytes_per_member": lds if resident else None, "reps": reps,
+            "two_runs_ms": round(med["two"], 3), "two_runs_ms_min": round(min(t["two"]), 3),
+            "two_runs_ms_all": [round(v, 3) for v in t["two"]],
+            "device_ms": round(med["device"], 3), "device_ms_min": round(min(t["device"]), 3),
+            "device_ms_all": [round(v, 3) for v in t["device"]],
+            "device_over_two_runs": round(med["device"] / med["two"], 3), "launches_per_gradient": launches,
+            "session_ms": round(med["session"], 3), "session_ms_min": round(min(t["session"]), 3),
+            "session_over_two_runs": round(med["session"] / med["two"], 3),
+            "session_over_device": round(med["session"] / med["device"], 3),
+            "launches_per_session_iteration": session_launches,
+            "residual_forward_max": float(np.max(info["residual_forward"])),
+            "residual_adjoint_max": float(np.max(info["residual_adjoint"]))}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--count", type=int)
@@ -522,7 +615,12 @@ def main():
     ap.add_argument("--lossy", action="store_true", help="time the lossy kernels against the point-source ones")
     ap.add_argument("--periodic", action="store_true", help="time the periodic kernels against the lossy PML ones")
     ap.add_argument("--bloch", action="store_true", help="time a Bloch batch against the plain periodic one")
+    ap.add_argument("--bloch-adjoint", action="store_true", help="time the adjoint gradient of a Bloch batch")
     a = ap.parse_args()
+    if a.bloch_adjoint:
+        print(json.dumps(bench_bloch_adjoint(a.count or 1024, a.rows or 60, a.cols or 60, a.steps or 1500,
+                                             np.dtype(a.dtype), a.reps, a.pml_cells)), flush=True)
+        return
     if a.bloch:
         print(json.dumps(bench_bloch(a.count or 1024, a.rows or 60, a.cols or 60, a.steps or 1000, np.dtype(a.dtype),
                                      a.reps, a.pml_cells)), flush=True)
