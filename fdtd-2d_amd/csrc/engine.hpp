@@ -21,6 +21,7 @@
 #include "kernels_split.hpp"
 #include "kernels_pml_split.hpp"
 #include "kernels_probe.hpp"
+#include "active_window.hpp"
 
 using fdtd::Geom;
 
@@ -218,6 +219,25 @@ struct fdtd2d {
     hipStream_t clk_stream = nullptr;
     int zone_split = -1;         // -1: by launch size; 0/1: force fused / side-stream zones (FDTD2D_OPT_ZONE_SPLIT)
     int max_nt = 20;             // longest pass; FDTD2D_OPT_MAX_PASS_STEPS (0: step kernels only)
+
+    // Active window (active_window.hpp): bounds on where the two buffer sets can be non-zero.  Committed passes of
+    // fdtd2d_run launch only the bands and strips that cover it while it is at most half the grid.
+    fdtd_aw::ActiveWindow aw;
+    int active_window = -1;      // FDTD2D_OPT_ACTIVE_WINDOW: -1 automatic (the tuner's size rule: >= 4 Mi cells), 0 off, 1 on
+    bool aw_ptr_out = false;     // fdtd2d_device_ptr handed a pointer out: the caller may write any cell at any time, so
+                                 // the automatic mode stays off (setting the option to 1 takes the promise back)
+    long long windowed_launches = 0;
+    // (FDTD2D_INFO_WINDOW_ENABLED.)  The automatic mode is off for a handle whose launches the caller pins with
+    // fdtd2d_set_shape -- such a caller measures or replays the whole-grid launch of that shape -- and for one whose
+    // device pointers are out.
+    bool window_enabled() const
+    {
+        if (!aw.tracking || active_window == 0) return false;
+        if (active_window == 1) return true;
+        for (const auto &g : given_shape)
+            if (g.second.band_rows > 0) return false;
+        return !aw_ptr_out && (size_t)rows * cols >= (size_t)4 << 20;
+    }
 };
 
 
@@ -257,13 +277,15 @@ template <class T> fdtd::PmlFactors<T> pml_factors(const fdtd2d *h)
 bool pass_geometry(const fdtd2d *h, int nt, int *band_lo, int *band_hi);
 
 // One pass of nt steps (or the rows [band_lo, band_hi) of it); see pass_impl.hpp.
+// win: the strips of a restricted launch (active_window.hpp; fdtd2d_run alone passes one, with the rows and zone tiles
+// in band_lo / band_hi / ztop / zbot); nullptr: every strip.
 template <class T>
 int launch_pass(fdtd2d *h, int nt, int band_lo, int band_hi, int src_row, int src_col,
                 const double *amps, bool ztop, bool zbot, bool commit, int full_lo, int full_hi,
-                int nlev = 0);
+                int nlev = 0, const fdtd_aw::Launch *win = nullptr);
 // the 16-step PML pass (pass_f32_pml.hip): k_bulk_split on the cells clear of the layer, k_bulk_split_pml on the rest
 int launch_pml_split_f32(fdtd2d *h, fdtd::PassParams<float> &p);
-extern template int launch_pass<float>(fdtd2d *, int, int, int, int, int, const double *, bool, bool, bool, int, int, int);
-extern template int launch_pass<double>(fdtd2d *, int, int, int, int, int, const double *, bool, bool, bool, int, int, int);
+extern template int launch_pass<float>(fdtd2d *, int, int, int, int, int, const double *, bool, bool, bool, int, int, int, const fdtd_aw::Launch *);
+extern template int launch_pass<double>(fdtd2d *, int, int, int, int, int, const double *, bool, bool, bool, int, int, int, const fdtd_aw::Launch *);
 
 }  // namespace fdtd_host

@@ -170,6 +170,7 @@ int zero_fields(fdtd2d *h)
     h->hcur = 0;
     h->ev = h->hv = Range{h->store_lo(), h->store_hi()};
     h->step = 0;
+    h->aw.reset();               // both buffer sets are zero everywhere
     return 0;
 }
 
@@ -299,6 +300,7 @@ int do_update_h(fdtd2d *h)
     int rc = h->dtype == FDTD2D_F32 ? launch_h<float>(h, lo, khi) : launch_h<double>(h, lo, khi);
     if (rc) return rc;
     h->hv = Range{lo, hi};
+    h->aw.half_step();
     return 0;
 }
 
@@ -317,6 +319,7 @@ int do_update_e(fdtd2d *h)
     if (rc) return rc;
     h->ev = Range{lo, hi};
     h->step++;
+    h->aw.half_step();
     return 0;
 }
 
@@ -365,6 +368,7 @@ int do_add_point(fdtd2d *h, int row, int col, double amp)
     if (row < 0 || row + h->src_rows > h->rows || col < 0 || col + h->src_cols > h->cols)
         return fail(h, FDTD2D_E_ARG, "source (%d,%d)+%dx%d outside the %dx%d grid", row, col,
                     h->src_rows, h->src_cols, h->rows, h->cols);
+    h->aw.add_source(fdtd_aw::Rect{row, row + h->src_rows, col, col + h->src_cols});
     return h->dtype == FDTD2D_F32 ? launch_point<float>(h, row, col, amp)
                                   : launch_point<double>(h, row, col, amp);
 }
@@ -502,6 +506,7 @@ int create_impl(fdtd2d_t **out, int rows, int cols, int row0, int nrows, int hal
     h->pitch = ((long long)cols + 63) / 64 * 64;
     h->stored = nrows + 2 * h->halo;
     h->field_bytes = (size_t)h->stored * h->pitch * h->esz;
+    h->aw.init(rows, cols, whole && boundary == FDTD2D_BOUNDARY_MUR5);
     int rc = use_device(h);
     auto bail = [&](int code) {
         g_create_error = h->err;
@@ -705,6 +710,12 @@ long long fdtd2d_info(const fdtd2d_t *h, int what)
     case FDTD2D_INFO_LAST_PASS_STEPS: return h->last_nt;
     case FDTD2D_INFO_LAST_SIDE_WAVES: return h->shape_last.side;
     case FDTD2D_INFO_LAST_XCD_MAP: return h->shape_last.xcd;
+    case FDTD2D_INFO_WINDOW_ROW_LO: return h->aw.support.empty() ? 0 : h->aw.support.r0;
+    case FDTD2D_INFO_WINDOW_ROW_HI: return h->aw.support.empty() ? 0 : h->aw.support.r1;
+    case FDTD2D_INFO_WINDOW_COL_LO: return h->aw.support.empty() ? 0 : h->aw.support.c0;
+    case FDTD2D_INFO_WINDOW_COL_HI: return h->aw.support.empty() ? 0 : h->aw.support.c1;
+    case FDTD2D_INFO_WINDOWED_LAUNCHES: return h->windowed_launches;
+    case FDTD2D_INFO_WINDOW_ENABLED: return h->window_enabled() ? 1 : 0;
     default: return FDTD2D_E_ARG;
     }
 }
@@ -799,6 +810,7 @@ int fdtd2d_transfer_ezx(fdtd2d_t *h, void *host, int host_dtype, int to_device)
     int rc = use_device(h);
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (to_device) h->aw.invalidate();
     return to_device ? copy_in(h, h->ezx(), host, host_dtype, h->halo, h->nrows, h->cols)
                      : copy_out(h, h->ezx(), host, host_dtype, h->halo, h->nrows, h->cols);
 }
@@ -818,6 +830,7 @@ int fdtd2d_upload(fdtd2d_t *h, const void *Ez, const void *Hx, const void *Hy, i
     int rc = use_device(h);
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->aw.invalidate();      // (the other set too: what it holds is no longer known to lie inside the new support)
     const int s = h->halo;   // stored row of the first owned row
     if (Ez && (rc = copy_in(h, h->ez[h->cur], Ez, host_dtype, s, h->nrows, h->cols))) return rc;
     if (Hx && (rc = copy_in(h, h->hx(), Hx, host_dtype, s, h->nrows, h->cols - 1))) return rc;
@@ -1326,7 +1339,8 @@ int fdtd2d_prepare_run(fdtd2d_t *h, int nsteps, int src_row, int src_col, int wi
     return hipStreamSynchronize(h->stream) == hipSuccess ? 0 : fail(h, FDTD2D_E_STATE, "stream sync failed");
 }
 
-int fdtd2d_run(fdtd2d_t *h, int nsteps, int src_row, int src_col, const double *amps)
+// may_window = false: every pass launches the whole grid (fdtd2d_time_launches measures the dense kernel)
+static int run_impl(fdtd2d_t *h, int nsteps, int src_row, int src_col, const double *amps, bool may_window)
 {
     int rc = need_stable(h);
     if (rc) return rc;
@@ -1341,14 +1355,38 @@ int fdtd2d_run(fdtd2d_t *h, int nsteps, int src_row, int src_col, const double *
         int nt = 0, nlev = 0, lo = 0, hi = 0;
         if (plan_pass(h, std::min(nsteps - n, h->dft_gap()), &nt, &nlev, &lo, &hi)) {
             const double *a = amps ? amps + n : nullptr;
+            // The active window (active_window.hpp): while the cells this pass can change and the cells the target set
+            // may hold cover at most half the grid, launch only the bands and strips that write them.  (Half: such a
+            // launch runs on a rule-made, untuned shape, and shapes differ by up to 25 %.)
+            int b_lo = lo, b_hi = hi;
+            bool zt = h->top(), zb = h->bottom();
+            fdtd_aw::Launch L;
+            bool windowed = false;
+            if (may_window && h->window_enabled()) {
+                const fdtd_aw::Rect src = amps ? fdtd_aw::Rect{src_row, src_row + h->src_rows, src_col, src_col + h->src_cols} : fdtd_aw::Rect{};
+                const fdtd_aw::Rect W = h->aw.window(src, nlev);
+                if (2 * W.cells() <= (long long)h->rows * h->cols) {
+                    const int hc = fdtd::stream_hc(nt), ow = 64 * (h->dtype == FDTD2D_F32 ? 4 : 2) - 2 * hc;
+                    L.band_lo = L.band_hi = lo;                  // (empty window: nothing to launch)
+                    if (!W.empty()) L = fdtd_aw::restrict_launch(W, src, h->rows, h->cols, nt, lo, hi, ow, hc, (h->cols + ow - 1) / ow);
+                    b_lo = L.band_lo, b_hi = L.band_hi, zt = L.ztop, zb = L.zbot;
+                    windowed = true;
+                }
+            }
+            const fdtd_aw::Launch *win = windowed ? &L : nullptr;
             // (only full passes are tuned: a one-off tail does not pay for 20-120 ms of trial launches;
-            // it uses the shape measured for full passes of its kernel if there is one)
-            if (nlev == nt && (rc = tune_pass(h, nt, lo, hi, h->top(), h->bottom(), src_row, src_col, amps != nullptr))) return rc;
+            // it uses the shape measured for full passes of its kernel if there is one; a windowed pass is never tuned)
+            if (nlev == nt && !windowed && (rc = tune_pass(h, nt, lo, hi, h->top(), h->bottom(), src_row, src_col, amps != nullptr))) return rc;
             h->probe_pending = h->probe_cap > 0;
+            const long long launches = h->pass_launches;
             rc = h->dtype == FDTD2D_F32
-                     ? launch_pass<float>(h, nt, lo, hi, src_row, src_col, a, h->top(), h->bottom(), true, lo, hi, nlev)
-                     : launch_pass<double>(h, nt, lo, hi, src_row, src_col, a, h->top(), h->bottom(), true, lo, hi, nlev);
+                     ? launch_pass<float>(h, nt, b_lo, b_hi, src_row, src_col, a, zt, zb, true, lo, hi, nlev, win)
+                     : launch_pass<double>(h, nt, b_lo, b_hi, src_row, src_col, a, zt, zb, true, lo, hi, nlev, win);
             if (rc) return rc;
+            if (windowed) {
+                h->windowed_launches++;
+                h->pass_launches = launches + 1;        // one per planned pass, also where the window was empty
+            }
             if ((rc = dft_after_step(h))) return rc;
             n += nlev;
             continue;
@@ -1361,6 +1399,11 @@ int fdtd2d_run(fdtd2d_t *h, int nsteps, int src_row, int src_col, const double *
         ++n;
     }
     return 0;
+}
+
+int fdtd2d_run(fdtd2d_t *h, int nsteps, int src_row, int src_col, const double *amps)
+{
+    return run_impl(h, nsteps, src_row, src_col, amps, true);
 }
 
 int fdtd2d_pass_rows(fdtd2d_t *h, int nt, int row_lo, int row_hi, int src_row, int src_col,
@@ -1399,6 +1442,7 @@ int fdtd2d_pass_rows(fdtd2d_t *h, int nt, int row_lo, int row_hi, int src_row, i
              ? launch_pass<float>(h, nt, b_lo, b_hi, src_row, src_col, amps, zt, zb, false, lo, hi)
              : launch_pass<double>(h, nt, b_lo, b_hi, src_row, src_col, amps, zt, zb, false, lo, hi);
     if (rc) return rc;
+    h->aw.invalidate();
     h->pend_nt = nt;
     h->pend_done.push_back(Range{row_lo, row_hi});
     return 0;
@@ -1431,6 +1475,7 @@ int fdtd2d_pass_commit(fdtd2d_t *h)
     // (a running Fourier transform samples at fixed steps: a pass issued in pieces must end ON the next sampled step or
     // before it -- fdtd2d_run cuts its passes there by itself, callers of fdtd2d_pass_rows choose nt accordingly)
     const bool skipped = h->dft_n && h->dft_gap() < nt;
+    h->aw.invalidate();
     h->cur ^= 1;
     h->hcur ^= 1;
     h->ev = h->hv = Range{c_lo, at};
@@ -1513,6 +1558,11 @@ int fdtd2d_set_option(fdtd2d_t *h, int option, long long value)
         if (value != 0 && value != 1 && value != 2 && value != 4) return fail(h, FDTD2D_E_ARG, "side waves must be 0, 1, 2 or 4");
         h->side_waves = (int)value;
         h->tuned.clear();
+        return 0;
+    case FDTD2D_OPT_ACTIVE_WINDOW:
+        if (value < -1 || value > 1) return fail(h, FDTD2D_E_ARG, "active window must be -1, 0 or 1");
+        h->active_window = (int)value;
+        if (value == 1) h->aw_ptr_out = false;     // the caller vouches for what it writes through device pointers
         return 0;
     default: return fail(h, FDTD2D_E_ARG, "unknown option %d", option);
     }
@@ -1605,6 +1655,7 @@ int fdtd2d_halo_unpack(fdtd2d_t *h, int side, const void *dev_buf)
     rc = h->dtype == FDTD2D_F32 ? launch_halo<float, false>(h, first, (void *)dev_buf)
                                 : launch_halo<double, false>(h, first, (void *)dev_buf);
     if (rc) return rc;
+    h->aw.invalidate();
     // the rows just written extend the current range, provided the owned rows adjoin it
     if (side == 0) {
         if (h->ev.lo <= h->row0) h->ev.lo = first;
@@ -1645,12 +1696,22 @@ int fdtd2d_snapshot_index(fdtd2d_t *h, double vmin, double vmax, int stride, uns
     return 0;
 }
 
+static void *field_ptr(fdtd2d_t *h, int field)
+{
+    switch (field) {
+    case FDTD2D_FIELD_EZ: return h->ez[h->cur];
+    case FDTD2D_FIELD_HX: return h->hx();
+    case FDTD2D_FIELD_HY: return h->hy();
+    default: return nullptr;
+    }
+}
+
 int fdtd2d_reduce(fdtd2d_t *h, int field, double *sum_sq, double *max_abs)
 {
     if (!h) return FDTD2D_E_ARG;
     int rc = use_device(h);
     if (rc) return rc;
-    const void *f = fdtd2d_device_ptr(h, field);
+    const void *f = field_ptr(h, field);         // (not fdtd2d_device_ptr: nothing is handed out, the window stays)
     if (!f) return fail(h, FDTD2D_E_ARG, "unknown field %d", field);
     const int r0 = h->row0, r1 = h->row0 + h->nrows;
     const Range &v = field == FDTD2D_FIELD_EZ ? h->ev : h->hv;
@@ -1708,7 +1769,7 @@ int fdtd2d_time_launches(fdtd2d_t *h, int nlaunch, int steps_each, float *ms)
         if (hipEventCreate(&e) != hipSuccess) { cleanup(); return fail(h, FDTD2D_E_NOMEM, "hipEventCreate failed"); }
     for (int n = 0; n < nlaunch && rc == 0; ++n) {
         if (hipEventRecord(ev[2 * n], h->stream) != hipSuccess) rc = fail(h, FDTD2D_E_STATE, "hipEventRecord failed");
-        if (!rc) rc = fdtd2d_run(h, steps_each, 0, 0, nullptr);
+        if (!rc) rc = run_impl(h, steps_each, 0, 0, nullptr, false);     // always the whole grid: this times the dense kernel
         if (!rc && hipEventRecord(ev[2 * n + 1], h->stream) != hipSuccess) rc = fail(h, FDTD2D_E_STATE, "hipEventRecord failed");
     }
     if (!rc && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(h, FDTD2D_E_STATE, "stream sync failed");
@@ -1765,6 +1826,7 @@ int fdtd2d_measure_copy(fdtd2d_t *h, int reps, double *gbps)
         for (int f = 0; f < 3; ++f)
             hipLaunchKernelGGL(k_copy16, dim3((unsigned)((n + 2047) / 2048)), dim3(256), 0, h->stream, (const uint4 *)src[f], (uint4 *)dst[f], n);
     };
+    h->aw.copied_to_other();
     once();                                  // first touch
     HIPCHK(h, hipEventRecord(h->t0, h->stream));
     for (int r = 0; r < reps; ++r) once();
@@ -1823,12 +1885,10 @@ int fdtd2d_bytes_per_cell_step(const fdtd2d_t *h)
 void *fdtd2d_device_ptr(fdtd2d_t *h, int field)
 {
     if (!h) return nullptr;
-    switch (field) {
-    case FDTD2D_FIELD_EZ: return h->ez[h->cur];
-    case FDTD2D_FIELD_HX: return h->hx();
-    case FDTD2D_FIELD_HY: return h->hy();
-    default: return nullptr;
-    }
+    // the caller may write through the pointer: nothing is known about the fields any more
+    h->aw.invalidate();
+    h->aw_ptr_out = true;
+    return field_ptr(h, field);
 }
 
 }  // extern "C"

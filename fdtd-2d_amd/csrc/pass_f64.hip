@@ -2,5 +2,5 @@
 #define FDTD_PASS_LONG_EXTERN
 #include "pass_impl.hpp"
 namespace fdtd_host {
-template int launch_pass<double>(fdtd2d *, int, int, int, int, int, const double *, bool, bool, bool, int, int, int);
+template int launch_pass<double>(fdtd2d *, int, int, int, int, int, const double *, bool, bool, bool, int, int, int, const fdtd_aw::Launch *);
 }

@@ -2,5 +2,5 @@
 // 79 KB of dynamic LDS beside the bulk).
 #include "pass_impl.hpp"
 namespace fdtd_host {
-template int launch_pass_nt<double, 16>(fdtd2d *, fdtd::PassParams<double> &);
+template int launch_pass_nt<double, 16>(fdtd2d *, fdtd::PassParams<double> &, const fdtd_aw::Launch *);
 }

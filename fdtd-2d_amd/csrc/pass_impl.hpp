@@ -12,13 +12,15 @@ inline int pass_strip_ow(int nt, int v, int nw, int sd)
 }
 
 template <class T, int NT, bool CE_ARR, bool CH_ARR, int V = fdtd::Vec<T>::N>
-int launch_pass_impl(fdtd2d *h, fdtd::PassParams<T> &p)
+int launch_pass_impl(fdtd2d *h, fdtd::PassParams<T> &p, const fdtd_aw::Launch *win)
 {
     using D = fdtd::ZoneDims<NT>;
     const int sd = h->shape_now.side > 1 ? h->shape_now.side : 1;
     const int region = std::max(0, p.band_hi - p.band_lo);
     p.nbands = (region + p.band_rows - 1) / p.band_rows;
     p.nbands_e = (region + p.band_rows_e - 1) / p.band_rows_e;
+    // a restricted launch: a run of inner strips (p.strip_first on), both edge strips or neither
+    if (win && !win->edges) p.nbands_e = 0;
     p.band_rows2 = p.nbands2 = 0;
     p.split_row = p.band_hi;
     // inner strips that hold source columns (at most two neighbours; wider sources get no special bands)
@@ -38,8 +40,7 @@ int launch_pass_impl(fdtd2d *h, fdtd::PassParams<T> &p)
         const int SWc = sd > 1 ? fdtd::strip_width(NT / 4, V, sd) : 64 * V, OWc = SWc - 2 * fdtd::stream_hc(NT);
         int s0 = -1, s1 = -1;
         for (int st = 1; st <= p.nstrips - 2; ++st) {
-            const int x0 = st * OWc - fdtd::stream_hc(NT);
-            if (p.src_col1 > x0 && p.src_col < x0 + SWc) {
+            if (fdtd_aw::strip_holds(st, OWc, fdtd::stream_hc(NT), p.src_col, p.src_col1)) {
                 if (s0 < 0) s0 = st;
                 s1 = st;
             }
@@ -55,7 +56,8 @@ int launch_pass_impl(fdtd2d *h, fdtd::PassParams<T> &p)
 #endif
     // launch order: zone tiles, 2 edge-strip slots (the second stays empty with one strip),
     // then strips 1 .. nstrips-2
-    p.n_inner = std::max(0, p.nstrips - 2 - p.n_src);
+    // (restrict_launch counts the strips that hold source columns among win->n_inner: they come off here as always)
+    p.n_inner = std::max(0, (win ? win->n_inner : p.nstrips - 2) - p.n_src);
     {   // filler bands (Shape::short_rows): the bottom rows of the inner strips in shorter bands that come last
         const fdtd2d::Shape &sh = h->shape_now;
         const bool xcd_now = h->xcd_map >= 0 ? h->xcd_map != 0 : sh.xcd != 0;
@@ -92,7 +94,7 @@ int launch_pass_impl(fdtd2d *h, fdtd::PassParams<T> &p)
     p.xcd_map = 0;
     p.main_pad = p.main_per = p.main_tasks = 0;
     const bool xcd = h->xcd_map >= 0 ? h->xcd_map != 0 : h->shape_now.xcd != 0;
-    if (xcd && NT >= 8 && h->use_level_split(NT, p.band_lo, p.band_hi) && p.nstrips - 2 - p.n_src > 0) {
+    if (xcd && NT >= 8 && h->use_level_split(NT, p.band_lo, p.band_hi) && p.n_inner > 0) {
         // (the zone tiles ride in front of the bulk when fused: the pad makes the first inner-strip task a multiple
         // of 8 in the index the hardware sees)
         const bool side = zones > 0 && (h->zone_split == 1 || (NT > 16 && !fuse_long) || sd > 1);
@@ -259,12 +261,12 @@ int launch_pass_impl(fdtd2d *h, fdtd::PassParams<T> &p)
     }
 }
 
-template <class T, int NT> int launch_pass_nt(fdtd2d *h, fdtd::PassParams<T> &p)
+template <class T, int NT> int launch_pass_nt(fdtd2d *h, fdtd::PassParams<T> &p, const fdtd_aw::Launch *win)
 {
-    if (h->ce_uniform && h->ch_uniform) return launch_pass_impl<T, NT, false, false>(h, p);
-    if (!h->ce_uniform && h->ch_uniform) return launch_pass_impl<T, NT, true, false>(h, p);
-    if (h->ce_uniform && !h->ch_uniform) return launch_pass_impl<T, NT, false, true>(h, p);
-    return launch_pass_impl<T, NT, true, true>(h, p);
+    if (h->ce_uniform && h->ch_uniform) return launch_pass_impl<T, NT, false, false>(h, p, win);
+    if (!h->ce_uniform && h->ch_uniform) return launch_pass_impl<T, NT, true, false>(h, p, win);
+    if (h->ce_uniform && !h->ch_uniform) return launch_pass_impl<T, NT, false, true>(h, p, win);
+    return launch_pass_impl<T, NT, true, true>(h, p, win);
 }
 
 template <class T, int NT> int launch_probe_nt(fdtd2d *h, const fdtd::PassParams<T> &p, const fdtd::ProbeParams &q)
@@ -300,15 +302,15 @@ template <class T> int launch_probe(fdtd2d *h, int nt, const fdtd::PassParams<T>
 }
 
 #ifdef FDTD_PASS_LONG_EXTERN   // the 16- and 20-step float32 kernels are built in translation units of their own
-extern template int launch_pass_nt<float, 16>(fdtd2d *, fdtd::PassParams<float> &);
-extern template int launch_pass_nt<float, 20>(fdtd2d *, fdtd::PassParams<float> &);
-extern template int launch_pass_nt<double, 16>(fdtd2d *, fdtd::PassParams<double> &);
+extern template int launch_pass_nt<float, 16>(fdtd2d *, fdtd::PassParams<float> &, const fdtd_aw::Launch *);
+extern template int launch_pass_nt<float, 20>(fdtd2d *, fdtd::PassParams<float> &, const fdtd_aw::Launch *);
+extern template int launch_pass_nt<double, 16>(fdtd2d *, fdtd::PassParams<double> &, const fdtd_aw::Launch *);
 #endif
 
 // One pass of nt in {1,2,4,8,16} steps; amps = nt amplitudes or nullptr.
 template <class T> int launch_pass(fdtd2d *h, int nt, int band_lo, int band_hi, int src_row,
                                    int src_col, const double *amps, bool ztop, bool zbot,
-                                   bool commit, int full_lo, int full_hi, int nlev)
+                                   bool commit, int full_lo, int full_hi, int nlev, const fdtd_aw::Launch *win)
 {
     // (k_bulk also instantiates with 2 columns per lane -- 86 VGPRs, 4-5 waves per SIMD -- but
     // that measured 20 % slower than 4 columns: profiles/r01_kpass_ablation.txt)
@@ -330,11 +332,15 @@ template <class T> int launch_pass(fdtd2d *h, int nt, int band_lo, int band_hi, 
     p.band_hi = band_hi;
     int br = h->stream_band_rows;
     h->shape_now = fdtd2d::Shape{0, 0};
-    if (const fdtd2d::Shape *gs = br <= 0 ? h->shape_given(nt) : nullptr) {
-        h->shape_now = *gs;
+    const bool windowed = win != nullptr;       // never tuned: a rule of its own below
+    const fdtd2d::Shape *gs = br <= 0 ? h->shape_given(nt) : nullptr;
+    if (gs) {
+        // (a window takes the band heights and the waves of a given shape; strips of several waves, the XCD map, filler
+        // bands and fused 20-step zone tiles belong to the whole-grid launch the shape was measured on)
+        h->shape_now = windowed ? fdtd2d::Shape{gs->band_rows, gs->waves, gs->edge_rows} : *gs;
         br = gs->band_rows;
     }
-    if (br <= 0) {
+    if (br <= 0 && !windowed) {
         auto it = h->tuned.find({nt, band_lo, band_hi});
         if (it != h->tuned.end()) {
             h->shape_now = it->second;
@@ -345,12 +351,29 @@ template <class T> int launch_pass(fdtd2d *h, int nt, int band_lo, int band_hi, 
     {
         int sd = h->side_waves > 0 ? h->side_waves : std::max(1, h->shape_now.side);
         if (!h->side_ok(nt, sd) || !h->use_level_split(nt, band_lo, band_hi) || h->pml_split(nt) ||
-            (h->split_waves != 0 && h->split_waves != 4))
-            sd = 1;
+            (h->split_waves != 0 && h->split_waves != 4) || windowed)
+            sd = 1;             // (a restricted launch: the narrowest strips)
         h->shape_now.side = sd;
         if (sd > 1) h->shape_now.waves = 4;
         const int OW = pass_strip_ow(nt, V, 4, sd);
         p.nstrips = (h->cols + OW - 1) / OW;
+    }
+    if (br <= 0 && windowed) {
+        // A window is a small launch: one round of workgroups where the strips allow it (a band lives its rows plus
+        // ~3 nt ticks of fill and drain, so one tall band per strip would set the launch time), bands of at least 32
+        // rows (shorter ones are mostly fill), at most the tallest the tuner ever tries.  DERIVED, NOT TUNED: the slot
+        // count (256 CUs x 16 wave slots / waves per workgroup, 90 % of it), the 32 and the 448 are reasoned from the
+        // dense launch's figures, and split_waves_for below sees the WINDOW's row count, so windows of fewer than
+        // 12 Mi (8-step passes: 3 Mi) cells run 8 waves per strip.  No shape sweep of windowed launches exists; what
+        // is measured is whole runs against the dense ones at 3072^2, 4096^2, 8192^2 and 16384^2, where the window
+        // covers 1 to 27 % of the grid (profiles/active_window.txt).
+        const int region = std::max(0, band_hi - band_lo);
+        const bool split4 = h->use_level_split(nt, band_lo, band_hi);
+        const int nw = split4 ? std::max(1, h->split_waves_for(nt, band_lo, band_hi)) : 1;
+        const int slots = split4 ? 256 * 16 / nw * 9 / 10 : 3072;
+        const int ns = std::max(1, win->n_inner + (win->edges ? 2 : 0));
+        const int per = std::max(1, slots / ns);
+        br = std::min(std::max((region + per - 1) / per, 32), 448);
     }
     if (br <= 0) {
         // Measured on MI355X (interleaved A/B, profiles/r01_band_sweep.txt): the pass is fastest
@@ -377,6 +400,14 @@ template <class T> int launch_pass(fdtd2d *h, int nt, int band_lo, int band_hi, 
     p.band_rows = std::max(br, 1);
     p.band_rows_e = h->shape_now.edge_rows > 0 ? h->shape_now.edge_rows : p.band_rows;
     h->last_nt = nt;
+    if (windowed && !gs) {
+        // fdtd2d_last_shape is the shape of the last WHOLE-GRID launch shape in use: callers hand it on to
+        // fdtd2d_set_shape, which pins dense launches, and a window's rule-made shape would be a poor one there.  After a
+        // windowed pass on the rule it is the shape the tuner holds for this pass over the whole grid, or zeros (= none);
+        // a window launched on a given shape reports that shape, like any other pass.
+        auto it = h->tuned.find({nt, full_lo, full_hi});
+        h->shape_last = it != h->tuned.end() ? it->second : fdtd2d::Shape{0, 0, 0, 0};
+    } else
     h->shape_last = fdtd2d::Shape{p.band_rows,
                                   h->pml_split(nt) ? 4 : (h->use_level_split(nt, band_lo, band_hi) ? h->split_waves_for(nt, band_lo, band_hi) : 1),
                                   h->pml_split(nt) ? (h->shape_now.edge_rows > 0 ? h->shape_now.edge_rows : h->pml_layer_rows) : p.band_rows_e,
@@ -393,7 +424,7 @@ template <class T> int launch_pass(fdtd2d *h, int nt, int band_lo, int band_hi, 
     p.src_col1 = amps ? src_col + h->src_cols : NONE;
     // a short pass: the nt-step kernel and geometry, advancing only nlev < nt levels (one sweep
     // over the grid for a tail of 3, 5, 6, 7, 9..15 steps instead of one per power of two)
-    p.strip_first = 1;
+    p.strip_first = windowed ? win->strip_first : 1;
     p.xcd_map = p.main_pad = p.main_per = p.main_tasks = p.n_inner = 0;
     p.zone_wgs = p.zone_last = 0;
     p.band_rows2 = p.nbands2 = 0;
@@ -453,21 +484,24 @@ template <class T> int launch_pass(fdtd2d *h, int nt, int band_lo, int band_hi, 
     } else
     switch (nt) {
     case 20:
-        if constexpr (sizeof(T) == 4) { rc = launch_pass_nt<T, 20>(h, p); break; }
+        if constexpr (sizeof(T) == 4) { rc = launch_pass_nt<T, 20>(h, p, win); break; }
         return fail(h, FDTD2D_E_ARG, "20-step passes are built for float32 only");
-    case 16: rc = launch_pass_nt<T, 16>(h, p); break;
-    case 8: rc = launch_pass_nt<T, 8>(h, p); break;
-    case 4: rc = launch_pass_nt<T, 4>(h, p); break;
-    case 2: rc = launch_pass_nt<T, 2>(h, p); break;
-    case 1: rc = launch_pass_nt<T, 1>(h, p); break;
+    case 16: rc = launch_pass_nt<T, 16>(h, p, win); break;
+    case 8: rc = launch_pass_nt<T, 8>(h, p, win); break;
+    case 4: rc = launch_pass_nt<T, 4>(h, p, win); break;
+    case 2: rc = launch_pass_nt<T, 2>(h, p, win); break;
+    case 1: rc = launch_pass_nt<T, 1>(h, p, win); break;
     default: return fail(h, FDTD2D_E_ARG, "unsupported pass length %d", nt);
     }
     if (rc) return rc;
     if (commit) {
+        h->aw.commit_pass(amps ? fdtd_aw::Rect{src_row, src_row + h->src_rows, src_col, src_col + h->src_cols} : fdtd_aw::Rect{}, p.nlev);
         h->cur ^= 1;
         h->hcur ^= 1;
         h->ev = h->hv = Range{h->top() ? 0 : full_lo, h->bottom() ? h->rows : full_hi};
         h->step += p.nlev;
+    } else {
+        h->aw.uncommitted();
     }
     return 0;
 }

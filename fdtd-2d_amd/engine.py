@@ -317,7 +317,7 @@ class Engine:
         return self
 
     def set_option(self, max_pass_steps=None, band_rows=None, zone_split=None, level_split=None,
-                   split_waves=None, autotune=None, xcd_map=None, side_waves=None):
+                   split_waves=None, autotune=None, xcd_map=None, side_waves=None, active_window=None):
         """Speed knobs of run(): longest temporally blocked pass (0 = single-step kernels
         only) and rows per streaming band.  Results do not depend on them."""
         if max_pass_steps is not None:
@@ -336,6 +336,8 @@ class Engine:
             self._ck(self._lib.fdtd2d_set_option(self._h, _abi.OPT_SIDE_WAVES, int(side_waves)))
         if xcd_map is not None:
             self._ck(self._lib.fdtd2d_set_option(self._h, _abi.OPT_XCD_MAP, int(xcd_map)))
+        if active_window is not None:      # -1 automatic (>= 4 Mi cells), 0 off, 1 on at any size
+            self._ck(self._lib.fdtd2d_set_option(self._h, _abi.OPT_ACTIVE_WINDOW, int(active_window)))
         return self
 
     def set_shape(self, shape, pass_steps=0):
@@ -493,6 +495,33 @@ class Engine:
     def cycle_steps(self) -> int:
         """Longest temporally blocked pass the current configuration runs (16 / 8 / 0)."""
         return self.info(_abi.INFO_CYCLE_STEPS)
+
+    @property
+    def active_window(self):
+        """(row_lo, row_hi, col_lo, col_hi): outside these half-open ranges Ez, Hx and Hy are known to be zero.  Empty
+        (all 0) after reset(), the whole grid where nothing is known (upload, slabs, PML engines)."""
+        return tuple(self.info(k) for k in (_abi.INFO_WINDOW_ROW_LO, _abi.INFO_WINDOW_ROW_HI,
+                                            _abi.INFO_WINDOW_COL_LO, _abi.INFO_WINDOW_COL_HI))
+
+    @property
+    def windowed_launches(self) -> int:
+        """Passes of run() so far that launched less than the whole grid."""
+        return self.info(_abi.INFO_WINDOWED_LAUNCHES)
+
+    @property
+    def window_enabled(self) -> bool:
+        """Whether run() may launch windows now: the option, the size rule of its automatic mode, and what switches
+        that mode off for a handle (a launch shape given with set_shape, a pointer handed out by device_ptr)."""
+        return bool(self.info(_abi.INFO_WINDOW_ENABLED))
+
+    def device_ptr(self, field="Ez") -> int:
+        """Device address of a field's storage (row-major, `pitch` elements per row) for zero-copy interop.  The caller
+        may write through it: the active window reports the whole grid from here on, and its automatic mode is off."""
+        f = {"Ez": _abi.FIELD_EZ, "Hx": _abi.FIELD_HX, "Hy": _abi.FIELD_HY}[field]
+        p = self._lib.fdtd2d_device_ptr(self._h, f)
+        if not p:
+            raise ValueError(f"no device pointer for field {field!r}")
+        return int(p)
 
     @property
     def step_count(self) -> int:

@@ -80,6 +80,8 @@ typedef struct fdtd2d fdtd2d_t;
 #define FDTD2D_INFO_STEP        15 /* completed E half-steps since create/upload */
 #define FDTD2D_INFO_PASS_LAUNCHES 16 /* temporally blocked pass kernels launched so far */
 #define FDTD2D_INFO_STEP_LAUNCHES 17 /* single half-step kernels launched so far */
+/* 19-21, 23, 24: the launch shape fdtd2d_last_shape returns, entry by entry -- see there for what it is after a pass
+   that launched a window */
 #define FDTD2D_INFO_LAST_BAND_ROWS 19 /* band height of the last temporally blocked pass */
 #define FDTD2D_INFO_LAST_WAVES    20 /* its waves per (band, strip): 1 (k_bulk), 4 or 8 (k_bulk_split) */
 #define FDTD2D_INFO_LAST_EDGE_ROWS 21 /* its band height on the first / last strip */
@@ -88,6 +90,14 @@ typedef struct fdtd2d fdtd2d_t;
 #define FDTD2D_INFO_LAST_XCD_MAP    24 /* 1 if its tasks were dealt out XCD by XCD */
 #define FDTD2D_INFO_CYCLE_STEPS   18 /* longest pass the current configuration runs: 16 (float32, Mur
                                          frame, >= 12 Mi cells per GPU), else 8, 0 if passes are off */
+#define FDTD2D_INFO_WINDOW_ROW_LO   25 /* the active window (FDTD2D_OPT_ACTIVE_WINDOW): rows [25, 26) x columns [27, 28) */
+#define FDTD2D_INFO_WINDOW_ROW_HI   26 /* outside which Ez, Hx and Hy are known to be zero; the whole grid where nothing */
+#define FDTD2D_INFO_WINDOW_COL_LO   27 /* is known (after an upload, on slabs and PML engines), all four 0 after a reset */
+#define FDTD2D_INFO_WINDOW_COL_HI   28
+#define FDTD2D_INFO_WINDOWED_LAUNCHES 29 /* passes of fdtd2d_run so far that launched less than the whole grid */
+#define FDTD2D_INFO_WINDOW_ENABLED  30 /* 1 while fdtd2d_run may launch windows on this handle: the option, the size
+                                         rule of its automatic mode, and what ends that mode for a handle (a shape given
+                                         with fdtd2d_set_shape, a pointer handed out by fdtd2d_device_ptr) */
 
 /* ---- lifetime ------------------------------------------------------------------ */
 
@@ -254,6 +264,16 @@ int fdtd2d_sync(fdtd2d_t *h);
                                          strip of 504 / 1000 columns and exchange their boundary columns through the
                                          LDS hand-off -- the 32 overlap columns of a strip are paid once per 504 / 1000
                                          columns instead of per 256; 1 = never; 0 (default) = the tuner decides. */
+#define FDTD2D_OPT_ACTIVE_WINDOW   9   /* Whole-grid engines with the Mur frame keep a bound on the cells that can be
+                                         non-zero: empty after fdtd2d_reset / fdtd2d_create, one cell wider on every side
+                                         per step (faster next to the frame), the whole grid after fdtd2d_upload and
+                                         whatever else writes fields from outside.  While that bound -- together with
+                                         what the target buffers may still hold -- covers at most half the grid, a pass
+                                         of fdtd2d_run / fdtd2d_run_waveform launches only the bands and strips that
+                                         cover it; everything else is zero before and after.  Results are the same but
+                                         for the sign of zeros.  -1 (default): on for grids of >= 4 Mi cells; 0: off;
+                                         1: on at any size.  fdtd2d_time_launches and the tuner's trial launches always
+                                         sweep the whole grid. */
 int fdtd2d_set_option(fdtd2d_t *h, int option, long long value);
 
 /* Launch shape of the temporally blocked passes of `pass_steps` steps (0 = the full-length passes, 16 or 8): re-use
@@ -263,7 +283,16 @@ int fdtd2d_set_option(fdtd2d_t *h, int option, long long value);
  * bands that take over the slots the zone tiles free (0, 0 = none), and for float32 20-step passes whether the zone tiles
  * ride in the bulk launch (1) or run as their own kernel on a side stream (0); missing trailing entries are 0 (side: 1);
  * shape[0] = 0 clears it.  fdtd2d_last_shape returns the shape the last pass ran with, in the same order.  Results never
- * depend on the shape. */
+ * depend on the shape.
+ * Giving a shape (band rows > 0, for any pass length) ends the automatic mode of the active window
+ * (FDTD2D_OPT_ACTIVE_WINDOW = -1) for this handle until the shape is cleared: a caller that pins its launches measures or
+ * replays the whole-grid launch of that shape -- profiler and roofline runs do.  FDTD2D_INFO_WINDOW_ENABLED shows it.  With
+ * the option at 1 the window stays, and its launch takes the band rows, the waves and the edge band rows of the shape
+ * (always one wave per level group side by side, no XCD map, no filler bands, zone tiles on the side stream).
+ * fdtd2d_last_shape is the shape of whole-grid launches, the one to hand on to fdtd2d_set_shape.  After a pass that
+ * launched a window on its own rule-made shape it returns the shape the tuner holds for that pass over the whole grid, or
+ * zeros if it holds none -- never the window's shape, which would pin a poor dense launch; after a window launched on a
+ * given shape it returns that shape as launched.  FDTD2D_INFO_LAST_PASS_STEPS is the last pass's either way. */
 #define FDTD2D_SHAPE_LEN 8
 int fdtd2d_set_shape(fdtd2d_t *h, int pass_steps, const int *shape, int n);
 int fdtd2d_last_shape(const fdtd2d_t *h, int *shape, int n);
@@ -372,7 +401,11 @@ int fdtd2d_clock_probe_read(fdtd2d_t *h, double *mhz8);
 int fdtd2d_bytes_per_cell_step(const fdtd2d_t *h);
 
 /* Device pointer of a field's storage (row-major, pitch elements per row, first
- * stored row = global row row0-halo) for zero-copy interop.  NULL on error. */
+ * stored row = global row row0-halo) for zero-copy interop.  NULL on error.
+ * The caller may write through the pointer, so the call marks every cell as possibly non-zero, and in its automatic
+ * mode the active window (FDTD2D_OPT_ACTIVE_WINDOW) stays off for this handle from then on.  A caller that sets the
+ * option to 1 afterwards vouches for its writes: it fetches the pointer anew (which marks the fields again) before
+ * every run that follows a write of its own. */
 void *fdtd2d_device_ptr(fdtd2d_t *h, int field);
 
 /* ---- batched grids ------------------------------------------------------------------
