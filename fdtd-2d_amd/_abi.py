@@ -55,6 +55,8 @@ BATCH_INFO_PERIODIC = 15
 BATCH_INFO_BLOCH = 16
 # include/fdtd2d_batch_bloch_adjoint.h
 BATCH_INFO_BLOCH_POINT_SOURCES, BATCH_INFO_HELD_BLOCH_WINDOW = 17, 18
+# include/fdtd2d_batch_dispersive.h
+BATCH_INFO_DISPERSIVE = 19
 
 _vp, _i, _d, _ll = C.c_void_p, C.c_int, C.c_double, C.c_longlong
 
@@ -197,6 +199,13 @@ BATCH_BLOCH_ADJOINT_SIGNATURES = {
     "fdtd2d_batch_bloch_field_absmax": (_i, [_vp, _i, C.POINTER(_d)]),
 }
 
+# every symbol include/fdtd2d_batch_dispersive.h declares (a Drude-Lorentz pole per member of a batch)
+BATCH_DISPERSIVE_SIGNATURES = {
+    "fdtd2d_batch_set_dispersion": (_i, [_vp, _vp, _i, C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_set_dispersion_window": (_i, [_vp, C.POINTER(_i), _vp, _i]),
+    "fdtd2d_batch_transfer_dispersion": (_i, [_vp, _vp, _vp, _i, _i]),
+}
+
 # transport callback of fdtd2d_slab_attach
 EXCHANGE_FN = C.CFUNCTYPE(_i, _vp, _vp, _vp, _vp, _vp, _ll, _vp)
 
@@ -247,7 +256,8 @@ def load():
         for name, (res, args) in {**SIGNATURES, **BATCH_PML_SIGNATURES, **BATCH_MONITOR_SIGNATURES,
                                    **BATCH_ADJOINT_SIGNATURES, **BATCH_DESIGN_SIGNATURES,
                                    **BATCH_LOSSY_SIGNATURES, **BATCH_PERIODIC_SIGNATURES,
-                                   **BATCH_BLOCH_SIGNATURES, **BATCH_BLOCH_ADJOINT_SIGNATURES}.items():
+                                   **BATCH_BLOCH_SIGNATURES, **BATCH_BLOCH_ADJOINT_SIGNATURES,
+                                   **BATCH_DISPERSIVE_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

@@ -266,6 +266,16 @@ def _refuse_bloch(eng):
     if getattr(eng, "_bloch", None) is not None:
         from ._abi import E_STATE, Fdtd2dError
         raise Fdtd2dError(E_STATE, "adjoint gradients are not available while a Bloch phase is set (complex fields)")
+    _refuse_dispersion(eng)
+
+
+def _refuse_dispersion(eng):
+    """The adjoint of a dispersive medium is not implemented: an engine with a Drude-Lorentz pole (an engine factory
+    that sets one, or set_dispersion on a session's engine) is refused before any run."""
+    if getattr(eng, "dispersive", False):
+        from ._abi import E_STATE, Fdtd2dError
+        raise Fdtd2dError(E_STATE, "adjoint gradients are not available while a dispersive pole is set: the adjoint of a "
+                          "dispersive medium is not implemented")
 
 
 def _cotangent(p, objective, spectra):
@@ -734,7 +744,7 @@ class BlochAdjointSession(AdjointSession):
     # the engine calls of an iteration: the complex counterparts
     @staticmethod
     def _check_engine(eng):
-        pass                                    # the engine's own calls refuse a batch without a phase
+        _refuse_dispersion(eng)                 # the engine's own calls refuse a batch without a phase
 
     def _setup_engine(self, eng):
         _bloch_setup(eng, self._p, None, self._phi, self._weights)

@@ -15,7 +15,8 @@ absorbers, resistive sheets); the batch then runs on the lossy step kernels.
 metasurface unit cells, photonic-crystal slabs): column C-1 is the image of column 0, rows end in the PML of ``set_pml``
 or in PEC (fdtd2d_batch_periodic.h).  ``set_bloch_phase`` gives a periodic batch one Bloch phase per member: the fields
 become complex and repeat as F(x + period) = F(x) e^{i phi} (oblique incidence, angle sweeps, band diagrams;
-fdtd2d_batch_bloch.h).
+fdtd2d_batch_bloch.h).  ``set_dispersion`` gives a PML or periodic batch one Drude-Lorentz pole per member with a strength
+per cell (metals, absorption lines; fdtd2d_batch_dispersive.h); the batch then runs on the dispersive step kernels.
 """
 from __future__ import annotations
 
@@ -155,6 +156,11 @@ class BatchEngine:
     def bloch(self) -> bool:
         """Whether a Bloch phase is set (complex fields, the batch runs on the Bloch kernels)."""
         return bool(self.info(_abi.BATCH_INFO_BLOCH))
+
+    def _no_dispersion(self, what):
+        """The library's refusal of `what` while a dispersive pole is set, before the call."""
+        if self.dispersive:
+            raise _abi.Fdtd2dError(_abi.E_STATE, f"{what} is not available while a dispersive pole is set")
 
     def _no_bloch(self, what):
         """The library's refusal of `what` while a Bloch phase is set, before the call."""
@@ -504,6 +510,7 @@ class BatchEngine:
     def hold_dft_window(self):
         """Keep a device copy of the window DFT as it is now; it survives reset() and further runs."""
         self._no_bloch("the held window")
+        self._no_dispersion("the held window (the adjoint of a dispersive medium)")
         self._ck(self._lib.fdtd2d_batch_hold_dft_window(self._h))
         return self
 
@@ -511,6 +518,7 @@ class BatchEngine:
         """float64 (B, nrows, ncols): sum_k Re(coef[b, k] * held[b, k] * current[b, k]) over the window, on the device.
         coef: complex (F,) for every member or (B, F)."""
         self._no_bloch("the window product")
+        self._no_dispersion("the window product (the adjoint of a dispersive medium)")
         f, nr, nc = self._win or (0, 1, 1)
         k = np.asarray(coef, dtype=np.complex128)
         if k.ndim == 1:
@@ -830,6 +838,81 @@ class BatchEngine:
         """Whether a conductivity is set (the batch runs on the lossy kernels)."""
         return bool(self.info(_abi.BATCH_INFO_LOSSY))
 
+    # -- dispersive materials (fdtd2d_batch_dispersive.h) --------------------------------------------------------
+    def set_dispersion(self, wp2, gamma=0.0, omega0=0.0):
+        """One Drude-Lorentz pole per member: chi(w) = wp2 / (omega0**2 - w**2 - 1j * gamma * w) for a field
+        ~ exp(-1j * w * t), so eps(w) = eps + EPS0 * chi(w).  wp2 in rad^2/s^2, >= 0: (B, R, C), or a scalar for every
+        cell that may carry it (zero in the margin of conductivity_margin), or None to remove the pole.  gamma and
+        omega0 in rad/s, >= 0: a scalar or (B,); omega0 = 0 is a Drude pole, a Lorentz pole of strength d_eps has
+        wp2 = d_eps * omega0**2.  Needs boundary="pml" with its layer set, or boundary="periodic", and materials.  The
+        state (download_dispersion) starts at zero and survives later calls; reset() zeroes it.  The library refuses
+        (E_ARG) a value that is negative or not finite, wp2 non-zero inside the margin, and a cell whose pole breaks
+        dt^2 (omega0^2 + wp2 EPS0 / eps) + 8 dt^2 / (eps mu dx^2) <= 4; while a pole is set it refuses (E_STATE) a Bloch
+        phase, removing the layer of a "pml" batch and the held window with its product."""
+        if wp2 is None:
+            self._ck(self._lib.fdtd2d_batch_set_dispersion(self._h, None, _code(self.dtype), None, None))
+            return self
+        shape = (self.count, self.rows, self.cols)
+        if np.isscalar(wp2):
+            g = self.conductivity_margin
+            w = np.zeros(shape, np.float64)
+            if self.boundary == "periodic":
+                w[:, g:self.rows - g, :] = float(wp2)
+            else:
+                w[:, g:self.rows - g, g:self.cols - g] = float(wp2)
+            if not float(wp2) >= 0:               # negative or NaN: let the library name it even where w is empty
+                w[...] = float(wp2)
+        else:
+            w = _host(wp2, "wp2")
+        self._shape(w, shape, "wp2")
+        per = []
+        for v, nm in ((gamma, "gamma"), (omega0, "omega0")):
+            a = np.asarray(v, dtype=np.float64)
+            if a.shape not in ((), (self.count,)):
+                raise ValueError(f"{nm} must be a scalar or have shape ({self.count},), got {a.shape}")
+            per.append(np.ascontiguousarray(np.broadcast_to(a, (self.count,))))
+        self._ck(self._lib.fdtd2d_batch_set_dispersion(self._h, w.ctypes.data, _code(w.dtype), _dptr(per[0]),
+                                                       _dptr(per[1])))
+        return self
+
+    def set_dispersion_window(self, window, wp2):
+        """New strengths for window = (row0, col0, nrows, ncols) of every member: wp2 (B, nrows, ncols).  The engine
+        is then as set_dispersion with the full updated array would leave it.  Needs a pole (E_STATE)."""
+        w = np.ascontiguousarray([int(v) for v in window], dtype=np.int32)
+        if w.shape != (4,):
+            raise ValueError(f"window must be 4 integers (row0, col0, nrows, ncols), got {window!r}")
+        s = _host(wp2, "wp2")
+        self._shape(s, (self.count, int(w[2]), int(w[3])), "wp2")
+        self._ck(self._lib.fdtd2d_batch_set_dispersion_window(self._h, w.ctypes.data_as(C.POINTER(C.c_int)),
+                                                              s.ctypes.data, _code(s.dtype)))
+        return self
+
+    @property
+    def dispersive(self) -> bool:
+        """Whether a dispersive pole is set (the batch runs on the dispersive kernels)."""
+        return bool(self.info(_abi.BATCH_INFO_DISPERSIVE))
+
+    def download_dispersion(self):
+        """(Jh, Q), each (B, R, C) of the engine dtype: dx times the polarisation current at the last half step, and
+        dx * P / dt (needs a pole)."""
+        jh = np.empty((self.count, self.rows, self.cols), self.dtype)
+        q = np.empty_like(jh)
+        self._ck(self._lib.fdtd2d_batch_transfer_dispersion(self._h, jh.ctypes.data, q.ctypes.data, _code(jh.dtype), 0))
+        return jh, q
+
+    def upload_dispersion(self, Jh=None, Q=None):
+        """(B, R, C) each, host -> device; one given as None is left as is.  On a periodic batch column C-1 is
+        overwritten with column 0 (needs a pole)."""
+        arrs = []
+        for a, nm in ((Jh, "Jh"), (Q, "Q")):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=self.dtype)
+                self._shape(a, (self.count, self.rows, self.cols), nm)
+            arrs.append(a)
+        ptr = [None if a is None else a.ctypes.data for a in arrs]
+        self._ck(self._lib.fdtd2d_batch_transfer_dispersion(self._h, ptr[0], ptr[1], _code(self.dtype), 1))
+        return self
+
     def sync(self):
         self._ck(self._lib.fdtd2d_batch_sync(self._h))
         return self
@@ -851,7 +934,8 @@ def _waveform_amps(kind, fc, nsteps, dt):
 
 def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker", dt=5e-14, dx=1e-4,
                    dtype=np.float64, boundary="mur", omega=None, dft_every=1, device=0, pml_cells=40,
-                   dft_window=None, window_omegas=None, probes=None, bloch_phase=None, source_weights=None):
+                   dft_window=None, window_omegas=None, probes=None, bloch_phase=None, source_weights=None,
+                   dispersion=None):
     """run_fdtd for B members of one shape at once: zero fields, Courant check per member, nsteps of
     H -> E -> source with t = i*dt.
 
@@ -866,7 +950,8 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
     (B, R, C) DFT when omega is given, then the complex (B, F, nrows, ncols) window DFT when dft_window is given, then
     the float64 (B, P, nsteps) probe traces when probes are given.  bloch_phase (boundary "periodic" alone): a scalar or
     (B,) in radians, the Bloch phase of set_bloch_phase; every returned array is then complex.  source_weights: "ramp",
-    None or an array as set_bloch_source takes them (needs bloch_phase).
+    None or an array as set_bloch_source takes them (needs bloch_phase).  dispersion = (wp2, gamma, omega0) as
+    set_dispersion takes them: one Drude-Lorentz pole per member (boundary "pml" or "periodic", not with bloch_phase).
     """
     from .api import MU0
     eps = np.asarray(eps)
@@ -901,6 +986,13 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
         raise ValueError("source_weights needs bloch_phase")
     if bloch_phase is not None and omega is not None:
         raise ValueError("omega (the whole-grid transform) is not available with bloch_phase: use dft_window")
+    if dispersion is not None:
+        if len(dispersion) != 3:
+            raise ValueError("dispersion must be (wp2, gamma, omega0)")
+        if boundary not in ("pml", "periodic"):
+            raise ValueError(f'dispersion needs boundary="pml" or "periodic", not {boundary!r}')
+        if bloch_phase is not None:
+            raise ValueError("dispersion is not available with bloch_phase")
     win, wom, cells = _check_monitors(B, R, Cc, dft_window, window_omegas, probes, dft_every)
     if bloch_phase is not None:
         if win is not None and win[1] + win[3] > Cc - 1:
@@ -912,6 +1004,8 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
         if layered:
             eng.set_pml(L, courant00=courant00)
         eng.set_sources(sources)
+        if dispersion is not None:
+            eng.set_dispersion(*dispersion)
         if bloch_phase is not None:
             eng.set_bloch_phase(bloch_phase)
             if source_weights is not None:

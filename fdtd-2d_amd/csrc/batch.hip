@@ -14,11 +14,13 @@
 // With a Bloch phase (fdtd2d_batch_bloch.h) every run takes the complex-field kernels of batch_bloch.hip.
 // fdtd2d_batch_run_bloch_channels (fdtd2d_batch_bloch_adjoint.h) takes their point-source instances
 // (batch_bloch_adjoint.hip), which also holds the product kernel of two complex windows.
+// With a Drude-Lorentz pole (fdtd2d_batch_dispersive.h) every run takes the dispersive kernels of batch_dispersive.hip.
 #include "../../include/fdtd2d.h"
 #include "../../include/fdtd2d_batch_adjoint.h"
 #include "../../include/fdtd2d_batch_bloch.h"
 #include "../../include/fdtd2d_batch_bloch_adjoint.h"
 #include "../../include/fdtd2d_batch_design.h"
+#include "../../include/fdtd2d_batch_dispersive.h"
 #include "../../include/fdtd2d_batch_lossy.h"
 #include "../../include/fdtd2d_batch_monitor.h"
 #include "../../include/fdtd2d_batch_periodic.h"
@@ -40,6 +42,7 @@
 #include "kernels_batch_bloch.hpp"
 #include "kernels_batch_bloch_adjoint.hpp"
 #include "kernels_batch_design.hpp"
+#include "kernels_batch_dispersive.hpp"
 #include "kernels_batch_lossy.hpp"
 #include "kernels_batch_monitor.hpp"
 #include "kernels_batch_periodic.hpp"
@@ -69,6 +72,10 @@ struct fdtd2d_batch {
     void *ca = nullptr, *cb = nullptr;
     std::vector<double> sigma_host;
     double eps_u = 0, mu_u = 0;           // uniform materials as given (a conductivity materialises them)
+    // fdtd2d_batch_set_dispersion: Jh, Q and cj beside the fields (nullptr = no pole), a and ck per member in T; the
+    // strengths (count x rows x cols), the dampings and the resonances as given
+    void *djh = nullptr, *dq = nullptr, *dcj = nullptr, *da = nullptr, *dck = nullptr;
+    std::vector<double> wp2_host, disp_gamma, disp_omega0;
     void *dsg = nullptr;                  // device scratch of the design-loop entry points
     size_t dsg_cap = 0;
     // fdtd2d_batch_set_periodic: column C-1 is the image of column 0.  The batch then always holds Ezx and the factors
@@ -246,6 +253,8 @@ int zero_fields(fdtd2d_batch *b)
 {
     for (void *p : {b->ez[0], b->ez[1], b->hx, b->hy}) BCHK(b, hipMemsetAsync(p, 0, b->field_bytes, b->stream));
     if (b->ezx) BCHK(b, hipMemsetAsync(b->ezx, 0, b->field_bytes, b->stream));
+    if (b->dcj)
+        for (void *p : {b->djh, b->dq}) BCHK(b, hipMemsetAsync(p, 0, b->field_bytes, b->stream));
     if (b->bloch)
         for (void *p : {b->ez_im, b->hx_im, b->hy_im, b->ezx_im}) BCHK(b, hipMemsetAsync(p, 0, b->field_bytes, b->stream));
     b->cur = 0;
@@ -257,10 +266,12 @@ int zero_fields(fdtd2d_batch *b)
 // ---- the capacity rule of the resident path ------------------------------------------------------------
 // Mur / none: Ez, Hx, Hy (+ ce, ch); PML: Ez, Hx, Hy, Ezx (+ ce, ch) and the 4R + 4C factors; with a conductivity
 // cb stands in ce's place and ca is one more array; a Bloch phase: the four fields twice and cb, ch, ca, the row
-// factors alone, the source weights with the tables and the accumulators twice
+// factors alone, the source weights with the tables and the accumulators twice; a pole: the lossy PML arrays and Jh,
+// Q, cj
 int lds_arrays(const fdtd2d_batch *b)
 {
     if (b->bloch) return 11;
+    if (b->dcj) return 10;
     if (b->periodic) return 7;
     if (b->ca) return b->ezx ? 7 : 6;
     return (b->have_mat && b->uniform) ? (b->ezx ? 4 : 3) : (b->ezx ? 6 : 5);
@@ -698,6 +709,67 @@ int run_periodic(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_
     return 0;
 }
 
+// ---- dispersive runs (fdtd2d_batch_dispersive.h): the lossy PML or the periodic paths with the kernels of
+// batch_dispersive.hip.  The streamed H launches are those paths' own: H does not see the pole.
+template <class T>
+int run_dispersive(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts)
+{
+    if (!b->ca || !b->ezx || !b->djh || !b->dq || !b->da || !b->dck)
+        return bfail(b, FDTD2D_E_STATE, "dispersive batch without its arrays");
+    const fdtd::BatchDispersiveKernels &K = fdtd::batch_dispersive_kernels<T>();
+    fdtd::BatchPml<T> p = pml_view<T>(b);
+    fdtd::BatchMon m = mon_view(b);
+    fdtd::BatchPts silent{};
+    if (!pts) pts = &silent;
+    fdtd::BatchDisp<T> d{(T *)b->djh, (T *)b->dq, (const T *)b->dcj, (const T *)b->da, (const T *)b->dck};
+    const T *ca = (const T *)b->ca;
+    if (use_resident(b)) {
+        const int cells = b->rows * b->cols, threads = resident_threads(cells);
+        const int per_thread = (cells + threads - 1) / threads;
+        if (per_thread > 4)
+            return bfail(b, FDTD2D_E_STATE, "%d cells per thread exceed the dispersive resident kernel's 4", per_thread);
+        const void *kern = b->periodic ? K.resident_periodic : K.resident_pml;
+        const size_t lds = lds_bytes(b);
+        BCHK(b, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        int per_cu = 0, cus = 0;
+        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds));
+        BCHK(b, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
+        if (per_cu < 1) return bfail(b, FDTD2D_E_STATE, "dispersive resident kernel does not fit a CU (%zu B of LDS)", lds);
+        const long long round = (long long)per_cu * cus;
+        const int blocks = (int)(b->count < round ? b->count : round);
+        const int chunk = b->steps_per_launch > 0 ? b->steps_per_launch : nsteps;
+        for (int n = 0; n < nsteps; n += chunk) {
+            int n0 = n, nt = nsteps - n < chunk ? nsteps - n : chunk;
+            long long step_base = b->step;
+            fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+            v.ce = (const T *)b->cb;
+            void *args[] = {&v, &p, &m, pts, &d, &ca, &n0, &nt, &step_base};
+            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads), args, lds);
+            if (rc) return rc;
+            b->launches++;
+            b->step += nt;
+        }
+        return 0;
+    }
+    const void *kh = b->periodic ? fdtd::batch_periodic_kernels<T>().h : fdtd::batch_pts_kernels<T>().h_pml[1];
+    const void *ke = b->periodic ? K.e_periodic : K.e_pml;
+    const int cells = b->rows * b->cols;
+    const dim3 grid((cells + 255) / 256, b->count < 65535 ? b->count : 65535);
+    for (int n = 0; n < nsteps; ++n) {
+        fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+        v.ce = (const T *)b->cb;
+        long long step = b->step + 1;
+        int rc;
+        void *h_args[] = {&v, &p, &m, pts, &n, &step};
+        void *e_args[] = {&v, &p, &m, pts, &d, &ca, &n, &step};
+        if ((rc = launch_ptr(b, kh, grid, dim3(256), h_args, 0))) return rc;
+        if ((rc = launch_ptr(b, ke, grid, dim3(256), e_args, 0))) return rc;
+        b->launches += 2;
+        b->step++;
+    }
+    return 0;
+}
+
 // ---- Bloch runs (fdtd2d_batch_bloch.h): the periodic paths with the complex-field kernels of batch_bloch.hip ----------
 template <class T> fdtd::BatchBloch<T> bloch_view(const fdtd2d_batch *b, bool conj)
 {
@@ -770,6 +842,7 @@ template <class T>
 int run_impl(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts = nullptr)
 {
     if (b->bloch) return run_bloch<T>(b, nsteps, amps, amp_stride);
+    if (b->dcj) return run_dispersive<T>(b, nsteps, amps, amp_stride, pts);
     if (b->periodic) return run_periodic<T>(b, nsteps, amps, amp_stride, pts);
     if (b->ca) return run_lossy<T>(b, nsteps, amps, amp_stride, pts);
     if (b->win_nf || b->nprobe || pts) return run_monitored<T>(b, nsteps, amps, amp_stride, pts);
@@ -1011,6 +1084,194 @@ int periodic_coefficients(fdtd2d_batch *b)
     return rc;
 }
 
+// ---- fdtd2d_batch_dispersive.h ---------------------------------------------------------------------------------
+int refuse_bloch(fdtd2d_batch *b, const char *what);
+
+constexpr double DISP_EPS0 = 8.85418e-12;     // the library's vacuum constant (the reference's literal)
+
+int refuse_dispersive(fdtd2d_batch *b, const char *what)
+{
+    return bfail(b, FDTD2D_E_STATE, "%s is not available while a dispersive pole is set", what);
+}
+
+// the first cell of wp2_host that is non-zero where sigma_barred bars it with the margin: member * cells + cell, or -1
+long long wp2_outside(const fdtd2d_batch *b, int margin)
+{
+    const size_t per = (size_t)b->rows * b->cols;
+    for (size_t t = 0; t < b->wp2_host.size(); ++t) {
+        const int i = (int)(t % per / b->cols), j = (int)(t % per % b->cols);
+        if (b->wp2_host[t] != 0 && sigma_barred(b, i, j, margin)) return (long long)t;
+    }
+    return -1;
+}
+
+// dt^2 (omega0^2 + wp2 EPS0 / eps) + 8 dt^2 / (eps mu dx^2): at most 4 for a cell with a pole
+double disp_stability(const fdtd2d_batch *b, double omega0, double wp2, double eps, double mu)
+{
+    const double dt2 = b->dt * b->dt;
+    return dt2 * (omega0 * omega0 + wp2 * DISP_EPS0 / eps) + 8.0 * dt2 / (eps * mu * b->dx * b->dx);
+}
+
+// The stability check over a window of every member: eps(m, i, j) and wp2(m, i, j) give the values to judge, mu_min the
+// members' smallest permeabilities.  FDTD2D_E_ARG naming the first offending member, or 0.
+template <class Eps, class Wp2>
+int disp_check_stability(fdtd2d_batch *b, const std::vector<double> &omega0, const std::vector<double> &mu_min, int r0,
+                         int c0, int nr, int nc, Eps eps, Wp2 wp2)
+{
+    for (int m = 0; m < b->count; ++m)
+        for (int i = r0; i < r0 + nr; ++i)
+            for (int j = c0; j < c0 + nc; ++j) {
+                const double w = wp2(m, i, j);
+                if (!(w > 0)) continue;
+                const double s = disp_stability(b, omega0[m], w, eps(m, i, j), mu_min[m]);
+                if (!(s <= 4.0))
+                    return bfail(b, FDTD2D_E_ARG, "member %d: the pole at cell (%d,%d) is unstable: dt^2 (omega0^2 + wp2 EPS0 / "
+                                 "eps) + 8 dt^2 / (eps mu dx^2) = %.6g > 4", m, i, j, s);
+            }
+    return 0;
+}
+
+// eps and the smallest mu as the engine stores them, whether the batch holds arrays or uniform materials
+double disp_eps_at(const fdtd2d_batch *b, int m, int i, int j)
+{
+    if (b->uniform) return as_engine(b, b->eps_u);
+    return b->eps_host[(size_t)m * b->rows * b->cols + (size_t)i * b->cols + j];
+}
+std::vector<double> disp_mu_min(const fdtd2d_batch *b)
+{
+    return b->uniform ? std::vector<double>((size_t)b->count, as_engine(b, b->mu_u)) : b->mu_min;
+}
+
+// cj of a window from wp2_host and the dampings: one upload, one launch (k_batch_wp2_window)
+int disp_reform(fdtd2d_batch *b, int r0, int c0, int nr, int nc)
+{
+    const size_t W = (size_t)nr * nc, n = (size_t)b->count * W, per = (size_t)b->rows * b->cols;
+    std::vector<double> w(n + (size_t)b->count);
+    for (int m = 0; m < b->count; ++m) {
+        for (int i = 0; i < nr; ++i)
+            for (int j = 0; j < nc; ++j)
+                w[m * W + (size_t)i * nc + j] = b->wp2_host[m * per + (size_t)(r0 + i) * b->cols + (c0 + j)];
+        w[n + m] = b->dt / (1.0 + b->disp_gamma[m] * b->dt / 2.0);
+    }
+    int rc = scratch(b, w.size() * sizeof(double));      // waits for launches that still read the coefficients
+    if (rc) return rc;
+    BCHK(b, hipMemcpyAsync(b->dsg, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    fdtd::batch_wp2_window_launch(b->dcj, (const double *)b->dsg, (const double *)b->dsg + n, b->dtype == FDTD2D_F64,
+                                  b->count, r0, c0, nr, nc, b->pitch, b->mstride, b->dx, DISP_EPS0, b->stream);
+    BCHK(b, hipGetLastError());
+    b->launches++;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+void disp_release(fdtd2d_batch *b)
+{
+    for (void **p : {&b->djh, &b->dq, &b->dcj, &b->da, &b->dck}) release(p);
+    b->wp2_host.clear();
+    b->disp_gamma.clear();
+    b->disp_omega0.clear();
+}
+
+// sets the pole (window == nullptr: wp2 whole with gamma and omega0) or patches its strengths
+int set_disp(fdtd2d_batch *b, const int *window, const void *wp2, int dtype, const double *gamma, const double *omega0)
+{
+    if (window && !b->dcj) return bfail(b, FDTD2D_E_STATE, "no pole is set: call fdtd2d_batch_set_dispersion first");
+    if (b->boundary != FDTD2D_BOUNDARY_NONE)
+        return bfail(b, FDTD2D_E_STATE, "a dispersive pole needs a FDTD2D_BOUNDARY_NONE batch with a PML layer or periodic "
+                     "columns, not the Mur frame");
+    if (!b->ezx && !b->periodic)
+        return bfail(b, FDTD2D_E_STATE, "a dispersive pole needs a PML layer (fdtd2d_batch_set_pml) or periodic columns: a "
+                     "plain box has no dispersive kernels");
+    if (b->bloch) return refuse_bloch(b, "a dispersive pole");
+    if (!b->have_mat) return bfail(b, FDTD2D_E_STATE, "materials not set: call fdtd2d_batch_set_materials first");
+    if (!wp2) return bfail(b, FDTD2D_E_ARG, "wp2 must not be NULL");
+    if (dtype != FDTD2D_F32 && dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad dtype");
+    const int r0 = window ? window[0] : 0, c0 = window ? window[1] : 0;
+    const int nr = window ? window[2] : b->rows, nc = window ? window[3] : b->cols;
+    if (nr < 1 || nc < 1 || r0 < 0 || c0 < 0 || (long long)r0 + nr > b->rows || (long long)c0 + nc > b->cols)
+        return bfail(b, FDTD2D_E_ARG, "window (%d,%d)+%dx%d is empty or outside the %dx%d grid", r0, c0, nr, nc, b->rows,
+                     b->cols);
+    std::vector<double> gam = b->disp_gamma, om0 = b->disp_omega0;
+    if (!window) {
+        gam.assign(gamma, gamma + b->count);
+        om0.assign(omega0, omega0 + b->count);
+        for (int m = 0; m < b->count; ++m) {
+            if (!(gam[m] >= 0) || !std::isfinite(gam[m]))
+                return bfail(b, FDTD2D_E_ARG, "member %d: gamma must be >= 0 and finite", m);
+            if (!(om0[m] >= 0) || !std::isfinite(om0[m]))
+                return bfail(b, FDTD2D_E_ARG, "member %d: omega0 must be >= 0 and finite", m);
+        }
+    }
+    const int mg = sigma_margin(b, b->ezx ? b->pml_L : 0);
+    const size_t W = (size_t)nr * nc, per = (size_t)b->rows * b->cols;
+    for (int m = 0; m < b->count; ++m)
+        for (size_t t = 0; t < W; ++t) {
+            const double s = get_elem(wp2, dtype, m * W + t);
+            const int i = r0 + (int)(t / nc), j = c0 + (int)(t % nc);
+            if (!(s >= 0) || !std::isfinite(s))
+                return bfail(b, FDTD2D_E_ARG, "member %d: wp2 must be >= 0 and finite (cell (%d,%d))", m, i, j);
+            if (s != 0 && sigma_barred(b, i, j, mg))
+                return bfail(b, FDTD2D_E_ARG, "member %d: wp2 is non-zero at cell (%d,%d), within %d cells of an edge "
+                             "(%s): only cells that take the plain update may carry a pole", m, i, j, mg,
+                             b->periodic ? "the PML rows, the PEC rows and cell [0, 0] of a periodic batch"
+                                         : "the PML layer, the frame and cell [0, 0]");
+        }
+    int rc = disp_check_stability(
+        b, om0, disp_mu_min(b), r0, c0, nr, nc, [&](int m, int i, int j) { return disp_eps_at(b, m, i, j); },
+        [&](int m, int i, int j) { return get_elem(wp2, dtype, m * W + (size_t)(i - r0) * nc + (j - c0)); });
+    if (rc) return rc;
+    if ((rc = use_device(b))) return rc;
+    if (b->uniform && (rc = materialise_uniform(b))) return rc;
+    if (!b->ca) {                           // no conductivity: ca = 1, cb = ce
+        const std::vector<double> zero((size_t)b->count * per, 0.0);
+        if ((rc = set_sigma(b, nullptr, zero.data(), FDTD2D_F64))) return rc;
+        b->sigma_implicit = true;
+    }
+    const bool fresh = !b->dcj;
+    if (fresh) {
+        const size_t mb = (size_t)b->count * b->esz;
+        for (void **p : {&b->djh, &b->dq, &b->dcj, &b->da, &b->dck}) {
+            const size_t bytes = (p == &b->da || p == &b->dck) ? mb : b->field_bytes;
+            hipError_t e = hipSuccess;
+            if ((rc = alloc(b, p, bytes)) || (e = hipMemsetAsync(*p, 0, bytes, b->stream)) != hipSuccess) {
+                if (!rc) rc = bfail(b, -(1000 + (int)e), "hipMemset of the pole's arrays failed: %s", hipGetErrorString(e));
+                disp_release(b);
+                return rc;
+            }
+        }
+        b->wp2_host.assign((size_t)b->count * per, 0.0);
+    }
+    for (int m = 0; m < b->count; ++m)
+        for (size_t t = 0; t < W; ++t)
+            b->wp2_host[m * per + (size_t)(r0 + t / nc) * b->cols + (c0 + t % nc)] = get_elem(wp2, dtype, m * W + t);
+    if (!window) {
+        b->disp_gamma = gam;
+        b->disp_omega0 = om0;
+        std::vector<unsigned char> at((size_t)b->count * b->esz), ckt(at.size());
+        for (int m = 0; m < b->count; ++m) {
+            const double g = gam[m] * b->dt / 2.0, bq = b->dt / (1.0 + g);
+            const double a = (1.0 - g) / (1.0 + g), ck = bq * (om0[m] * om0[m]) * b->dt;
+            if (b->dtype == FDTD2D_F32) {
+                ((float *)at.data())[m] = (float)a;
+                ((float *)ckt.data())[m] = (float)ck;
+            } else {
+                ((double *)at.data())[m] = a;
+                ((double *)ckt.data())[m] = ck;
+            }
+        }
+        hipError_t e = hipStreamSynchronize(b->stream);      // a running launch may still read the old scalars
+        if (e == hipSuccess) e = hipMemcpy(b->da, at.data(), at.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(b->dck, ckt.data(), ckt.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            if (fresh) disp_release(b);
+            return bfail(b, -(1000 + (int)e), "upload of the pole's scalars failed: %s", hipGetErrorString(e));
+        }
+    }
+    rc = window ? disp_reform(b, r0, c0, nr, nc) : disp_reform(b, 0, 0, b->rows, b->cols);
+    if (rc && fresh) disp_release(b);
+    return rc;
+}
+
 // ---- fdtd2d_batch_bloch.h ----------------------------------------------------------------------------------------
 // rho * (re, im) as the kernels form it (batch_bloch_rot), in the engine's type: part 0 = real, 1 = imaginary
 template <class T> double bloch_rot_host(double c, double s, double re, double im, int part)
@@ -1188,7 +1449,8 @@ void fdtd2d_batch_destroy(fdtd2d_batch_t *b)
                      (void **)&b->probe_trace, (void **)&b->win_held, (void **)&b->pts_cells, (void **)&b->pts_own,
                      (void **)&b->pts_w, (void **)&b->pts_tab, (void **)&b->chan, &b->dsg, &b->ca, &b->cb,
                      &b->ez_im, &b->hx_im, &b->hy_im, &b->ezx_im, &b->rho, (void **)&b->bloch_w, (void **)&b->amps_im,
-                     (void **)&b->win_acc_im, (void **)&b->probe_trace_im, &b->rho_conj, (void **)&b->win_held_im})
+                     (void **)&b->win_acc_im, (void **)&b->probe_trace_im, &b->rho_conj, (void **)&b->win_held_im,
+                     &b->djh, &b->dq, &b->dcj, &b->da, &b->dck})
         release(p);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -1226,6 +1488,7 @@ long long fdtd2d_batch_info(const fdtd2d_batch_t *b, int what)
     case FDTD2D_BATCH_INFO_LOSSY: return b->ca && !b->sigma_implicit ? 1 : 0;
     case FDTD2D_BATCH_INFO_PERIODIC: return b->periodic ? 1 : 0;
     case FDTD2D_BATCH_INFO_BLOCH: return b->bloch ? 1 : 0;
+    case FDTD2D_BATCH_INFO_DISPERSIVE: return b->dcj ? 1 : 0;
     default: return FDTD2D_E_ARG;
     }
 }
@@ -1277,8 +1540,14 @@ int fdtd2d_batch_set_materials(fdtd2d_batch_t *b, const void *eps, const void *m
         const double e00 = get_elem(eps, host_dtype, m * per), u00 = get_elem(mu, host_dtype, m * per);
         kmur[m] = b->dtype == FDTD2D_F32 ? mur_of<float>(e00, u00, b->dt, b->dx) : mur_of<double>(e00, u00, b->dt, b->dx);
     }
-    int rc = use_device(b);
-    if (rc) return rc;
+    int rc;
+    if (b->dcj &&           // the pole's stability with the new materials, before anything changes
+        (rc = disp_check_stability(
+             b, b->disp_omega0, mmin, 0, 0, b->rows, b->cols,
+             [&](int m, int i, int j) { return eps_host[m * per + (size_t)i * b->cols + j]; },
+             [&](int m, int i, int j) { return b->wp2_host[m * per + (size_t)i * b->cols + j]; })))
+        return rc;
+    if ((rc = use_device(b))) return rc;
     b->have_mat = false;
     for (void **p : {&b->ce, &b->ch})
         if (!*p && (rc = alloc(b, p, b->field_bytes))) return rc;
@@ -1315,9 +1584,17 @@ int fdtd2d_batch_set_materials_uniform(fdtd2d_batch_t *b, double eps, double mu)
 {
     if (!b) return FDTD2D_E_ARG;
     if (!(eps > 0) || !(mu > 0)) return bfail(b, FDTD2D_E_ARG, "eps and mu must be positive");
+    const double eps_was = b->eps_u, mu_was = b->mu_u;
     b->eps_u = eps;
     b->mu_u = mu;
-    if (b->ca) return materialise_uniform(b);      // a lossy batch keeps coefficient arrays
+    if (b->ca) {                                   // a lossy batch keeps coefficient arrays
+        const int rc = materialise_uniform(b);
+        if (rc && b->dcj) {                        // refused (the pole's stability): as it was
+            b->eps_u = eps_was;
+            b->mu_u = mu_was;
+        }
+        return rc;
+    }
     int rc = use_device(b);
     if (rc) return rc;
     BCHK(b, hipStreamSynchronize(b->stream));
@@ -1354,6 +1631,9 @@ int fdtd2d_batch_set_pml(fdtd2d_batch_t *b, const void *row_factors, const void 
     int rc = use_device(b);
     if (rc) return rc;
     if (!row_factors && !col_factors && b->periodic) return unit_layer(b);   // PEC top and bottom
+    if (!row_factors && !col_factors && b->dcj)
+        return refuse_dispersive(b, "removing the layer of a batch without periodic columns (a plain box has no "
+                                    "dispersive kernels)");
     if (!row_factors && !col_factors) {     // remove the layer: a plain NONE batch again
         BCHK(b, hipStreamSynchronize(b->stream));
         for (void **p : {&b->ezx, &b->pml_row, &b->pml_col}) release(p);
@@ -1375,6 +1655,13 @@ int fdtd2d_batch_set_pml(fdtd2d_batch_t *b, const void *row_factors, const void 
         const long long t = sigma_outside(b, mg);
         if (t >= 0)
             return bfail(b, FDTD2D_E_ARG, "member %d: sigma is non-zero within %d cells of an edge (the PML layer, the "
+                         "frame and cell [0, 0])", (int)(t / ((long long)b->rows * b->cols)), mg);
+    }
+    if (b->dcj) {
+        const int mg = sigma_margin(b, layer_cells);
+        const long long t = wp2_outside(b, mg);
+        if (t >= 0)
+            return bfail(b, FDTD2D_E_ARG, "member %d: wp2 is non-zero within %d cells of an edge (the PML layer, the "
                          "frame and cell [0, 0])", (int)(t / ((long long)b->rows * b->cols)), mg);
     }
     const size_t rbytes = (size_t)b->count * 4 * b->rows * b->esz, cbytes = (size_t)b->count * 4 * b->cols * b->esz;
@@ -1840,6 +2127,7 @@ int fdtd2d_batch_hold_dft_window(fdtd2d_batch_t *b)
 {
     if (!b) return FDTD2D_E_ARG;
     if (b->bloch) return refuse_bloch(b, "the held window");
+    if (b->dcj) return refuse_dispersive(b, "the held window (the adjoint of a dispersive medium)");
     if (!b->win_nf) return bfail(b, FDTD2D_E_STATE, "no window DFT is set");
     int rc = use_device(b);
     if (rc) return rc;
@@ -1855,6 +2143,7 @@ int fdtd2d_batch_dft_window_product(fdtd2d_batch_t *b, const double *coef_re, co
     if (!b) return FDTD2D_E_ARG;
     if (!coef_re || !coef_im || !out) return bfail(b, FDTD2D_E_ARG, "coef_re, coef_im and out must not be NULL");
     if (b->bloch) return refuse_bloch(b, "the window product");
+    if (b->dcj) return refuse_dispersive(b, "the window product (the adjoint of a dispersive medium)");
     if (!b->win_nf) return bfail(b, FDTD2D_E_STATE, "no window DFT is set");
     if (!b->win_held) return bfail(b, FDTD2D_E_STATE, "no held window: call fdtd2d_batch_hold_dft_window first");
     int rc = use_device(b);
@@ -1980,8 +2269,16 @@ int fdtd2d_batch_set_eps_window(fdtd2d_batch_t *b, int row0, int col0, int nrows
             else ((double *)stage_w.data())[m * W + t] = e;
             wmin[m] = e < wmin[m] ? e : wmin[m];
         }
-    int rc = use_device(b);
-    if (rc) return rc;
+    int rc;
+    if (b->dcj &&           // the pole's stability with the new permittivity, before anything changes
+        (rc = disp_check_stability(
+             b, b->disp_omega0, b->mu_min, row0, col0, nrows, ncols,
+             [&](int m, int i, int j) {
+                 return as_engine(b, get_elem(eps, host_dtype, m * W + (size_t)(i - row0) * ncols + (j - col0)));
+             },
+             [&](int m, int i, int j) { return b->wp2_host[m * per + (size_t)i * b->cols + j]; })))
+        return rc;
+    if ((rc = use_device(b))) return rc;
     if ((rc = scratch(b, stage_w.size()))) return rc;      // waits for launches that still read the coefficients
     BCHK(b, hipMemcpyAsync(b->dsg, stage_w.data(), stage_w.size(), hipMemcpyHostToDevice, b->stream));
     fdtd::batch_eps_window_launch(b->ce, b->dsg, b->dtype == FDTD2D_F64, b->count, row0, col0, nrows, ncols, b->pitch,
@@ -2024,7 +2321,7 @@ int fdtd2d_batch_set_conductivity(fdtd2d_batch_t *b, const void *sigma, int dtyp
         if (!b->ca) return 0;
         int rc = use_device(b);
         if (rc) return rc;
-        if (b->periodic) {                  // a periodic batch keeps its arrays, with ca = 1 and cb = ce
+        if (b->periodic || b->dcj) {        // a periodic or dispersive batch keeps its arrays, with ca = 1 and cb = ce
             std::fill(b->sigma_host.begin(), b->sigma_host.end(), 0.0);
             b->sigma_implicit = true;
             return lossy_reform(b, 0, 0, b->rows, b->cols);
@@ -2049,6 +2346,55 @@ int fdtd2d_batch_set_conductivity_window(fdtd2d_batch_t *b, const int window[4],
     return rc;
 }
 
+// ---- fdtd2d_batch_dispersive.h ---------------------------------------------------------------------------------
+
+int fdtd2d_batch_set_dispersion(fdtd2d_batch_t *b, const void *wp2, int dtype, const double *gamma, const double *omega0)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!wp2 && !gamma && !omega0) {        // remove the pole: the other kernels again
+        if (!b->dcj) return 0;
+        int rc = use_device(b);
+        if (rc) return rc;
+        BCHK(b, hipStreamSynchronize(b->stream));
+        disp_release(b);
+        if (b->sigma_implicit && !b->periodic) {     // the all-zero conductivity the pole brought
+            release(&b->ca);
+            release(&b->cb);
+            b->sigma_host.clear();
+            b->sigma_implicit = false;
+        }
+        return 0;
+    }
+    if (!wp2 || !gamma || !omega0)
+        return bfail(b, FDTD2D_E_ARG, "wp2, gamma and omega0 must all be given (or all NULL)");
+    return set_disp(b, nullptr, wp2, dtype, gamma, omega0);
+}
+
+int fdtd2d_batch_set_dispersion_window(fdtd2d_batch_t *b, const int window[4], const void *wp2, int dtype)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!window) return bfail(b, FDTD2D_E_ARG, "window must not be NULL");
+    return set_disp(b, window, wp2, dtype, nullptr, nullptr);
+}
+
+int fdtd2d_batch_transfer_dispersion(fdtd2d_batch_t *b, void *jh, void *q, int host_dtype, int to_device)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!b->dcj) return bfail(b, FDTD2D_E_STATE, "no pole is set: call fdtd2d_batch_set_dispersion first");
+    if (host_dtype != FDTD2D_F32 && host_dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad host_dtype");
+    int rc = use_device(b);
+    if (rc) return rc;
+    void *dev[2] = {b->djh, b->dq}, *host[2] = {jh, q};
+    for (int k = 0; k < 2; ++k) {
+        if (!host[k]) continue;
+        if (!to_device) rc = copy_out(b, dev[k], host[k], host_dtype, b->rows, b->cols);
+        else if (!(rc = copy_in(b, dev[k], host[k], host_dtype, b->rows, b->cols)) && b->periodic)
+            rc = copy_image(b, dev[k]);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
 // ---- fdtd2d_batch_periodic.h -----------------------------------------------------------------------------------
 
 int fdtd2d_batch_set_periodic(fdtd2d_batch_t *b, int on)
@@ -2061,11 +2407,23 @@ int fdtd2d_batch_set_periodic(fdtd2d_batch_t *b, int on)
     int rc = use_device(b);
     if (rc) return rc;
     BCHK(b, hipStreamSynchronize(b->stream));
+    if (!on && b->dcj) {                    // the refusals of a dispersive batch, before anything changes
+        if (b->pml_L == 0)
+            return refuse_dispersive(b, "turning periodic columns off without a layer (a plain box has no dispersive "
+                                        "kernels)");
+        b->periodic = false;
+        const int mg = sigma_margin(b, b->pml_L);
+        const long long t = wp2_outside(b, mg);
+        b->periodic = true;
+        if (t >= 0)
+            return bfail(b, FDTD2D_E_ARG, "member %d: wp2 is non-zero within %d cells of an edge (the PML layer, the "
+                         "frame and cell [0, 0])", (int)(t / ((long long)b->rows * b->cols)), mg);
+    }
     if (!on) {
         if (b->bloch && (rc = bloch_off(b))) return rc;
         if ((rc = fdtd2d_batch_set_point_sources(b, 0, nullptr, 0, nullptr))) return rc;
         b->periodic = false;
-        if (b->sigma_implicit) {
+        if (b->sigma_implicit && !b->dcj) {
             release(&b->ca);
             release(&b->cb);
             b->sigma_host.clear();
@@ -2108,6 +2466,7 @@ int fdtd2d_batch_set_periodic(fdtd2d_batch_t *b, int on)
     if ((rc = fdtd2d_batch_set_point_sources(b, 0, nullptr, 0, nullptr))) return undo(rc);
     if (!b->ezx && (rc = unit_layer(b))) return undo(rc);
     if ((rc = copy_image(b, b->ez[b->cur])) || (rc = copy_image(b, b->ezx))) return undo(rc);
+    if (b->dcj && ((rc = copy_image(b, b->djh)) || (rc = copy_image(b, b->dq)))) return undo(rc);
     if (b->have_mat && !b->ca && (rc = periodic_coefficients(b))) return undo(rc);
     return 0;
 }
@@ -2121,6 +2480,7 @@ int fdtd2d_batch_set_bloch(fdtd2d_batch_t *b, const double *cos_phi, const doubl
     int rc = use_device(b);
     if (rc) return rc;
     if (!cos_phi) return b->bloch ? bloch_off(b) : 0;
+    if (b->dcj) return refuse_dispersive(b, "a Bloch phase");
     if (!b->periodic)
         return bfail(b, FDTD2D_E_STATE, "a Bloch phase needs periodic columns: call fdtd2d_batch_set_periodic first");
     for (int m = 0; m < b->count; ++m)

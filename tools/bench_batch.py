@@ -63,9 +63,16 @@ array eps with random binary permittivity, a ricker line source per member):
                               rectangle source) and session_ms (one value_and_grad of a standing BlochAdjointSession),
                               timed alternately in one process: device_over_two_runs, session_over_two_runs, the path
                               and the LDS size.  Default: 1024 members of 60 x 60, a 10-cell layer, 1500 steps.
+  --dispersive                instead: the dispersive step kernels (BatchEngine.set_dispersion: a Drude block, wp = 2 pi
+                              70 GHz and gamma = 1e11, on the middle third of every member) against the lossy PML
+                              kernels they were copied from, on the same members with the same layer, conductivity and
+                              one silent point source, timed alternately in one process: dispersive_ms, lossy_pml_ms,
+                              dispersive_over_lossy_pml, both paths and LDS sizes.  By this script's LDS count the pole
+                              adds three reads and two writes per interior cell-step to the lossy PML kernel's 17 reads
+                              and 3 writes.  Default: 1024 members of 60 x 60, a 10-cell layer, 1000 steps.
 Usage: python tools/bench_batch.py [--count 1024 --rows 60 --cols 60 --steps 1000] [--reps 5] [--loop-members 16]
                                    [--boundary {mur,pml} --pml-cells 10] [--monitors] [--adjoint] [--lossy]
-                                   [--periodic] [--bloch] [--bloch-adjoint]
+                                   [--periodic] [--bloch] [--bloch-adjoint] [--dispersive]
 """
 import argparse
 import json
@@ -329,6 +336,61 @@ def bench_periodic(count, rows, cols, steps, dtype, reps, pml_cells):
             "periodic_ms_all": [round(v, 4) for v in per_ms],
             "periodic_over_lossy_pml": round(med_p / med_l, 3), "launches_per_run": launches,
             "periodic_mcell_steps_per_s": round(count * rows * cols * steps / (med_p * 1e-3) / 1e6, 1)}
+
+
+def bench_dispersive(count, rows, cols, steps, dtype, reps, pml_cells):
+    eps, rects, amps = members(count, rows, cols, steps)
+    c00 = courant00(eps, dtype)
+    rng = np.random.default_rng(1)
+    g = max(6, pml_cells)
+    sigma = np.zeros((count, rows, cols))
+    sigma[:, g:rows - g, g:cols - g] = 20.0 * rng.random((count, rows - 2 * g, cols - 2 * g))
+    wp2 = np.zeros((count, rows, cols))
+    wp2[:, rows // 3:2 * rows // 3, cols // 3:2 * cols // 3] = (2 * np.pi * 70e9) ** 2
+    chan = np.zeros((1, steps))
+
+    def batch(pole):
+        b = fd.BatchEngine(count, rows, cols, DT, DX, dtype=dtype, boundary="pml")
+        b.set_materials(eps.astype(dtype), fd.MU0).set_sources(rects)
+        b.set_pml(pml_cells, courant00=c00)
+        b.set_point_sources([[rows // 2, cols // 2]], np.zeros((1, 1)))
+        b.set_conductivity(sigma)
+        if pole:
+            b.set_dispersion(wp2, 1e11, 0.0)
+        b.run(steps, amps, chan).sync()                # warm-up: code objects, clocks
+        return b
+
+    def timed(b):
+        b.reset().sync()
+        t0 = time.perf_counter()
+        b.run(steps, amps, chan).sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    with batch(False) as pml, batch(True) as dis:
+        assert dis.dispersive and dis.lossy and pml.lossy and not pml.dispersive
+        l0 = dis.launches
+        dis.reset().run(steps, amps, chan).sync()
+        launches = dis.launches - l0
+        pml_ms, dis_ms = [], []
+        for _ in range(reps):
+            pml_ms.append(timed(pml))
+            dis_ms.append(timed(dis))
+        paths = ["resident" if b.resident else "streamed" for b in (pml, dis)]
+        lds = [b.lds_bytes for b in (pml, dis)]
+    med_l, med_d = float(np.median(pml_ms)), float(np.median(dis_ms))
+    return {"count": count, "rows": rows, "cols": cols, "steps": steps, "dtype": np.dtype(dtype).name,
+            "materials": "arrays", "pml_cells": pml_cells, "reps": reps, "lossy_pml_path": paths[0],
+            "dispersive_path": paths[1], "lossy_pml_lds_bytes_per_member": lds[0],
+            "dispersive_lds_bytes_per_member": lds[1],
+            "lossy_pml_workgroups_per_cu": 163840 // lds[0], "dispersive_workgroups_per_cu": 163840 // lds[1],
+            "lds_reads_per_cell_step": {"lossy_pml": 17, "dispersive": 20},
+            "lds_writes_per_cell_step": {"lossy_pml": 3, "dispersive": 5},
+            "lossy_pml_ms": round(med_l, 4), "lossy_pml_ms_min": round(min(pml_ms), 4),
+            "lossy_pml_ms_all": [round(v, 4) for v in pml_ms],
+            "dispersive_ms": round(med_d, 4), "dispersive_ms_min": round(min(dis_ms), 4),
+            "dispersive_ms_all": [round(v, 4) for v in dis_ms],
+            "dispersive_over_lossy_pml": round(med_d / med_l, 3), "launches_per_run": launches,
+            "dispersive_mcell_steps_per_s": round(count * rows * cols * steps / (med_d * 1e-3) / 1e6, 1)}
 
 
 def bench_bloch(count, rows, cols, steps, dtype, reps, pml_cells):
@@ -616,7 +678,12 @@ def main():
     ap.add_argument("--periodic", action="store_true", help="time the periodic kernels against the lossy PML ones")
     ap.add_argument("--bloch", action="store_true", help="time a Bloch batch against the plain periodic one")
     ap.add_argument("--bloch-adjoint", action="store_true", help="time the adjoint gradient of a Bloch batch")
+    ap.add_argument("--dispersive", action="store_true", help="time the dispersive kernels against the lossy PML ones")
     a = ap.parse_args()
+    if a.dispersive:
+        print(json.dumps(bench_dispersive(a.count or 1024, a.rows or 60, a.cols or 60, a.steps or 1000,
+                                          np.dtype(a.dtype), a.reps, a.pml_cells)), flush=True)
+        return
     if a.bloch_adjoint:
         print(json.dumps(bench_bloch_adjoint(a.count or 1024, a.rows or 60, a.cols or 60, a.steps or 1500,
                                              np.dtype(a.dtype), a.reps, a.pml_cells)), flush=True)
