@@ -206,6 +206,12 @@ BATCH_DISPERSIVE_SIGNATURES = {
     "fdtd2d_batch_transfer_dispersion": (_i, [_vp, _vp, _vp, _i, _i]),
 }
 
+# every symbol include/fdtd2d_batch_lattice.h declares (doubly periodic Bloch batches: the unit cell of a 2D lattice)
+BATCH_LATTICE_SIGNATURES = {
+    "fdtd2d_batch_set_lattice": (_i, [_vp, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_is_lattice": (_i, [_vp]),
+}
+
 # transport callback of fdtd2d_slab_attach
 EXCHANGE_FN = C.CFUNCTYPE(_i, _vp, _vp, _vp, _vp, _vp, _ll, _vp)
 
@@ -257,7 +263,7 @@ def load():
                                    **BATCH_ADJOINT_SIGNATURES, **BATCH_DESIGN_SIGNATURES,
                                    **BATCH_LOSSY_SIGNATURES, **BATCH_PERIODIC_SIGNATURES,
                                    **BATCH_BLOCH_SIGNATURES, **BATCH_BLOCH_ADJOINT_SIGNATURES,
-                                   **BATCH_DISPERSIVE_SIGNATURES}.items():
+                                   **BATCH_DISPERSIVE_SIGNATURES, **BATCH_LATTICE_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

@@ -17,6 +17,9 @@ or in PEC (fdtd2d_batch_periodic.h).  ``set_bloch_phase`` gives a periodic batch
 become complex and repeat as F(x + period) = F(x) e^{i phi} (oblique incidence, angle sweeps, band diagrams;
 fdtd2d_batch_bloch.h).  ``set_dispersion`` gives a PML or periodic batch one Drude-Lorentz pole per member with a strength
 per cell (metals, absorption lines; fdtd2d_batch_dispersive.h); the batch then runs on the dispersive step kernels.
+``boundary="lattice"`` makes every member the unit cell of a rectangular 2D lattice: row R-1 is the image of row 0 and
+column C-1 the image of column 0, the fields are complex, and ``set_lattice_phase`` gives every member one Bloch phase
+across each pair of edges (band diagrams of 2D photonic crystals: a k-path is one batch; fdtd2d_batch_lattice.h).
 """
 from __future__ import annotations
 
@@ -92,8 +95,11 @@ class BatchEngine:
     edge is PEC).  "periodic": the columns wrap around with the period C - 1 (column C-1 is the image of column 0 and
     is output only: no source there, materials there are never read, upload() overwrites it with column 0); set_pml()
     lays the layer on the top and bottom rows alone, clear_pml() leaves PEC there.  set_bloch_phase() makes the fields
-    complex with one Bloch phase per member.  There are no periodic rows.
+    complex with one Bloch phase per member.  "lattice": rows and columns both wrap around, with the periods R - 1 and
+    C - 1 (row R-1 and column C-1 are images and output only); the fields are complex, set_lattice_phase() sets the two
+    Bloch phases of every member (zero until then), there is no layer, and the engine starts with vacuum materials.
     """
+    _lattice = None               # ((cr, sr), (cc, sc)): the (B,) rotations of a lattice engine (None: not one)
 
     def __init__(self, count, rows, cols, dt=5e-14, dx=1e-4, dtype=np.float32, boundary="mur", device=0):
         self._lib = _abi.load()
@@ -102,7 +108,7 @@ class BatchEngine:
         self.dt, self.dx = float(dt), float(dx)
         self.dtype = np.dtype(dtype)
         self.boundary = boundary
-        if boundary not in _BOUNDARY and boundary != "periodic":
+        if boundary not in _BOUNDARY and boundary not in ("periodic", "lattice"):
             raise ValueError(f"unknown boundary {boundary!r}")
         self._pml_on = False          # a layer is set
         self._pml_chosen = False      # set_pml (or clear_pml) has been called: a "pml" batch may run
@@ -112,7 +118,7 @@ class BatchEngine:
         self._npoint = (0, 0)         # (P, K) of the point sources
         self._bloch = None            # (c, s): the (B,) rotations of a Bloch phase
         self._phi = None              # the phases as given (None with rotation=)
-        code = _abi.BOUNDARY_NONE if boundary in ("pml", "periodic") else _BOUNDARY[boundary]
+        code = _abi.BOUNDARY_NONE if boundary in ("pml", "periodic", "lattice") else _BOUNDARY[boundary]
         rc = self._lib.fdtd2d_batch_create(C.byref(self._h), self.count, self.rows, self.cols, self.dt, self.dx,
                                            _code(dtype), code, int(device))
         if rc != 0:
@@ -126,6 +132,15 @@ class BatchEngine:
                 self.close()
                 raise
             self._pml_chosen = True   # without set_pml() the rows end in PEC
+        if boundary == "lattice":
+            try:
+                self.set_materials()  # the lattice mode needs materials: vacuum until set_materials()
+                self._ck(self._lib.fdtd2d_batch_set_periodic(self._h, 1))
+                self.set_lattice_phase(0.0, 0.0, rotation=((1.0, 0.0), (1.0, 0.0)))
+            except BaseException:
+                self.close()
+                raise
+            self._pml_chosen = True
 
     # -- lifetime -------------------------------------------------------------------
     def close(self):
@@ -157,6 +172,45 @@ class BatchEngine:
         """Whether a Bloch phase is set (complex fields, the batch runs on the Bloch kernels)."""
         return bool(self.info(_abi.BATCH_INFO_BLOCH))
 
+    @property
+    def lattice(self) -> bool:
+        """Whether the lattice mode is on (complex fields, Bloch conditions on both pairs of edges)."""
+        return bool(self._lib.fdtd2d_batch_is_lattice(self._h))
+
+    def _no_lattice(self, what):
+        """The library's refusal of `what` in the lattice mode, before the call."""
+        if self._lattice is not None:
+            raise _abi.Fdtd2dError(_abi.E_STATE, f"{what} is not available in the lattice mode (complex fields)")
+
+    def set_lattice_phase(self, phi_rows, phi_cols, rotation=None):
+        """The two Bloch phases of every member of a boundary="lattice" engine: F(r + a_rows) = F(r) * exp(1j * phi_rows)
+        across the row seam and F(r + a_cols) = F(r) * exp(1j * phi_cols) across the column seam.  Scalars or (B,) in
+        radians; the library takes their cos and sin, rounded to the batch dtype.  rotation=((cr, sr), (cc, sc)), scalars
+        or (B,), gives those pairs directly, so that exact ones such as (-1, 0) and (0, 1) can be set (the phases are
+        then not read).  Fields, monitors and sources are not touched: a k-point sweep is B members that differ in
+        their phases alone."""
+        if self.boundary != "lattice":
+            raise _abi.Fdtd2dError(_abi.E_STATE, f'set_lattice_phase needs boundary="lattice", not {self.boundary!r}')
+        if rotation is not None:
+            if len(rotation) != 2 or any(not isinstance(r, (tuple, list)) or len(r) != 2 for r in rotation):
+                raise ValueError(f"rotation must be two pairs ((cr, sr), (cc, sc)), got {rotation!r}")
+            vals = [np.asarray(v, dtype=np.float64) for r in rotation for v in r]
+            names = ("cr", "sr", "cc", "sc")
+            ph = None
+        else:
+            ph = [np.asarray(phi_rows, dtype=np.float64), np.asarray(phi_cols, dtype=np.float64)]
+            vals = [np.cos(ph[0]), np.sin(ph[0]), np.cos(ph[1]), np.sin(ph[1])]
+            names = ("phi_rows", "phi_rows", "phi_cols", "phi_cols")
+        for v, nm in zip(vals if ph is None else (ph[0], ph[0], ph[1], ph[1]), names):
+            if v.shape not in ((), (self.count,)):
+                raise ValueError(f"{nm} must be a scalar or have shape ({self.count},), got {v.shape}")
+        cr, sr, cc, sc = (np.ascontiguousarray(np.broadcast_to(v, (self.count,))) for v in vals)
+        self._ck(self._lib.fdtd2d_batch_set_lattice(self._h, _dptr(cr), _dptr(sr), _dptr(cc), _dptr(sc)))
+        self._lattice = ((cr, sr), (cc, sc))
+        self._bloch = (cc, sc)        # upload, download, run and the monitors then behave as on a Bloch engine
+        self._phi = None if ph is None else np.ascontiguousarray(np.broadcast_to(ph[1], (self.count,)))
+        return self
+
     def _no_dispersion(self, what):
         """The library's refusal of `what` while a dispersive pole is set, before the call."""
         if self.dispersive:
@@ -164,6 +218,7 @@ class BatchEngine:
 
     def _no_bloch(self, what):
         """The library's refusal of `what` while a Bloch phase is set, before the call."""
+        self._no_lattice(what)
         if self._bloch is not None:
             raise _abi.Fdtd2dError(_abi.E_STATE, f"{what} is not available while a Bloch phase is set (complex fields)")
 
@@ -178,6 +233,7 @@ class BatchEngine:
         window, probe_spectra, field_absmax and the real adjoint helpers are refused, as are windows and probes touching
         column C-1.  Their complex counterparts are set_bloch_point_sources, run_bloch_channels, hold_bloch_window,
         bloch_window_product, bloch_probe_spectra and bloch_field_absmax (batch_bloch_gradient, BlochAdjointSession)."""
+        self._no_lattice("set_bloch_phase (use set_lattice_phase)")
         if phi is None and rotation is None:
             self._ck(self._lib.fdtd2d_batch_set_bloch(self._h, None, None))
             if self._bloch is not None:
@@ -232,9 +288,18 @@ class BatchEngine:
 
     def _touches_image(self, what, cols):
         """The library's refusal of a monitor in column C-1 while a Bloch phase is set."""
+        if self._lattice is not None:
+            return
         if self._bloch is not None and np.any(np.asarray(cols) >= self.cols - 1):
             raise _abi.Fdtd2dError(_abi.E_ARG, f"{what} touches column {self.cols - 1}, the image of column 0: not "
                                    "while a Bloch phase is set")
+
+    def _touches_lattice_image(self, what, rows, cols):
+        """The library's refusal of a monitor in row R-1 or column C-1 in the lattice mode."""
+        if self._lattice is not None and (np.any(np.asarray(rows) >= self.rows - 1) or
+                                          np.any(np.asarray(cols) >= self.cols - 1)):
+            raise _abi.Fdtd2dError(_abi.E_ARG, f"{what} touches row {self.rows - 1} or column {self.cols - 1}, the images "
+                                   "of row 0 and column 0: not in the lattice mode")
 
     @property
     def resident(self) -> bool:
@@ -302,6 +367,7 @@ class BatchEngine:
         themselves (ahr bhr aer ber of length rows, ahc bhc aec bec of length cols), each (n,) for every member
         or (B, n), instead of the graded ones.  Ezx starts at zero.  boundary="periodic": the layer lies on the top and
         bottom rows alone (2 L + 3 <= rows), the column factors are exactly 1 (the library refuses others)."""
+        self._no_lattice("a PML layer (every edge is periodic)")
         periodic = self.boundary == "periodic"
         if self.boundary != "pml" and not periodic:
             raise _abi.Fdtd2dError(_abi.E_STATE, f'set_pml needs boundary="pml" or "periodic", not {self.boundary!r}')
@@ -349,6 +415,7 @@ class BatchEngine:
 
     def upload_ezx(self, Ezx):
         """(B, R, C) split field, host -> device (needs a layer)."""
+        self._no_lattice("upload_ezx (there is no Ezx)")
         z = np.asarray(Ezx)
         if np.iscomplexobj(z) and self._bloch is None:
             raise ValueError("complex fields need a Bloch phase (set_bloch_phase)")
@@ -362,6 +429,7 @@ class BatchEngine:
 
     def download_ezx(self):
         """(B, R, C) split field, device -> host (needs a layer)."""
+        self._no_lattice("download_ezx (there is no Ezx)")
         a = np.empty((self.count, self.rows, self.cols), self.dtype)
         self._ck(self._lib.fdtd2d_batch_transfer_ezx(self._h, a.ctypes.data, _code(a.dtype), 0))
         if self._bloch is not None:
@@ -541,6 +609,7 @@ class BatchEngine:
         part of Ez after the rectangle source of step n of a run_bloch_channels (the imaginary part takes nothing; the
         seam carries the series into it).  Cells lie in columns 0..C-2; cells None removes them, and so does turning
         the phase off."""
+        self._no_lattice("a point source")
         self._need_bloch()
         if cells is None:
             self._ck(self._lib.fdtd2d_batch_set_bloch_point_sources(self._h, 0, None, 0, None))
@@ -570,6 +639,7 @@ class BatchEngine:
         steps with the rotation conj(rho) = (c, -s): the transpose of the one-step operator, what an adjoint run needs;
         downloads after it rotate the image column by that rotation."""
         nsteps = int(nsteps)
+        self._no_lattice("a run with channels")
         self._need_bloch()
         self._need_pml()
         a = ai = None
@@ -595,6 +665,7 @@ class BatchEngine:
 
     def hold_bloch_window(self):
         """hold_dft_window for a Bloch batch: a device copy of both parts of the window DFT."""
+        self._no_lattice("the held window")
         self._need_bloch()
         self._ck(self._lib.fdtd2d_batch_hold_bloch_window(self._h))
         return self
@@ -602,6 +673,7 @@ class BatchEngine:
     def bloch_window_product(self, coef) -> np.ndarray:
         """float64 (B, nrows, ncols): sum_k Re(coef[b, k] * held[b, k] * current[b, k]) of the complex windows
         W(re) + 1j * W(im), on the device; the plain product, nothing conjugated.  coef: complex (F,) or (B, F)."""
+        self._no_lattice("the window product")
         self._need_bloch()
         f, nr, nc = self._win or (0, 1, 1)
         k = np.asarray(coef, dtype=np.complex128)
@@ -680,6 +752,7 @@ class BatchEngine:
         w = _window_omegas(omegas, self.count)
         r0, c0, nr, nc = (int(v) for v in window)
         self._touches_image(f"window ({r0},{c0})+{nr}x{nc}", c0 + nc - 1)
+        self._touches_lattice_image(f"window ({r0},{c0})+{nr}x{nc}", r0 + nr - 1, c0 + nc - 1)
         self._ck(self._lib.fdtd2d_batch_set_dft_window(self._h, r0, c0, nr, nc, int(w.shape[1]), _dptr(w), int(every)))
         self._win = (int(w.shape[1]), nr, nc)
         return self
@@ -718,6 +791,7 @@ class BatchEngine:
             return self
         c = _probe_cells(cells, self.count)
         self._touches_image("a probe", c[..., 1])
+        self._touches_lattice_image("a probe", c[..., 0], c[..., 1])
         self._ck(self._lib.fdtd2d_batch_set_probes(self._h, int(c.shape[1]), c.ctypes.data_as(C.POINTER(C.c_int)),
                                                    int(capacity)))
         self._nprobe = int(c.shape[1])
@@ -791,6 +865,8 @@ class BatchEngine:
         it counts rows alone (the layer's depth, at least 6): every column of the period may conduct."""
         if self.boundary == "mur":
             return 6
+        if self.boundary == "lattice":
+            return 0                  # no edge: every cell of the period may conduct
         if self.boundary == "periodic":
             return max(6, self._pml_L)
         return max(6, self._pml_L) if self._pml_on else 1
@@ -808,7 +884,7 @@ class BatchEngine:
         if np.isscalar(sigma):
             g = self.conductivity_margin
             s = np.zeros(shape, np.float64)
-            if self.boundary == "periodic":
+            if self.boundary in ("periodic", "lattice"):
                 s[:, g:self.rows - g, :] = float(sigma)
             else:
                 s[:, g:self.rows - g, g:self.cols - g] = float(sigma)
@@ -849,6 +925,7 @@ class BatchEngine:
         (E_ARG) a value that is negative or not finite, wp2 non-zero inside the margin, and a cell whose pole breaks
         dt^2 (omega0^2 + wp2 EPS0 / eps) + 8 dt^2 / (eps mu dx^2) <= 4; while a pole is set it refuses (E_STATE) a Bloch
         phase, removing the layer of a "pml" batch and the held window with its product."""
+        self._no_lattice("a dispersive pole")
         if wp2 is None:
             self._ck(self._lib.fdtd2d_batch_set_dispersion(self._h, None, _code(self.dtype), None, None))
             return self
@@ -878,6 +955,7 @@ class BatchEngine:
     def set_dispersion_window(self, window, wp2):
         """New strengths for window = (row0, col0, nrows, ncols) of every member: wp2 (B, nrows, ncols).  The engine
         is then as set_dispersion with the full updated array would leave it.  Needs a pole (E_STATE)."""
+        self._no_lattice("a dispersive pole")
         w = np.ascontiguousarray([int(v) for v in window], dtype=np.int32)
         if w.shape != (4,):
             raise ValueError(f"window must be 4 integers (row0, col0, nrows, ncols), got {window!r}")
@@ -952,6 +1030,10 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
     (B,) in radians, the Bloch phase of set_bloch_phase; every returned array is then complex.  source_weights: "ramp",
     None or an array as set_bloch_source takes them (needs bloch_phase).  dispersion = (wp2, gamma, omega0) as
     set_dispersion takes them: one Drude-Lorentz pole per member (boundary "pml" or "periodic", not with bloch_phase).
+    boundary "lattice": every member is the unit cell of a rectangular lattice (periods R - 1 and C - 1, no layer:
+    pml_cells is not read) and bloch_phase = (phi_rows, phi_cols), each a scalar or (B,), gives its two Bloch phases
+    (set_lattice_phase; default zero); every returned array is complex.  A band-path sweep is one call: B copies of the
+    unit cell with the phases of the k-points along the path.
     """
     from .api import MU0
     eps = np.asarray(eps)
@@ -980,8 +1062,19 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
         L = int(pml_cells)
         m00 = mu_arr[:, 0, 0] if mu_arr.ndim == 3 else np.full(B, float(mu_arr))
         courant00 = np.array([(1 / np.sqrt(float(e) * float(u)) * dt) / dx for e, u in zip(eps[:, 0, 0], m00)])
-    if bloch_phase is not None and boundary != "periodic":
-        raise ValueError(f'bloch_phase needs boundary="periodic", not {boundary!r}')
+    lattice = boundary == "lattice"
+    if lattice:
+        if bloch_phase is None:
+            bloch_phase = (0.0, 0.0)
+        if not isinstance(bloch_phase, (tuple, list)) or len(bloch_phase) != 2:
+            raise ValueError(f'boundary="lattice" takes bloch_phase=(phi_rows, phi_cols), got {bloch_phase!r}')
+        for v, nm in zip(bloch_phase, ("phi_rows", "phi_cols")):
+            if np.shape(v) not in ((), (B,)):
+                raise ValueError(f"{nm} must be a scalar or have shape ({B},), got {np.shape(v)}")
+        if dispersion is not None:
+            raise ValueError('dispersion is not available with boundary="lattice"')
+    if bloch_phase is not None and boundary not in ("periodic", "lattice"):
+        raise ValueError(f'bloch_phase needs boundary="periodic" or "lattice", not {boundary!r}')
     if source_weights is not None and bloch_phase is None:
         raise ValueError("source_weights needs bloch_phase")
     if bloch_phase is not None and omega is not None:
@@ -999,6 +1092,11 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
             raise ValueError(f"dft_window {win} touches column {Cc - 1}, the image of column 0: not with bloch_phase")
         if cells is not None and np.any(cells[..., 1] >= Cc - 1):
             raise ValueError(f"a probe lies in column {Cc - 1}, the image of column 0: not with bloch_phase")
+    if lattice:
+        if win is not None and win[0] + win[2] > R - 1:
+            raise ValueError(f'dft_window {win} touches row {R - 1}, the image of row 0: not with boundary="lattice"')
+        if cells is not None and np.any(cells[..., 0] >= R - 1):
+            raise ValueError(f'a probe lies in row {R - 1}, the image of row 0: not with boundary="lattice"')
     with BatchEngine(B, R, Cc, dt, dx, dtype=dtype, boundary=boundary, device=device) as eng:
         eng.set_materials(eps, mu)
         if layered:
@@ -1006,8 +1104,11 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
         eng.set_sources(sources)
         if dispersion is not None:
             eng.set_dispersion(*dispersion)
-        if bloch_phase is not None:
+        if lattice:
+            eng.set_lattice_phase(*bloch_phase)
+        elif bloch_phase is not None:
             eng.set_bloch_phase(bloch_phase)
+        if bloch_phase is not None:
             if source_weights is not None:
                 eng.set_bloch_source(source_weights)
         if omega is not None:

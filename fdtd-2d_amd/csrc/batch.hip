@@ -15,12 +15,15 @@
 // fdtd2d_batch_run_bloch_channels (fdtd2d_batch_bloch_adjoint.h) takes their point-source instances
 // (batch_bloch_adjoint.hip), which also holds the product kernel of two complex windows.
 // With a Drude-Lorentz pole (fdtd2d_batch_dispersive.h) every run takes the dispersive kernels of batch_dispersive.hip.
+// In the lattice mode (fdtd2d_batch_lattice.h: Bloch conditions on both pairs of edges) every run takes the kernels of
+// batch_lattice.hip; the mode shares the Bloch phase's host state (`bloch` is set too) and adds the row rotation.
 #include "../../include/fdtd2d.h"
 #include "../../include/fdtd2d_batch_adjoint.h"
 #include "../../include/fdtd2d_batch_bloch.h"
 #include "../../include/fdtd2d_batch_bloch_adjoint.h"
 #include "../../include/fdtd2d_batch_design.h"
 #include "../../include/fdtd2d_batch_dispersive.h"
+#include "../../include/fdtd2d_batch_lattice.h"
 #include "../../include/fdtd2d_batch_lossy.h"
 #include "../../include/fdtd2d_batch_monitor.h"
 #include "../../include/fdtd2d_batch_periodic.h"
@@ -43,6 +46,7 @@
 #include "kernels_batch_bloch_adjoint.hpp"
 #include "kernels_batch_design.hpp"
 #include "kernels_batch_dispersive.hpp"
+#include "kernels_batch_lattice.hpp"
 #include "kernels_batch_lossy.hpp"
 #include "kernels_batch_monitor.hpp"
 #include "kernels_batch_periodic.hpp"
@@ -97,6 +101,12 @@ struct fdtd2d_batch {
     void *rho_conj = nullptr;
     bool run_conj = false;
     double *win_held_im = nullptr;
+    // fdtd2d_batch_set_lattice: row R-1 is the image of row 0 too.  `bloch` is set as well (the imaginary parts, the
+    // weights and the monitors are the Bloch phase's, without Ezx's imaginary part), rho / rho_host hold the column
+    // rotation and these the row rotation
+    bool lattice = false;
+    void *rho_r = nullptr;
+    std::vector<double> rho_r_host;       // count x {c, s} as the engine stores them
 
     int *rect = nullptr;                  // device copy of the source rectangles (4 per member)
     bool have_src = false;                // some member has a non-empty rectangle
@@ -256,7 +266,8 @@ int zero_fields(fdtd2d_batch *b)
     if (b->dcj)
         for (void *p : {b->djh, b->dq}) BCHK(b, hipMemsetAsync(p, 0, b->field_bytes, b->stream));
     if (b->bloch)
-        for (void *p : {b->ez_im, b->hx_im, b->hy_im, b->ezx_im}) BCHK(b, hipMemsetAsync(p, 0, b->field_bytes, b->stream));
+        for (void *p : {b->ez_im, b->hx_im, b->hy_im, b->ezx_im})
+            if (p) BCHK(b, hipMemsetAsync(p, 0, b->field_bytes, b->stream));     // a lattice batch has no Ezx
     b->cur = 0;
     b->step = 0;
     b->run_conj = false;
@@ -267,9 +278,10 @@ int zero_fields(fdtd2d_batch *b)
 // Mur / none: Ez, Hx, Hy (+ ce, ch); PML: Ez, Hx, Hy, Ezx (+ ce, ch) and the 4R + 4C factors; with a conductivity
 // cb stands in ce's place and ca is one more array; a Bloch phase: the four fields twice and cb, ch, ca, the row
 // factors alone, the source weights with the tables and the accumulators twice; a pole: the lossy PML arrays and Jh,
-// Q, cj
+// Q, cj; the lattice mode: Ez, Hx, Hy twice and cb, ch, ca, no factors
 int lds_arrays(const fdtd2d_batch *b)
 {
+    if (b->lattice) return 9;
     if (b->bloch) return 11;
     if (b->dcj) return 10;
     if (b->periodic) return 7;
@@ -280,7 +292,7 @@ int lds_arrays(const fdtd2d_batch *b)
 // bytes of the PML factors in LDS (0 without a layer)
 size_t lds_factor_bytes(const fdtd2d_batch *b)
 {
-    if (!b->ezx && !b->periodic) return 0;
+    if ((!b->ezx && !b->periodic) || b->lattice) return 0;
     if (b->bloch)                           // the row factors alone
         return b->dtype == FDTD2D_F32 ? fdtd::batch_lds_seg<float>(4 * b->rows) * 4
                                       : fdtd::batch_lds_seg<double>(4 * b->rows) * 8;
@@ -838,9 +850,63 @@ int run_bloch(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_str
     return 0;
 }
 
+// ---- lattice runs (fdtd2d_batch_lattice.h): the Bloch paths with the kernels of batch_lattice.hip --------------------
+template <class T> int run_lattice(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride)
+{
+    if (!b->ca || !b->ez_im || !b->rho || !b->rho_r) return bfail(b, FDTD2D_E_STATE, "lattice batch without its arrays");
+    const fdtd::BatchLatticeKernels &K = fdtd::batch_lattice_kernels<T>();
+    fdtd::BatchMon m = mon_view(b);
+    fdtd::BatchLattice<T> la{(T *)b->ez_im, (T *)b->hx_im, (T *)b->hy_im, (const T *)b->rho_r, (const T *)b->rho,
+                             b->bloch_w, b->have_src ? b->run_amps_im : nullptr, b->win_acc_im, b->probe_trace_im};
+    const T *ca = (const T *)b->ca;
+    if (use_resident(b)) {
+        const int cells = b->rows * b->cols, threads = resident_threads(cells);
+        const int per_thread = (cells + threads - 1) / threads;
+        const void *kern = per_thread <= 4 ? K.resident[0] : per_thread <= 5 ? K.resident[1] : nullptr;
+        if (!kern) return bfail(b, FDTD2D_E_STATE, "%d cells per thread exceed the lattice resident kernels", per_thread);
+        const size_t lds = lds_bytes(b);
+        BCHK(b, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        int per_cu = 0, cus = 0;
+        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds));
+        BCHK(b, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
+        if (per_cu < 1) return bfail(b, FDTD2D_E_STATE, "lattice resident kernel does not fit a CU (%zu B of LDS)", lds);
+        const long long round = (long long)per_cu * cus;
+        const int blocks = (int)(b->count < round ? b->count : round);
+        const int chunk = b->steps_per_launch > 0 ? b->steps_per_launch : nsteps;
+        for (int n = 0; n < nsteps; n += chunk) {
+            int n0 = n, nt = nsteps - n < chunk ? nsteps - n : chunk;
+            long long step_base = b->step;
+            fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+            v.ce = (const T *)b->cb;
+            void *args[] = {&v, &m, &la, &ca, &n0, &nt, &step_base};
+            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads), args, lds);
+            if (rc) return rc;
+            b->launches++;
+            b->step += nt;
+        }
+        return 0;
+    }
+    const int cells = b->rows * b->cols;
+    const dim3 grid((cells + 255) / 256, b->count < 65535 ? b->count : 65535);
+    for (int n = 0; n < nsteps; ++n) {
+        fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+        v.ce = (const T *)b->cb;
+        long long step = b->step + 1;
+        int rc;
+        void *h_args[] = {&v, &m, &la, &step};
+        void *e_args[] = {&v, &m, &la, &ca, &n, &step};
+        if ((rc = launch_ptr(b, K.h, grid, dim3(256), h_args, 0))) return rc;
+        if ((rc = launch_ptr(b, K.e, grid, dim3(256), e_args, 0))) return rc;
+        b->launches += 2;
+        b->step++;
+    }
+    return 0;
+}
+
 template <class T>
 int run_impl(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts = nullptr)
 {
+    if (b->lattice) return run_lattice<T>(b, nsteps, amps, amp_stride);
     if (b->bloch) return run_bloch<T>(b, nsteps, amps, amp_stride);
     if (b->dcj) return run_dispersive<T>(b, nsteps, amps, amp_stride, pts);
     if (b->periodic) return run_periodic<T>(b, nsteps, amps, amp_stride, pts);
@@ -914,6 +980,7 @@ int scratch(fdtd2d_batch *b, size_t bytes)
 // cells nearer than this to an edge take no plain update (or, like [0, 0], set the Mur factor and the PML grading)
 int sigma_margin(const fdtd2d_batch *b, int layer)
 {
+    if (b->lattice) return 0;                           // no edge: every cell of the period takes the plain update
     if (b->periodic) return layer > 6 ? layer : 6;      // rows alone (sigma_barred)
     return b->boundary == FDTD2D_BOUNDARY_MUR5 ? 6 : layer > 0 ? (layer > 6 ? layer : 6) : 1;
 }
@@ -922,6 +989,7 @@ int sigma_margin(const fdtd2d_batch *b, int layer)
 // never read)
 bool sigma_barred(const fdtd2d_batch *b, int i, int j, int mg)
 {
+    if (b->lattice) return false;
     if (b->periodic) return j < b->cols - 1 && (i < mg || i > b->rows - 1 - mg);
     return i < mg || i > b->rows - 1 - mg || j < mg || j > b->cols - 1 - mg;
 }
@@ -1036,6 +1104,16 @@ int copy_image(fdtd2d_batch *b, void *field)
     return 0;
 }
 
+// row 0 of a field over its image row R-1, every member (one strided device copy); after copy_image the corner slot
+// holds cell (0, 0)
+int copy_row_image(fdtd2d_batch *b, void *field)
+{
+    BCHK(b, hipStreamSynchronize(b->stream));
+    BCHK(b, hipMemcpy2D((char *)field + (size_t)(b->rows - 1) * b->pitch * b->esz, b->mstride * b->esz, field,
+                        b->mstride * b->esz, (size_t)b->cols * b->esz, (size_t)b->count, hipMemcpyDeviceToDevice));
+    return 0;
+}
+
 // no layer on a periodic batch: Ezx and the factor arrays stay (the periodic kernels always take them), every factor
 // exactly 1 and pml_L = 0, so that every row takes the plain update (PEC top and bottom)
 int unit_layer(fdtd2d_batch *b)
@@ -1060,7 +1138,7 @@ int unit_layer(fdtd2d_batch *b)
     BCHK(b, hipMemcpy(b->pml_row, ones.data(), rn * b->esz, hipMemcpyHostToDevice));
     BCHK(b, hipMemcpy(b->pml_col, ones.data(), cn * b->esz, hipMemcpyHostToDevice));
     BCHK(b, hipMemsetAsync(b->ezx, 0, b->field_bytes, b->stream));
-    if (b->bloch) BCHK(b, hipMemsetAsync(b->ezx_im, 0, b->field_bytes, b->stream));
+    if (b->ezx_im) BCHK(b, hipMemsetAsync(b->ezx_im, 0, b->field_bytes, b->stream));
     BCHK(b, hipStreamSynchronize(b->stream));
     b->pml_L = 0;
     return 0;
@@ -1317,6 +1395,38 @@ int copy_out_bloch(fdtd2d_batch *b, const void *re, const void *im, void *host, 
     return 0;
 }
 
+// Ez of a lattice batch, device -> host (count x rows x cols): one part, the images delivered rotated: column C-1 as
+// rho_c * its slot, row R-1 as rho_r * its slot, the corner as rho_r * (rho_c * its slot), each rotation rounded to T
+// (the slots hold the unrotated copies of column 0, of row 0 and of cell (0, 0))
+int copy_out_lattice(fdtd2d_batch *b, const void *re, const void *im, void *host, int host_dtype, int part)
+{
+    const int R = b->rows, C = b->cols;
+    std::vector<unsigned char> sr(b->field_bytes), si(b->field_bytes);
+    BCHK(b, hipStreamSynchronize(b->stream));
+    BCHK(b, hipMemcpy(sr.data(), re, b->field_bytes, hipMemcpyDeviceToHost));
+    BCHK(b, hipMemcpy(si.data(), im, b->field_bytes, hipMemcpyDeviceToHost));
+    const bool f32 = b->dtype == FDTD2D_F32;
+    auto rot = [&](double c, double s, double &zr, double &zi) {
+        const double nr = f32 ? bloch_rot_host<float>(c, s, zr, zi, 0) : bloch_rot_host<double>(c, s, zr, zi, 0);
+        const double ni = f32 ? bloch_rot_host<float>(c, s, zr, zi, 1) : bloch_rot_host<double>(c, s, zr, zi, 1);
+        zr = nr;
+        zi = ni;
+    };
+    for (int m = 0; m < b->count; ++m)
+        for (int i = 0; i < R; ++i) {
+            const size_t dst = ((size_t)m * R + i) * C, src = (size_t)m * b->mstride + (size_t)i * b->pitch;
+            for (int j = 0; j < C; ++j) {
+                double zr = get_elem(sr.data(), b->dtype, src + j), zi = get_elem(si.data(), b->dtype, src + j);
+                if (j == C - 1) rot(b->rho_host[2 * m], b->rho_host[2 * m + 1], zr, zi);
+                if (i == R - 1) rot(b->rho_r_host[2 * m], b->rho_r_host[2 * m + 1], zr, zi);
+                const double v = part ? zi : zr;
+                if (host_dtype == FDTD2D_F32) ((float *)host)[dst + j] = (float)v;
+                else ((double *)host)[dst + j] = v;
+            }
+        }
+    return 0;
+}
+
 // the imaginary part of the window DFT / of the probe traces: there (zeroed) exactly while a Bloch phase and the
 // monitor are both set.  The caller has waited for the stream.
 int bloch_window(fdtd2d_batch *b)
@@ -1355,19 +1465,46 @@ long long probe_in_image(const fdtd2d_batch *b, const std::vector<int> &lin)
 int bloch_off(fdtd2d_batch *b)
 {
     BCHK(b, hipStreamSynchronize(b->stream));
-    for (void **p : {&b->ez_im, &b->hx_im, &b->hy_im, &b->ezx_im, &b->rho, &b->rho_conj, (void **)&b->bloch_w,
+    for (void **p : {&b->ez_im, &b->hx_im, &b->hy_im, &b->ezx_im, &b->rho, &b->rho_conj, &b->rho_r, (void **)&b->bloch_w,
                      (void **)&b->amps_im, (void **)&b->win_acc_im, (void **)&b->probe_trace_im,
                      (void **)&b->win_held, (void **)&b->win_held_im})     // a held window here is a Bloch one
         release(p);
     b->amps_im_cap = 0;
     b->rho_host.clear();
-    b->bloch = b->run_conj = false;
+    b->rho_r_host.clear();
+    b->bloch = b->run_conj = b->lattice = false;
     return batch_set_points(b, 0, nullptr, 0, nullptr);      // the point sources of a Bloch batch go with the phase
+}
+
+// leaving the lattice mode makes a plain periodic batch: the first cell of sigma_host that is non-zero where that batch
+// allows none (member * cells + cell), or -1
+long long lattice_sigma_outside(fdtd2d_batch *b)
+{
+    if (!b->lattice || !b->ca) return -1;
+    b->lattice = false;
+    const long long t = sigma_outside(b, sigma_margin(b, 0));
+    b->lattice = true;
+    return t;
+}
+
+int refuse_lattice_off(fdtd2d_batch *b, long long t)
+{
+    return bfail(b, FDTD2D_E_ARG, "member %d: sigma is non-zero within 6 rows of the top or bottom edge, where a periodic "
+                 "batch without the lattice mode allows none: remove it first", (int)(t / ((long long)b->rows * b->cols)));
 }
 
 int refuse_bloch(fdtd2d_batch *b, const char *what)
 {
+    if (b->lattice) return bfail(b, FDTD2D_E_STATE, "%s is not available in the lattice mode (complex fields)", what);
     return bfail(b, FDTD2D_E_STATE, "%s is not available while a Bloch phase is set (complex fields)", what);
+}
+
+// the first probe in row R-1 or column C-1 (member * nprobe + probe), or -1
+long long probe_in_lattice_image(const fdtd2d_batch *b, const std::vector<int> &lin)
+{
+    for (size_t k = 0; k < lin.size(); ++k)
+        if (lin[k] % b->cols == b->cols - 1 || lin[k] / b->cols == b->rows - 1) return (long long)k;
+    return -1;
 }
 
 }  // namespace
@@ -1449,7 +1586,8 @@ void fdtd2d_batch_destroy(fdtd2d_batch_t *b)
                      (void **)&b->probe_trace, (void **)&b->win_held, (void **)&b->pts_cells, (void **)&b->pts_own,
                      (void **)&b->pts_w, (void **)&b->pts_tab, (void **)&b->chan, &b->dsg, &b->ca, &b->cb,
                      &b->ez_im, &b->hx_im, &b->hy_im, &b->ezx_im, &b->rho, (void **)&b->bloch_w, (void **)&b->amps_im,
-                     (void **)&b->win_acc_im, (void **)&b->probe_trace_im, &b->rho_conj, (void **)&b->win_held_im,
+                     (void **)&b->win_acc_im, (void **)&b->probe_trace_im, &b->rho_conj, &b->rho_r,
+                     (void **)&b->win_held_im,
                      &b->djh, &b->dq, &b->dcj, &b->da, &b->dck})
         release(p);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
@@ -1487,7 +1625,7 @@ long long fdtd2d_batch_info(const fdtd2d_batch_t *b, int what)
     case FDTD2D_BATCH_INFO_HELD_BLOCH_WINDOW: return b->win_held && b->win_held_im && b->bloch ? 1 : 0;
     case FDTD2D_BATCH_INFO_LOSSY: return b->ca && !b->sigma_implicit ? 1 : 0;
     case FDTD2D_BATCH_INFO_PERIODIC: return b->periodic ? 1 : 0;
-    case FDTD2D_BATCH_INFO_BLOCH: return b->bloch ? 1 : 0;
+    case FDTD2D_BATCH_INFO_BLOCH: return b->bloch && !b->lattice ? 1 : 0;
     case FDTD2D_BATCH_INFO_DISPERSIVE: return b->dcj ? 1 : 0;
     default: return FDTD2D_E_ARG;
     }
@@ -1630,6 +1768,7 @@ int fdtd2d_batch_set_pml(fdtd2d_batch_t *b, const void *row_factors, const void 
         return bfail(b, FDTD2D_E_STATE, "the PML needs a batch created with FDTD2D_BOUNDARY_NONE (its outer edge is PEC)");
     int rc = use_device(b);
     if (rc) return rc;
+    if (!row_factors && !col_factors && b->lattice) return 0;                // there is no layer to remove
     if (!row_factors && !col_factors && b->periodic) return unit_layer(b);   // PEC top and bottom
     if (!row_factors && !col_factors && b->dcj)
         return refuse_dispersive(b, "removing the layer of a batch without periodic columns (a plain box has no "
@@ -1640,6 +1779,7 @@ int fdtd2d_batch_set_pml(fdtd2d_batch_t *b, const void *row_factors, const void 
         b->pml_L = 0;
         return 0;
     }
+    if (b->lattice) return refuse_bloch(b, "a PML layer (every edge is periodic)");
     if (!row_factors || !col_factors) return bfail(b, FDTD2D_E_ARG, "factor arrays must both be given (or both NULL)");
     if (host_dtype != b->dtype) return bfail(b, FDTD2D_E_ARG, "PML factors must have the batch's dtype");
     if (layer_cells < 1 || 2 * layer_cells + 3 > (b->periodic || b->rows < b->cols ? b->rows : b->cols) || b->cols < 3)
@@ -1678,7 +1818,7 @@ int fdtd2d_batch_set_pml(fdtd2d_batch_t *b, const void *row_factors, const void 
     BCHK(b, hipMemcpy(b->pml_row, row_factors, rbytes, hipMemcpyHostToDevice));
     BCHK(b, hipMemcpy(b->pml_col, col_factors, cbytes, hipMemcpyHostToDevice));
     BCHK(b, hipMemsetAsync(b->ezx, 0, b->field_bytes, b->stream));
-    if (b->bloch) BCHK(b, hipMemsetAsync(b->ezx_im, 0, b->field_bytes, b->stream));
+    if (b->ezx_im) BCHK(b, hipMemsetAsync(b->ezx_im, 0, b->field_bytes, b->stream));
     BCHK(b, hipStreamSynchronize(b->stream));
     b->pml_L = layer_cells;
     return 0;
@@ -1687,6 +1827,7 @@ int fdtd2d_batch_set_pml(fdtd2d_batch_t *b, const void *row_factors, const void 
 int fdtd2d_batch_transfer_ezx(fdtd2d_batch_t *b, void *host, int host_dtype, int to_device)
 {
     if (!b || !host) return FDTD2D_E_ARG;
+    if (b->lattice) return refuse_bloch(b, "fdtd2d_batch_transfer_ezx (there is no Ezx)");
     if (!b->ezx) return bfail(b, FDTD2D_E_STATE, "no PML layer is set: call fdtd2d_batch_set_pml first");
     if (host_dtype != FDTD2D_F32 && host_dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad host_dtype");
     int rc = use_device(b);
@@ -1713,6 +1854,7 @@ int fdtd2d_batch_upload(fdtd2d_batch_t *b, const void *Ez, const void *Hx, const
     if (rc) return rc;
     if (Ez && (rc = copy_in(b, b->ez[b->cur], Ez, host_dtype, b->rows, b->cols))) return rc;
     if (Ez && b->periodic && (rc = copy_image(b, b->ez[b->cur]))) return rc;
+    if (Ez && b->lattice && (rc = copy_row_image(b, b->ez[b->cur]))) return rc;
     if (Hx && (rc = copy_in(b, b->hx, Hx, host_dtype, b->rows, b->cols - 1))) return rc;
     if (Hy && (rc = copy_in(b, b->hy, Hy, host_dtype, b->rows - 1, b->cols))) return rc;
     return 0;
@@ -1724,7 +1866,11 @@ int fdtd2d_batch_download(fdtd2d_batch_t *b, void *Ez, void *Hx, void *Hy, int h
     if (host_dtype != FDTD2D_F32 && host_dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad host_dtype");
     int rc = use_device(b);
     if (rc) return rc;
-    if (Ez && b->bloch && (rc = copy_out_bloch(b, b->ez[b->cur], b->ez_im, Ez, host_dtype, 0))) return rc;
+    if (Ez && b->lattice) {
+        if ((rc = copy_out_lattice(b, b->ez[b->cur], b->ez_im, Ez, host_dtype, 0))) return rc;
+    } else if (Ez && b->bloch) {
+        if ((rc = copy_out_bloch(b, b->ez[b->cur], b->ez_im, Ez, host_dtype, 0))) return rc;
+    }
     if (Ez && !b->bloch && (rc = copy_out(b, b->ez[b->cur], Ez, host_dtype, b->rows, b->cols))) return rc;
     if (Hx && (rc = copy_out(b, b->hx, Hx, host_dtype, b->rows, b->cols - 1))) return rc;
     if (Hy && (rc = copy_out(b, b->hy, Hy, host_dtype, b->rows - 1, b->cols))) return rc;
@@ -1766,6 +1912,9 @@ int fdtd2d_batch_set_sources(fdtd2d_batch_t *b, const int *rect)
         if (b->periodic && c + nc > b->cols - 1)
             return bfail(b, FDTD2D_E_ARG, "member %d: source (%d,%d)+%dx%d reaches column %d, the image of column 0 of a "
                          "periodic batch", m, r, c, nr, nc, b->cols - 1);
+        if (b->lattice && r + nr > b->rows - 1)
+            return bfail(b, FDTD2D_E_ARG, "member %d: source (%d,%d)+%dx%d reaches row %d, the image of row 0 of a lattice "
+                         "batch", m, r, c, nr, nc, b->rows - 1);
         any = true;
     }
     int rc = use_device(b);
@@ -1868,6 +2017,9 @@ int fdtd2d_batch_set_dft_window(fdtd2d_batch_t *b, int row0, int col0, int nrows
         if (b->bloch && col0 + ncols > b->cols - 1)
             return bfail(b, FDTD2D_E_ARG, "window (%d,%d)+%dx%d touches column %d, the image of column 0: not while a "
                          "Bloch phase is set", row0, col0, nrows, ncols, b->cols - 1);
+        if (b->lattice && row0 + nrows > b->rows - 1)
+            return bfail(b, FDTD2D_E_ARG, "window (%d,%d)+%dx%d touches row %d, the image of row 0: not in the lattice "
+                         "mode", row0, col0, nrows, ncols, b->rows - 1);
     }
     int rc = use_device(b);
     if (rc) return rc;
@@ -1928,6 +2080,11 @@ int fdtd2d_batch_set_probes(fdtd2d_batch_t *b, int nprobe, const int *cells, lon
                              (int)(k / nprobe), (int)(k % nprobe), r, c, b->rows, b->cols);
             lin[k] = r * b->cols + c;
         }
+        const long long kl = b->lattice ? probe_in_lattice_image(b, lin) : -1;
+        if (kl >= 0)
+            return bfail(b, FDTD2D_E_ARG, "member %d probe %d: cell (%d,%d) lies in row %d or column %d, the images of row 0 "
+                         "and column 0: not in the lattice mode", (int)(kl / nprobe), (int)(kl % nprobe),
+                         lin[kl] / b->cols, lin[kl] % b->cols, b->rows - 1, b->cols - 1);
         const long long k = b->bloch ? probe_in_image(b, lin) : -1;
         if (k >= 0)
             return bfail(b, FDTD2D_E_ARG, "member %d probe %d: column %d is the image of column 0: not while a Bloch "
@@ -2419,6 +2576,10 @@ int fdtd2d_batch_set_periodic(fdtd2d_batch_t *b, int on)
             return bfail(b, FDTD2D_E_ARG, "member %d: wp2 is non-zero within %d cells of an edge (the PML layer, the "
                          "frame and cell [0, 0])", (int)(t / ((long long)b->rows * b->cols)), mg);
     }
+    if (!on && b->lattice) {
+        const long long t = lattice_sigma_outside(b);
+        if (t >= 0) return refuse_lattice_off(b, t);
+    }
     if (!on) {
         if (b->bloch && (rc = bloch_off(b))) return rc;
         if ((rc = fdtd2d_batch_set_point_sources(b, 0, nullptr, 0, nullptr))) return rc;
@@ -2479,6 +2640,7 @@ int fdtd2d_batch_set_bloch(fdtd2d_batch_t *b, const double *cos_phi, const doubl
     if (!cos_phi != !sin_phi) return bfail(b, FDTD2D_E_ARG, "cos_phi and sin_phi must both be given (or both NULL)");
     int rc = use_device(b);
     if (rc) return rc;
+    if (b->lattice) return refuse_bloch(b, "fdtd2d_batch_set_bloch (use fdtd2d_batch_set_lattice)");
     if (!cos_phi) return b->bloch ? bloch_off(b) : 0;
     if (b->dcj) return refuse_dispersive(b, "a Bloch phase");
     if (!b->periodic)
@@ -2594,11 +2756,13 @@ int fdtd2d_batch_transfer_bloch(fdtd2d_batch_t *b, void *Ez_im, void *Hx_im, voi
     if (!b) return FDTD2D_E_ARG;
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
     if (host_dtype != FDTD2D_F32 && host_dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad host_dtype");
+    if (b->lattice && Ezx_im) return refuse_bloch(b, "Ezx (pass Ezx_im as NULL)");
     int rc = use_device(b);
     if (rc) return rc;
     if (to_device) {
         if (Ez_im && ((rc = copy_in(b, b->ez_im, Ez_im, host_dtype, b->rows, b->cols)) || (rc = copy_image(b, b->ez_im))))
             return rc;
+        if (Ez_im && b->lattice && (rc = copy_row_image(b, b->ez_im))) return rc;
         if (Hx_im && (rc = copy_in(b, b->hx_im, Hx_im, host_dtype, b->rows, b->cols - 1))) return rc;
         if (Hy_im && (rc = copy_in(b, b->hy_im, Hy_im, host_dtype, b->rows - 1, b->cols))) return rc;
         if (Ezx_im && ((rc = copy_in(b, b->ezx_im, Ezx_im, host_dtype, b->rows, b->cols)) ||
@@ -2606,7 +2770,11 @@ int fdtd2d_batch_transfer_bloch(fdtd2d_batch_t *b, void *Ez_im, void *Hx_im, voi
             return rc;
         return 0;
     }
-    if (Ez_im && (rc = copy_out_bloch(b, b->ez[b->cur], b->ez_im, Ez_im, host_dtype, 1))) return rc;
+    if (Ez_im && b->lattice) {
+        if ((rc = copy_out_lattice(b, b->ez[b->cur], b->ez_im, Ez_im, host_dtype, 1))) return rc;
+    } else if (Ez_im) {
+        if ((rc = copy_out_bloch(b, b->ez[b->cur], b->ez_im, Ez_im, host_dtype, 1))) return rc;
+    }
     if (Hx_im && (rc = copy_out(b, b->hx_im, Hx_im, host_dtype, b->rows, b->cols - 1))) return rc;
     if (Hy_im && (rc = copy_out(b, b->hy_im, Hy_im, host_dtype, b->rows - 1, b->cols))) return rc;
     if (Ezx_im && (rc = copy_out_bloch(b, b->ezx, b->ezx_im, Ezx_im, host_dtype, 1))) return rc;
@@ -2649,6 +2817,109 @@ int fdtd2d_batch_read_probes_bloch(fdtd2d_batch_t *b, double *out, long long fir
     return 0;
 }
 
+// ---- fdtd2d_batch_lattice.h --------------------------------------------------------------------------------------
+
+int fdtd2d_batch_set_lattice(fdtd2d_batch_t *b, const double *cos_r, const double *sin_r, const double *cos_c,
+                             const double *sin_c)
+{
+    if (!b) return FDTD2D_E_ARG;
+    const int given = !!cos_r + !!sin_r + !!cos_c + !!sin_c;
+    if (given != 0 && given != 4)
+        return bfail(b, FDTD2D_E_ARG, "cos_r, sin_r, cos_c and sin_c must all be given (or all NULL)");
+    int rc = use_device(b);
+    if (rc) return rc;
+    if (!given) {
+        if (!b->lattice) return 0;
+        const long long t = lattice_sigma_outside(b);
+        if (t >= 0) return refuse_lattice_off(b, t);
+        return bloch_off(b);
+    }
+    if (b->bloch && !b->lattice) return refuse_bloch(b, "the lattice mode (turn the phase of fdtd2d_batch_set_bloch off)");
+    if (b->dcj) return refuse_dispersive(b, "the lattice mode");
+    if (!b->periodic)
+        return bfail(b, FDTD2D_E_STATE, "the lattice mode needs periodic columns: call fdtd2d_batch_set_periodic first");
+    if (!b->have_mat) return bfail(b, FDTD2D_E_STATE, "materials not set: call fdtd2d_batch_set_materials first");
+    const int R = b->rows, C = b->cols;
+    if (!b->lattice) {
+        if (b->pml_L > 0)
+            return bfail(b, FDTD2D_E_STATE, "the lattice mode has no layer: remove it (fdtd2d_batch_set_pml with NULL) first");
+        if (b->dft)
+            return bfail(b, FDTD2D_E_STATE, "the whole-grid transform is not available in the lattice mode (remove it, use "
+                         "fdtd2d_batch_set_dft_window)");
+        if (b->npts) return bfail(b, FDTD2D_E_STATE, "a point source is not available in the lattice mode (remove them)");
+        if (b->win_held)
+            return bfail(b, FDTD2D_E_STATE, "the held window is not available in the lattice mode (set the window again)");
+    }
+    for (int m = 0; m < b->count; ++m)
+        if (!std::isfinite(cos_r[m]) || !std::isfinite(sin_r[m]) || !std::isfinite(cos_c[m]) || !std::isfinite(sin_c[m]))
+            return bfail(b, FDTD2D_E_ARG, "member %d: the rotations (%g, %g), (%g, %g) are not finite", m, cos_r[m], sin_r[m],
+                         cos_c[m], sin_c[m]);
+    if (!b->lattice) {
+        if (b->win_nf && (b->win_c0 + b->win_nc > C - 1 || b->win_r0 + b->win_nr > R - 1))
+            return bfail(b, FDTD2D_E_ARG, "window (%d,%d)+%dx%d touches row %d or column %d, the images of row 0 and column "
+                         "0: not in the lattice mode", b->win_r0, b->win_c0, b->win_nr, b->win_nc, R - 1, C - 1);
+        const long long k = probe_in_lattice_image(b, b->probe_host);
+        if (k >= 0)
+            return bfail(b, FDTD2D_E_ARG, "member %d probe %d: cell (%d,%d) lies in row %d or column %d, the images of row 0 "
+                         "and column 0: not in the lattice mode", (int)(k / b->nprobe), (int)(k % b->nprobe),
+                         b->probe_host[k] / C, b->probe_host[k] % C, R - 1, C - 1);
+        for (int m = 0; m < b->count && !b->rect_host.empty(); ++m) {
+            const int *r = b->rect_host.data() + 4 * m;
+            if (r[2] > 0 && r[0] + r[2] > R - 1)
+                return bfail(b, FDTD2D_E_ARG, "member %d: source (%d,%d)+%dx%d reaches row %d, the image of row 0 of a "
+                             "lattice batch", m, r[0], r[1], r[2], r[3], R - 1);
+        }
+    }
+    // (c, s) of the row seam and of the column seam, as the engine stores them
+    std::vector<double> rr((size_t)b->count * 2), rc2(rr.size());
+    std::vector<unsigned char> rrt(rr.size() * b->esz), rct(rrt.size());
+    for (size_t k = 0; k < rr.size(); ++k) {
+        rr[k] = as_engine(b, k % 2 ? sin_r[k / 2] : cos_r[k / 2]);
+        rc2[k] = as_engine(b, k % 2 ? sin_c[k / 2] : cos_c[k / 2]);
+        if (b->dtype == FDTD2D_F32) {
+            ((float *)rrt.data())[k] = (float)rr[k];
+            ((float *)rct.data())[k] = (float)rc2[k];
+        } else {
+            ((double *)rrt.data())[k] = rr[k];
+            ((double *)rct.data())[k] = rc2[k];
+        }
+    }
+    BCHK(b, hipStreamSynchronize(b->stream));   // a running launch may still read the old rotations
+    if (!b->lattice) {
+        const size_t wn = (size_t)b->count * 2 * (C - 1);
+        auto undo = [&](int code) {
+            bloch_off(b);
+            return code;
+        };
+        for (void **p : {&b->ez_im, &b->hx_im, &b->hy_im}) {
+            if ((rc = alloc(b, p, b->field_bytes))) return undo(rc);
+            if (hipMemsetAsync(*p, 0, b->field_bytes, b->stream) != hipSuccess)
+                return undo(bfail(b, FDTD2D_E_NOMEM, "hipMemset of the imaginary fields failed"));
+        }
+        if (hipStreamSynchronize(b->stream) != hipSuccess)
+            return undo(bfail(b, FDTD2D_E_NOMEM, "hipMemset of the imaginary fields failed"));
+        if ((rc = alloc(b, &b->rho, rct.size())) || (rc = alloc(b, &b->rho_r, rrt.size())) ||
+            (rc = alloc(b, (void **)&b->bloch_w, wn * sizeof(double))))
+            return undo(rc);
+        b->bloch = b->lattice = true;
+        if ((rc = fdtd2d_batch_set_bloch_source(b, nullptr, nullptr)) || (rc = bloch_window(b)) || (rc = bloch_probes(b)) ||
+            (rc = copy_image(b, b->ez[b->cur])) || (rc = copy_row_image(b, b->ez[b->cur])))
+            return undo(rc);
+    }
+    BCHK(b, hipMemcpy(b->rho, rct.data(), rct.size(), hipMemcpyHostToDevice));
+    BCHK(b, hipMemcpy(b->rho_r, rrt.data(), rrt.size(), hipMemcpyHostToDevice));
+    b->rho_host.swap(rc2);
+    b->rho_r_host.swap(rr);
+    b->run_conj = false;
+    return 0;
+}
+
+int fdtd2d_batch_is_lattice(const fdtd2d_batch_t *b)
+{
+    if (!b) return FDTD2D_E_ARG;
+    return b->lattice ? 1 : 0;
+}
+
 // ---- fdtd2d_batch_bloch_adjoint.h ----------------------------------------------------------------------------------
 
 int fdtd2d_batch_set_bloch_point_sources(fdtd2d_batch_t *b, int ncell, const int *cells, int nchan,
@@ -2656,6 +2927,7 @@ int fdtd2d_batch_set_bloch_point_sources(fdtd2d_batch_t *b, int ncell, const int
 {
     if (!b) return FDTD2D_E_ARG;
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (ncell > 0 && b->lattice) return refuse_bloch(b, "a point source");
     return batch_set_points(b, ncell, cells, nchan, weights);     // a periodic batch: column C-1 is refused there
 }
 
@@ -2664,6 +2936,7 @@ int fdtd2d_batch_run_bloch_channels(fdtd2d_batch_t *b, int nsteps, const double 
 {
     if (!b) return FDTD2D_E_ARG;
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (b->lattice) return refuse_bloch(b, "a run with channels");
     if (nsteps < 0) return bfail(b, FDTD2D_E_ARG, "nsteps < 0");
     if (!chan) return bfail(b, FDTD2D_E_ARG, "chan must not be NULL");
     if (amps_im && !amps_re) return bfail(b, FDTD2D_E_ARG, "amps_im needs amps_re (zeros for a purely imaginary source)");
@@ -2708,6 +2981,7 @@ int fdtd2d_batch_hold_bloch_window(fdtd2d_batch_t *b)
 {
     if (!b) return FDTD2D_E_ARG;
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (b->lattice) return refuse_bloch(b, "the held window");
     if (!b->win_nf || !b->win_acc_im) return bfail(b, FDTD2D_E_STATE, "no window DFT is set");
     int rc = use_device(b);
     if (rc) return rc;
@@ -2725,6 +2999,7 @@ int fdtd2d_batch_bloch_window_product(fdtd2d_batch_t *b, const double *coef_re, 
     if (!b) return FDTD2D_E_ARG;
     if (!coef_re || !coef_im || !out) return bfail(b, FDTD2D_E_ARG, "coef_re, coef_im and out must not be NULL");
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (b->lattice) return refuse_bloch(b, "the window product");
     if (!b->win_nf || !b->win_acc_im) return bfail(b, FDTD2D_E_STATE, "no window DFT is set");
     if (!b->win_held || !b->win_held_im)
         return bfail(b, FDTD2D_E_STATE, "no held window: call fdtd2d_batch_hold_bloch_window first");
@@ -2813,10 +3088,12 @@ int fdtd2d_batch_bloch_field_absmax(fdtd2d_batch_t *b, int field, double *out)
     const void *re = field == FDTD2D_FIELD_EZ ? b->ez[b->cur] : field == FDTD2D_FIELD_HX ? b->hx : b->hy;
     const void *im = field == FDTD2D_FIELD_EZ ? b->ez_im : field == FDTD2D_FIELD_HX ? b->hx_im : b->hy_im;
     for (int q = 0; q < 2; ++q) {
-        // Ez: columns 0..C-2 (the image slot holds a copy of column 0); Hx has C-1 columns, Hy has R-1 rows
+        // Ez: columns 0..C-2 (the image slot holds a copy of column 0); Hx has C-1 columns, Hy has R-1 rows; a lattice
+        // batch: rows 0..R-2 and columns 0..C-2 of each
         fdtd::batch_field_absmax_launch(q ? im : re, b->dtype == FDTD2D_F64, (double *)b->dsg + (size_t)q * b->count,
-                                        b->count, b->rows - (field == FDTD2D_FIELD_HY),
-                                        b->cols - (field != FDTD2D_FIELD_HY), b->pitch, b->mstride, b->stream);
+                                        b->count, b->rows - (field == FDTD2D_FIELD_HY || b->lattice),
+                                        b->cols - (field != FDTD2D_FIELD_HY || b->lattice), b->pitch, b->mstride,
+                                        b->stream);
         BCHK(b, hipGetLastError());
         b->launches++;
     }

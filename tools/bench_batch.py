@@ -70,9 +70,16 @@ array eps with random binary permittivity, a ricker line source per member):
                               dispersive_over_lossy_pml, both paths and LDS sizes.  By this script's LDS count the pole
                               adds three reads and two writes per interior cell-step to the lossy PML kernel's 17 reads
                               and 3 writes.  Default: 1024 members of 60 x 60, a 10-cell layer, 1000 steps.
+  --lattice                   instead: a lattice batch (boundary="lattice": Bloch conditions on both pairs of edges, a
+                              k-path sweep Gamma-X-M-Gamma over the members, ramp weights) against the Bloch batch of the
+                              same members without a layer (PEC rows, the members' column phases), with the same
+                              conductivity (zero within 6 rows of the top and bottom, where the Bloch batch allows none),
+                              timed alternately in one process: lattice_ms, bloch_ms, lattice_over_bloch, both paths and
+                              LDS sizes.  The lattice kernel carries 9 arrays against 11 and has no layer branch, so
+                              the number to beat is 1.  Default: 1024 members of 33 x 33, 1000 steps.
 Usage: python tools/bench_batch.py [--count 1024 --rows 60 --cols 60 --steps 1000] [--reps 5] [--loop-members 16]
                                    [--boundary {mur,pml} --pml-cells 10] [--monitors] [--adjoint] [--lossy]
-                                   [--periodic] [--bloch] [--bloch-adjoint] [--dispersive]
+                                   [--periodic] [--bloch] [--bloch-adjoint] [--dispersive] [--lattice]
 """
 import argparse
 import json
@@ -440,6 +447,61 @@ def bench_bloch(count, rows, cols, steps, dtype, reps, pml_cells):
             "bloch_mcell_steps_per_s": round(count * rows * cols * steps / (med_b * 1e-3) / 1e6, 1)}
 
 
+def k_path(count):
+    """(phi_rows, phi_cols), each (count,): the path Gamma-X-M-Gamma of a rectangular lattice, a third of the members on
+    each leg."""
+    t = np.linspace(0.0, 3.0, count, endpoint=False)
+    phi_r = np.pi * np.where(t < 1, t, np.where(t < 2, 1.0, 3.0 - t))
+    phi_c = np.pi * np.where(t < 1, 0.0, np.where(t < 2, t - 1.0, 3.0 - t))
+    return phi_r, phi_c
+
+
+def bench_lattice(count, rows, cols, steps, dtype, reps):
+    eps, rects, amps = members(count, rows, cols, steps)
+    rng = np.random.default_rng(1)
+    sigma = np.zeros((count, rows, cols))
+    sigma[:, 6:rows - 6, :] = 20.0 * rng.random((count, rows - 12, cols))
+    phi_r, phi_c = k_path(count)
+
+    def batch(lattice):
+        b = fd.BatchEngine(count, rows, cols, DT, DX, dtype=dtype, boundary="lattice" if lattice else "periodic")
+        b.set_materials(eps.astype(dtype), fd.MU0).set_sources(rects).set_conductivity(sigma)
+        if lattice:
+            b.set_lattice_phase(phi_r, phi_c).set_bloch_source("ramp")
+        else:
+            b.set_bloch_phase(phi_c).set_bloch_source("ramp")
+        b.run(steps, amps).sync()                      # warm-up: code objects, clocks
+        return b
+
+    def timed(b):
+        b.reset().sync()
+        t0 = time.perf_counter()
+        b.run(steps, amps).sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    with batch(False) as blo, batch(True) as lat:
+        assert lat.lattice and lat.periodic and blo.bloch and not blo.lattice and not blo.pml
+        l0 = lat.launches
+        lat.reset().run(steps, amps).sync()
+        launches = lat.launches - l0
+        blo_ms, lat_ms = [], []
+        for _ in range(reps):
+            blo_ms.append(timed(blo))
+            lat_ms.append(timed(lat))
+        paths = ["resident" if b.resident else "streamed" for b in (blo, lat)]
+        lds = [b.lds_bytes for b in (blo, lat)]
+    med_b, med_l = float(np.median(blo_ms)), float(np.median(lat_ms))
+    return {"count": count, "rows": rows, "cols": cols, "steps": steps, "dtype": np.dtype(dtype).name,
+            "materials": "arrays", "k_path": "Gamma-X-M-Gamma", "reps": reps, "bloch_path": paths[0],
+            "lattice_path": paths[1], "bloch_lds_bytes_per_member": lds[0], "lattice_lds_bytes_per_member": lds[1],
+            "bloch_ms": round(med_b, 4), "bloch_ms_min": round(min(blo_ms), 4),
+            "bloch_ms_all": [round(v, 4) for v in blo_ms],
+            "lattice_ms": round(med_l, 4), "lattice_ms_min": round(min(lat_ms), 4),
+            "lattice_ms_all": [round(v, 4) for v in lat_ms],
+            "lattice_over_bloch": round(med_l / med_b, 3), "launches_per_run": launches,
+            "lattice_mcell_steps_per_s": round(count * rows * cols * steps / (med_l * 1e-3) / 1e6, 1)}
+
+
 def bench_adjoint(count, rows, cols, steps, dtype, reps, pml_cells):
     from fdtd2d_amd.adjoint import channel_system, gradient_coefficients
     dt = 2e-13                                   # the Gaussian envelope of the channels (t0 = 4.5 / fc) ends by step 1200
@@ -679,7 +741,12 @@ def main():
     ap.add_argument("--bloch", action="store_true", help="time a Bloch batch against the plain periodic one")
     ap.add_argument("--bloch-adjoint", action="store_true", help="time the adjoint gradient of a Bloch batch")
     ap.add_argument("--dispersive", action="store_true", help="time the dispersive kernels against the lossy PML ones")
+    ap.add_argument("--lattice", action="store_true", help="time a lattice batch against the Bloch batch without a layer")
     a = ap.parse_args()
+    if a.lattice:
+        print(json.dumps(bench_lattice(a.count or 1024, a.rows or 33, a.cols or a.rows or 33, a.steps or 1000,
+                                       np.dtype(a.dtype), a.reps)), flush=True)
+        return
     if a.dispersive:
         print(json.dumps(bench_dispersive(a.count or 1024, a.rows or 60, a.cols or 60, a.steps or 1000,
                                           np.dtype(a.dtype), a.reps, a.pml_cells)), flush=True)
