@@ -212,6 +212,13 @@ BATCH_LATTICE_SIGNATURES = {
     "fdtd2d_batch_is_lattice": (_i, [_vp]),
 }
 
+# every symbol include/fdtd2d_batch_bloch_dispersive.h declares (the pole of a Bloch or lattice batch: complex Jh and Q)
+BATCH_BLOCH_DISPERSIVE_SIGNATURES = {
+    "fdtd2d_batch_set_bloch_dispersion": (_i, [_vp, _vp, _i, C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_set_bloch_dispersion_window": (_i, [_vp, C.POINTER(_i), _vp, _i]),
+    "fdtd2d_batch_transfer_bloch_dispersion": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i]),
+}
+
 # transport callback of fdtd2d_slab_attach
 EXCHANGE_FN = C.CFUNCTYPE(_i, _vp, _vp, _vp, _vp, _vp, _ll, _vp)
 
@@ -263,7 +270,8 @@ def load():
                                    **BATCH_ADJOINT_SIGNATURES, **BATCH_DESIGN_SIGNATURES,
                                    **BATCH_LOSSY_SIGNATURES, **BATCH_PERIODIC_SIGNATURES,
                                    **BATCH_BLOCH_SIGNATURES, **BATCH_BLOCH_ADJOINT_SIGNATURES,
-                                   **BATCH_DISPERSIVE_SIGNATURES, **BATCH_LATTICE_SIGNATURES}.items():
+                                   **BATCH_DISPERSIVE_SIGNATURES, **BATCH_LATTICE_SIGNATURES,
+                                   **BATCH_BLOCH_DISPERSIVE_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

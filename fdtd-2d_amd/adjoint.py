@@ -271,7 +271,7 @@ def _refuse_bloch(eng):
 
 def _refuse_dispersion(eng):
     """The adjoint of a dispersive medium is not implemented: an engine with a Drude-Lorentz pole (an engine factory
-    that sets one, or set_dispersion on a session's engine) is refused before any run."""
+    that sets one, or set_dispersion / set_bloch_dispersion on a session's engine) is refused before any run."""
     if getattr(eng, "dispersive", False):
         from ._abi import E_STATE, Fdtd2dError
         raise Fdtd2dError(E_STATE, "adjoint gradients are not available while a dispersive pole is set: the adjoint of a "
@@ -690,6 +690,7 @@ def batch_bloch_gradient(eps, sigma=None, mu=None, *, bloch_phase, source_weight
     with engine(B, p.R, p.Cc, dt, dx, dtype=dtype, boundary="periodic", device=device) as eng:
         # 1. forward: the member's own source and phase
         _bloch_setup(eng, p, s, phi, weights)
+        _refuse_dispersion(eng)                 # an engine factory that sets the pole of set_bloch_dispersion
         eng.run(nsteps, p.amps)
         traces = eng.read_probes(0, nsteps)
         end_fwd = _part_peak(eng.download()[0][:, :, :-1])

@@ -17,6 +17,8 @@ or in PEC (fdtd2d_batch_periodic.h).  ``set_bloch_phase`` gives a periodic batch
 become complex and repeat as F(x + period) = F(x) e^{i phi} (oblique incidence, angle sweeps, band diagrams;
 fdtd2d_batch_bloch.h).  ``set_dispersion`` gives a PML or periodic batch one Drude-Lorentz pole per member with a strength
 per cell (metals, absorption lines; fdtd2d_batch_dispersive.h); the batch then runs on the dispersive step kernels.
+``set_bloch_dispersion`` is that pole for a batch with complex fields (a Bloch phase or the lattice mode;
+fdtd2d_batch_bloch_dispersive.h): a metal unit cell with one angle of incidence or one k-point per member.
 ``boundary="lattice"`` makes every member the unit cell of a rectangular 2D lattice: row R-1 is the image of row 0 and
 column C-1 the image of column 0, the fields are complex, and ``set_lattice_phase`` gives every member one Bloch phase
 across each pair of edges (band diagrams of 2D photonic crystals: a k-path is one batch; fdtd2d_batch_lattice.h).
@@ -991,6 +993,85 @@ class BatchEngine:
         self._ck(self._lib.fdtd2d_batch_transfer_dispersion(self._h, ptr[0], ptr[1], _code(self.dtype), 1))
         return self
 
+    # -- the pole of a Bloch or lattice batch (fdtd2d_batch_bloch_dispersive.h) ----------------------------------
+    def _need_complex(self, what):
+        """The library's refusal of a complex pole's call on a batch with real fields, before the call."""
+        if self._bloch is None:
+            raise _abi.Fdtd2dError(_abi.E_STATE, f"{what} needs a Bloch phase or the lattice mode: a batch with real "
+                                   "fields takes set_dispersion")
+
+    def set_bloch_dispersion(self, wp2, gamma=0.0, omega0=0.0):
+        """set_dispersion for an engine with complex fields (set_bloch_phase, or boundary="lattice"): one Drude-Lorentz
+        pole per member, acting on the real and on the imaginary part alike (every coefficient is real).  wp2: (B, R, C),
+        or a scalar for every cell that may carry it (with a Bloch phase: zero in the margin of conductivity_margin on
+        the rows; on a lattice: every cell), or None to remove the pole.  gamma and omega0: a scalar or (B,).  The state
+        (download_bloch_dispersion) is complex, starts at zero and survives later calls; reset() zeroes it.  The library
+        refuses what set_dispersion refuses for these values (E_ARG), and (E_STATE) an engine without complex fields, one
+        with Bloch point sources or a held Bloch window; while this pole is set it refuses (E_STATE) turning the phase
+        off, set_bloch_point_sources, run_bloch_channels, hold_bloch_window and bloch_window_product, so
+        batch_bloch_gradient and BlochAdjointSession refuse too.  New phases (a k-point or angle sweep with the metal in
+        place) keep working."""
+        self._need_complex("set_bloch_dispersion")
+        if wp2 is None:
+            self._ck(self._lib.fdtd2d_batch_set_bloch_dispersion(self._h, None, _code(self.dtype), None, None))
+            return self
+        shape = (self.count, self.rows, self.cols)
+        if np.isscalar(wp2):
+            g = self.conductivity_margin
+            w = np.zeros(shape, np.float64)
+            w[:, g:self.rows - g, :] = float(wp2)
+            if not float(wp2) >= 0:               # negative or NaN: let the library name it even where w is empty
+                w[...] = float(wp2)
+        else:
+            w = _host(wp2, "wp2")
+        self._shape(w, shape, "wp2")
+        per = []
+        for v, nm in ((gamma, "gamma"), (omega0, "omega0")):
+            a = np.asarray(v, dtype=np.float64)
+            if a.shape not in ((), (self.count,)):
+                raise ValueError(f"{nm} must be a scalar or have shape ({self.count},), got {a.shape}")
+            per.append(np.ascontiguousarray(np.broadcast_to(a, (self.count,))))
+        self._ck(self._lib.fdtd2d_batch_set_bloch_dispersion(self._h, w.ctypes.data, _code(w.dtype), _dptr(per[0]),
+                                                             _dptr(per[1])))
+        return self
+
+    def set_bloch_dispersion_window(self, window, wp2):
+        """set_dispersion_window for the pole of set_bloch_dispersion (E_STATE without it)."""
+        self._need_complex("set_bloch_dispersion_window")
+        w = np.ascontiguousarray([int(v) for v in window], dtype=np.int32)
+        if w.shape != (4,):
+            raise ValueError(f"window must be 4 integers (row0, col0, nrows, ncols), got {window!r}")
+        s = _host(wp2, "wp2")
+        self._shape(s, (self.count, int(w[2]), int(w[3])), "wp2")
+        self._ck(self._lib.fdtd2d_batch_set_bloch_dispersion_window(self._h, w.ctypes.data_as(C.POINTER(C.c_int)),
+                                                                    s.ctypes.data, _code(s.dtype)))
+        return self
+
+    def download_bloch_dispersion(self):
+        """Complex (Jh, Q), each (B, R, C): the state of the pole of set_bloch_dispersion, the image column (on a lattice
+        also the image row) rotated by the member's phases, as download() delivers Ez."""
+        self._need_complex("download_bloch_dispersion")
+        out = [np.empty((self.count, self.rows, self.cols), self.dtype) for _ in range(4)]
+        self._ck(self._lib.fdtd2d_batch_transfer_bloch_dispersion(self._h, *(a.ctypes.data for a in out),
+                                                                  _code(self.dtype), 0))
+        return out[0] + 1j * out[1], out[2] + 1j * out[3]
+
+    def upload_bloch_dispersion(self, Jh=None, Q=None):
+        """(B, R, C) each, real or complex, host -> device; one given as None is left as is.  The image column (on a
+        lattice also the image row) is overwritten from column 0 (row 0)."""
+        self._need_complex("upload_bloch_dispersion")
+        ptr, keep = [], []
+        for a, nm in ((Jh, "Jh"), (Q, "Q")):
+            if a is None:
+                ptr += [None, None]
+                continue
+            a = np.asarray(a)
+            self._shape(a, (self.count, self.rows, self.cols), nm)
+            keep += [np.ascontiguousarray(a.real, dtype=self.dtype), np.ascontiguousarray(a.imag, dtype=self.dtype)]
+            ptr += [keep[-2].ctypes.data, keep[-1].ctypes.data]
+        self._ck(self._lib.fdtd2d_batch_transfer_bloch_dispersion(self._h, *ptr, _code(self.dtype), 1))
+        return self
+
     def sync(self):
         self._ck(self._lib.fdtd2d_batch_sync(self._h))
         return self
@@ -1013,7 +1094,7 @@ def _waveform_amps(kind, fc, nsteps, dt):
 def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker", dt=5e-14, dx=1e-4,
                    dtype=np.float64, boundary="mur", omega=None, dft_every=1, device=0, pml_cells=40,
                    dft_window=None, window_omegas=None, probes=None, bloch_phase=None, source_weights=None,
-                   dispersion=None):
+                   dispersion=None, bloch_dispersion=None):
     """run_fdtd for B members of one shape at once: zero fields, Courant check per member, nsteps of
     H -> E -> source with t = i*dt.
 
@@ -1033,7 +1114,9 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
     boundary "lattice": every member is the unit cell of a rectangular lattice (periods R - 1 and C - 1, no layer:
     pml_cells is not read) and bloch_phase = (phi_rows, phi_cols), each a scalar or (B,), gives its two Bloch phases
     (set_lattice_phase; default zero); every returned array is complex.  A band-path sweep is one call: B copies of the
-    unit cell with the phases of the k-points along the path.
+    unit cell with the phases of the k-points along the path.  bloch_dispersion = (wp2, gamma, omega0) as
+    set_bloch_dispersion takes them: the pole of a run with complex fields (boundary "periodic" with bloch_phase, or
+    "lattice"): a metal unit cell swept over the angle of incidence or along a band path.
     """
     from .api import MU0
     eps = np.asarray(eps)
@@ -1086,6 +1169,14 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
             raise ValueError(f'dispersion needs boundary="pml" or "periodic", not {boundary!r}')
         if bloch_phase is not None:
             raise ValueError("dispersion is not available with bloch_phase")
+    if bloch_dispersion is not None:
+        if len(bloch_dispersion) != 3:
+            raise ValueError("bloch_dispersion must be (wp2, gamma, omega0)")
+        if bloch_phase is None:
+            raise ValueError('bloch_dispersion needs bloch_phase (boundary="periodic") or boundary="lattice": without a '
+                             "phase use dispersion")
+        if dispersion is not None:
+            raise ValueError("bloch_dispersion and dispersion exclude each other")
     win, wom, cells = _check_monitors(B, R, Cc, dft_window, window_omegas, probes, dft_every)
     if bloch_phase is not None:
         if win is not None and win[1] + win[3] > Cc - 1:
@@ -1111,6 +1202,8 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
         if bloch_phase is not None:
             if source_weights is not None:
                 eng.set_bloch_source(source_weights)
+        if bloch_dispersion is not None:
+            eng.set_bloch_dispersion(*bloch_dispersion)
         if omega is not None:
             eng.set_dft(omega, dft_every)
         if win is not None:

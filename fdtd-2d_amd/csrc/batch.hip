@@ -17,10 +17,14 @@
 // With a Drude-Lorentz pole (fdtd2d_batch_dispersive.h) every run takes the dispersive kernels of batch_dispersive.hip.
 // In the lattice mode (fdtd2d_batch_lattice.h: Bloch conditions on both pairs of edges) every run takes the kernels of
 // batch_lattice.hip; the mode shares the Bloch phase's host state (`bloch` is set too) and adds the row rotation.
+// With the pole of fdtd2d_batch_bloch_dispersive.h a Bloch or lattice batch takes the kernels of
+// batch_bloch_dispersive.hip; the pole shares the host state of fdtd2d_batch_dispersive.h's (`dcj` is set too) and adds
+// the imaginary parts of Jh and Q.
 #include "../../include/fdtd2d.h"
 #include "../../include/fdtd2d_batch_adjoint.h"
 #include "../../include/fdtd2d_batch_bloch.h"
 #include "../../include/fdtd2d_batch_bloch_adjoint.h"
+#include "../../include/fdtd2d_batch_bloch_dispersive.h"
 #include "../../include/fdtd2d_batch_design.h"
 #include "../../include/fdtd2d_batch_dispersive.h"
 #include "../../include/fdtd2d_batch_lattice.h"
@@ -44,6 +48,7 @@
 #include "kernels_batch_adjoint.hpp"
 #include "kernels_batch_bloch.hpp"
 #include "kernels_batch_bloch_adjoint.hpp"
+#include "kernels_batch_bloch_dispersive.hpp"
 #include "kernels_batch_design.hpp"
 #include "kernels_batch_dispersive.hpp"
 #include "kernels_batch_lattice.hpp"
@@ -80,6 +85,10 @@ struct fdtd2d_batch {
     // strengths (count x rows x cols), the dampings and the resonances as given
     void *djh = nullptr, *dq = nullptr, *dcj = nullptr, *da = nullptr, *dck = nullptr;
     std::vector<double> wp2_host, disp_gamma, disp_omega0;
+    // fdtd2d_batch_set_bloch_dispersion: the pole of a Bloch or lattice batch.  Everything above is set too (Jh and Q
+    // hold the real parts) and these hold the imaginary parts
+    bool bdisp = false;
+    void *djh_im = nullptr, *dq_im = nullptr;
     void *dsg = nullptr;                  // device scratch of the design-loop entry points
     size_t dsg_cap = 0;
     // fdtd2d_batch_set_periodic: column C-1 is the image of column 0.  The batch then always holds Ezx and the factors
@@ -264,7 +273,8 @@ int zero_fields(fdtd2d_batch *b)
     for (void *p : {b->ez[0], b->ez[1], b->hx, b->hy}) BCHK(b, hipMemsetAsync(p, 0, b->field_bytes, b->stream));
     if (b->ezx) BCHK(b, hipMemsetAsync(b->ezx, 0, b->field_bytes, b->stream));
     if (b->dcj)
-        for (void *p : {b->djh, b->dq}) BCHK(b, hipMemsetAsync(p, 0, b->field_bytes, b->stream));
+        for (void *p : {b->djh, b->dq, b->djh_im, b->dq_im})
+            if (p) BCHK(b, hipMemsetAsync(p, 0, b->field_bytes, b->stream));     // the imaginary parts: a complex pole's
     if (b->bloch)
         for (void *p : {b->ez_im, b->hx_im, b->hy_im, b->ezx_im})
             if (p) BCHK(b, hipMemsetAsync(p, 0, b->field_bytes, b->stream));     // a lattice batch has no Ezx
@@ -278,11 +288,12 @@ int zero_fields(fdtd2d_batch *b)
 // Mur / none: Ez, Hx, Hy (+ ce, ch); PML: Ez, Hx, Hy, Ezx (+ ce, ch) and the 4R + 4C factors; with a conductivity
 // cb stands in ce's place and ca is one more array; a Bloch phase: the four fields twice and cb, ch, ca, the row
 // factors alone, the source weights with the tables and the accumulators twice; a pole: the lossy PML arrays and Jh,
-// Q, cj; the lattice mode: Ez, Hx, Hy twice and cb, ch, ca, no factors
+// Q, cj; the lattice mode: Ez, Hx, Hy twice and cb, ch, ca, no factors; a Bloch or lattice batch with a pole: Jh and Q
+// twice and cj more
 int lds_arrays(const fdtd2d_batch *b)
 {
-    if (b->lattice) return 9;
-    if (b->bloch) return 11;
+    if (b->lattice) return b->bdisp ? 14 : 9;
+    if (b->bloch) return b->bdisp ? 16 : 11;
     if (b->dcj) return 10;
     if (b->periodic) return 7;
     if (b->ca) return b->ezx ? 7 : 6;
@@ -903,9 +914,78 @@ template <class T> int run_lattice(fdtd2d_batch *b, int nsteps, const double *am
     return 0;
 }
 
+// ---- Bloch and lattice runs with a pole (fdtd2d_batch_bloch_dispersive.h): the paths of run_bloch and run_lattice with
+// the kernels of batch_bloch_dispersive.hip.  The streamed H launches are those families' own: H does not see the pole.
+template <class T> int run_bloch_dispersive(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride)
+{
+    if (!b->ca || !b->ez_im || !b->rho || (b->lattice ? !b->rho_r : !b->ezx) || !b->djh || !b->dq || !b->djh_im ||
+        !b->dq_im || !b->dcj || !b->da || !b->dck)
+        return bfail(b, FDTD2D_E_STATE, "dispersive Bloch batch without its arrays");
+    const fdtd::BatchBlochDispersiveKernels &K = fdtd::batch_bloch_dispersive_kernels<T>();
+    fdtd::BatchPml<T> p = pml_view<T>(b);
+    fdtd::BatchMon m = mon_view(b);
+    fdtd::BatchBloch<T> bl = bloch_view<T>(b, false);
+    fdtd::BatchLattice<T> la{(T *)b->ez_im, (T *)b->hx_im, (T *)b->hy_im, (const T *)b->rho_r, (const T *)b->rho,
+                             b->bloch_w, b->have_src ? b->run_amps_im : nullptr, b->win_acc_im, b->probe_trace_im};
+    fdtd::BatchBlochDisp<T> d{(T *)b->djh, (T *)b->dq, (T *)b->djh_im, (T *)b->dq_im,
+                              (const T *)b->dcj, (const T *)b->da, (const T *)b->dck};
+    b->run_conj = false;
+    const T *ca = (const T *)b->ca;
+    if (use_resident(b)) {
+        const int cells = b->rows * b->cols, threads = resident_threads(cells);
+        const int per_thread = (cells + threads - 1) / threads;
+        if (per_thread > 4)
+            return bfail(b, FDTD2D_E_STATE, "%d cells per thread exceed the dispersive Bloch resident kernels' 4", per_thread);
+        const void *kern = b->lattice ? K.resident_lattice : K.resident_bloch;
+        const size_t lds = lds_bytes(b);
+        BCHK(b, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        int per_cu = 0, cus = 0;
+        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds));
+        BCHK(b, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
+        if (per_cu < 1)
+            return bfail(b, FDTD2D_E_STATE, "dispersive Bloch resident kernel does not fit a CU (%zu B of LDS)", lds);
+        const long long round = (long long)per_cu * cus;
+        const int blocks = (int)(b->count < round ? b->count : round);
+        const int chunk = b->steps_per_launch > 0 ? b->steps_per_launch : nsteps;
+        for (int n = 0; n < nsteps; n += chunk) {
+            int n0 = n, nt = nsteps - n < chunk ? nsteps - n : chunk;
+            long long step_base = b->step;
+            fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+            v.ce = (const T *)b->cb;
+            void *args_bloch[] = {&v, &p, &m, &bl, &d, &ca, &n0, &nt, &step_base};
+            void *args_lattice[] = {&v, &m, &la, &d, &ca, &n0, &nt, &step_base};
+            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads), b->lattice ? args_lattice : args_bloch, lds);
+            if (rc) return rc;
+            b->launches++;
+            b->step += nt;
+        }
+        return 0;
+    }
+    const void *kh = b->lattice ? fdtd::batch_lattice_kernels<T>().h : fdtd::batch_bloch_kernels<T>().h;
+    const void *ke = b->lattice ? K.e_lattice : K.e_bloch;
+    const int cells = b->rows * b->cols;
+    const dim3 grid((cells + 255) / 256, b->count < 65535 ? b->count : 65535);
+    for (int n = 0; n < nsteps; ++n) {
+        fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+        v.ce = (const T *)b->cb;
+        long long step = b->step + 1;
+        int rc;
+        void *h_bloch[] = {&v, &p, &m, &bl, &step};
+        void *e_bloch[] = {&v, &p, &m, &bl, &d, &ca, &n, &step};
+        void *h_lattice[] = {&v, &m, &la, &step};
+        void *e_lattice[] = {&v, &m, &la, &d, &ca, &n, &step};
+        if ((rc = launch_ptr(b, kh, grid, dim3(256), b->lattice ? h_lattice : h_bloch, 0))) return rc;
+        if ((rc = launch_ptr(b, ke, grid, dim3(256), b->lattice ? e_lattice : e_bloch, 0))) return rc;
+        b->launches += 2;
+        b->step++;
+    }
+    return 0;
+}
+
 template <class T>
 int run_impl(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts = nullptr)
 {
+    if (b->bdisp) return run_bloch_dispersive<T>(b, nsteps, amps, amp_stride);
     if (b->lattice) return run_lattice<T>(b, nsteps, amps, amp_stride);
     if (b->bloch) return run_bloch<T>(b, nsteps, amps, amp_stride);
     if (b->dcj) return run_dispersive<T>(b, nsteps, amps, amp_stride, pts);
@@ -1244,23 +1324,38 @@ int disp_reform(fdtd2d_batch *b, int r0, int c0, int nr, int nc)
 
 void disp_release(fdtd2d_batch *b)
 {
-    for (void **p : {&b->djh, &b->dq, &b->dcj, &b->da, &b->dck}) release(p);
+    for (void **p : {&b->djh, &b->dq, &b->dcj, &b->da, &b->dck, &b->djh_im, &b->dq_im}) release(p);
+    b->bdisp = false;
     b->wp2_host.clear();
     b->disp_gamma.clear();
     b->disp_omega0.clear();
 }
 
-// sets the pole (window == nullptr: wp2 whole with gamma and omega0) or patches its strengths
-int set_disp(fdtd2d_batch *b, const int *window, const void *wp2, int dtype, const double *gamma, const double *omega0)
+// the refusal of a call of fdtd2d_batch_dispersive.h while the pole of fdtd2d_batch_bloch_dispersive.h is set
+int refuse_bloch_pole(fdtd2d_batch *b, const char *what, const char *use)
 {
-    if (window && !b->dcj) return bfail(b, FDTD2D_E_STATE, "no pole is set: call fdtd2d_batch_set_dispersion first");
+    return bfail(b, FDTD2D_E_STATE, "%s is not available on a batch with complex fields (a Bloch phase or the lattice "
+                 "mode): use %s", what, use);
+}
+
+// sets the pole (window == nullptr: wp2 whole with gamma and omega0) or patches its strengths; complex: the pole of
+// fdtd2d_batch_bloch_dispersive.h, whose entry point has made its own refusals
+int set_disp(fdtd2d_batch *b, const int *window, const void *wp2, int dtype, const double *gamma, const double *omega0,
+             bool complex = false)
+{
+    if (b->bdisp && !complex)
+        return refuse_bloch_pole(b, window ? "fdtd2d_batch_set_dispersion_window" : "fdtd2d_batch_set_dispersion",
+                                 window ? "fdtd2d_batch_set_bloch_dispersion_window" : "fdtd2d_batch_set_bloch_dispersion");
+    if (window && !b->dcj)
+        return bfail(b, FDTD2D_E_STATE, "no pole is set: call %s first",
+                     complex ? "fdtd2d_batch_set_bloch_dispersion" : "fdtd2d_batch_set_dispersion");
     if (b->boundary != FDTD2D_BOUNDARY_NONE)
         return bfail(b, FDTD2D_E_STATE, "a dispersive pole needs a FDTD2D_BOUNDARY_NONE batch with a PML layer or periodic "
                      "columns, not the Mur frame");
     if (!b->ezx && !b->periodic)
         return bfail(b, FDTD2D_E_STATE, "a dispersive pole needs a PML layer (fdtd2d_batch_set_pml) or periodic columns: a "
                      "plain box has no dispersive kernels");
-    if (b->bloch) return refuse_bloch(b, "a dispersive pole");
+    if (b->bloch && !complex) return refuse_bloch(b, "a dispersive pole");
     if (!b->have_mat) return bfail(b, FDTD2D_E_STATE, "materials not set: call fdtd2d_batch_set_materials first");
     if (!wp2) return bfail(b, FDTD2D_E_ARG, "wp2 must not be NULL");
     if (dtype != FDTD2D_F32 && dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad dtype");
@@ -1308,7 +1403,8 @@ int set_disp(fdtd2d_batch *b, const int *window, const void *wp2, int dtype, con
     const bool fresh = !b->dcj;
     if (fresh) {
         const size_t mb = (size_t)b->count * b->esz;
-        for (void **p : {&b->djh, &b->dq, &b->dcj, &b->da, &b->dck}) {
+        for (void **p : {&b->djh, &b->dq, &b->dcj, &b->da, &b->dck, &b->djh_im, &b->dq_im}) {
+            if (!complex && (p == &b->djh_im || p == &b->dq_im)) continue;
             const size_t bytes = (p == &b->da || p == &b->dck) ? mb : b->field_bytes;
             hipError_t e = hipSuccess;
             if ((rc = alloc(b, p, bytes)) || (e = hipMemsetAsync(*p, 0, bytes, b->stream)) != hipSuccess) {
@@ -1318,6 +1414,7 @@ int set_disp(fdtd2d_batch *b, const int *window, const void *wp2, int dtype, con
             }
         }
         b->wp2_host.assign((size_t)b->count * per, 0.0);
+        b->bdisp = complex;
     }
     for (int m = 0; m < b->count; ++m)
         for (size_t t = 0; t < W; ++t)
@@ -1588,7 +1685,7 @@ void fdtd2d_batch_destroy(fdtd2d_batch_t *b)
                      &b->ez_im, &b->hx_im, &b->hy_im, &b->ezx_im, &b->rho, (void **)&b->bloch_w, (void **)&b->amps_im,
                      (void **)&b->win_acc_im, (void **)&b->probe_trace_im, &b->rho_conj, &b->rho_r,
                      (void **)&b->win_held_im,
-                     &b->djh, &b->dq, &b->dcj, &b->da, &b->dck})
+                     &b->djh, &b->dq, &b->dcj, &b->da, &b->dck, &b->djh_im, &b->dq_im})
         release(p);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -2509,6 +2606,7 @@ int fdtd2d_batch_set_dispersion(fdtd2d_batch_t *b, const void *wp2, int dtype, c
 {
     if (!b) return FDTD2D_E_ARG;
     if (!wp2 && !gamma && !omega0) {        // remove the pole: the other kernels again
+        if (b->bdisp) return refuse_bloch_pole(b, "fdtd2d_batch_set_dispersion", "fdtd2d_batch_set_bloch_dispersion");
         if (!b->dcj) return 0;
         int rc = use_device(b);
         if (rc) return rc;
@@ -2537,6 +2635,8 @@ int fdtd2d_batch_set_dispersion_window(fdtd2d_batch_t *b, const int window[4], c
 int fdtd2d_batch_transfer_dispersion(fdtd2d_batch_t *b, void *jh, void *q, int host_dtype, int to_device)
 {
     if (!b) return FDTD2D_E_ARG;
+    if (b->bdisp)
+        return refuse_bloch_pole(b, "fdtd2d_batch_transfer_dispersion", "fdtd2d_batch_transfer_bloch_dispersion");
     if (!b->dcj) return bfail(b, FDTD2D_E_STATE, "no pole is set: call fdtd2d_batch_set_dispersion first");
     if (host_dtype != FDTD2D_F32 && host_dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad host_dtype");
     int rc = use_device(b);
@@ -2552,6 +2652,65 @@ int fdtd2d_batch_transfer_dispersion(fdtd2d_batch_t *b, void *jh, void *q, int h
     return 0;
 }
 
+// ---- fdtd2d_batch_bloch_dispersive.h ---------------------------------------------------------------------------
+
+int fdtd2d_batch_set_bloch_dispersion(fdtd2d_batch_t *b, const void *wp2, int dtype, const double *gamma,
+                                      const double *omega0)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!b->bloch)
+        return bfail(b, FDTD2D_E_STATE, "fdtd2d_batch_set_bloch_dispersion needs a Bloch phase or the lattice mode: a batch "
+                     "with real fields takes fdtd2d_batch_set_dispersion");
+    if (!wp2 && !gamma && !omega0) {        // remove the pole: the Bloch or lattice kernels again
+        if (!b->bdisp) return 0;
+        int rc = use_device(b);
+        if (rc) return rc;
+        BCHK(b, hipStreamSynchronize(b->stream));
+        disp_release(b);
+        return 0;
+    }
+    if (!wp2 || !gamma || !omega0)
+        return bfail(b, FDTD2D_E_ARG, "wp2, gamma and omega0 must all be given (or all NULL)");
+    if (b->npts)
+        return bfail(b, FDTD2D_E_STATE, "a dispersive pole is not available beside Bloch point sources (remove them: the "
+                     "adjoint of a dispersive medium is not implemented)");
+    if (b->win_held)
+        return bfail(b, FDTD2D_E_STATE, "a dispersive pole is not available beside the held window (set the window again: "
+                     "the adjoint of a dispersive medium is not implemented)");
+    return set_disp(b, nullptr, wp2, dtype, gamma, omega0, true);
+}
+
+int fdtd2d_batch_set_bloch_dispersion_window(fdtd2d_batch_t *b, const int window[4], const void *wp2, int dtype)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!window) return bfail(b, FDTD2D_E_ARG, "window must not be NULL");
+    if (!b->bdisp) return bfail(b, FDTD2D_E_STATE, "no pole is set: call fdtd2d_batch_set_bloch_dispersion first");
+    return set_disp(b, window, wp2, dtype, nullptr, nullptr, true);
+}
+
+int fdtd2d_batch_transfer_bloch_dispersion(fdtd2d_batch_t *b, void *jh_re, void *jh_im, void *q_re, void *q_im,
+                                           int host_dtype, int to_device)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!b->bdisp) return bfail(b, FDTD2D_E_STATE, "no pole is set: call fdtd2d_batch_set_bloch_dispersion first");
+    if (host_dtype != FDTD2D_F32 && host_dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad host_dtype");
+    int rc = use_device(b);
+    if (rc) return rc;
+    void *re[2] = {b->djh, b->dq}, *im[2] = {b->djh_im, b->dq_im}, *host[2][2] = {{jh_re, jh_im}, {q_re, q_im}};
+    for (int k = 0; k < 2; ++k)
+        for (int part = 0; part < 2; ++part) {
+            void *h = host[k][part], *dev = part ? im[k] : re[k];
+            if (!h) continue;
+            if (to_device) {
+                if ((rc = copy_in(b, dev, h, host_dtype, b->rows, b->cols)) || (rc = copy_image(b, dev))) return rc;
+                if (b->lattice && (rc = copy_row_image(b, dev))) return rc;
+            } else if ((rc = b->lattice ? copy_out_lattice(b, re[k], im[k], h, host_dtype, part)
+                                        : copy_out_bloch(b, re[k], im[k], h, host_dtype, part)))
+                return rc;
+        }
+    return 0;
+}
+
 // ---- fdtd2d_batch_periodic.h -----------------------------------------------------------------------------------
 
 int fdtd2d_batch_set_periodic(fdtd2d_batch_t *b, int on)
@@ -2564,6 +2723,8 @@ int fdtd2d_batch_set_periodic(fdtd2d_batch_t *b, int on)
     int rc = use_device(b);
     if (rc) return rc;
     BCHK(b, hipStreamSynchronize(b->stream));
+    if (!on && b->bdisp)
+        return refuse_dispersive(b, "turning periodic columns (and with them the phase or the lattice mode) off");
     if (!on && b->dcj) {                    // the refusals of a dispersive batch, before anything changes
         if (b->pml_L == 0)
             return refuse_dispersive(b, "turning periodic columns off without a layer (a plain box has no dispersive "
@@ -2641,8 +2802,9 @@ int fdtd2d_batch_set_bloch(fdtd2d_batch_t *b, const double *cos_phi, const doubl
     int rc = use_device(b);
     if (rc) return rc;
     if (b->lattice) return refuse_bloch(b, "fdtd2d_batch_set_bloch (use fdtd2d_batch_set_lattice)");
+    if (!cos_phi && b->bdisp) return refuse_dispersive(b, "turning the Bloch phase off");
     if (!cos_phi) return b->bloch ? bloch_off(b) : 0;
-    if (b->dcj) return refuse_dispersive(b, "a Bloch phase");
+    if (b->dcj && !b->bdisp) return refuse_dispersive(b, "a Bloch phase");
     if (!b->periodic)
         return bfail(b, FDTD2D_E_STATE, "a Bloch phase needs periodic columns: call fdtd2d_batch_set_periodic first");
     for (int m = 0; m < b->count; ++m)
@@ -2830,12 +2992,13 @@ int fdtd2d_batch_set_lattice(fdtd2d_batch_t *b, const double *cos_r, const doubl
     if (rc) return rc;
     if (!given) {
         if (!b->lattice) return 0;
+        if (b->bdisp) return refuse_dispersive(b, "turning the lattice mode off");
         const long long t = lattice_sigma_outside(b);
         if (t >= 0) return refuse_lattice_off(b, t);
         return bloch_off(b);
     }
     if (b->bloch && !b->lattice) return refuse_bloch(b, "the lattice mode (turn the phase of fdtd2d_batch_set_bloch off)");
-    if (b->dcj) return refuse_dispersive(b, "the lattice mode");
+    if (b->dcj && !b->bdisp) return refuse_dispersive(b, "the lattice mode");
     if (!b->periodic)
         return bfail(b, FDTD2D_E_STATE, "the lattice mode needs periodic columns: call fdtd2d_batch_set_periodic first");
     if (!b->have_mat) return bfail(b, FDTD2D_E_STATE, "materials not set: call fdtd2d_batch_set_materials first");
@@ -2928,6 +3091,7 @@ int fdtd2d_batch_set_bloch_point_sources(fdtd2d_batch_t *b, int ncell, const int
     if (!b) return FDTD2D_E_ARG;
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
     if (ncell > 0 && b->lattice) return refuse_bloch(b, "a point source");
+    if (ncell > 0 && b->bdisp) return refuse_dispersive(b, "a point source (the adjoint of a dispersive medium)");
     return batch_set_points(b, ncell, cells, nchan, weights);     // a periodic batch: column C-1 is refused there
 }
 
@@ -2937,6 +3101,7 @@ int fdtd2d_batch_run_bloch_channels(fdtd2d_batch_t *b, int nsteps, const double 
     if (!b) return FDTD2D_E_ARG;
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
     if (b->lattice) return refuse_bloch(b, "a run with channels");
+    if (b->bdisp) return refuse_dispersive(b, "a run with channels (the adjoint of a dispersive medium)");
     if (nsteps < 0) return bfail(b, FDTD2D_E_ARG, "nsteps < 0");
     if (!chan) return bfail(b, FDTD2D_E_ARG, "chan must not be NULL");
     if (amps_im && !amps_re) return bfail(b, FDTD2D_E_ARG, "amps_im needs amps_re (zeros for a purely imaginary source)");
@@ -2982,6 +3147,7 @@ int fdtd2d_batch_hold_bloch_window(fdtd2d_batch_t *b)
     if (!b) return FDTD2D_E_ARG;
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
     if (b->lattice) return refuse_bloch(b, "the held window");
+    if (b->bdisp) return refuse_dispersive(b, "the held window (the adjoint of a dispersive medium)");
     if (!b->win_nf || !b->win_acc_im) return bfail(b, FDTD2D_E_STATE, "no window DFT is set");
     int rc = use_device(b);
     if (rc) return rc;
@@ -3000,6 +3166,7 @@ int fdtd2d_batch_bloch_window_product(fdtd2d_batch_t *b, const double *coef_re, 
     if (!coef_re || !coef_im || !out) return bfail(b, FDTD2D_E_ARG, "coef_re, coef_im and out must not be NULL");
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
     if (b->lattice) return refuse_bloch(b, "the window product");
+    if (b->bdisp) return refuse_dispersive(b, "the window product (the adjoint of a dispersive medium)");
     if (!b->win_nf || !b->win_acc_im) return bfail(b, FDTD2D_E_STATE, "no window DFT is set");
     if (!b->win_held || !b->win_held_im)
         return bfail(b, FDTD2D_E_STATE, "no held window: call fdtd2d_batch_hold_bloch_window first");

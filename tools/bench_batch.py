@@ -77,9 +77,17 @@ array eps with random binary permittivity, a ricker line source per member):
                               timed alternately in one process: lattice_ms, bloch_ms, lattice_over_bloch, both paths and
                               LDS sizes.  The lattice kernel carries 9 arrays against 11 and has no layer branch, so
                               the number to beat is 1.  Default: 1024 members of 33 x 33, 1000 steps.
+  --bloch-dispersive          instead: the Drude-Lorentz pole of complex batches (BatchEngine.set_bloch_dispersion: a Drude
+                              block, wp = 2 pi 70 GHz and gamma = 1e11, on the middle third of every member) against the
+                              same members without it, timed alternately in one process; two lines: a lattice batch
+                              (the k-path sweep of --lattice) and a Bloch batch with a --pml-cells layer (the phase sweep
+                              of --bloch): dispersive_ms, plain_ms, dispersive_over_plain, both paths, the LDS bytes per
+                              workgroup and the workgroups per CU they admit (160 KiB per CU): 14 arrays against 9 and
+                              16 against 11 may cost a workgroup per CU.  Default: 1024 members of 33 x 33, 1000 steps.
 Usage: python tools/bench_batch.py [--count 1024 --rows 60 --cols 60 --steps 1000] [--reps 5] [--loop-members 16]
                                    [--boundary {mur,pml} --pml-cells 10] [--monitors] [--adjoint] [--lossy]
                                    [--periodic] [--bloch] [--bloch-adjoint] [--dispersive] [--lattice]
+                                   [--bloch-dispersive]
 """
 import argparse
 import json
@@ -502,6 +510,62 @@ def bench_lattice(count, rows, cols, steps, dtype, reps):
             "lattice_mcell_steps_per_s": round(count * rows * cols * steps / (med_l * 1e-3) / 1e6, 1)}
 
 
+def bench_bloch_dispersive(count, rows, cols, steps, dtype, reps, pml_cells, lattice):
+    eps, rects, amps = members(count, rows, cols, steps)
+    c00 = courant00(eps, dtype)
+    rng = np.random.default_rng(1)
+    g = 0 if lattice else max(6, pml_cells)
+    sigma = np.zeros((count, rows, cols))
+    sigma[:, g:rows - g, :] = 20.0 * rng.random((count, rows - 2 * g, cols))
+    wp2 = np.zeros((count, rows, cols))
+    wp2[:, rows // 3:2 * rows // 3, cols // 3:2 * cols // 3] = (2 * np.pi * 70e9) ** 2
+    assert not wp2[:, :g].any() and not wp2[:, rows - g:].any(), "the block must keep clear of the layer"
+    phi_r, phi_c = k_path(count)
+
+    def batch(pole):
+        b = fd.BatchEngine(count, rows, cols, DT, DX, dtype=dtype, boundary="lattice" if lattice else "periodic")
+        b.set_materials(eps.astype(dtype), fd.MU0).set_sources(rects)
+        if lattice:
+            b.set_lattice_phase(phi_r, phi_c)
+        else:
+            b.set_pml(pml_cells, courant00=c00).set_bloch_phase(np.linspace(0.0, np.pi, count))
+        b.set_conductivity(sigma).set_bloch_source("ramp")
+        if pole:
+            b.set_bloch_dispersion(wp2, 1e11, 0.0)
+        b.run(steps, amps).sync()                      # warm-up: code objects, clocks
+        return b
+
+    def timed(b):
+        b.reset().sync()
+        t0 = time.perf_counter()
+        b.run(steps, amps).sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    with batch(False) as pla, batch(True) as dis:
+        assert dis.dispersive and not pla.dispersive and dis.lattice == pla.lattice == lattice
+        l0 = dis.launches
+        dis.reset().run(steps, amps).sync()
+        launches = dis.launches - l0
+        pla_ms, dis_ms = [], []
+        for _ in range(reps):
+            pla_ms.append(timed(pla))
+            dis_ms.append(timed(dis))
+        paths = ["resident" if b.resident else "streamed" for b in (pla, dis)]
+        lds = [b.lds_bytes for b in (pla, dis)]
+    med_p, med_d = float(np.median(pla_ms)), float(np.median(dis_ms))
+    return {"family": "lattice" if lattice else "bloch", "count": count, "rows": rows, "cols": cols, "steps": steps,
+            "dtype": np.dtype(dtype).name, "materials": "arrays", "pml_cells": 0 if lattice else pml_cells,
+            "sweep": "Gamma-X-M-Gamma" if lattice else "0..pi", "reps": reps, "arithmetic": fd.ARITHMETIC,
+            "plain_path": paths[0], "dispersive_path": paths[1], "plain_lds_bytes_per_workgroup": lds[0],
+            "dispersive_lds_bytes_per_workgroup": lds[1], "plain_workgroups_per_cu": 163840 // lds[0],
+            "dispersive_workgroups_per_cu": 163840 // lds[1],
+            "plain_ms": round(med_p, 4), "plain_ms_min": round(min(pla_ms), 4), "plain_ms_all": [round(v, 4) for v in pla_ms],
+            "dispersive_ms": round(med_d, 4), "dispersive_ms_min": round(min(dis_ms), 4),
+            "dispersive_ms_all": [round(v, 4) for v in dis_ms],
+            "dispersive_over_plain": round(med_d / med_p, 3), "launches_per_run": launches,
+            "dispersive_mcell_steps_per_s": round(count * rows * cols * steps / (med_d * 1e-3) / 1e6, 1)}
+
+
 def bench_adjoint(count, rows, cols, steps, dtype, reps, pml_cells):
     from fdtd2d_amd.adjoint import channel_system, gradient_coefficients
     dt = 2e-13                                   # the Gaussian envelope of the channels (t0 = 4.5 / fc) ends by step 1200
@@ -742,7 +806,14 @@ def main():
     ap.add_argument("--bloch-adjoint", action="store_true", help="time the adjoint gradient of a Bloch batch")
     ap.add_argument("--dispersive", action="store_true", help="time the dispersive kernels against the lossy PML ones")
     ap.add_argument("--lattice", action="store_true", help="time a lattice batch against the Bloch batch without a layer")
+    ap.add_argument("--bloch-dispersive", action="store_true",
+                    help="time the pole of a lattice and of a Bloch batch against the same batches without it")
     a = ap.parse_args()
+    if a.bloch_dispersive:
+        for lattice in (True, False):
+            print(json.dumps(bench_bloch_dispersive(a.count or 1024, a.rows or 33, a.cols or a.rows or 33, a.steps or 1000,
+                                                    np.dtype(a.dtype), a.reps, a.pml_cells, lattice)), flush=True)
+        return
     if a.lattice:
         print(json.dumps(bench_lattice(a.count or 1024, a.rows or 33, a.cols or a.rows or 33, a.steps or 1000,
                                        np.dtype(a.dtype), a.reps)), flush=True)
