@@ -810,9 +810,15 @@ int fdtd2d_transfer_ezx(fdtd2d_t *h, void *host, int host_dtype, int to_device)
     int rc = use_device(h);
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (to_device) h->aw.invalidate();
-    return to_device ? copy_in(h, h->ezx(), host, host_dtype, h->halo, h->nrows, h->cols)
-                     : copy_out(h, h->ezx(), host, host_dtype, h->halo, h->nrows, h->cols);
+    if (!to_device) return copy_out(h, h->ezx(), host, host_dtype, h->halo, h->nrows, h->cols);
+    h->aw.invalidate();
+    // Into BOTH buffers: a pass writes Ezx only where its layer tasks run -- the plain tasks (k_bulk_split beside
+    // k_bulk_split_pml, the plain waves of k_pass_pml) carry no Ezx and leave the pass's output buffer as it is.  Outside
+    // the layer no update ever changes Ezx, so a value given there must already stand in the buffer the next pass
+    // makes current (fdtd2d_reset zeroes both for the same reason).
+    for (int b = 0; b < 2; ++b)
+        if ((rc = copy_in(h, h->ezxb[b], host, host_dtype, h->halo, h->nrows, h->cols))) return rc;
+    return 0;
 }
 
 double fdtd2d_courant(const fdtd2d_t *h)

@@ -314,8 +314,11 @@ __global__ __launch_bounds__(64, 2) void k_pass_pml(const PassParams<T> p, const
     if (ra >= rb) return;
     const int x0 = strip_x0<T, NT>(p, strip);
     const int L = q.f.L;
-    // does the wave's cone (rows [ra-2NT, rb+NT), columns [x0, x0+SW)) touch the layer or the edge?
-    const bool layer = x0 < L + 1 || x0 + SW > p.g.C - 1 - L || ra - 2 * NT < L + 1 ||
+    // does the wave's cone (rows [ra-2NT, rb+NT), columns [x0, x0+SW)) touch the layer or the edge?  (Columns: a layer
+    // thinner than 4 cells counts as 4 -- with the source in its cone a plain wave runs stream_body's general form,
+    // which applies the Mur frame's rule to the columns < 5 and >= C - 5 it holds.)
+    const int Lc = max(L, 4);
+    const bool layer = x0 < Lc + 1 || x0 + SW > p.g.C - 1 - Lc || ra - 2 * NT < L + 1 ||
                        rb + NT > p.g.R - 1 - L;
     const bool src = p.src_row1 > ra - 2 * NT && p.src_row < rb + NT && p.src_col1 > x0 &&
                      p.src_col < x0 + SW;

@@ -15,10 +15,13 @@ template <bool CE_ARR> static int launch_pml_split(fdtd2d *h, fdtd::PassParams<f
         if (s == ns - 1) x = std::min(x, (C - SW + 3) & ~3);
         return x;
     };
-    // strips whose columns reach into the layer (or the grid edge) at either end
+    // strips whose columns reach into the layer (or the grid edge) at either end.  A layer thinner than 4 cells counts
+    // as 4 here: the plain kernel takes its general body for a strip that holds a column < 5 or >= C - 5 and applies
+    // the Mur frame's rule there, so such a strip must not be one of its own.
+    const int Lc = std::max(L, 4);
     int n_left = 0, n_right = 0;
-    while (n_left < ns && x0_of(n_left) < L + 1) ++n_left;
-    while (n_right < ns - n_left && x0_of(ns - 1 - n_right) + SW > C - 1 - L) ++n_right;
+    while (n_left < ns && x0_of(n_left) < Lc + 1) ++n_left;
+    while (n_right < ns - n_left && x0_of(ns - 1 - n_right) + SW > C - 1 - Lc) ++n_right;
     const int inner = ns - n_left - n_right;
     // Rows the plain kernel must stay clear of: a band [ra, rb) computes level t >= 1 on the rows >= ra - NT (level 1
     // reaches furthest up; rows above that only enter as level-0 data), and every row it COMPUTES must be outside the row

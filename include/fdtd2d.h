@@ -147,7 +147,10 @@ int fdtd2d_set_materials_uniform(fdtd2d_t *h, double eps, double mu);
  * outside the layer; see oracle/pml_numpy.py / fdtd2d_amd.pml_profiles), in the engine's
  * dtype, for the GLOBAL grid (slabs index them by global row); layer_cells = L, the depth of
  * the layer: only cells within L of an edge use the split update, the rest the reference's
- * (main.py:21-27).  Ez is stored as total field plus its x-part Ezx (zero outside the layer); fdtd2d_transfer_ezx moves the owned rows of Ezx (rows x cols). */
+ * (main.py:21-27).  Ez is stored as total field plus its x-part Ezx (zero outside the layer in
+ * every state reached from rest); fdtd2d_transfer_ezx moves the owned rows of Ezx (rows x cols).
+ * An upload may hold anything outside the layer: no update reads or changes Ezx there, and every
+ * path (single steps, 8- and 16-step passes) gives the uploaded value back. */
 int fdtd2d_set_pml(fdtd2d_t *h, const void *row_factors, const void *col_factors, int host_dtype,
                    int layer_cells);
 int fdtd2d_transfer_ezx(fdtd2d_t *h, void *host, int host_dtype, int to_device);
