@@ -57,6 +57,9 @@ BATCH_INFO_BLOCH = 16
 BATCH_INFO_BLOCH_POINT_SOURCES, BATCH_INFO_HELD_BLOCH_WINDOW = 17, 18
 # include/fdtd2d_batch_dispersive.h
 BATCH_INFO_DISPERSIVE = 19
+# include/fdtd2d_batch_dispersive_adjoint.h
+BATCH_INFO_HELD_DISPERSIVE_WINDOW = 20
+BATCH_MAX_PRODUCT_SETS = 3
 
 _vp, _i, _d, _ll = C.c_void_p, C.c_int, C.c_double, C.c_longlong
 
@@ -219,6 +222,14 @@ BATCH_BLOCH_DISPERSIVE_SIGNATURES = {
     "fdtd2d_batch_transfer_bloch_dispersion": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i]),
 }
 
+# every symbol include/fdtd2d_batch_dispersive_adjoint.h declares (the held window of a batch with a pole and its product
+# for up to three coefficient sets: what the adjoint of a dispersive batch needs)
+BATCH_DISPERSIVE_ADJOINT_SIGNATURES = {
+    "fdtd2d_batch_hold_dispersive_window": (_i, [_vp]),
+    "fdtd2d_batch_dispersive_window_product": (_i, [_vp, _i, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d),
+                                                    C.POINTER(_d)]),
+}
+
 # transport callback of fdtd2d_slab_attach
 EXCHANGE_FN = C.CFUNCTYPE(_i, _vp, _vp, _vp, _vp, _vp, _ll, _vp)
 
@@ -271,7 +282,8 @@ def load():
                                    **BATCH_LOSSY_SIGNATURES, **BATCH_PERIODIC_SIGNATURES,
                                    **BATCH_BLOCH_SIGNATURES, **BATCH_BLOCH_ADJOINT_SIGNATURES,
                                    **BATCH_DISPERSIVE_SIGNATURES, **BATCH_LATTICE_SIGNATURES,
-                                   **BATCH_BLOCH_DISPERSIVE_SIGNATURES}.items():
+                                   **BATCH_BLOCH_DISPERSIVE_SIGNATURES,
+                                   **BATCH_DISPERSIVE_ADJOINT_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

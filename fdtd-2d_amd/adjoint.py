@@ -33,6 +33,18 @@ So the adjoint field is a Bloch run of the same member with the rotation conjuga
 True)``) and sources at the probe cells, and the gradients are the formulas above with the plain, unconjugated product of
 the two complex window DFTs.  The injected series stay real (added to the real part of Ez alone, the seam carries them into
 the imaginary part), so the channel systems and their real weights are unchanged.
+
+With a Drude-Lorentz pole per member (``BatchEngine.set_dispersion``; ``batch_dispersive_gradient``,
+``DispersiveAdjointSession``) and the member's a, bq, ck of include/fdtd2d_batch_dispersive.h (cj = dx bq EPS0 wp2) the
+operator gains the diagonal term cj (z - 1)^2 / ((z - a)(z - 1) + ck z).  It stays symmetric, so the adjoint field is an
+ordinary dispersive run of the same member with sources at the probe cells, dJ/d eps and dJ/d sigma keep their formulas,
+and
+
+    dJ/d wp2[i] = dx * bq * EPS0 * sum_k Re( -(z_k - 1) / ((z_k - a)(z_k - 1) + ck z_k) * E_k[i] * Eadj_k[i] )
+
+from the same two windows.  The held window and the product are calls of their own (``hold_dispersive_window``,
+``dispersive_window_product``: up to three coefficient sets in one pass); the helpers above and ``AdjointSession`` keep
+refusing an engine with a pole.
 """
 from __future__ import annotations
 
@@ -90,10 +102,12 @@ def sigma_coefficients(omegas, dt):
     return -(z + 1) / z
 
 
-def _check_sigma(p, sigma, window=None):
+def _check_sigma(p, sigma, window=None, name="sigma", may="conduct",
+                 probe_why="would be conj(g) / (D + G), which is not implemented"):
     """The host checks of a conductivity (ValueError naming the first offending member): (B, R, C), or (B, nrows, ncols)
     for window = (row0, col0, nrows, ncols); >= 0 and finite; zero in the boundary frame or the PML layer and at every
-    probe cell.  Returns it as a float64 array."""
+    probe cell.  Returns it as a float64 array.  name, may, probe_why: the wording for another quantity under the same
+    rules (_check_wp2)."""
     r0, c0, nr, nc = (0, 0, p.R, p.Cc) if window is None else window
     s = np.asarray(sigma, dtype=np.float64)
     if s.ndim == 0 and window is None:
@@ -106,10 +120,10 @@ def _check_sigma(p, sigma, window=None):
             full[...] = s
         s = full
     if s.shape != (p.B, nr, nc):
-        raise ValueError(f"sigma must have shape ({p.B}, {nr}, {nc}), got {s.shape}")
+        raise ValueError(f"{name} must have shape ({p.B}, {nr}, {nc}), got {s.shape}")
     bad = ~(np.isfinite(s) & (s >= 0))
     if bad.any():
-        raise ValueError(f"member {int(np.nonzero(bad.reshape(p.B, -1).any(axis=1))[0][0])}: sigma must be >= 0 and "
+        raise ValueError(f"member {int(np.nonzero(bad.reshape(p.B, -1).any(axis=1))[0][0])}: {name} must be >= 0 and "
                          f"finite")
     rows, cols = np.arange(r0, r0 + nr), np.arange(c0, c0 + nc)
     if p.periodic:       # no column margin; the image column C-1 is accepted and never read
@@ -121,14 +135,14 @@ def _check_sigma(p, sigma, window=None):
     if out.any():
         b = int(np.nonzero(out.reshape(p.B, -1).any(axis=1))[0][0])
         i, j = (int(v[0]) for v in np.nonzero(out[b]))
-        raise ValueError(f"member {b}: sigma is non-zero at cell ({r0 + i}, {c0 + j}), within {p.margin} cells of an "
-                         f"edge ({p.margin_why}): only cells that take the plain update may conduct")
+        raise ValueError(f"member {b}: {name} is non-zero at cell ({r0 + i}, {c0 + j}), within {p.margin} cells of an "
+                         f"edge ({p.margin_why}): only cells that take the plain update may {may}")
     for b in range(p.B):
         for r, c in p.cells[b]:
             r, c = int(r) - r0, int(c) - c0
             if 0 <= r < nr and 0 <= c < nc and s[b, r, c] != 0:
-                raise ValueError(f"member {b}: sigma is non-zero at the probe cell ({r + r0}, {c + c0}); the adjoint "
-                                 f"injection there would be conj(g) / (D + G), which is not implemented")
+                raise ValueError(f"member {b}: {name} is non-zero at the probe cell ({r + r0}, {c + c0}); the adjoint "
+                                 f"injection there {probe_why}")
     return s
 
 
@@ -785,4 +799,236 @@ class BlochAdjointSession(AdjointSession):
             self._eng.set_bloch_source(self._weights)
         self._phi = ph
         self._ran = False                       # the windows on the device belong to the old phases
+        return self
+
+
+# ---- dispersive batches: one Drude-Lorentz pole per member ----------------------------------------------------------------
+
+def pole_coefficients(omegas, dt, gamma, omega0):
+    """The factor of E_k * Eadj_k in the gradient with respect to the pole strength, and its scale's member part.
+
+    omegas: (F,) or (B, F); gamma, omega0: scalars or (B,).  With z = exp(i omega dt), g = gamma dt / 2,
+    a = (1 - g) / (1 + g), bq = dt / (1 + g) and ck = bq omega0^2 dt (include/fdtd2d_batch_dispersive.h, in float64)
+    returns (-(z - 1) / ((z - a)(z - 1) + ck z) as complex (B, F), bq as (B,)):
+    dJ/d wp2[i] = dx * bq * EPS0 * sum_k Re(factor_k * E_k[i] * Eadj_k[i])."""
+    gam, om0 = np.atleast_1d(np.asarray(gamma, dtype=np.float64)), np.atleast_1d(np.asarray(omega0, dtype=np.float64))
+    w = np.asarray(omegas, dtype=np.float64)
+    B = max(gam.size, om0.size, w.shape[0] if w.ndim == 2 else 1)
+    w = np.broadcast_to(w, (B, w.shape[-1]))
+    g = np.broadcast_to(gam, (B,)) * dt / 2
+    a, bq = (1 - g) / (1 + g), dt / (1 + g)
+    ck = bq * np.broadcast_to(om0, (B,)) ** 2 * dt
+    z = np.exp(1j * w * dt)
+    return -(z - 1) / ((z - a[:, None]) * (z - 1) + ck[:, None] * z), bq
+
+
+def _refuse_phase(eng):
+    """_refuse_bloch without its refusal of a pole: complex fields are refused, the pole is what these calls are for."""
+    if getattr(eng, "_bloch", None) is not None:
+        from ._abi import E_STATE, Fdtd2dError
+        raise Fdtd2dError(E_STATE, "adjoint gradients are not available while a Bloch phase is set (complex fields)")
+
+
+def _check_pole_boundary(boundary):
+    if boundary not in ("pml", "periodic"):
+        raise ValueError(f'boundary must be "pml" or "periodic", not {boundary!r}: a dispersive pole needs the PML layer '
+                         f'or periodic columns')
+
+
+def _check_wp2(p, wp2, window=None):
+    """_check_sigma's rules for the strength of a pole: the shape, >= 0 and finite, zero in the margin and the layer and
+    at every probe cell."""
+    return _check_sigma(p, wp2, window, name="wp2", may="carry a pole",
+                        probe_why="assumes conj(g) / D, which a pole at the cell would change")
+
+
+def _check_dispersion(p, dispersion):
+    """The host checks of dispersion = (wp2, gamma, omega0) (ValueError naming the member).  Returns the three as float64
+    arrays (B, R, C), (B,), (B,)."""
+    if dispersion is None or len(dispersion) != 3:
+        raise ValueError("dispersion must be (wp2, gamma, omega0)")
+    wp2, gamma, omega0 = dispersion
+    per = []
+    for v, nm in ((gamma, "gamma"), (omega0, "omega0")):
+        a = np.asarray(v, dtype=np.float64)
+        if a.shape not in ((), (p.B,)):
+            raise ValueError(f"{nm} must be a scalar or have shape ({p.B},), got {a.shape}")
+        a = np.ascontiguousarray(np.broadcast_to(a, (p.B,)))
+        bad = ~(np.isfinite(a) & (a >= 0))
+        if bad.any():
+            raise ValueError(f"member {int(np.nonzero(bad)[0][0])}: {nm} must be >= 0 and finite")
+        per.append(a)
+    if wp2 is None:
+        raise ValueError("member 0 (and every other): wp2 is required (a scalar or (B, R, C)); without a pole use "
+                         "batch_material_gradient")
+    return _check_wp2(p, wp2), per[0], per[1]
+
+
+def _pole_products(p, gamma, omega0):
+    """The three coefficient sets (3, B, F) and their scales (B, 3): eps, sigma, wp2."""
+    from .api import EPS0
+    cw, bq = pole_coefficients(p.om, p.dt, gamma, omega0)
+    scales = np.stack([np.full(p.B, p.dx / p.dt), np.full(p.B, p.dx / 2), p.dx * bq * EPS0], axis=1)
+    return np.stack([p.coef, p.coef_sigma, cw]), scales
+
+
+def batch_dispersive_gradient(eps, sigma, dispersion, mu=None, *, nsteps, sources, probes, omegas, design, objective,
+                              fc=30e9, waveform="ricker", dt=5e-14, dx=1e-4, dtype=np.float64, boundary="pml",
+                              pml_cells=40, device=0, engine=None):
+    """batch_material_gradient for members with a Drude-Lorentz pole: the gradients of the objective with respect to eps,
+    to the conductivity sigma and to the pole strength wp2 over the design window, from the same two runs.
+
+    dispersion = (wp2, gamma, omega0) as run_fdtd_batch(dispersion=) and BatchEngine.set_dispersion take them: wp2
+    (B, R, C) in rad^2/s^2 (a scalar: every cell that may carry it), gamma and omega0 scalars or (B,) in rad/s.  sigma:
+    as batch_material_gradient takes it (None: zero).  boundary "pml" or "periodic": a pole needs the layer or periodic
+    columns.  The other arguments, the conditions and their checks are batch_material_gradient's.  In addition, checked
+    on the host with a ValueError that names the member, before any engine work: wp2 under the rules of sigma (the shape,
+    >= 0 and finite, zero in the margin and the layer) and zero at every probe cell (the injection assumes
+    conj(g) / D); gamma and omega0 >= 0 and finite.  The library adds its stability refusal (E_ARG, set_dispersion).
+
+    The method is batch_material_gradient's: the pole adds a diagonal term to the one-step operator, which stays
+    symmetric, so the adjoint run is a dispersive run of the same member with sources at the probe cells.  The forward
+    window is held with hold_dispersive_window, and one dispersive_window_product forms the three gradients in one pass
+    over the two windows.  gamma and omega0 are not differentiated.
+
+    Returns (J (B,), grad_eps, grad_sigma, grad_wp2 (B, nrows, ncols) float64 each, spectra (B, P, F) complex128,
+    info)."""
+    _check_pole_boundary(boundary)
+    p = _plan(eps, mu, nsteps, sources, probes, omegas, design, fc, waveform, dt, dx, boundary, pml_cells)
+    s = _check_sigma(p, 0.0 if sigma is None else sigma)
+    wp2, gamma, omega0 = _check_dispersion(p, dispersion)
+    coefs, scales = _pole_products(p, gamma, omega0)
+    if engine is None:
+        from .batch import BatchEngine as engine
+    B = p.B
+    with engine(B, p.R, p.Cc, dt, dx, dtype=dtype, boundary=boundary, device=device) as eng:
+        _refuse_phase(eng)
+        # 1. forward: the member's own source; the pole after the materials, the layer and the conductivity
+        _setup(eng, p)
+        eng.set_conductivity(s)
+        eng.set_dispersion(wp2, gamma, omega0)
+        eng.run(nsteps, p.amps)
+        traces = eng.read_probes(0, nsteps)
+        end_fwd = np.abs(eng.download()[0].astype(np.float64)).reshape(B, -1).max(axis=1)
+        eng.hold_dispersive_window()
+        spectra = probe_spectra(traces, p.om, dt)
+
+        # 2. the cotangent
+        J, g = _cotangent(p, objective, spectra)
+
+        # 3. adjoint: same materials and pole, fields and pole state zero, step 0
+        c = _injections(p, g, p.eps, dtype)
+        weights = np.empty((B, p.P, 2 * p.F))
+        for b in range(B):
+            weights[b] = np.linalg.solve(p.systems[p.which[b]][1], np.concatenate([c[b].real, c[b].imag], axis=1).T).T
+        eng.reset()
+        eng.set_point_sources(p.cells, weights)
+        eng.run(nsteps, None, p.channels)
+        adj_traces = eng.read_probes(0, nsteps)
+        end_adj = np.abs(eng.download()[0].astype(np.float64)).reshape(B, -1).max(axis=1)
+
+        # 4. the three gradients: one pass over the two windows
+        grads = eng.dispersive_window_product(coefs, scales)
+
+    def peak(tr):
+        flat = tr.reshape(B, -1)
+        return np.maximum(flat.max(axis=1), -flat.min(axis=1))
+    info = {"condition": max(v[2] for v in p.systems.values()),
+            "residual_forward": _residual(end_fwd, peak(traces)), "residual_adjoint": _residual(end_adj, peak(adj_traces)),
+            "channels_shared": p.shared}
+    return J, grads[0], grads[1], grads[2], spectra, info
+
+
+class DispersiveAdjointSession(AdjointSession):
+    """AdjointSession for members with a Drude-Lorentz pole: batch_dispersive_gradient as a loop on a standing engine.
+
+    The constructor takes batch_dispersive_gradient's arguments (without the objective; dispersion and sigma by keyword),
+    makes its host checks and sets the engine up once, conductivity and pole included.  value_and_grad(objective)
+    returns (J, grad_eps, spectra, info) as the base class does and keeps the windows; sigma_gradient() and
+    wp2_gradient() belong to the latest value_and_grad.  The three gradients come from one dispersive_window_product, one
+    launch and one read-back per iteration, and are kept until the next value_and_grad.  set_design_eps,
+    set_design_sigma and set_conductivity are AdjointSession's; set_design_wp2(wp2_window) replaces the strengths of the
+    design window.  A set_design_eps or set_design_wp2 that the library's stability check refuses (E_ARG) leaves the
+    engine and the session as they were.
+
+        with DispersiveAdjointSession(eps, dispersion=(wp2, gamma, omega0), nsteps=..., ..., design=win) as s:
+            for it in range(100):
+                J, g_eps, spectra, info = s.value_and_grad(objective)
+                s.set_design_wp2(np.clip(s.wp2[:, r0:r0 + nr, c0:c0 + nc] + step * s.wp2_gradient(), 0, hi))
+    """
+
+    def __init__(self, eps, mu=None, *, dispersion, sigma=None, nsteps, sources, probes, omegas, design, fc=30e9,
+                 waveform="ricker", dt=5e-14, dx=1e-4, dtype=np.float64, boundary="pml", pml_cells=40, device=0,
+                 engine=None):
+        self._eng = None
+        _check_pole_boundary(boundary)
+        p = _plan(eps, mu, nsteps, sources, probes, omegas, design, fc, waveform, dt, dx, boundary, pml_cells)
+        self._sigma0 = None if sigma is None else _check_sigma(p, sigma)
+        self._wp2, self._gamma, self._omega0 = _check_dispersion(p, dispersion)
+        self._wp2 = self._wp2.copy()
+        self._coefs, self._scales = _pole_products(p, self._gamma, self._omega0)
+        self._scales[:, 0] = 1.0                # value_and_grad scales the eps gradient itself, as the base class does
+        self._grads = None                      # the three products of the latest value_and_grad
+        self._pole_set = False
+        self._open(p, dtype, engine, device)
+
+    def _check_engine(self, eng):
+        """A Bloch phase is refused as for AdjointSession; the pole, once set, is required."""
+        _refuse_phase(eng)
+        if self._pole_set and not eng.dispersive:
+            from ._abi import E_STATE, Fdtd2dError
+            raise Fdtd2dError(E_STATE, "DispersiveAdjointSession needs its dispersive pole: it was removed from the "
+                              "session's engine (a batch without one takes AdjointSession)")
+
+    def _setup_engine(self, eng):
+        _setup(eng, self._p)
+        if self._sigma0 is not None:
+            eng.set_conductivity(self._sigma0)
+            self._sigma = self._sigma0.copy()
+        eng.set_dispersion(self._wp2, self._gamma, self._omega0)
+        self._pole_set = True
+
+    def _hold(self, eng):
+        eng.hold_dispersive_window()
+
+    def _product(self, eng, coef):
+        # the base class asks for the eps product; the other two ride along in the same pass
+        self._grads = eng.dispersive_window_product(self._coefs, self._scales)
+        return self._grads[0]
+
+    def _latest(self, k):
+        if self._eng is None:
+            raise RuntimeError("the session is closed")
+        if not self._ran or self._grads is None:
+            raise RuntimeError("no gradient yet: call value_and_grad first")
+        return self._grads[k].copy()
+
+    def sigma_gradient(self):
+        """dJ/d sigma over the design window, (B, nrows, ncols) float64, for the latest value_and_grad (formed with it:
+        no further launch)."""
+        return self._latest(1)
+
+    def wp2_gradient(self):
+        """dJ/d wp2 over the design window, (B, nrows, ncols) float64, for the latest value_and_grad (formed with it: no
+        further launch)."""
+        return self._latest(2)
+
+    @property
+    def wp2(self):
+        """The members' pole strengths as the session holds them, (B, R, C) float64, read-only."""
+        v = self._wp2.view()
+        v.flags.writeable = False
+        return v
+
+    def set_design_wp2(self, wp2_window):
+        """New pole strengths of the design window for every member: (B, nrows, ncols).  Checked on the host (ValueError,
+        nothing changed): the shape, values >= 0 and finite, zero at probe cells; the library's stability refusal
+        (E_ARG) changes nothing either."""
+        p = self._p
+        if self._eng is None:
+            raise RuntimeError("the session is closed")
+        r0, c0, nr, nc = p.win
+        w = _check_wp2(p, wp2_window, p.win)
+        self._eng.set_dispersion_window(p.win, w)
+        self._wp2[:, r0:r0 + nr, c0:c0 + nc] = w
         return self

@@ -16,7 +16,9 @@ metasurface unit cells, photonic-crystal slabs): column C-1 is the image of colu
 or in PEC (fdtd2d_batch_periodic.h).  ``set_bloch_phase`` gives a periodic batch one Bloch phase per member: the fields
 become complex and repeat as F(x + period) = F(x) e^{i phi} (oblique incidence, angle sweeps, band diagrams;
 fdtd2d_batch_bloch.h).  ``set_dispersion`` gives a PML or periodic batch one Drude-Lorentz pole per member with a strength
-per cell (metals, absorption lines; fdtd2d_batch_dispersive.h); the batch then runs on the dispersive step kernels.
+per cell (metals, absorption lines; fdtd2d_batch_dispersive.h); the batch then runs on the dispersive step kernels, and
+``hold_dispersive_window`` / ``dispersive_window_product`` are what its adjoint gradients need
+(fdtd2d_batch_dispersive_adjoint.h).
 ``set_bloch_dispersion`` is that pole for a batch with complex fields (a Bloch phase or the lattice mode;
 fdtd2d_batch_bloch_dispersive.h): a metal unit cell with one angle of incidence or one k-point per member.
 ``boundary="lattice"`` makes every member the unit cell of a rectangular 2D lattice: row R-1 is the image of row 0 and
@@ -598,6 +600,47 @@ class BatchEngine:
         re, im = np.ascontiguousarray(k.real), np.ascontiguousarray(k.imag)
         out = np.empty((self.count, nr, nc))
         self._ck(self._lib.fdtd2d_batch_dft_window_product(self._h, _dptr(re), _dptr(im), _dptr(out)))
+        return out
+
+    # -- the same for a batch with a dispersive pole (fdtd2d_batch_dispersive_adjoint.h) ----------------------------
+    def _need_dispersion(self, what, plain):
+        """The library's refusals of a dispersive adjoint call, before the call."""
+        self._no_bloch(what)
+        if not self.dispersive:
+            raise _abi.Fdtd2dError(_abi.E_STATE, f"{what} needs a dispersive pole (fdtd2d_batch_set_dispersion): a batch "
+                                   f"without one takes {plain}")
+
+    def hold_dispersive_window(self):
+        """hold_dft_window for a batch with a dispersive pole: a device copy of the window DFT in a buffer of its own
+        (hold_dft_window keeps refusing such a batch).  It survives reset(), set_point_sources and further runs, and
+        goes with the window or the pole."""
+        self._need_dispersion("the held dispersive window", "fdtd2d_batch_hold_dft_window")
+        self._ck(self._lib.fdtd2d_batch_hold_dispersive_window(self._h))
+        return self
+
+    def dispersive_window_product(self, coefs, scales=None) -> np.ndarray:
+        """float64 (ncoef, B, nrows, ncols): scales[b, c] * sum_k Re(coefs[c, b, k] * held[b, k] * current[b, k]) over the
+        window for ncoef = 1..3 coefficient sets, in one pass over the two windows, one launch and one read-back.
+        coefs: complex (ncoef, F) for every member or (ncoef, B, F); scales: None (ones), (ncoef,) or (B, ncoef).  With
+        one set and no scales it is dft_window_product's arithmetic bit for bit."""
+        self._need_dispersion("the dispersive window product", "fdtd2d_batch_dft_window_product")
+        f, nr, nc = self._win or (0, 1, 1)
+        k = np.asarray(coefs, dtype=np.complex128)
+        if k.ndim == 2:
+            k = np.broadcast_to(k[:, None, :], (k.shape[0], self.count, k.shape[1]))
+        if k.ndim != 3 or not 1 <= k.shape[0] <= _abi.BATCH_MAX_PRODUCT_SETS or \
+                (self._win is not None and k.shape[1:] != (self.count, f)):
+            raise ValueError(f"coefs must have shape (ncoef, {f}) or (ncoef, {self.count}, {f}) with ncoef in 1.."
+                             f"{_abi.BATCH_MAX_PRODUCT_SETS}, got {np.shape(coefs)}")
+        n = int(k.shape[0])
+        s = np.ones((self.count, n)) if scales is None else np.asarray(scales, dtype=np.float64)
+        if s.shape == (n,):
+            s = np.broadcast_to(s, (self.count, n))
+        if s.shape != (self.count, n):
+            raise ValueError(f"scales must have shape ({n},) or ({self.count}, {n}), got {np.shape(scales)}")
+        re, im, s = np.ascontiguousarray(k.real), np.ascontiguousarray(k.imag), np.ascontiguousarray(s)
+        out = np.empty((n, self.count, nr, nc))
+        self._ck(self._lib.fdtd2d_batch_dispersive_window_product(self._h, n, _dptr(re), _dptr(im), _dptr(s), _dptr(out)))
         return out
 
     # -- the same for a Bloch batch (fdtd2d_batch_bloch_adjoint.h) -----------------------------------------------------

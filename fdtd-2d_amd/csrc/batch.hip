@@ -27,6 +27,7 @@
 #include "../../include/fdtd2d_batch_bloch_dispersive.h"
 #include "../../include/fdtd2d_batch_design.h"
 #include "../../include/fdtd2d_batch_dispersive.h"
+#include "../../include/fdtd2d_batch_dispersive_adjoint.h"
 #include "../../include/fdtd2d_batch_lattice.h"
 #include "../../include/fdtd2d_batch_lossy.h"
 #include "../../include/fdtd2d_batch_monitor.h"
@@ -143,6 +144,7 @@ struct fdtd2d_batch {
     double *probe_trace = nullptr;
     long long probe_cap = 0, probe_step0 = 0;
     double *win_held = nullptr;           // fdtd2d_batch_hold_dft_window: a copy of win_acc
+    double *win_held_disp = nullptr;      // fdtd2d_batch_hold_dispersive_window: a copy of win_acc while a pole is set
     // point sources (fdtd2d_batch_set_point_sources), every table in the resident owners' order
     int npts = 0, pts_nchan = 0;
     int npts_user = 0;                    // npts without the image entries of a periodic batch
@@ -1325,6 +1327,7 @@ int disp_reform(fdtd2d_batch *b, int r0, int c0, int nr, int nc)
 void disp_release(fdtd2d_batch *b)
 {
     for (void **p : {&b->djh, &b->dq, &b->dcj, &b->da, &b->dck, &b->djh_im, &b->dq_im}) release(p);
+    release((void **)&b->win_held_disp);     // the held dispersive window goes with the pole
     b->bdisp = false;
     b->wp2_host.clear();
     b->disp_gamma.clear();
@@ -1684,7 +1687,7 @@ void fdtd2d_batch_destroy(fdtd2d_batch_t *b)
                      (void **)&b->pts_w, (void **)&b->pts_tab, (void **)&b->chan, &b->dsg, &b->ca, &b->cb,
                      &b->ez_im, &b->hx_im, &b->hy_im, &b->ezx_im, &b->rho, (void **)&b->bloch_w, (void **)&b->amps_im,
                      (void **)&b->win_acc_im, (void **)&b->probe_trace_im, &b->rho_conj, &b->rho_r,
-                     (void **)&b->win_held_im,
+                     (void **)&b->win_held_im, (void **)&b->win_held_disp,
                      &b->djh, &b->dq, &b->dcj, &b->da, &b->dck, &b->djh_im, &b->dq_im})
         release(p);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
@@ -1724,6 +1727,7 @@ long long fdtd2d_batch_info(const fdtd2d_batch_t *b, int what)
     case FDTD2D_BATCH_INFO_PERIODIC: return b->periodic ? 1 : 0;
     case FDTD2D_BATCH_INFO_BLOCH: return b->bloch && !b->lattice ? 1 : 0;
     case FDTD2D_BATCH_INFO_DISPERSIVE: return b->dcj ? 1 : 0;
+    case FDTD2D_BATCH_INFO_HELD_DISPERSIVE_WINDOW: return b->win_held_disp ? 1 : 0;
     default: return FDTD2D_E_ARG;
     }
 }
@@ -2121,7 +2125,8 @@ int fdtd2d_batch_set_dft_window(fdtd2d_batch_t *b, int row0, int col0, int nrows
     int rc = use_device(b);
     if (rc) return rc;
     BCHK(b, hipStreamSynchronize(b->stream));   // a running launch may still use the old window
-    for (void **p : {(void **)&b->win_acc, (void **)&b->win_omega, (void **)&b->win_ph, (void **)&b->win_held})
+    for (void **p : {(void **)&b->win_acc, (void **)&b->win_omega, (void **)&b->win_ph, (void **)&b->win_held,
+                     (void **)&b->win_held_disp})
         release(p);
     b->win_nf = 0;
     if (nfreq == 0) return bloch_window(b);
@@ -2649,6 +2654,68 @@ int fdtd2d_batch_transfer_dispersion(fdtd2d_batch_t *b, void *jh, void *q, int h
             rc = copy_image(b, dev[k]);
         if (rc) return rc;
     }
+    return 0;
+}
+
+// ---- fdtd2d_batch_dispersive_adjoint.h -------------------------------------------------------------------------
+
+namespace {
+// what both calls refuse: complex fields, a batch without a pole, a batch without a window
+int dispersive_window_state(fdtd2d_batch *b, const char *what, const char *plain)
+{
+    if (b->bloch) return refuse_bloch(b, what);
+    if (!b->dcj)
+        return bfail(b, FDTD2D_E_STATE, "%s needs a dispersive pole (fdtd2d_batch_set_dispersion): a batch without one "
+                     "takes %s", what, plain);
+    if (!b->win_nf) return bfail(b, FDTD2D_E_STATE, "no window DFT is set");
+    return 0;
+}
+}  // namespace
+
+int fdtd2d_batch_hold_dispersive_window(fdtd2d_batch_t *b)
+{
+    if (!b) return FDTD2D_E_ARG;
+    int rc = dispersive_window_state(b, "the held dispersive window", "fdtd2d_batch_hold_dft_window");
+    if (rc) return rc;
+    if ((rc = use_device(b))) return rc;
+    const size_t bytes = (size_t)b->count * win_acc_bytes(b);
+    if (!b->win_held_disp && (rc = alloc(b, (void **)&b->win_held_disp, bytes))) return rc;
+    BCHK(b, hipMemcpyAsync(b->win_held_disp, b->win_acc, bytes, hipMemcpyDeviceToDevice, b->stream));
+    BCHK(b, hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+int fdtd2d_batch_dispersive_window_product(fdtd2d_batch_t *b, int ncoef, const double *coef_re, const double *coef_im,
+                                           const double *scale, double *out)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!coef_re || !coef_im || !scale || !out)
+        return bfail(b, FDTD2D_E_ARG, "coef_re, coef_im, scale and out must not be NULL");
+    if (ncoef < 1 || ncoef > FDTD2D_BATCH_MAX_PRODUCT_SETS)
+        return bfail(b, FDTD2D_E_ARG, "ncoef %d outside 1..%d", ncoef, (int)FDTD2D_BATCH_MAX_PRODUCT_SETS);
+    int rc = dispersive_window_state(b, "the dispersive window product", "fdtd2d_batch_dft_window_product");
+    if (rc) return rc;
+    if (!b->win_held_disp)
+        return bfail(b, FDTD2D_E_STATE, "no held dispersive window: call fdtd2d_batch_hold_dispersive_window first");
+    if ((rc = use_device(b))) return rc;
+    const size_t W = (size_t)b->win_nr * b->win_nc, nk = (size_t)ncoef * b->count * b->win_nf;
+    const size_t ns = (size_t)b->count * ncoef, nout = (size_t)ncoef * b->count * W;
+    std::vector<double> host(2 * nk + ns);      // the interleaved coefficients, then the scales: one upload
+    for (size_t k = 0; k < nk; ++k) {
+        host[2 * k] = coef_re[k];
+        host[2 * k + 1] = coef_im[k];
+    }
+    std::copy(scale, scale + ns, host.begin() + 2 * nk);
+    // scratch, as fdtd2d_batch_bloch_window_product: coef (ncoef x count x nf x 2), scale (count x ncoef), out
+    if ((rc = scratch(b, (host.size() + nout) * sizeof(double)))) return rc;
+    double *dcoef = (double *)b->dsg, *dout = dcoef + host.size();
+    BCHK(b, hipMemcpyAsync(dcoef, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    fdtd::batch_window_product_multi_launch(b->win_held_disp, b->win_acc, dcoef, dcoef + 2 * nk, dout, b->count,
+                                            b->win_nf, W, ncoef, b->stream);
+    BCHK(b, hipGetLastError());
+    b->launches++;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    BCHK(b, hipMemcpy(out, dout, nout * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 

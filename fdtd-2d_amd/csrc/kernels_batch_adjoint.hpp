@@ -424,5 +424,8 @@ __global__ __launch_bounds__(256) void k_batch_e_pml_mon_pts(BatchView<T> v, Bat
 template <class T> const BatchMonKernels &batch_pts_kernels();
 void batch_window_product_launch(const double *held, const double *cur, const double *coef, double *out, int B, int nf,
                                  size_t W, hipStream_t stream);
+// the same for ncoef = 1..3 coefficient sets with a scale per member and set (fdtd2d_batch_dispersive_adjoint.h)
+void batch_window_product_multi_launch(const double *held, const double *cur, const double *coef, const double *scale,
+                                       double *out, int B, int nf, size_t W, int ncoef, hipStream_t stream);
 
 }  // namespace fdtd

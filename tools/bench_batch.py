@@ -84,10 +84,20 @@ array eps with random binary permittivity, a ricker line source per member):
                               of --bloch): dispersive_ms, plain_ms, dispersive_over_plain, both paths, the LDS bytes per
                               workgroup and the workgroups per CU they admit (160 KiB per CU): 14 arrays against 9 and
                               16 against 11 may cost a workgroup per CU.  Default: 1024 members of 33 x 33, 1000 steps.
+  --dispersive-adjoint        instead: the three gradients of a dispersive batch (a Drude block, wp = 2 pi 70 GHz and
+                              gamma = 1e11, and a conductivity on the design window of 100 cells; PML, 10 frequencies, 30
+                              probes, 20 channels, dt = 2e-13): dispersive_ms, one DispersiveAdjointSession.value_and_grad
+                              + sigma_gradient + wp2_gradient, against lossy_ms, the same members without the pole as an
+                              AdjointSession.value_and_grad + sigma_gradient, timed alternately in one process:
+                              dispersive_over_lossy, both paths, LDS sizes and launches per iteration.  Also, on the
+                              dispersive session's windows: multi_product_ms, one dispersive_window_product of three
+                              coefficient sets, against three_products_ms, three calls of one set each (three launches,
+                              three read-backs): multi_over_three.  Default: 1024 members of 60 x 60, a 10-cell layer,
+                              1500 steps.
 Usage: python tools/bench_batch.py [--count 1024 --rows 60 --cols 60 --steps 1000] [--reps 5] [--loop-members 16]
                                    [--boundary {mur,pml} --pml-cells 10] [--monitors] [--adjoint] [--lossy]
                                    [--periodic] [--bloch] [--bloch-adjoint] [--dispersive] [--lattice]
-                                   [--bloch-dispersive]
+                                   [--bloch-dispersive] [--dispersive-adjoint]
 """
 import argparse
 import json
@@ -786,6 +796,87 @@ def bench_bloch_adjoint(count, rows, cols, steps, dtype, reps, pml_cells):
             "residual_adjoint_max": float(np.max(info["residual_adjoint"]))}
 
 
+def bench_dispersive_adjoint(count, rows, cols, steps, dtype, reps, pml_cells):
+    dt = 2e-13                                   # as --adjoint: the channels' envelope ends by step 1200
+    rng = np.random.default_rng(0)
+    eps = np.where(rng.random((count, rows, cols)) < 0.5, fd.EPS0, 5 * fd.EPS0)
+    side, g = 10, max(6, pml_cells)
+    r0, c0 = (rows - side) // 2, (cols - side) // 2
+    design = (r0, c0, side, side)
+    rects = np.tile([g + 2, g + 2, 1, 1], (count, 1))
+    probes = np.array([[rows // 2 - 15 + k, c0 + side + 8] for k in range(30)])
+    sigma, wp2 = np.zeros((count, rows, cols)), np.zeros((count, rows, cols))
+    sigma[:, r0:r0 + side, c0:c0 + side] = 2.0 * rng.random((count, side, side))
+    wp2[:, r0:r0 + side, c0:c0 + side] = (2 * np.pi * 70e9) ** 2 * (0.5 + rng.random((count, side, side)))
+    omegas = 2 * np.pi * np.linspace(10e9, 100e9, 10)
+    args = dict(nsteps=steps, sources=rects, probes=probes, omegas=omegas, design=design, fc=FC, dt=dt, dx=DX,
+                dtype=dtype, boundary="pml", pml_cells=pml_cells)
+
+    def objective(spectra):
+        mag = np.abs(spectra)
+        return mag.mean(axis=1).sum(axis=1), spectra / np.maximum(mag, 1e-300) / spectra.shape[1]
+
+    info = {}
+    with fd.DispersiveAdjointSession(eps, dispersion=(wp2, 1e11, 0.0), sigma=sigma, **args) as pole, \
+            fd.AdjointSession(eps, **args) as lossy:
+        lossy.set_conductivity(sigma)
+
+        def dispersive():
+            t0 = time.perf_counter()
+            info.update(pole.value_and_grad(objective)[3])
+            pole.sigma_gradient(), pole.wp2_gradient()
+            return (time.perf_counter() - t0) * 1e3
+
+        def plain():
+            t0 = time.perf_counter()
+            lossy.value_and_grad(objective)
+            lossy.sigma_gradient()
+            return (time.perf_counter() - t0) * 1e3
+
+        eng, coefs, scales = pole.engine, pole._coefs, pole._scales
+
+        def multi():
+            t0 = time.perf_counter()
+            eng.dispersive_window_product(coefs, scales)
+            return (time.perf_counter() - t0) * 1e3
+
+        def three():
+            t0 = time.perf_counter()
+            for k in range(3):
+                eng.dispersive_window_product(coefs[k:k + 1], scales[:, k:k + 1])
+            return (time.perf_counter() - t0) * 1e3
+
+        dispersive(), plain(), multi(), three()      # warm-up: code objects, clocks
+        launches = {}
+        for name, s, call in (("dispersive", pole, dispersive), ("lossy", lossy, plain)):
+            l0 = s.engine.launches
+            call()
+            launches[name] = s.engine.launches - l0
+        t = {k: [] for k in ("dispersive", "lossy", "multi", "three")}
+        for _ in range(reps):
+            t["dispersive"].append(dispersive())
+            t["lossy"].append(plain())
+            t["multi"].append(multi())
+            t["three"].append(three())
+        paths = {k: "resident" if s.engine.resident else "streamed" for k, s in (("dispersive", pole), ("lossy", lossy))}
+        lds = {k: s.engine.lds_bytes for k, s in (("dispersive", pole), ("lossy", lossy))}
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    return {"count": count, "rows": rows, "cols": cols, "steps": steps, "dtype": np.dtype(dtype).name, "dt": dt,
+            "boundary": "pml", "pml_cells": pml_cells, "design": list(design), "freqs": 10, "probes": 30, "channels": 20,
+            "reps": reps, "dispersive_path": paths["dispersive"], "lossy_path": paths["lossy"],
+            "dispersive_lds_bytes": lds["dispersive"], "lossy_lds_bytes": lds["lossy"],
+            "dispersive_ms": round(med["dispersive"], 3), "dispersive_ms_all": [round(v, 3) for v in t["dispersive"]],
+            "lossy_ms": round(med["lossy"], 3), "lossy_ms_all": [round(v, 3) for v in t["lossy"]],
+            "dispersive_over_lossy": round(med["dispersive"] / med["lossy"], 3),
+            "launches_per_dispersive_iteration": launches["dispersive"],
+            "launches_per_lossy_iteration": launches["lossy"],
+            "multi_product_ms": round(med["multi"], 3), "multi_product_ms_all": [round(v, 3) for v in t["multi"]],
+            "three_products_ms": round(med["three"], 3), "three_products_ms_all": [round(v, 3) for v in t["three"]],
+            "multi_over_three": round(med["multi"] / med["three"], 3),
+            "residual_forward_max": float(np.max(info["residual_forward"])),
+            "residual_adjoint_max": float(np.max(info["residual_adjoint"]))}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--count", type=int)
@@ -808,7 +899,13 @@ def main():
     ap.add_argument("--lattice", action="store_true", help="time a lattice batch against the Bloch batch without a layer")
     ap.add_argument("--bloch-dispersive", action="store_true",
                     help="time the pole of a lattice and of a Bloch batch against the same batches without it")
+    ap.add_argument("--dispersive-adjoint", action="store_true",
+                    help="time the three gradients of a dispersive batch against the two of the same lossy batch")
     a = ap.parse_args()
+    if a.dispersive_adjoint:
+        print(json.dumps(bench_dispersive_adjoint(a.count or 1024, a.rows or 60, a.cols or 60, a.steps or 1500,
+                                                  np.dtype(a.dtype), a.reps, a.pml_cells)), flush=True)
+        return
     if a.bloch_dispersive:
         for lattice in (True, False):
             print(json.dumps(bench_bloch_dispersive(a.count or 1024, a.rows or 33, a.cols or a.rows or 33, a.steps or 1000,
