@@ -64,11 +64,13 @@ def set_threads(rows, cols):
     return n
 
 
-def _suf(a):
+def _suf(a, fused=False):
+    """fused: the variant that states the arithmetic of libfdtd2d_fused.so (fdtd_oracle.c: four forms as one fma each)."""
+    tail = "_fma" if fused else ""
     if a.dtype == np.float32:
-        return "f32"
+        return "f32" + tail
     if a.dtype == np.float64:
-        return "f64"
+        return "f64" + tail
     raise TypeError(f"unsupported dtype {a.dtype}")
 
 
@@ -78,9 +80,9 @@ def _p(a, dtype):
     return a.ctypes.data_as(C.c_void_p)
 
 
-def update_h(Ez, Hx, Hy, mu, eps, dt, dx):
+def update_h(Ez, Hx, Hy, mu, eps, dt, dx, fused=False):
     R, Cc = Ez.shape
-    f = getattr(lib(), "orc_update_h_" + _suf(Ez))
+    f = getattr(lib(), "orc_update_h_" + _suf(Ez, fused))
     rc = f(_p(Ez, Ez.dtype), _p(Hx, Ez.dtype), _p(Hy, Ez.dtype), _p(mu, Ez.dtype),
            C.c_int(R), C.c_int(Cc), C.c_double(dt), C.c_double(dx))
     if rc:
@@ -88,9 +90,9 @@ def update_h(Ez, Hx, Hy, mu, eps, dt, dx):
     return Hx, Hy
 
 
-def update_e(Ez, Hx, Hy, mu, eps, dt, dx):
+def update_e(Ez, Hx, Hy, mu, eps, dt, dx, fused=False):
     R, Cc = Ez.shape
-    f = getattr(lib(), "orc_update_e_" + _suf(Ez))
+    f = getattr(lib(), "orc_update_e_" + _suf(Ez, fused))
     rc = f(_p(Ez, Ez.dtype), _p(Hx, Ez.dtype), _p(Hy, Ez.dtype), _p(mu, Ez.dtype),
            _p(eps, Ez.dtype), C.c_int(R), C.c_int(Cc), C.c_double(dt), C.c_double(dx),
            C.c_void_p(None))
@@ -109,9 +111,10 @@ def add_point(Ez, row, col, amp):
     return Ez
 
 
-def run(Ez, Hx, Hy, eps, mu, dt, dx, nsteps, src_row, src_col, amps=None, fc=30e9, step0=0):
+def run(Ez, Hx, Hy, eps, mu, dt, dx, nsteps, src_row, src_col, amps=None, fc=30e9, step0=0,
+        fused=False):
     R, Cc = Ez.shape
-    f = getattr(lib(), "orc_run_" + _suf(Ez))
+    f = getattr(lib(), "orc_run_" + _suf(Ez, fused))
     set_threads(R, Cc)
     if amps is not None:
         amps = np.ascontiguousarray(amps, dtype=np.float64)

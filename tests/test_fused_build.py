@@ -12,7 +12,8 @@ Stated tolerances (e = max|x - ref| / max|ref| per field):
                                                          float64: measured 7.1e-5)
   float64 fused vs the float64 reference                 e <= 1e-12
 and the fused build is still deterministic in the launch shape: temporally blocked passes equal its own single-step
-kernels bit for bit (every kernel contracts the same expressions the same way).
+kernels bit for bit on the one case below.  The bit-for-bit claim itself -- every launch shape of the Mur engine equal to an
+oracle that fuses exactly the stated four forms -- is tests/test_gpu_fused_parity.py's (oracle: tests/test_fused_oracle_cpu.py).
 
 The library is chosen when the package is first imported, so the GPU part runs in a child process."""
 import json
