@@ -1440,6 +1440,12 @@ int fdtd2d_pass_rows(fdtd2d_t *h, int nt, int row_lo, int row_hi, int src_row, i
         return fail(h, FDTD2D_E_ARG, "rows cut through the bottom zone [%d,%d)", h->rows - zo, h->rows);
     if (h->bottom() && row_hi == h->rows && row_lo > h->rows - zo)
         return fail(h, FDTD2D_E_ARG, "rows cut through the bottom zone [%d,%d)", h->rows - zo, h->rows);
+    // (a running Fourier transform samples at fixed steps: a pass issued in pieces must end ON the next sampled step or
+    // before it -- fdtd2d_run cuts its passes there by itself, callers of fdtd2d_pass_rows choose nt accordingly.  Refused
+    // here, before anything is launched or becomes pending: after the commit the sample could not be taken any more)
+    if (h->dft_n && nt > h->dft_gap())
+        return fail(h, FDTD2D_E_ARG, "a %d-step pass from step %lld would run over step %lld, which the running Fourier "
+                    "transform samples (every %d steps)", nt, h->step, h->step + h->dft_gap(), h->dft_every);
     const bool zt = h->top() && row_lo == 0, zb = h->bottom() && row_hi == h->rows;
     const int b_lo = std::max(row_lo, lo), b_hi = std::min(row_hi, hi);
     if ((rc = tune_pass(h, nt, b_lo, b_hi, zt, zb, src_row, src_col, amps != nullptr))) return rc;
@@ -1478,9 +1484,7 @@ int fdtd2d_pass_commit(fdtd2d_t *h)
         return fail(h, FDTD2D_E_STATE, "pending pass covers rows [%d,%d) of the owned [%d,%d): dropped",
                     c_lo, at, own_lo, own_hi);
     }
-    // (a running Fourier transform samples at fixed steps: a pass issued in pieces must end ON the next sampled step or
-    // before it -- fdtd2d_run cuts its passes there by itself, callers of fdtd2d_pass_rows choose nt accordingly)
-    const bool skipped = h->dft_n && h->dft_gap() < nt;
+    // (fdtd2d_pass_rows refused a pass that would run over a sampled step: this one ends on it or before it)
     h->aw.invalidate();
     h->cur ^= 1;
     h->hcur ^= 1;
@@ -1488,9 +1492,6 @@ int fdtd2d_pass_commit(fdtd2d_t *h)
     h->step += nt;
     h->pend_nt = 0;
     h->pend_done.clear();
-    if (skipped)
-        return fail(h, FDTD2D_E_STATE, "the %d-step pass ran over a step the running Fourier transform samples (every %d steps)",
-                    nt, h->dft_every);
     return dft_after_step(h);
 }
 

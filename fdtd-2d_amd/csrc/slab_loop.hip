@@ -322,6 +322,12 @@ int fdtd2d_run_slab(fdtd2d_t *h, int nsteps, int cycle, int overlap, int src_row
         return fail(h, FDTD2D_E_ARG, "need nsteps >= 0 and 1 <= cycle <= halo (%d)", h->halo);
     if (h->dft_n && h->dft_every % cycle != 0)
         return fail(h, FDTD2D_E_ARG, "a running Fourier transform samples every %d steps: not a multiple of the %d-step cycle", h->dft_every, cycle);
+    // ... and the cycles must start on the transform's grid: with both rules no full cycle crosses a sampled step (a
+    // tail shorter than the cycle goes through fdtd2d_run, which cuts itself).  Every rank sets the same transform and
+    // counts the same steps, so every rank decides alike -- before anything is posted.
+    if (h->dft_n && (h->step - h->dft_step0) % cycle != 0)
+        return fail(h, FDTD2D_E_ARG, "a running Fourier transform is set and the run would start %lld steps after it was: "
+                    "not a multiple of the %d-step cycle", h->step - h->dft_step0, cycle);
     if (hipSetDevice(h->device) != hipSuccess) return fail(h, FDTD2D_E_NODEVICE, "hipSetDevice failed");
     // Overlapped cycles need a temporally blocked pass of `cycle` steps.  Only quantities every rank
     // shares enter this decision (whether EVERY slab is tall enough for two edge pieces and an
@@ -329,6 +335,14 @@ int fdtd2d_run_slab(fdtd2d_t *h, int nsteps, int cycle, int overlap, int src_row
     // differently would post their transfers in different orders.
     const bool can_overlap = overlap && h->rows >= 2 * (2 * cycle + 6) && (cycle == 8 || cycle == 16);
     if (can_overlap) {
+        // a handle that cannot issue a pass of `cycle` steps in pieces says so before anything is posted, not from inside
+        // its first cycle: the PML passes have no probe tile (pass_geometry), float64's 16-step kernel has none either
+        // (cycle_steps() says 8 then: the caller has to agree on the cycle after the probe is set)
+        if (h->probe_cap && h->boundary == FDTD2D_BOUNDARY_PML)
+            return fail(h, FDTD2D_E_ARG, "a probe is set and the PML passes have no probe tile: pass overlap = 0 on every rank");
+        if (cycle == 16 && h->cycle_steps() != 16)
+            return fail(h, FDTD2D_E_ARG, "overlapped 16-step cycles need 16-step passes and this handle runs %d-step ones: "
+                        "agree on the cycle after the probe and the options are set", h->cycle_steps());
         // two edge pieces of `halo` rows and an interior; on the first / last rank the interior piece must hold
         // the whole top / bottom zone (5 + cycle rows with the Mur frame), which is written as a whole or not at
         // all.  Checked before anything is posted: the caller passes overlap != 0 only when EVERY slab is at least

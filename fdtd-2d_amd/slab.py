@@ -317,6 +317,7 @@ class SlabRunner:
             raise RuntimeError("SlabRunner.set_materials() must be called (by every rank) before run()")
         # steps per exchange: the longest pass every rank's engine runs (16 or 8), see _agree_cycle
         cycle = self.cycle
+        self._check_dft(cycle)       # before any stream switch or engine call: a refusal leaves everything as it was
         # grids below 2*(2*cycle+6) rows have no temporally blocked pass (the engine advances
         # them with its single-step kernels), hence nothing to issue in pieces
         can_overlap = self.overlap and self.rows >= 2 * (2 * cycle + 6)
@@ -364,7 +365,8 @@ class SlabRunner:
     # -- point probe ---------------------------------------------------------
     def set_probe(self, row, col, capacity):
         """Ez[row, col] after every step of the following run() calls; recorded on the rank that
-        owns the row (read it there with read_probe)."""
+        owns the row (read it there with read_probe).  EVERY rank calls it: the exchange mode and the
+        steps per exchange are settled again here, from what all ranks report."""
         self._probe_owner = self.r0 <= int(row) < self.r1
         if self.boundary == "pml" and self.world > 1:
             # the PML passes have no probe tile: the owner advances by single steps, and a rank that runs
@@ -373,6 +375,10 @@ class SlabRunner:
             self.overlap = False
         if self._probe_owner or self.world == 1:
             self.engine.set_probe(row, col, capacity)
+        if self.world > 1 and self.cycle is not None:
+            # a probe can shorten the owner's longest pass (float64's 16-step kernel has no probe tile, the PML passes
+            # have none at all): the steps per exchange are agreed again, like after set_option
+            self._agree_cycle()
         return self
 
     def read_probe(self, first=0, count=None):
@@ -381,6 +387,43 @@ class SlabRunner:
             return None
         with self._on_stream():
             return self.engine.read_probe(first, count)
+
+    # -- running Fourier transform -------------------------------------------
+    def set_dft(self, window, omegas, every=16):
+        """Engine.set_dft on the whole decomposed grid: window = (row0, col0, nrows, ncols) in global rows.  EVERY rank
+        calls it with the same arguments, also a rank that owns no window row (whether a cycle may run is decided from
+        the transform, and all ranks must decide alike).  The cycles of run() must not cross a sampled step: `every` has
+        to be a multiple of the steps per exchange, and every later run() has to start a multiple of them after this
+        call -- both are refused with ValueError otherwise.  omegas = () removes the transform."""
+        nfreq = int(np.asarray(omegas).size)
+        if self.world > 1 and nfreq:
+            if self.cycle is None:
+                raise RuntimeError("SlabRunner.set_materials() must be called (by every rank) before set_dft()")
+            if int(every) < 1 or int(every) % self.cycle != 0:
+                raise ValueError(f"the transform samples every {every} steps: not a multiple of the {self.cycle} steps "
+                                 f"per exchange")
+        with self._on_stream():
+            self.engine.set_dft(window, omegas, every)
+        self._dft = (int(every), self.steps_done) if nfreq else None
+        return self
+
+    def read_dft(self):
+        """complex128 (frequencies, window rows this rank owns, window columns); the ranks' parts concatenated along the
+        row axis are the whole window.  A rank without window rows returns shape (F, 0, ncols)."""
+        with self._on_stream():
+            return self.engine.read_dft()
+
+    def _check_dft(self, cycle):
+        """The two rules of set_dft for a run() that starts now, from quantities every rank shares."""
+        dft = getattr(self, "_dft", None)
+        if dft is None or self.world == 1 or not cycle:
+            return
+        every, step0 = dft
+        if every % cycle != 0:
+            raise ValueError(f"the transform samples every {every} steps: not a multiple of the {cycle} steps per exchange")
+        if (self.steps_done - step0) % cycle != 0:
+            raise ValueError(f"run() would start {self.steps_done - step0} steps after set_dft(): not a multiple of the "
+                             f"{cycle} steps per exchange, a cycle would cross a sampled step")
 
     def gather(self, dst=0):
         """Full fields on rank `dst` (None elsewhere).  Test/diagnostic helper."""

@@ -219,7 +219,11 @@ int fdtd2d_prepare_run(fdtd2d_t *h, int nsteps, int src_row, int src_col, int wi
  * the current fields, writing the other buffer set; pieces may go to different streams via
  * fdtd2d_set_stream); fdtd2d_pass_commit() makes the new set current once the pieces tile
  * everything a full pass writes.  Between the two, fdtd2d_halo_pack() packs from the NEW
- * set.  amps = nt amplitudes (the same for every piece) or NULL. */
+ * set.  amps = nt amplitudes (the same for every piece) or NULL.
+ * While a running Fourier transform is set (fdtd2d_set_dft) a pass must end ON the next sampled step or before it:
+ * fdtd2d_pass_rows returns FDTD2D_E_ARG for an nt larger than the steps left until that sample, before it launches
+ * anything -- nothing becomes pending, no state changes.  fdtd2d_pass_commit then takes the sample where the pass
+ * ends on one; it has no error of its own for this. */
 int fdtd2d_pass_rows(fdtd2d_t *h, int nt, int row_lo, int row_hi, int src_row, int src_col,
                      const double *amps);
 int fdtd2d_pass_commit(fdtd2d_t *h);
@@ -333,7 +337,16 @@ int fdtd2d_halo_unpack(fdtd2d_t *h, int side, const void *dev_buf);
  * overlap != 0 needs EVERY slab to be at least 2 * halo + 5 rows tall (two edge pieces of `halo` rows and an
  * interior that holds the whole top / bottom zone on the first / last rank); a rank whose slab is shorter
  * returns FDTD2D_E_ARG before it posts anything.  With the PML and a probe set no temporally blocked pass
- * exists (fdtd2d_info(CYCLE_STEPS) says 8, passes fail): run such handles with overlap = 0 on every rank.
+ * exists (fdtd2d_info(CYCLE_STEPS) says 8, passes fail): the caller must pass overlap = 0 on EVERY rank then, also on
+ * the ranks that do not hold the probe -- the handle that holds it returns an error for overlap != 0 before it posts
+ * anything, and a rank that ran plain cycles beside overlapped ones would post its transfers in another order.
+ * With a running Fourier transform (fdtd2d_set_dft) no full cycle may cross a sampled step.  Two rules ensure it, both
+ * checked before anything is posted, both FDTD2D_E_ARG: `every` is a multiple of `cycle`, and the call starts a
+ * multiple of `cycle` steps after the fdtd2d_set_dft call (so nsteps of an earlier fdtd2d_run_slab since then was
+ * one; a tail shorter than the cycle runs through fdtd2d_run, which cuts its passes itself, but it leaves the next
+ * call misaligned).  The decision uses the transform and the step count only, so EVERY rank must set the same
+ * transform at the same step -- also a rank that owns no row of the window (its handle keeps the transform and
+ * accumulates nothing).
  * The loop state belongs to the handle (no global table): distinct handles may run on distinct threads. */
 typedef int (*fdtd2d_exchange_fn)(void *ctx, void *send_top, void *recv_top, void *send_bottom,
                                   void *recv_bottom, long long bytes, void *stream);
@@ -358,8 +371,10 @@ int fdtd2d_run_slab(fdtd2d_t *h, int nsteps, int cycle, int overlap, int src_row
  * every `every`-th completed step n (counted by fdtd2d_info(STEP)) the engine adds Ez[i,j] * exp(-i * omega_k * n * dt) to
  * accumulator k of every cell of the window [row0, row0+nrows) x [col0, col0+ncols) (float64 accumulation on the device; a
  * slab accumulates the window rows it owns).  While a transform is set the loop cuts its temporally blocked passes at the
- * sampled steps (every = 16 costs nothing, every = 1 runs single steps); fdtd2d_run_slab needs `every` to be a multiple of
- * its cycle.  nfreq <= 16.  nfreq = 0 removes it.  fdtd2d_read_dft copies the accumulators: re and im, each nfreq x (owned
+ * sampled steps (every = 16 costs nothing, every = 1 runs single steps).  Passes issued in pieces cannot be cut: fdtd2d_pass_rows
+ * refuses a pass that would run over a sampled step, and fdtd2d_run_slab needs `every` to be a multiple of its cycle and every
+ * call to start a multiple of its cycle after this one (see there); on slabs every rank sets the same transform at the same
+ * step, whether it owns window rows or not.  nfreq <= 16.  nfreq = 0 removes it.  fdtd2d_read_dft copies the accumulators: re and im, each nfreq x (owned
  * window rows) x ncols float64, row-major; synchronous. */
 int fdtd2d_set_dft(fdtd2d_t *h, int row0, int col0, int nrows, int ncols, int nfreq, const double *omega, int every);
 int fdtd2d_read_dft(fdtd2d_t *h, double *re, double *im);

@@ -57,10 +57,40 @@ def worker(rank, world, port, job, outdir):
             assert runner.cycle == job["expect_cycle"], (runner.cycle, job["expect_cycle"])
         if job.get("expect_overlap") is not None:
             assert runner.overlap == job["expect_overlap"], (rank, runner.overlap)
-        done = 0
-        for n in job["chunks"]:
+        # dft = (window, omegas, every): runner.set_dft before chunk number dft_at (default: the first); dft_refused = an
+        # `every` that set_dft must refuse first.  refuse = the chunks whose run() must raise ValueError on this rank
+        # without an engine call; they are skipped (refused_rank{rank}.txt keeps the messages).
+        done, refused = 0, []
+        for i, n in enumerate(job["chunks"]):
+            if job.get("dft") and i == job.get("dft_at", 0):
+                win, om, every = job["dft"]
+                if job.get("dft_refused"):
+                    try:
+                        runner.set_dft(win, om, job["dft_refused"])
+                    except ValueError as exc:
+                        refused.append(f"set_dft: {exc}")
+                    else:
+                        raise AssertionError(f"rank {rank}: set_dft(every={job['dft_refused']}) was accepted")
+                runner.set_dft(win, om, every)
+            if i in job.get("refuse", ()):
+                calls = list(getattr(runner.engine, "calls", ()))
+                steps = runner.engine.step_count
+                try:
+                    runner.run(n, job["src"][0], job["src"][1], st["amps"][done:done + n])
+                except ValueError as exc:
+                    refused.append(f"chunk {i}: {exc}")
+                else:
+                    raise AssertionError(f"rank {rank}: run({n}) of chunk {i} was accepted")
+                assert calls == list(getattr(runner.engine, "calls", ())), (rank, "a refused run() called the engine")
+                assert steps == runner.engine.step_count == runner.steps_done == done, rank
+                continue
             runner.run(n, job["src"][0], job["src"][1], st["amps"][done:done + n])
             done += n
+        if refused:
+            with open(os.path.join(outdir, f"refused_rank{rank}.txt"), "w") as f:
+                f.write("\n".join(refused))
+        if job.get("dft"):
+            np.save(os.path.join(outdir, f"dft_rank{rank}.npy"), runner.read_dft())
         if job.get("probe"):
             pr = runner.read_probe()
             if pr is not None:

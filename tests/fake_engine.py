@@ -34,10 +34,15 @@ class FakeEngine:
         self.eps = self.mu = None
         self.valid = [max(0, self.row0 - self.halo) if slab is None else self.row0,
                       self.row0 + self.nrows]
+        self.step, self.dft, self.calls = 0, None, []      # calls: the names of the calls that advance or switch streams
 
     @property
     def stored_rows(self):
         return max(0, self.row0 - self.halo), min(self.rows, self.row0 + self.nrows + self.halo)
+
+    @property
+    def step_count(self):
+        return self.step
 
     @property
     def owned_rows(self):
@@ -48,7 +53,34 @@ class FakeEngine:
         return 3 * self.halo * self.cols * self.dtype.itemsize
 
     def set_stream(self, s):
-        pass
+        self.calls.append("set_stream")
+
+    # -- running transform (Engine.set_dft / read_dft): float64 sums over the owned window rows, sampled in run() ---------
+    def set_dft(self, window, omegas, every=16):
+        assert self.pending is None
+        w = np.asarray(omegas, dtype=np.float64).reshape(-1)
+        r0, c0, nr, nc = (int(v) for v in window)
+        lo, hi = max(r0, self.row0), min(r0 + nr, self.row0 + self.nrows)
+        self.dft = None if not w.size else dict(rows=(lo, max(lo, hi)), cols=(c0, c0 + nc), om=w, every=int(every), step0=self.step,
+                                                acc=np.zeros((w.size, max(0, hi - lo), nc), np.complex128))
+        return self
+
+    def read_dft(self):
+        return self.dft["acc"].copy()
+
+    def _dft_gap(self):
+        d = self.dft
+        return 1 << 30 if d is None else d["every"] - (self.step - d["step0"]) % d["every"]
+
+    def _dft_sample(self):
+        d = self.dft
+        if d is None or (self.step - d["step0"]) % d["every"]:
+            return
+        (lo, hi), (c0, c1) = d["rows"], d["cols"]
+        w = self.Ez[lo:hi, c0:c1].astype(np.float64)
+        for f, om in enumerate(d["om"]):
+            t = om * (self.step * self.dt)
+            d["acc"][f] += w * np.cos(t) + 1j * (w * -np.sin(t))
 
     def set_option(self, max_pass_steps=None, **_):
         if max_pass_steps is not None:
@@ -138,10 +170,12 @@ class FakeEngine:
     pending = None
 
     def pass_rows(self, nt, row_lo, row_hi, src_row=0, src_col=0, amps=None):
+        self.calls.append("pass_rows")
+        assert nt <= self._dft_gap(), "the pass would run over a step the transform samples"
         if self.pending is None:
             keep = (self.Ez, self.Hx, self.Hy, list(self.valid))
             self.Ez, self.Hx, self.Hy = self.Ez.copy(), self.Hx.copy(), self.Hy.copy()
-            self.run(nt, src_row, src_col, amps)
+            self._advance(nt, src_row, src_col, amps)
             new = (self.Ez, self.Hx, self.Hy)
             self.Ez, self.Hx, self.Hy, self.valid = keep
             self.pending = dict(new=new, rows=[], nt=nt, amps=None if amps is None else np.array(amps[:nt]))
@@ -161,12 +195,18 @@ class FakeEngine:
         self.Ez, self.Hx, self.Hy = p["new"]
         self.valid = [self.row0, self.row0 + self.nrows]
         self.pending = None
+        self.step += p["nt"]
+        self._dft_sample()                 # the pass ended on the sampled step or before it
 
     def set_source_extent(self, nrows=1, ncols=1):
         self.extent = (int(nrows), int(ncols))
         return self
 
     def run(self, nsteps, src_row=0, src_col=0, amps=None):
+        self.calls.append("run")
+        self._advance(nsteps, src_row, src_col, amps, count=True)
+
+    def _advance(self, nsteps, src_row=0, src_col=0, amps=None, count=False):
         lo = 0 if self.row0 == 0 else self.valid[0]
         hi = self.rows if self.row0 + self.nrows == self.rows else self.valid[1]
         need_lo = 0 if self.row0 == 0 else self.row0 - nsteps
@@ -182,4 +222,7 @@ class FakeEngine:
                 r0, r1 = max(src_row, slo), min(src_row + nr, shi)
                 if r0 < r1:
                     onp.add_source(self.Ez, r0, src_col, a[n], (r1 - r0, nc))
+            if count:
+                self.step += 1
+                self._dft_sample()
         self.valid = [self.row0, self.row0 + self.nrows]

@@ -15,9 +15,17 @@ import numpy as np
 
 
 def run_local_slabs(fd, world, shape, dtype, boundary, st, nsteps, src, *, cycle_opt=None, overlap=True,
-                    materials="array", extent=None, pml=None, options=None):
-    """Returns (Ez, Hx, Hy) of the whole grid assembled from the ranks' owned rows, plus the cycle used.
-    st: dict with full-grid Ez, Hx, Hy, eps, mu, amps (float64; cast here)."""
+                    materials="array", extent=None, pml=None, options=None, setup=None, collect=None, between=None,
+                    chunks=None, overlap_arg=None):
+    """Returns (Ez, Hx, Hy) of the whole grid assembled from the ranks' owned rows, the cycle used, whether the cycles
+    overlapped and the passes launched per rank.  st: dict with full-grid Ez, Hx, Hy, eps, mu, amps (float64; cast here).
+
+    Hooks, each optional and called with (rank, engine): setup after the upload and before the transport is attached,
+    collect after the run and before the engine is closed.  chunks = [n0, n1, ...] (default [nsteps]): one run_slab call
+    each, all ranks meeting in between; between(rank, engine, i) runs in the rank's thread after chunk i, before that
+    meeting.  With a hook given a fifth item is returned: {"setup": [per rank], "collect": [per rank]}.  overlap_arg: the
+    overlap flag handed to run_slab where it is not the one worked out here.  When ranks fail, the first one's exception is
+    raised with all of them in its attribute per_rank = [(rank, exception), ...]."""
     import hipmem
     from fdtd2d_amd.slab import plan_slabs, HALO
     rows, cols = shape
@@ -44,6 +52,8 @@ def run_local_slabs(fd, world, shape, dtype, boundary, st, nsteps, src, *, cycle
         eng.upload(st["Ez"][r0:r1].astype(dt_), st["Hx"][r0:r1].astype(dt_),
                    st["Hy"][r0:min(r1, rows - 1)].astype(dt_))
         engines.append(eng)
+    # (the hook runs before the cycle is agreed: a probe can shorten the longest pass of the handle that holds it)
+    hooked = {"setup": [setup(k, eng) for k, eng in enumerate(engines)] if setup else [None] * world, "collect": [None] * world}
     cycle = min(halo, min(e.cycle_steps for e in engines))
     for e in engines:
         if e.cycle_steps != cycle:
@@ -76,13 +86,31 @@ def run_local_slabs(fd, world, shape, dtype, boundary, st, nsteps, src, *, cycle
     min_slab = min(b - a for a, b in plan)
     can_overlap = bool(overlap) and min_slab >= 2 * halo + 5 and rows >= 2 * (2 * cycle + 6)
 
+    chunks = [nsteps] if chunks is None else list(chunks)
+    assert sum(chunks) == nsteps
+    flag = can_overlap if overlap_arg is None else overlap_arg
+
+    # (a barrier of its own after every chunk: a rank that fails right after one must not break it for the ranks that are
+    # still leaving it -- it aborts the transport's barrier and the meetings still ahead of it)
+    meet = [threading.Barrier(world) for _ in chunks[1:]]
+
     def work(k):
+        i = 0
         try:
-            engines[k].run_slab(nsteps, cycle, can_overlap, src[0], src[1], st["amps"])
-            engines[k].sync()
+            done = 0
+            for i, n in enumerate(chunks):
+                engines[k].run_slab(n, cycle, flag, src[0], src[1], st["amps"][done:done + n])
+                engines[k].sync()
+                done += n
+                if i + 1 < len(chunks):
+                    if between:
+                        between(k, engines[k], i)
+                    meet[i].wait(timeout=120)
         except BaseException as exc:      # a rank that dies must not leave the others at the barrier
             errors.append((k, exc))
             barrier.abort()
+            for b in meet[i:]:
+                b.abort()
 
     threads = [threading.Thread(target=work, args=(k,)) for k in range(world)]
     for t in threads:
@@ -92,9 +120,13 @@ def run_local_slabs(fd, world, shape, dtype, boundary, st, nsteps, src, *, cycle
     if errors:
         for e in engines:
             e.close()
+        errors[0][1].per_rank = sorted(errors, key=lambda e: e[0])
         raise errors[0][1]
     parts = [e.download() for e in engines]
     launches = [e.info(16) for e in engines]
+    if collect:
+        hooked["collect"] = [collect(k, eng) for k, eng in enumerate(engines)]
     for e in engines:
         e.close()
-    return tuple(np.concatenate([p[k] for p in parts], axis=0) for k in range(3)), cycle, can_overlap, launches
+    out = tuple(np.concatenate([p[k] for p in parts], axis=0) for k in range(3)), cycle, can_overlap, launches
+    return out + (hooked,) if (setup or collect or between) else out

@@ -195,7 +195,8 @@ def test_running_fourier_transform_matches_oracle(tag, dtype, every, max_steps):
 
 def test_running_fourier_transform_on_slabs_needs_an_aligned_cycle():
     """A slab handle whose passes are issued in pieces: a 16-step pass may end on a sampled step (every = 16) but not run
-    over one (every = 10) -- the commit says so instead of silently losing samples; fdtd2d_run_slab refuses up front."""
+    over one (every = 10) -- fdtd2d_pass_rows says so before it launches anything, instead of the commit finding out with
+    the sample already lost; fdtd2d_run_slab refuses up front."""
     import fdtd2d_amd as fd
     r, c = 200, 300
     om = 2 * np.pi * np.array([30e9])
@@ -208,6 +209,8 @@ def test_running_fourier_transform_on_slabs_needs_an_aligned_cycle():
     with fd.Engine(r, c, 5e-14, 1e-4, dtype=np.float32, slab=(0, 100, 16)) as eng:
         eng.set_materials().set_option(max_pass_steps=16)
         eng.set_dft((10, 10, 50, 50), om, 10)
-        eng.pass_rows(16, 0, 100)
-        with pytest.raises(fd.Fdtd2dError):
+        with pytest.raises(fd.Fdtd2dError) as e:
+            eng.pass_rows(16, 0, 100)
+        assert e.value.code == -1 and eng.step_count == 0          # FDTD2D_E_ARG, nothing advanced
+        with pytest.raises(fd.Fdtd2dError, match="no partial pass is pending"):
             eng.pass_commit()

@@ -148,3 +148,55 @@ def test_four_and_eight_slabs(tmp_path, world, rows):
     job = dict(engine="fake", shape=(rows, c), dtype="float32", dt=DT, dx=DX, state=path, src=src,
                chunks=[16, 19], materials="array", overlap=True, cycle=16, expect_overlap=tall)
     _check(run_job(world, job, str(tmp_path)), st, "float32", n, src)
+
+
+# ---- the running transform on slabs: SlabRunner.set_dft / read_dft and the refusals of run() ----------------------------------
+
+DFT_WIN, DFT_OM = (30, 2, 50, 14), 2 * np.pi * np.array([13e9, 41e9])      # rows 30..79 of 111: over both cuts (37, 74)
+
+
+def _dft_job(tmp_path, cycle, chunks, every, **kw):
+    from test_gpu_consumers import dft_want
+    rows, c, n = (111 if cycle == 16 else 120), 18, sum(chunks)
+    st, path = _state(str(tmp_path), rows, c, rows + every, n, vary_mu=True)
+    src = (rows // 3, 5)
+    job = dict(engine="fake", shape=(rows, c), dtype="float32", dt=DT, dx=DX, state=path, src=src, chunks=chunks,
+               materials="array", overlap=True, cycle=cycle, expect_cycle=cycle, expect_overlap=True,
+               dft=(DFT_WIN, DFT_OM, every))
+    job.update(kw)
+    got = run_job(3, job, str(tmp_path))
+    seq = []
+    ref = [st[k].astype(np.float32) for k in ("Ez", "Hx", "Hy")]
+    onp.leapfrog(*ref, st["eps"].astype(np.float32), st["mu"].astype(np.float32), DT, DX, n, src[0], src[1], amps=st["amps"],
+                 on_step=lambda i, E, *_: seq.append(E.copy()))
+    parts = [np.load(os.path.join(str(tmp_path), f"dft_rank{k}.npy")) for k in range(3)]
+    return got, parts, seq, lambda upto, step0: dft_want(seq[:upto], DFT_WIN, DFT_OM, every, step0=step0)
+
+
+@pytest.mark.parametrize("cycle,chunks,every,dft_at", [(16, [50], 32, 0), (16, [50], 48, 0), (8, [50], 16, 0),
+                                                       (16, [16, 34], 16, 1), (16, [8, 40], 16, 1)])
+def test_slab_runner_transform_on_aligned_runs(tmp_path, cycle, chunks, every, dft_at):
+    """every = 32 and 48 on 16-step cycles, 16 on 8-step cycles, and a transform set after a first chunk of 16 or of 8
+    steps (the cycles are aligned to the step it was set at, not to step 0): run() accepts them, the fields equal the
+    oracle's and the ranks' read_dft() parts, along the row axis, are the float64 sum over its Ez sequence."""
+    n = sum(chunks)
+    got, parts, seq, want = _dft_job(tmp_path, cycle, chunks, every, dft_at=dft_at)
+    assert np.array_equal(got[0], seq[n - 1])
+    own = [(30, 37), (37, 74), (74, 80)] if cycle == 16 else [(30, 40), (40, 80), (80, 80)]
+    assert [p.shape for p in parts] == [(2, b - a, 14) for a, b in own]
+    w = want(n, chunks[0] if dft_at else 0)
+    assert np.abs(w).max() > 0 and np.abs(np.concatenate(parts, axis=1) - w).max() <= 1e-12 * np.abs(w).max()
+
+
+def test_slab_runner_refuses_a_transform_off_the_cycle_and_a_misaligned_run(tmp_path):
+    """set_dft(every = 8) on 16-step cycles raises ValueError.  With every = 16 a second chunk that starts 24 steps
+    after set_dft raises ValueError on every rank before any engine call (the harness compares the fake engine's record
+    of pass_rows / run / set_stream calls and the step counts before and after); the first chunk's results stay."""
+    got, parts, seq, want = _dft_job(tmp_path, 16, [24, 16], 16, refuse=[1], dft_refused=8)
+    for k in range(3):
+        text = open(os.path.join(str(tmp_path), f"refused_rank{k}.txt")).read().splitlines()
+        assert len(text) == 2 and text[0].startswith("set_dft: ") and "not a multiple of the 16 steps" in text[0], text
+        assert text[1].startswith("chunk 1: ") and "24 steps after set_dft" in text[1], text
+    assert np.array_equal(got[0], seq[23])
+    w = want(24, 0)
+    assert np.abs(w).max() > 0 and np.abs(np.concatenate(parts, axis=1) - w).max() <= 1e-12 * np.abs(w).max()
