@@ -36,6 +36,9 @@ E_ARG, E_NODEVICE, E_NOMEM, E_STATE, E_COURANT = -1, -2, -3, -4, -5
  INFO_LAST_PASS_STEPS, INFO_LAST_SIDE_WAVES, INFO_LAST_XCD_MAP) = range(25)
 (INFO_WINDOW_ROW_LO, INFO_WINDOW_ROW_HI, INFO_WINDOW_COL_LO, INFO_WINDOW_COL_HI, INFO_WINDOWED_LAUNCHES,
  INFO_WINDOW_ENABLED) = range(25, 31)
+# what the last windowed pass launched (read-only; fdtd2d.h)
+(INFO_WIN_BAND_ROWS, INFO_WIN_WAVES, INFO_WIN_STRIP_FIRST, INFO_WIN_INNER, INFO_WIN_N_SRC, INFO_WIN_EDGES, INFO_WIN_ZTOP,
+ INFO_WIN_ZBOT, INFO_WIN_XCD_MAP, INFO_WIN_XCD_PAD, INFO_WIN_EDGE_ROWS) = range(31, 42)
 
 (BATCH_INFO_COUNT, BATCH_INFO_ROWS, BATCH_INFO_COLS, BATCH_INFO_DTYPE, BATCH_INFO_STEP, BATCH_INFO_RESIDENT,
  BATCH_INFO_LAUNCHES, BATCH_INFO_RESIDENT_MAX_CELLS, BATCH_INFO_LDS_BYTES, BATCH_INFO_PITCH) = range(10)

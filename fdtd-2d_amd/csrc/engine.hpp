@@ -227,6 +227,11 @@ struct fdtd2d {
     bool aw_ptr_out = false;     // fdtd2d_device_ptr handed a pointer out: the caller may write any cell at any time, so
                                  // the automatic mode stays off (setting the option to 1 takes the promise back)
     long long windowed_launches = 0;
+    // what the last windowed pass launched (FDTD2D_INFO_WIN_*; filled by launch_pass_impl, read by fdtd2d_info only)
+    struct WinLast {
+        int band_rows = 0, waves = 0, strip_first = 0, inner = 0, n_src = 0, edges = 0, ztop = 0, zbot = 0, xcd_map = 0,
+            xcd_pad = 0, edge_rows = 0;
+    } win_last;
     // (FDTD2D_INFO_WINDOW_ENABLED.)  The automatic mode is off for a handle whose launches the caller pins with
     // fdtd2d_set_shape -- such a caller measures or replays the whole-grid launch of that shape -- and for one whose
     // device pointers are out.

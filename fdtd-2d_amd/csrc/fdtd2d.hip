@@ -716,6 +716,17 @@ long long fdtd2d_info(const fdtd2d_t *h, int what)
     case FDTD2D_INFO_WINDOW_COL_HI: return h->aw.support.empty() ? 0 : h->aw.support.c1;
     case FDTD2D_INFO_WINDOWED_LAUNCHES: return h->windowed_launches;
     case FDTD2D_INFO_WINDOW_ENABLED: return h->window_enabled() ? 1 : 0;
+    case FDTD2D_INFO_WIN_BAND_ROWS: return h->win_last.band_rows;
+    case FDTD2D_INFO_WIN_WAVES: return h->win_last.waves;
+    case FDTD2D_INFO_WIN_STRIP_FIRST: return h->win_last.strip_first;
+    case FDTD2D_INFO_WIN_INNER: return h->win_last.inner;
+    case FDTD2D_INFO_WIN_N_SRC: return h->win_last.n_src;
+    case FDTD2D_INFO_WIN_EDGES: return h->win_last.edges;
+    case FDTD2D_INFO_WIN_ZTOP: return h->win_last.ztop;
+    case FDTD2D_INFO_WIN_ZBOT: return h->win_last.zbot;
+    case FDTD2D_INFO_WIN_XCD_MAP: return h->win_last.xcd_map;
+    case FDTD2D_INFO_WIN_XCD_PAD: return h->win_last.xcd_pad;
+    case FDTD2D_INFO_WIN_EDGE_ROWS: return h->win_last.edge_rows;
     default: return FDTD2D_E_ARG;
     }
 }

@@ -105,6 +105,9 @@ int launch_pass_impl(fdtd2d *h, fdtd::PassParams<T> &p, const fdtd_aw::Launch *w
         p.main_pad = (int)((8 - front % 8) % 8);
         bulk = 2LL * p.nbands_e + (long long)p.n_src * p.nbands_s + p.main_pad + 8LL * p.main_per;
     }
+    if (win)        // the path a test can assert (FDTD2D_INFO_WIN_*): as decoded by strip_of_block and the zone tiles
+        h->win_last = fdtd2d::WinLast{p.band_rows, nw_now, p.strip_first, win->n_inner, p.n_src, win->edges ? 1 : 0,
+                                      p.zone_top ? 1 : 0, p.zone_bot ? 1 : 0, p.xcd_map, p.main_pad, p.band_rows_e};
     if (bulk + zones == 0) return 0;
     if constexpr (NT >= 8) {
         if (h->use_level_split(NT, p.band_lo, p.band_hi)) {     // 4 waves per (band, strip), 2 levels each

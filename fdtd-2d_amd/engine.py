@@ -509,6 +509,15 @@ class Engine:
         return self.info(_abi.INFO_WINDOWED_LAUNCHES)
 
     @property
+    def last_window_launch(self) -> dict:
+        """What the last windowed pass launched (all 0 before the first): band_rows, waves, strip_first, inner (strips of
+        the inner run, source strips included), n_src, edges, ztop, zbot, xcd_map, xcd_pad, edge_rows.  last_shape
+        reports the whole-grid shape after such a pass; this is the window's own."""
+        keys = ("band_rows", "waves", "strip_first", "inner", "n_src", "edges", "ztop", "zbot", "xcd_map", "xcd_pad",
+                "edge_rows")
+        return {k: self.info(_abi.INFO_WIN_BAND_ROWS + n) for n, k in enumerate(keys)}
+
+    @property
     def window_enabled(self) -> bool:
         """Whether run() may launch windows now: the option, the size rule of its automatic mode, and what switches
         that mode off for a handle (a launch shape given with set_shape, a pointer handed out by device_ptr)."""

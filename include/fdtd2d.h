@@ -98,6 +98,19 @@ typedef struct fdtd2d fdtd2d_t;
 #define FDTD2D_INFO_WINDOW_ENABLED  30 /* 1 while fdtd2d_run may launch windows on this handle: the option, the size
                                          rule of its automatic mode, and what ends that mode for a handle (a shape given
                                          with fdtd2d_set_shape, a pointer handed out by fdtd2d_device_ptr) */
+/* 31-41: what the last pass that launched a window (29 counted it) really launched, read-only, for tests that assert the
+   path they took -- fdtd2d_last_shape deliberately reports the whole-grid shape there.  All 0 before the first one. */
+#define FDTD2D_INFO_WIN_BAND_ROWS   31 /* band height of its inner strips (given, or made by the rule of a window) */
+#define FDTD2D_INFO_WIN_WAVES       32 /* its waves per (band, strip): 1, 4 or 8 */
+#define FDTD2D_INFO_WIN_STRIP_FIRST 33 /* first strip of its run of inner strips */
+#define FDTD2D_INFO_WIN_INNER       34 /* strips of that run, those that hold source columns included (0: none) */
+#define FDTD2D_INFO_WIN_N_SRC       35 /* strips of the run that got short bands around the source rows: 0, 1 or 2 */
+#define FDTD2D_INFO_WIN_EDGES       36 /* 1 if the first and the last strip were launched */
+#define FDTD2D_INFO_WIN_ZTOP        37 /* 1 if the zone tiles of the top rows were launched */
+#define FDTD2D_INFO_WIN_ZBOT        38 /* 1 if those of the bottom rows were */
+#define FDTD2D_INFO_WIN_XCD_MAP     39 /* 1 if its inner tasks were dealt out XCD by XCD */
+#define FDTD2D_INFO_WIN_XCD_PAD     40 /* empty workgroups in front of them then (0..7) */
+#define FDTD2D_INFO_WIN_EDGE_ROWS   41 /* band height of its first / last strip */
 
 /* ---- lifetime ------------------------------------------------------------------ */
 

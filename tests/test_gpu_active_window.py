@@ -4,7 +4,10 @@ the bands and strips the fields can have reached.
 Every case forces active_window=1 (the automatic mode only starts at 4 Mi cells; one case below is that large) and
 compares EVERY cell of Ez, Hx and Hy with the oracle by np.array_equal -- which treats -0 and +0 alike, the contract of
 the window: a cell it never writes stays +0 where the dense sweep may compute -0.  Grids are a few strips wide (a strip
-writes 224 columns in float32 16-step passes, 96 in float64) so that a window is a real restriction."""
+writes 224 columns in float32 16-step passes, 96 in float64) so that a window is a real restriction.
+
+Every case here runs at a Courant number of 0.15, where the field underflows some 30 cells from a point source: the outer
+part of these windows holds zeros.  tests/test_gpu_active_window_filled.py runs the window where the field fills it."""
 import functools
 
 import numpy as np
