@@ -63,6 +63,10 @@ BATCH_INFO_DISPERSIVE = 19
 # include/fdtd2d_batch_dispersive_adjoint.h
 BATCH_INFO_HELD_DISPERSIVE_WINDOW = 20
 BATCH_MAX_PRODUCT_SETS = 3
+# include/fdtd2d_batch_flux.h
+BATCH_INFO_FLUX_LINES, BATCH_INFO_FLUX_LDS = 21, 22
+BATCH_OPT_FLUX_LDS = 3
+BATCH_MAX_FLUX_LINES, BATCH_MAX_FLUX_FREQS = 4, 16
 
 _vp, _i, _d, _ll = C.c_void_p, C.c_int, C.c_double, C.c_longlong
 
@@ -233,6 +237,14 @@ BATCH_DISPERSIVE_ADJOINT_SIGNATURES = {
                                                     C.POINTER(_d)]),
 }
 
+# every symbol include/fdtd2d_batch_flux.h declares (flux lines of a PML or periodic batch: the transforms of Ez and of
+# the tangential H on up to 4 lines, and the power that crosses them per frequency)
+BATCH_FLUX_SIGNATURES = {
+    "fdtd2d_batch_set_flux_lines": (_i, [_vp, _i, C.POINTER(_i), _i, C.POINTER(_d), _i]),
+    "fdtd2d_batch_read_flux_lines": (_i, [_vp, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_flux": (_i, [_vp, C.POINTER(_d)]),
+}
+
 # transport callback of fdtd2d_slab_attach
 EXCHANGE_FN = C.CFUNCTYPE(_i, _vp, _vp, _vp, _vp, _vp, _ll, _vp)
 
@@ -286,7 +298,7 @@ def load():
                                    **BATCH_BLOCH_SIGNATURES, **BATCH_BLOCH_ADJOINT_SIGNATURES,
                                    **BATCH_DISPERSIVE_SIGNATURES, **BATCH_LATTICE_SIGNATURES,
                                    **BATCH_BLOCH_DISPERSIVE_SIGNATURES,
-                                   **BATCH_DISPERSIVE_ADJOINT_SIGNATURES}.items():
+                                   **BATCH_DISPERSIVE_ADJOINT_SIGNATURES, **BATCH_FLUX_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

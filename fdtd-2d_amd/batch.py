@@ -64,6 +64,38 @@ def _probe_cells(cells, count):
     return np.ascontiguousarray(c, dtype=np.int32)
 
 
+def _flux_lines(lines, omegas, every, count, rows, cols, periodic):
+    """The arguments of set_flux_lines, checked on the host as the library would refuse them: ((N, 4) int32 lines as
+    {orientation, index, first, count}, (B, F) float64 omegas, every)."""
+    lines = list(lines)
+    if not 1 <= len(lines) <= _abi.BATCH_MAX_FLUX_LINES:
+        raise ValueError(f"flux lines: 1..{_abi.BATCH_MAX_FLUX_LINES} lines, got {len(lines)}")
+    out = np.empty((len(lines), 4), np.int32)
+    for k, line in enumerate(lines):
+        if len(line) != 4 or line[0] not in ("row", "col"):
+            raise ValueError(f'flux line {k}: ("row", i, c0, nc) or ("col", j, r0, nr), got {line!r}')
+        col = line[0] == "col"
+        at, first, n = (int(v) for v in line[1:])
+        if not col and not 1 <= at <= rows - 2:
+            raise ValueError(f"flux line {k}: row {at} outside 1..{rows - 2}")
+        lo = 0 if periodic else 1
+        if col and not lo <= at <= cols - 2:
+            raise ValueError(f"flux line {k}: column {at} outside {lo}..{cols - 2}"
+                             + (f" (column {cols - 1} is the image of column 0)" if periodic else ""))
+        extent = rows if col else cols - 1 if periodic else cols
+        if n < 1 or first < 0 or first + n > extent:
+            raise ValueError(f"flux line {k}: cells [{first}, {first} + {n}) are empty or run past {extent}")
+        out[k] = (int(col), at, first, n)
+    w = _window_omegas(omegas, count)
+    if not 1 <= w.shape[1] <= _abi.BATCH_MAX_FLUX_FREQS:
+        raise ValueError(f"flux omegas must hold 1..{_abi.BATCH_MAX_FLUX_FREQS} frequencies, got {w.shape[1]}")
+    if not np.all(np.isfinite(w)):
+        raise ValueError("flux omegas must be finite")
+    if int(every) < 1:
+        raise ValueError(f"every must be >= 1, got {every}")
+    return out, w, int(every)
+
+
 def pml_fits(rows, cols, L, periodic=False):
     """Whether an L-cell layer fits a rows x cols member (the rule of fdtd2d_set_pml / fdtd2d_batch_set_pml).
     periodic: the layer of a batch with periodic columns, which lies on rows alone."""
@@ -119,6 +151,7 @@ class BatchEngine:
         self._pml_L = 0               # the layer's depth
         self._win = None              # (F, nrows, ncols) of the window DFT
         self._nprobe = 0
+        self._flux = None             # ((N, 4) lines, (B, F) omegas) of the flux lines
         self._npoint = (0, 0)         # (P, K) of the point sources
         self._bloch = None            # (c, s): the (B,) rotations of a Bloch phase
         self._phi = None              # the phases as given (None with rotation=)
@@ -826,6 +859,56 @@ class BatchEngine:
         self._ck(self._lib.fdtd2d_batch_set_option(self._h, _abi.BATCH_OPT_DFT_WINDOW_LDS, -1 if allow else 0))
         return self
 
+    # -- flux lines (fdtd2d_batch_flux.h) --------------------------------------------------------------
+    def set_flux_lines(self, lines, omegas, every=1):
+        """Flux monitors on a "pml" or "periodic" engine: up to 4 lines, ("row", i, c0, nc) counting power towards
+        increasing row or ("col", j, r0, nr) towards increasing column, the same for all members, at up to 16 angular
+        frequencies per member: omegas (F,) for every member or (B, F).  After every `every`-th step n (counted from
+        this call) the engine adds Ez * exp(-1j * omega * n * dt) and Ht * exp(-1j * omega * n * dt) on the line cells in
+        float64, Ht being the tangential H of the step's H half-step centred on the cell (fdtd2d_batch_flux.h).  lines
+        None or empty removes them.  A lossless "pml" engine runs the lossy kernels with a zero conductivity while
+        lines are set (bit-identical fields, a smaller resident capacity: see resident_max_cells)."""
+        if lines is None or len(lines) == 0:
+            self._ck(self._lib.fdtd2d_batch_set_flux_lines(self._h, 0, None, 0, None, 1))
+            self._flux = None
+            return self
+        ln, w, every = _flux_lines(lines, omegas, every, self.count, self.rows, self.cols, self.boundary == "periodic")
+        self._ck(self._lib.fdtd2d_batch_set_flux_lines(self._h, len(ln), ln.ctypes.data_as(C.POINTER(C.c_int)),
+                                                       int(w.shape[1]), _dptr(w), every))
+        self._flux = (ln, w)
+        return self
+
+    def read_flux_lines(self, raw=False):
+        """(Ez_hat, Ht_hat), each complex128 (B, F, cells): the transforms on the line cells, lines concatenated in the
+        order given.  Ht_hat carries the half-step factor exp(+1j * omega * dt / 2) (the H of a step lives half a step
+        before its Ez) unless raw, which returns the sums as accumulated."""
+        ln, w = self._flux or (np.zeros((0, 4), np.int32), np.zeros((self.count, 0)))
+        shape = (self.count, w.shape[1], int(ln[:, 3].sum()))
+        a = [np.empty(shape) if self._flux is not None else np.empty(1) for _ in range(4)]
+        self._ck(self._lib.fdtd2d_batch_read_flux_lines(self._h, *(_dptr(x) for x in a)))
+        e, h = a[0] + 1j * a[1], a[2] + 1j * a[3]
+        return (e, h) if raw else (e, h * np.exp(0.5j * w * self.dt)[:, :, None])
+
+    def flux(self) -> np.ndarray:
+        """float64 (B, N, F): the power that crosses each line per frequency, P = s * dx * sum over the line's cells of
+        Re(Ez_hat * conj(Ht_hat)), s = +1 for a row line and -1 for a column line, formed on the device.  No factor 1/2
+        and no normalisation: take ratios."""
+        ln, w = self._flux or (np.zeros((0, 4), np.int32), np.zeros((self.count, 0)))
+        out = np.empty((self.count, len(ln), w.shape[1]))
+        buf = out if out.size else np.empty(1)     # a refused read still passes a valid pointer
+        self._ck(self._lib.fdtd2d_batch_flux(self._h, _dptr(buf)))
+        return out
+
+    @property
+    def flux_lines_in_lds(self) -> bool:
+        """Whether the flux lines' sums live in LDS on the resident path now."""
+        return bool(self.info(_abi.BATCH_INFO_FLUX_LDS))
+
+    def set_flux_lds(self, allow=True):
+        """allow False keeps the flux lines' sums in global memory (results never depend on it)."""
+        self._ck(self._lib.fdtd2d_batch_set_option(self._h, _abi.BATCH_OPT_FLUX_LDS, -1 if allow else 0))
+        return self
+
     def set_probes(self, cells, capacity):
         """Record Ez after the source of every following step at up to 64 cells per member: cells (P, 2) {row, col}
         for every member or (B, P, 2); `capacity` float64 samples per probe, sample 0 = the next step.  None (or no
@@ -1137,7 +1220,7 @@ def _waveform_amps(kind, fc, nsteps, dt):
 def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker", dt=5e-14, dx=1e-4,
                    dtype=np.float64, boundary="mur", omega=None, dft_every=1, device=0, pml_cells=40,
                    dft_window=None, window_omegas=None, probes=None, bloch_phase=None, source_weights=None,
-                   dispersion=None, bloch_dispersion=None):
+                   dispersion=None, bloch_dispersion=None, flux_lines=None, flux_omegas=None):
     """run_fdtd for B members of one shape at once: zero fields, Courant check per member, nsteps of
     H -> E -> source with t = i*dt.
 
@@ -1159,7 +1242,9 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
     (set_lattice_phase; default zero); every returned array is complex.  A band-path sweep is one call: B copies of the
     unit cell with the phases of the k-points along the path.  bloch_dispersion = (wp2, gamma, omega0) as
     set_bloch_dispersion takes them: the pole of a run with complex fields (boundary "periodic" with bloch_phase, or
-    "lattice"): a metal unit cell swept over the angle of incidence or along a band path.
+    "lattice"): a metal unit cell swept over the angle of incidence or along a band path.  flux_lines with flux_omegas
+    (boundary "pml" or "periodic", not with bloch_phase): flux monitors as set_flux_lines takes them, sampled every
+    `dft_every` steps; the float64 (B, N, F) flux array of BatchEngine.flux() is then appended to the returned tuple.
     """
     from .api import MU0
     eps = np.asarray(eps)
@@ -1221,6 +1306,14 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
         if dispersion is not None:
             raise ValueError("bloch_dispersion and dispersion exclude each other")
     win, wom, cells = _check_monitors(B, R, Cc, dft_window, window_omegas, probes, dft_every)
+    if (flux_lines is None) != (flux_omegas is None):
+        raise ValueError("flux_lines and flux_omegas must be given together")
+    if flux_lines is not None:
+        if boundary not in ("pml", "periodic"):
+            raise ValueError(f'flux_lines needs boundary="pml" or "periodic", not {boundary!r}')
+        if bloch_phase is not None:
+            raise ValueError("flux_lines is not available with bloch_phase")
+        _flux_lines(flux_lines, flux_omegas, dft_every, B, R, Cc, boundary == "periodic")
     if bloch_phase is not None:
         if win is not None and win[1] + win[3] > Cc - 1:
             raise ValueError(f"dft_window {win} touches column {Cc - 1}, the image of column 0: not with bloch_phase")
@@ -1253,6 +1346,8 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
             eng.set_dft_window(win, wom, dft_every)
         if cells is not None:
             eng.set_probes(cells, max(1, int(nsteps)))
+        if flux_lines is not None:
+            eng.set_flux_lines(flux_lines, flux_omegas, dft_every)
         eng.run(nsteps, None if waveform is None else _waveform_amps(waveform, fcs, nsteps, dt))
         out = eng.download()
         if omega is not None:
@@ -1261,6 +1356,8 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
             out += (eng.read_dft_window(),)
         if cells is not None:
             out += (eng.read_probes(0, int(nsteps)),)
+        if flux_lines is not None:
+            out += (eng.flux(),)
         return out
 
 

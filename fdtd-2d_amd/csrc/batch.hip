@@ -20,6 +20,8 @@
 // With the pole of fdtd2d_batch_bloch_dispersive.h a Bloch or lattice batch takes the kernels of
 // batch_bloch_dispersive.hip; the pole shares the host state of fdtd2d_batch_dispersive.h's (`dcj` is set too) and adds
 // the imaginary parts of Jh and Q.
+// With flux lines (fdtd2d_batch_flux.h) a PML or periodic batch takes the kernels of batch_flux.hip, with or without a
+// pole; a lossless PML batch then holds an all-zero conductivity of its own (sigma_implicit), like a batch with a pole.
 #include "../../include/fdtd2d.h"
 #include "../../include/fdtd2d_batch_adjoint.h"
 #include "../../include/fdtd2d_batch_bloch.h"
@@ -28,6 +30,7 @@
 #include "../../include/fdtd2d_batch_design.h"
 #include "../../include/fdtd2d_batch_dispersive.h"
 #include "../../include/fdtd2d_batch_dispersive_adjoint.h"
+#include "../../include/fdtd2d_batch_flux.h"
 #include "../../include/fdtd2d_batch_lattice.h"
 #include "../../include/fdtd2d_batch_lossy.h"
 #include "../../include/fdtd2d_batch_monitor.h"
@@ -52,6 +55,7 @@
 #include "kernels_batch_bloch_dispersive.hpp"
 #include "kernels_batch_design.hpp"
 #include "kernels_batch_dispersive.hpp"
+#include "kernels_batch_flux.hpp"
 #include "kernels_batch_lattice.hpp"
 #include "kernels_batch_lossy.hpp"
 #include "kernels_batch_monitor.hpp"
@@ -143,6 +147,14 @@ struct fdtd2d_batch {
     int *probe_cells = nullptr;           // count x nprobe, row * C + col
     double *probe_trace = nullptr;
     long long probe_cap = 0, probe_step0 = 0;
+    // flux lines (fdtd2d_batch_set_flux_lines): per member Ez re[nff][cells], Ez im, Ht re, Ht im, cells = the lines'
+    // counts together; flux_line holds {orientation, index, first, count} per line
+    int flux_nl = 0, flux_nff = 0, flux_every = 1, flux_cells = 0;
+    int flux_line[4 * FDTD2D_BATCH_MAX_FLUX_LINES] = {};
+    long long flux_step0 = 0;
+    double *flux_acc = nullptr, *flux_omega = nullptr;
+    double *flux_ph = nullptr;            // streamed path: count x nff phasors of the step being completed
+    int flux_lds_opt = -1;                // -1: sums in LDS when they fit, 0: never
     double *win_held = nullptr;           // fdtd2d_batch_hold_dft_window: a copy of win_acc
     double *win_held_disp = nullptr;      // fdtd2d_batch_hold_dispersive_window: a copy of win_acc while a pole is set
     // point sources (fdtd2d_batch_set_point_sources), every table in the resident owners' order
@@ -323,10 +335,11 @@ size_t lds_field_bytes(const fdtd2d_batch *b)
 }
 
 // window DFT: the phasor table (part of the capacity rule) and the accumulators (in LDS only when they fit too);
-// point sources: the sums of a step, behind the phasor table
+// flux lines: their phasor table behind the window's; point sources: the sums of a step, behind the phasor tables
 size_t lds_table_bytes(const fdtd2d_batch *b)
 {
-    return 16 * (size_t)b->win_nf + 8 * (size_t)b->npts + (b->bloch ? 16 * (size_t)(b->cols - 1) : 0);
+    return 16 * (size_t)b->win_nf + 16 * (size_t)(b->flux_nl ? b->flux_nff : 0) + 8 * (size_t)b->npts +
+           (b->bloch ? 16 * (size_t)(b->cols - 1) : 0);
 }
 size_t win_acc_bytes(const fdtd2d_batch *b) { return 16 * (size_t)b->win_nf * b->win_nr * b->win_nc; }
 size_t lds_acc_bytes(const fdtd2d_batch *b) { return (b->bloch ? 2 : 1) * win_acc_bytes(b); }   // both parts
@@ -336,9 +349,19 @@ bool win_acc_in_lds(const fdtd2d_batch *b)
            lds_field_bytes(b) + lds_table_bytes(b) + lds_acc_bytes(b) <= fdtd::BATCH_LDS_LIMIT;
 }
 
+// flux lines: the sums of one member; in LDS behind the window's accumulators (wherever those live) when they fit too
+size_t flux_acc_bytes(const fdtd2d_batch *b) { return b->flux_nl ? 32 * (size_t)b->flux_nff * b->flux_cells : 0; }
+bool flux_acc_in_lds(const fdtd2d_batch *b)
+{
+    return b->flux_nl && b->flux_lds_opt != 0 &&
+           lds_field_bytes(b) + lds_table_bytes(b) + (win_acc_in_lds(b) ? lds_acc_bytes(b) : 0) + flux_acc_bytes(b) <=
+               fdtd::BATCH_LDS_LIMIT;
+}
+
 size_t lds_bytes(const fdtd2d_batch *b)
 {
-    return lds_field_bytes(b) + lds_table_bytes(b) + (win_acc_in_lds(b) ? lds_acc_bytes(b) : 0);
+    return lds_field_bytes(b) + lds_table_bytes(b) + (win_acc_in_lds(b) ? lds_acc_bytes(b) : 0) +
+           (flux_acc_in_lds(b) ? flux_acc_bytes(b) : 0);
 }
 
 // largest R*C whose arrays fit in one workgroup's LDS (materials as currently set; arrays before any call;
@@ -795,6 +818,92 @@ int run_dispersive(fdtd2d_batch *b, int nsteps, const double *amps, long long am
     return 0;
 }
 
+// ---- runs with flux lines (fdtd2d_batch_flux.h): the lossy PML, the periodic or the dispersive paths with the kernels
+// of batch_flux.hip, whose streamed H launches also write the lines' phasors
+fdtd::BatchFlux flux_view(const fdtd2d_batch *b)
+{
+    fdtd::BatchFlux f{};
+    f.acc = b->flux_acc;
+    f.omega = b->flux_omega;
+    f.ph = b->flux_ph;
+    f.step0 = b->flux_step0;
+    f.nl = b->flux_nl;
+    f.nff = b->flux_nff;
+    f.every = b->flux_every;
+    f.cells = b->flux_cells;
+    f.lds_acc = flux_acc_in_lds(b) ? 1 : 0;
+    int off = 0;
+    for (int k = 0; k < b->flux_nl; ++k) {
+        f.orient[k] = b->flux_line[4 * k];
+        f.index[k] = b->flux_line[4 * k + 1];
+        f.first[k] = b->flux_line[4 * k + 2];
+        f.count[k] = b->flux_line[4 * k + 3];
+        f.offset[k] = off;
+        off += f.count[k];
+    }
+    return f;
+}
+
+template <class T>
+int run_flux(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts)
+{
+    if (!b->ca || !b->ezx || !b->flux_acc || (b->dcj && (!b->djh || !b->dq || !b->da || !b->dck)))
+        return bfail(b, FDTD2D_E_STATE, "batch with flux lines without its arrays");
+    const fdtd::BatchFluxKernels &K = fdtd::batch_flux_kernels<T>();
+    const int per = b->periodic ? 1 : 0, disp = b->dcj ? 1 : 0;
+    fdtd::BatchPml<T> p = pml_view<T>(b);
+    fdtd::BatchMon m = mon_view(b);
+    fdtd::BatchFlux f = flux_view(b);
+    fdtd::BatchPts silent{};
+    if (!pts) pts = &silent;
+    fdtd::BatchDisp<T> d{(T *)b->djh, (T *)b->dq, (const T *)b->dcj, (const T *)b->da, (const T *)b->dck};
+    const T *ca = (const T *)b->ca;
+    if (use_resident(b)) {
+        const int cells = b->rows * b->cols, threads = resident_threads(cells);
+        const int per_thread = (cells + threads - 1) / threads;
+        const int mi = per_thread <= 4 ? 0 : per_thread <= 8 ? 1 : per_thread <= 16 ? 2 : -1;
+        if (mi < 0 || (disp && mi > 0))
+            return bfail(b, FDTD2D_E_STATE, "%d cells per thread exceed the resident kernel's %d", per_thread, disp ? 4 : 16);
+        const void *kern = disp ? K.resident_disp[per] : K.resident[per][mi];
+        const size_t lds = lds_bytes(b);
+        BCHK(b, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        int per_cu = 0, cus = 0;
+        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds));
+        BCHK(b, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
+        if (per_cu < 1) return bfail(b, FDTD2D_E_STATE, "flux resident kernel does not fit a CU (%zu B of LDS)", lds);
+        const long long round = (long long)per_cu * cus;
+        const int blocks = (int)(b->count < round ? b->count : round);
+        const int chunk = b->steps_per_launch > 0 ? b->steps_per_launch : nsteps;
+        for (int n = 0; n < nsteps; n += chunk) {
+            int n0 = n, nt = nsteps - n < chunk ? nsteps - n : chunk;
+            long long step_base = b->step;
+            fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+            v.ce = (const T *)b->cb;
+            void *args[] = {&v, &p, &m, pts, &d, &f, &ca, &n0, &nt, &step_base};
+            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads), args, lds);
+            if (rc) return rc;
+            b->launches++;
+            b->step += nt;
+        }
+        return 0;
+    }
+    const int cells = b->rows * b->cols;
+    const dim3 grid((cells + 255) / 256, b->count < 65535 ? b->count : 65535);
+    for (int n = 0; n < nsteps; ++n) {
+        fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+        v.ce = (const T *)b->cb;
+        long long step = b->step + 1;
+        int rc;
+        void *h_args[] = {&v, &p, &m, pts, &f, &n, &step};
+        void *e_args[] = {&v, &p, &m, pts, &d, &f, &ca, &n, &step};
+        if ((rc = launch_ptr(b, K.h[per], grid, dim3(256), h_args, 0))) return rc;
+        if ((rc = launch_ptr(b, K.e[per][disp], grid, dim3(256), e_args, 0))) return rc;
+        b->launches += 2;
+        b->step++;
+    }
+    return 0;
+}
+
 // ---- Bloch runs (fdtd2d_batch_bloch.h): the periodic paths with the complex-field kernels of batch_bloch.hip ----------
 template <class T> fdtd::BatchBloch<T> bloch_view(const fdtd2d_batch *b, bool conj)
 {
@@ -990,6 +1099,7 @@ int run_impl(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stri
     if (b->bdisp) return run_bloch_dispersive<T>(b, nsteps, amps, amp_stride);
     if (b->lattice) return run_lattice<T>(b, nsteps, amps, amp_stride);
     if (b->bloch) return run_bloch<T>(b, nsteps, amps, amp_stride);
+    if (b->flux_nl) return run_flux<T>(b, nsteps, amps, amp_stride, pts);
     if (b->dcj) return run_dispersive<T>(b, nsteps, amps, amp_stride, pts);
     if (b->periodic) return run_periodic<T>(b, nsteps, amps, amp_stride, pts);
     if (b->ca) return run_lossy<T>(b, nsteps, amps, amp_stride, pts);
@@ -1248,6 +1358,13 @@ int periodic_coefficients(fdtd2d_batch *b)
 int refuse_bloch(fdtd2d_batch *b, const char *what);
 
 constexpr double DISP_EPS0 = 8.85418e-12;     // the library's vacuum constant (the reference's literal)
+
+// what a batch with flux lines cannot do (fdtd2d_batch_flux.h, "Scope")
+int refuse_flux(fdtd2d_batch *b, const char *what)
+{
+    return bfail(b, FDTD2D_E_STATE, "%s is not available while flux lines are set: remove them first "
+                 "(fdtd2d_batch_set_flux_lines with nlines = 0)", what);
+}
 
 int refuse_dispersive(fdtd2d_batch *b, const char *what)
 {
@@ -1688,7 +1805,8 @@ void fdtd2d_batch_destroy(fdtd2d_batch_t *b)
                      &b->ez_im, &b->hx_im, &b->hy_im, &b->ezx_im, &b->rho, (void **)&b->bloch_w, (void **)&b->amps_im,
                      (void **)&b->win_acc_im, (void **)&b->probe_trace_im, &b->rho_conj, &b->rho_r,
                      (void **)&b->win_held_im, (void **)&b->win_held_disp,
-                     &b->djh, &b->dq, &b->dcj, &b->da, &b->dck, &b->djh_im, &b->dq_im})
+                     &b->djh, &b->dq, &b->dcj, &b->da, &b->dck, &b->djh_im, &b->dq_im,
+                     (void **)&b->flux_acc, (void **)&b->flux_omega, (void **)&b->flux_ph})
         release(p);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -1728,6 +1846,8 @@ long long fdtd2d_batch_info(const fdtd2d_batch_t *b, int what)
     case FDTD2D_BATCH_INFO_BLOCH: return b->bloch && !b->lattice ? 1 : 0;
     case FDTD2D_BATCH_INFO_DISPERSIVE: return b->dcj ? 1 : 0;
     case FDTD2D_BATCH_INFO_HELD_DISPERSIVE_WINDOW: return b->win_held_disp ? 1 : 0;
+    case FDTD2D_BATCH_INFO_FLUX_LINES: return b->flux_nl;
+    case FDTD2D_BATCH_INFO_FLUX_LDS: return use_resident(b) && flux_acc_in_lds(b) ? 1 : 0;
     default: return FDTD2D_E_ARG;
     }
 }
@@ -1747,6 +1867,10 @@ int fdtd2d_batch_set_option(fdtd2d_batch_t *b, int option, long long value)
     case FDTD2D_BATCH_OPT_DFT_WINDOW_LDS:
         if (value != -1 && value != 0) return bfail(b, FDTD2D_E_ARG, "window LDS must be -1 (auto) or 0 (never)");
         b->win_lds_opt = (int)value;
+        return 0;
+    case FDTD2D_BATCH_OPT_FLUX_LDS:
+        if (value != -1 && value != 0) return bfail(b, FDTD2D_E_ARG, "flux LDS must be -1 (auto) or 0 (never)");
+        b->flux_lds_opt = (int)value;
         return 0;
     default: return bfail(b, FDTD2D_E_ARG, "unknown option %d", option);
     }
@@ -1874,6 +1998,7 @@ int fdtd2d_batch_set_pml(fdtd2d_batch_t *b, const void *row_factors, const void 
     if (!row_factors && !col_factors && b->dcj)
         return refuse_dispersive(b, "removing the layer of a batch without periodic columns (a plain box has no "
                                     "dispersive kernels)");
+    if (!row_factors && !col_factors && b->flux_nl) return refuse_flux(b, "removing the layer of a batch without periodic columns");
     if (!row_factors && !col_factors) {     // remove the layer: a plain NONE batch again
         BCHK(b, hipStreamSynchronize(b->stream));
         for (void **p : {&b->ezx, &b->pml_row, &b->pml_col}) release(p);
@@ -1993,8 +2118,11 @@ int fdtd2d_batch_reset(fdtd2d_batch_t *b)
     if (b->probe_trace_im)
         BCHK(b, hipMemsetAsync(b->probe_trace_im, 0, (size_t)b->count * b->nprobe * b->probe_cap * sizeof(double),
                                b->stream));
+    if (b->flux_nl)
+        BCHK(b, hipMemsetAsync(b->flux_acc, 0, (size_t)b->count * flux_acc_bytes(b), b->stream));
     b->win_step0 = 0;
     b->probe_step0 = 0;
+    b->flux_step0 = 0;
     return 0;
 }
 
@@ -2580,7 +2708,7 @@ int fdtd2d_batch_set_conductivity(fdtd2d_batch_t *b, const void *sigma, int dtyp
         if (!b->ca) return 0;
         int rc = use_device(b);
         if (rc) return rc;
-        if (b->periodic || b->dcj) {        // a periodic or dispersive batch keeps its arrays, with ca = 1 and cb = ce
+        if (b->periodic || b->dcj || b->flux_nl) {   // such a batch keeps its arrays, with ca = 1 and cb = ce
             std::fill(b->sigma_host.begin(), b->sigma_host.end(), 0.0);
             b->sigma_implicit = true;
             return lossy_reform(b, 0, 0, b->rows, b->cols);
@@ -2617,7 +2745,7 @@ int fdtd2d_batch_set_dispersion(fdtd2d_batch_t *b, const void *wp2, int dtype, c
         if (rc) return rc;
         BCHK(b, hipStreamSynchronize(b->stream));
         disp_release(b);
-        if (b->sigma_implicit && !b->periodic) {     // the all-zero conductivity the pole brought
+        if (b->sigma_implicit && !b->periodic && !b->flux_nl) {     // the all-zero conductivity the pole brought
             release(&b->ca);
             release(&b->cb);
             b->sigma_host.clear();
@@ -2787,6 +2915,7 @@ int fdtd2d_batch_set_periodic(fdtd2d_batch_t *b, int on)
         return bfail(b, FDTD2D_E_STATE, "periodic columns need a batch created with FDTD2D_BOUNDARY_NONE: the Mur frame "
                      "and a periodic boundary exclude each other");
     if ((on != 0) == b->periodic) return 0;
+    if (b->flux_nl) return refuse_flux(b, "switching periodic columns");
     int rc = use_device(b);
     if (rc) return rc;
     BCHK(b, hipStreamSynchronize(b->stream));
@@ -2872,6 +3001,7 @@ int fdtd2d_batch_set_bloch(fdtd2d_batch_t *b, const double *cos_phi, const doubl
     if (!cos_phi && b->bdisp) return refuse_dispersive(b, "turning the Bloch phase off");
     if (!cos_phi) return b->bloch ? bloch_off(b) : 0;
     if (b->dcj && !b->bdisp) return refuse_dispersive(b, "a Bloch phase");
+    if (b->flux_nl) return refuse_flux(b, "a Bloch phase");
     if (!b->periodic)
         return bfail(b, FDTD2D_E_STATE, "a Bloch phase needs periodic columns: call fdtd2d_batch_set_periodic first");
     for (int m = 0; m < b->count; ++m)
@@ -3066,6 +3196,7 @@ int fdtd2d_batch_set_lattice(fdtd2d_batch_t *b, const double *cos_r, const doubl
     }
     if (b->bloch && !b->lattice) return refuse_bloch(b, "the lattice mode (turn the phase of fdtd2d_batch_set_bloch off)");
     if (b->dcj && !b->bdisp) return refuse_dispersive(b, "the lattice mode");
+    if (b->flux_nl) return refuse_flux(b, "the lattice mode");
     if (!b->periodic)
         return bfail(b, FDTD2D_E_STATE, "the lattice mode needs periodic columns: call fdtd2d_batch_set_periodic first");
     if (!b->have_mat) return bfail(b, FDTD2D_E_STATE, "materials not set: call fdtd2d_batch_set_materials first");
@@ -3344,6 +3475,130 @@ int fdtd2d_batch_sync(fdtd2d_batch_t *b)
     int rc = use_device(b);
     if (rc) return rc;
     BCHK(b, hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- fdtd2d_batch_flux.h ------------------------------------------------------------------------------------------
+
+extern "C" {
+
+int fdtd2d_batch_set_flux_lines(fdtd2d_batch_t *b, int nlines, const int *lines, int nfreq, const double *omega,
+                                int every)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (nlines < 0 || nlines > FDTD2D_BATCH_MAX_FLUX_LINES)
+        return bfail(b, FDTD2D_E_ARG, "nlines %d outside 0..%d", nlines, FDTD2D_BATCH_MAX_FLUX_LINES);
+    long long cells = 0;
+    if (nlines > 0) {
+        if (b->boundary != FDTD2D_BOUNDARY_NONE)
+            return bfail(b, FDTD2D_E_STATE, "flux lines need a PML or periodic batch: the kernels of the Mur frame carry none");
+        if (b->lattice) return bfail(b, FDTD2D_E_STATE, "flux lines are not available in the lattice mode");
+        if (b->bloch) return bfail(b, FDTD2D_E_STATE, "flux lines are not available with a Bloch phase");
+        if (!b->ezx && !b->periodic)
+            return bfail(b, FDTD2D_E_STATE, "flux lines need a PML layer (fdtd2d_batch_set_pml) or periodic columns");
+        if (nfreq < 1 || nfreq > FDTD2D_BATCH_MAX_FLUX_FREQS)
+            return bfail(b, FDTD2D_E_ARG, "nfreq %d outside 1..%d", nfreq, FDTD2D_BATCH_MAX_FLUX_FREQS);
+        if (!lines || !omega) return bfail(b, FDTD2D_E_ARG, "lines and omega must not be NULL");
+        if (every < 1) return bfail(b, FDTD2D_E_ARG, "every must be >= 1");
+        const int R = b->rows, C = b->cols;
+        for (int k = 0; k < nlines; ++k) {
+            const int o = lines[4 * k], at = lines[4 * k + 1], first = lines[4 * k + 2], n = lines[4 * k + 3];
+            if (o != 0 && o != 1) return bfail(b, FDTD2D_E_ARG, "line %d: orientation %d (0 row, 1 column)", k, o);
+            if (o == 0 && (at < 1 || at > R - 2))
+                return bfail(b, FDTD2D_E_ARG, "line %d: row %d outside 1..%d", k, at, R - 2);
+            const int lo = b->periodic ? 0 : 1;
+            if (o == 1 && (at < lo || at > C - 2))
+                return bfail(b, FDTD2D_E_ARG, "line %d: column %d outside %d..%d%s", k, at, lo, C - 2,
+                             b->periodic ? " (column C-1 is the image of column 0)" : "");
+            const int extent = o == 1 ? R : b->periodic ? C - 1 : C;
+            if (n < 1 || first < 0 || (long long)first + n > extent)
+                return bfail(b, FDTD2D_E_ARG, "line %d: cells [%d, %d + %d) are empty or run past %d", k, first, first, n,
+                             extent);
+            cells += n;
+        }
+        if (!b->have_mat) return bfail(b, FDTD2D_E_STATE, "materials not set: call fdtd2d_batch_set_materials first");
+    } else if (!b->flux_nl) {
+        return 0;
+    }
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));   // a running launch may still use the old lines
+    if (nlines == 0) {
+        for (void **p : {(void **)&b->flux_acc, (void **)&b->flux_omega, (void **)&b->flux_ph}) release(p);
+        b->flux_nl = b->flux_nff = b->flux_cells = 0;
+        if (b->sigma_implicit && !b->periodic && !b->dcj) {   // the all-zero conductivity the lines brought
+            release(&b->ca);
+            release(&b->cb);
+            b->sigma_host.clear();
+            b->sigma_implicit = false;
+        }
+        return 0;
+    }
+    if (!b->ca) {                               // a lossless PML batch: the lossy kernels with ca = 1, cb = ce
+        const std::vector<double> zero((size_t)b->count * b->rows * b->cols, 0.0);
+        if ((rc = set_sigma(b, nullptr, zero.data(), FDTD2D_F64))) return rc;
+        b->sigma_implicit = true;
+    }
+    const size_t acc = (size_t)b->count * 32 * nfreq * (size_t)cells, om = (size_t)b->count * nfreq * sizeof(double);
+    double *nacc = nullptr, *nom = nullptr, *nph = nullptr;
+    if ((rc = alloc(b, (void **)&nacc, acc)) || (rc = alloc(b, (void **)&nom, om)) ||
+        (rc = alloc(b, (void **)&nph, 2 * om))) {
+        for (void **p : {(void **)&nacc, (void **)&nom, (void **)&nph}) release(p);
+        return rc;
+    }
+    hipError_t e = hipMemsetAsync(nacc, 0, acc, b->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    if (e == hipSuccess) e = hipMemcpy(nom, omega, om, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        for (void **p : {(void **)&nacc, (void **)&nom, (void **)&nph}) release(p);
+        return bfail(b, -(1000 + (int)e), "setting up the flux lines failed: %s", hipGetErrorString(e));
+    }
+    for (void **p : {(void **)&b->flux_acc, (void **)&b->flux_omega, (void **)&b->flux_ph}) release(p);
+    b->flux_acc = nacc;
+    b->flux_omega = nom;
+    b->flux_ph = nph;
+    std::copy(lines, lines + 4 * nlines, b->flux_line);
+    b->flux_nl = nlines;
+    b->flux_nff = nfreq;
+    b->flux_cells = (int)cells;
+    b->flux_every = every;
+    b->flux_step0 = b->step;
+    return 0;
+}
+
+int fdtd2d_batch_read_flux_lines(fdtd2d_batch_t *b, double *ez_re, double *ez_im, double *ht_re, double *ht_im)
+{
+    if (!b || !ez_re || !ez_im || !ht_re || !ht_im) return FDTD2D_E_ARG;
+    if (!b->flux_nl) return bfail(b, FDTD2D_E_STATE, "no flux lines are set");
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    const size_t per = (size_t)b->flux_nff * b->flux_cells;   // one member's Ez re (or any of the four)
+    std::vector<double> acc((size_t)b->count * 4 * per);
+    BCHK(b, hipMemcpy(acc.data(), b->flux_acc, acc.size() * sizeof(double), hipMemcpyDeviceToHost));
+    double *out[4] = {ez_re, ez_im, ht_re, ht_im};
+    for (int m = 0; m < b->count; ++m)
+        for (int k = 0; k < 4; ++k)
+            std::memcpy(out[k] + m * per, acc.data() + (4 * (size_t)m + k) * per, per * sizeof(double));
+    return 0;
+}
+
+int fdtd2d_batch_flux(fdtd2d_batch_t *b, double *out)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!out) return bfail(b, FDTD2D_E_ARG, "out must not be NULL");
+    if (!b->flux_nl) return bfail(b, FDTD2D_E_STATE, "no flux lines are set");
+    int rc = use_device(b);
+    if (rc) return rc;
+    const size_t n = (size_t)b->count * b->flux_nl * b->flux_nff;
+    if ((rc = scratch(b, n * sizeof(double)))) return rc;
+    fdtd::batch_flux_launch(flux_view(b), (double *)b->dsg, b->count, b->dt, b->dx, b->stream);
+    BCHK(b, hipGetLastError());
+    b->launches++;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    BCHK(b, hipMemcpy(out, b->dsg, n * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 

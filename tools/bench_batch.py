@@ -94,10 +94,16 @@ array eps with random binary permittivity, a ricker line source per member):
                               coefficient sets, against three_products_ms, three calls of one set each (three launches,
                               three read-backs): multi_over_three.  Default: 1024 members of 60 x 60, a 10-cell layer,
                               1500 steps.
+  --flux                      instead: flux lines (BatchEngine.set_flux_lines: two whole-period row lines, 10
+                              frequencies, every step) on a periodic batch resident in LDS, against the same batch
+                              without monitors and, for scale, with a window DFT of 16 frequencies over as many cells
+                              (Ez alone), timed alternately in one process: plain_ms, flux_ms, window_ms,
+                              flux_over_plain, window_over_plain, the LDS sizes and flux_call_ms (one BatchEngine.flux).
+                              Default: 1024 members of 60 rows x 61 columns, a 10-cell layer, 2000 steps.
 Usage: python tools/bench_batch.py [--count 1024 --rows 60 --cols 60 --steps 1000] [--reps 5] [--loop-members 16]
                                    [--boundary {mur,pml} --pml-cells 10] [--monitors] [--adjoint] [--lossy]
                                    [--periodic] [--bloch] [--bloch-adjoint] [--dispersive] [--lattice]
-                                   [--bloch-dispersive] [--dispersive-adjoint]
+                                   [--bloch-dispersive] [--dispersive-adjoint] [--flux]
 """
 import argparse
 import json
@@ -361,6 +367,59 @@ def bench_periodic(count, rows, cols, steps, dtype, reps, pml_cells):
             "periodic_ms_all": [round(v, 4) for v in per_ms],
             "periodic_over_lossy_pml": round(med_p / med_l, 3), "launches_per_run": launches,
             "periodic_mcell_steps_per_s": round(count * rows * cols * steps / (med_p * 1e-3) / 1e6, 1)}
+
+
+def bench_flux(count, rows, cols, steps, dtype, reps, pml_cells):
+    """Flux lines against the same periodic batch without monitors, and against a window DFT for scale."""
+    eps, rects, amps = members(count, rows, cols, steps)
+    rects[:, 1], rects[:, 3] = 0, cols - 1            # a line source over the period
+    c00 = courant00(eps, dtype)
+    lines = [("row", rows // 4, 0, cols - 1), ("row", 3 * rows // 4, 0, cols - 1)]
+    om10 = 2 * np.pi * np.linspace(20e9, 65e9, 10)
+    om16 = 2 * np.pi * np.linspace(20e9, 65e9, 16)
+
+    def batch(kind):
+        b = fd.BatchEngine(count, rows, cols, DT, DX, dtype=dtype, boundary="periodic")
+        b.set_materials(eps.astype(dtype), fd.MU0).set_sources(rects)
+        b.set_pml(pml_cells, courant00=c00)
+        if kind == "flux":
+            b.set_flux_lines(lines, om10)
+        if kind == "window":                          # as many cells as the two lines, 16 frequencies of Ez alone
+            b.set_dft_window((rows // 4, 0, 2, cols - 1), om16)
+        b.run(steps, amps).sync()                     # warm-up: code objects, clocks
+        return b
+
+    def timed(b):
+        b.reset().sync()
+        t0 = time.perf_counter()
+        b.run(steps, amps).sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    with batch("plain") as plain, batch("flux") as flux, batch("window") as win:
+        assert flux.resident and flux.flux_lines_in_lds and win.window_in_lds and plain.resident
+        l0 = flux.launches
+        flux.reset().run(steps, amps).sync()
+        launches = flux.launches - l0
+        t0 = time.perf_counter()
+        P = flux.flux()
+        flux_call_ms = (time.perf_counter() - t0) * 1e3
+        ms = {"plain": [], "flux": [], "window": []}
+        for _ in range(reps):
+            for k, b in (("plain", plain), ("flux", flux), ("window", win)):
+                ms[k].append(timed(b))
+        lds = {k: b.lds_bytes for k, b in (("plain", plain), ("flux", flux), ("window", win))}
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    out = {"count": count, "rows": rows, "cols": cols, "steps": steps, "dtype": np.dtype(dtype).name,
+           "materials": "arrays", "pml_cells": pml_cells, "reps": reps, "lines": 2, "line_cells": 2 * (cols - 1),
+           "flux_freqs": 10, "window_freqs": 16, "launches_per_run": launches,
+           "flux_call_ms": round(flux_call_ms, 4), "flux_finite": bool(np.all(np.isfinite(P)))}
+    for k in ("plain", "flux", "window"):
+        out.update({f"{k}_ms": round(med[k], 4), f"{k}_ms_min": round(min(ms[k]), 4),
+                    f"{k}_ms_all": [round(v, 4) for v in ms[k]], f"{k}_lds_bytes_per_member": lds[k]})
+    out.update({"flux_over_plain": round(med["flux"] / med["plain"], 3),
+                "window_over_plain": round(med["window"] / med["plain"], 3),
+                "flux_mcell_steps_per_s": round(count * rows * cols * steps / (med["flux"] * 1e-3) / 1e6, 1)})
+    return out
 
 
 def bench_dispersive(count, rows, cols, steps, dtype, reps, pml_cells):
@@ -901,7 +960,12 @@ def main():
                     help="time the pole of a lattice and of a Bloch batch against the same batches without it")
     ap.add_argument("--dispersive-adjoint", action="store_true",
                     help="time the three gradients of a dispersive batch against the two of the same lossy batch")
+    ap.add_argument("--flux", action="store_true", help="time flux lines against the same batch without monitors")
     a = ap.parse_args()
+    if a.flux:
+        print(json.dumps(bench_flux(a.count or 1024, a.rows or 60, a.cols or 61, a.steps or 2000, np.dtype(a.dtype),
+                                    a.reps, a.pml_cells)), flush=True)
+        return
     if a.dispersive_adjoint:
         print(json.dumps(bench_dispersive_adjoint(a.count or 1024, a.rows or 60, a.cols or 60, a.steps or 1500,
                                                   np.dtype(a.dtype), a.reps, a.pml_cells)), flush=True)
