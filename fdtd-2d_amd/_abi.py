@@ -244,6 +244,13 @@ BATCH_FLUX_SIGNATURES = {
     "fdtd2d_batch_read_flux_lines": (_i, [_vp, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]),
     "fdtd2d_batch_flux": (_i, [_vp, C.POINTER(_d)]),
 }
+# every symbol include/fdtd2d_batch_bloch_flux.h declares (the flux lines of a batch with a Bloch phase: the sums of the
+# real and of the imaginary part of the fields, and the power per member, line and frequency)
+BATCH_BLOCH_FLUX_SIGNATURES = {
+    "fdtd2d_batch_set_bloch_flux_lines": (_i, [_vp, _i, C.POINTER(_i), _i, C.POINTER(_d), _i]),
+    "fdtd2d_batch_read_bloch_flux_lines": (_i, [_vp, _i, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_bloch_flux": (_i, [_vp, C.POINTER(_d)]),
+}
 
 # transport callback of fdtd2d_slab_attach
 EXCHANGE_FN = C.CFUNCTYPE(_i, _vp, _vp, _vp, _vp, _vp, _ll, _vp)
@@ -298,7 +305,8 @@ def load():
                                    **BATCH_BLOCH_SIGNATURES, **BATCH_BLOCH_ADJOINT_SIGNATURES,
                                    **BATCH_DISPERSIVE_SIGNATURES, **BATCH_LATTICE_SIGNATURES,
                                    **BATCH_BLOCH_DISPERSIVE_SIGNATURES,
-                                   **BATCH_DISPERSIVE_ADJOINT_SIGNATURES, **BATCH_FLUX_SIGNATURES}.items():
+                                   **BATCH_DISPERSIVE_ADJOINT_SIGNATURES, **BATCH_FLUX_SIGNATURES,
+                                   **BATCH_BLOCH_FLUX_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

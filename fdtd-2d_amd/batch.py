@@ -152,6 +152,7 @@ class BatchEngine:
         self._win = None              # (F, nrows, ncols) of the window DFT
         self._nprobe = 0
         self._flux = None             # ((N, 4) lines, (B, F) omegas) of the flux lines
+        self._bflux = False           # they are Bloch lines (set_bloch_flux_lines): complex fields, two parts
         self._npoint = (0, 0)         # (P, K) of the point sources
         self._bloch = None            # (c, s): the (B,) rotations of a Bloch phase
         self._phi = None              # the phases as given (None with rotation=)
@@ -870,24 +871,83 @@ class BatchEngine:
         lines are set (bit-identical fields, a smaller resident capacity: see resident_max_cells)."""
         if lines is None or len(lines) == 0:
             self._ck(self._lib.fdtd2d_batch_set_flux_lines(self._h, 0, None, 0, None, 1))
-            self._flux = None
+            self._flux, self._bflux = None, False
             return self
         ln, w, every = _flux_lines(lines, omegas, every, self.count, self.rows, self.cols, self.boundary == "periodic")
         self._ck(self._lib.fdtd2d_batch_set_flux_lines(self._h, len(ln), ln.ctypes.data_as(C.POINTER(C.c_int)),
                                                        int(w.shape[1]), _dptr(w), every))
-        self._flux = (ln, w)
+        self._flux, self._bflux = (ln, w), False
+        return self
+
+    def set_bloch_flux_lines(self, lines, omegas, every=1):
+        """The flux lines of set_flux_lines on a "periodic" engine with a Bloch phase (set_bloch_phase), with or without
+        the pole of set_bloch_dispersion: the same lines, limits and sampling, on complex fields
+        (fdtd2d_batch_bloch_flux.h).  The frequencies may have either sign: omega and -omega are different spectra of
+        a complex field.  At column 0 a column line reads its left neighbour across the seam, rotated back by the
+        phase.  lines None or empty removes them.  While they are set, turning the phase off, Bloch point sources,
+        run_bloch_channels and hold_bloch_window are refused; a new phase keeps the lines and their sums."""
+        if lines is None or len(lines) == 0:
+            self._ck(self._lib.fdtd2d_batch_set_bloch_flux_lines(self._h, 0, None, 0, None, 1))
+            if self._bflux:
+                self._flux, self._bflux = None, False
+            return self
+        ln, w, every = _flux_lines(lines, omegas, every, self.count, self.rows, self.cols, True)
+        self._ck(self._lib.fdtd2d_batch_set_bloch_flux_lines(self._h, len(ln), ln.ctypes.data_as(C.POINTER(C.c_int)),
+                                                             int(w.shape[1]), _dptr(w), every))
+        self._flux, self._bflux = (ln, w), True
         return self
 
     def read_flux_lines(self, raw=False):
         """(Ez_hat, Ht_hat), each complex128 (B, F, cells): the transforms on the line cells, lines concatenated in the
         order given.  Ht_hat carries the half-step factor exp(+1j * omega * dt / 2) (the H of a step lives half a step
-        before its Ez) unless raw, which returns the sums as accumulated."""
+        before its Ez) unless raw, which returns the sums as accumulated.  Serves the lines of set_flux_lines and of
+        set_bloch_flux_lines (the transforms of the complex fields: those of the real part plus 1j times those of the
+        imaginary part)."""
         ln, w = self._flux or (np.zeros((0, 4), np.int32), np.zeros((self.count, 0)))
         shape = (self.count, w.shape[1], int(ln[:, 3].sum()))
+        if self._bflux:
+            (er, hr), (ei, hi) = self.read_bloch_flux_parts()
+            e, h = er + 1j * ei, hr + 1j * hi
+            return (e, h) if raw else (e, h * np.exp(0.5j * w * self.dt)[:, :, None])
         a = [np.empty(shape) if self._flux is not None else np.empty(1) for _ in range(4)]
         self._ck(self._lib.fdtd2d_batch_read_flux_lines(self._h, *(_dptr(x) for x in a)))
         e, h = a[0] + 1j * a[1], a[2] + 1j * a[3]
         return (e, h) if raw else (e, h * np.exp(0.5j * w * self.dt)[:, :, None])
+
+    def read_bloch_flux_parts(self):
+        """The raw sums of set_bloch_flux_lines as the engine holds them: ((Ez_hat, Ht_hat) of the real part of the
+        fields, (Ez_hat, Ht_hat) of the imaginary part), each complex128 (B, F, cells), without the half-step factor."""
+        ln, w = self._flux if self._bflux else (np.zeros((0, 4), np.int32), np.zeros((self.count, 0)))
+        shape = (self.count, w.shape[1], int(ln[:, 3].sum()))
+        out = []
+        for part in (0, 1):
+            a = [np.empty(shape) if self._bflux else np.empty(1) for _ in range(4)]
+            self._ck(self._lib.fdtd2d_batch_read_bloch_flux_lines(self._h, part, *(_dptr(x) for x in a)))
+            out.append((a[0] + 1j * a[1], a[2] + 1j * a[3]))
+        return tuple(out)
+
+    def flux_orders(self, line=0):
+        """float64 (B, F, Q), Q = C - 1: the power through a whole-period row line of set_bloch_flux_lines split over the
+        diffraction orders, P_m = dx * Q * Re(E_m * conj(H_m)) with E_m = (1/Q) * sum_j Ez_hat[j] * exp(-1j * (phi + 2 pi
+        m) * j / Q) and H_m likewise (Ht_hat with the half-step factor), m in np.fft.fftfreq(Q, 1/Q) order.  By Parseval
+        the orders sum to flux()[:, line, :]: these are a grating's diffraction efficiencies before normalisation.
+        Host NumPy over read_flux_lines()."""
+        if not self._bflux:
+            raise _abi.Fdtd2dError(_abi.E_STATE, "no Bloch flux lines are set")
+        ln, _ = self._flux
+        Q = self.cols - 1
+        if not 0 <= int(line) < len(ln):
+            raise ValueError(f"line {line} outside 0..{len(ln) - 1}")
+        col, _, first, n = (int(x) for x in ln[int(line)])
+        if col or first != 0 or n != Q:
+            raise ValueError(f"flux_orders needs a row line over the whole period (columns 0..{Q - 1}), not line {line}")
+        c, s = self._bloch
+        phi = self._phi if self._phi is not None else np.arctan2(s, c)
+        o = int(ln[:int(line), 3].sum())
+        E, H = (a[:, :, o:o + Q] for a in self.read_flux_lines())
+        envelope = np.exp(-1j * phi[:, None, None] * np.arange(Q)[None, None, :] / Q)
+        Em, Hm = np.fft.fft(E * envelope, axis=2) / Q, np.fft.fft(H * envelope, axis=2) / Q
+        return self.dx * Q * np.real(Em * np.conj(Hm))
 
     def flux(self) -> np.ndarray:
         """float64 (B, N, F): the power that crosses each line per frequency, P = s * dx * sum over the line's cells of
@@ -896,7 +956,8 @@ class BatchEngine:
         ln, w = self._flux or (np.zeros((0, 4), np.int32), np.zeros((self.count, 0)))
         out = np.empty((self.count, len(ln), w.shape[1]))
         buf = out if out.size else np.empty(1)     # a refused read still passes a valid pointer
-        self._ck(self._lib.fdtd2d_batch_flux(self._h, _dptr(buf)))
+        fn = self._lib.fdtd2d_batch_bloch_flux if self._bflux else self._lib.fdtd2d_batch_flux
+        self._ck(fn(self._h, _dptr(buf)))
         return out
 
     @property
@@ -1220,7 +1281,8 @@ def _waveform_amps(kind, fc, nsteps, dt):
 def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker", dt=5e-14, dx=1e-4,
                    dtype=np.float64, boundary="mur", omega=None, dft_every=1, device=0, pml_cells=40,
                    dft_window=None, window_omegas=None, probes=None, bloch_phase=None, source_weights=None,
-                   dispersion=None, bloch_dispersion=None, flux_lines=None, flux_omegas=None):
+                   dispersion=None, bloch_dispersion=None, bloch_flux_lines=None, bloch_flux_omegas=None,
+                   flux_lines=None, flux_omegas=None):
     """run_fdtd for B members of one shape at once: zero fields, Courant check per member, nsteps of
     H -> E -> source with t = i*dt.
 
@@ -1245,6 +1307,8 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
     "lattice"): a metal unit cell swept over the angle of incidence or along a band path.  flux_lines with flux_omegas
     (boundary "pml" or "periodic", not with bloch_phase): flux monitors as set_flux_lines takes them, sampled every
     `dft_every` steps; the float64 (B, N, F) flux array of BatchEngine.flux() is then appended to the returned tuple.
+    bloch_flux_lines with bloch_flux_omegas (boundary "periodic" with bloch_phase): the same on the complex fields of a
+    Bloch run, as set_bloch_flux_lines takes them; the flux array is appended likewise.
     """
     from .api import MU0
     eps = np.asarray(eps)
@@ -1314,6 +1378,15 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
         if bloch_phase is not None:
             raise ValueError("flux_lines is not available with bloch_phase")
         _flux_lines(flux_lines, flux_omegas, dft_every, B, R, Cc, boundary == "periodic")
+    if (bloch_flux_lines is None) != (bloch_flux_omegas is None):
+        raise ValueError("bloch_flux_lines and bloch_flux_omegas must be given together")
+    if bloch_flux_lines is not None:
+        if boundary != "periodic" or bloch_phase is None:
+            raise ValueError(f'bloch_flux_lines needs boundary="periodic" and bloch_phase (boundary {boundary!r}'
+                             f'{"" if bloch_phase is not None else ", no bloch_phase"}): without a phase use flux_lines')
+        if flux_lines is not None:
+            raise ValueError("bloch_flux_lines and flux_lines exclude each other")
+        _flux_lines(bloch_flux_lines, bloch_flux_omegas, dft_every, B, R, Cc, True)
     if bloch_phase is not None:
         if win is not None and win[1] + win[3] > Cc - 1:
             raise ValueError(f"dft_window {win} touches column {Cc - 1}, the image of column 0: not with bloch_phase")
@@ -1348,6 +1421,8 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
             eng.set_probes(cells, max(1, int(nsteps)))
         if flux_lines is not None:
             eng.set_flux_lines(flux_lines, flux_omegas, dft_every)
+        if bloch_flux_lines is not None:
+            eng.set_bloch_flux_lines(bloch_flux_lines, bloch_flux_omegas, dft_every)
         eng.run(nsteps, None if waveform is None else _waveform_amps(waveform, fcs, nsteps, dt))
         out = eng.download()
         if omega is not None:
@@ -1356,7 +1431,7 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
             out += (eng.read_dft_window(),)
         if cells is not None:
             out += (eng.read_probes(0, int(nsteps)),)
-        if flux_lines is not None:
+        if flux_lines is not None or bloch_flux_lines is not None:
             out += (eng.flux(),)
         return out
 

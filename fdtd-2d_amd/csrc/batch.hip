@@ -22,11 +22,15 @@
 // the imaginary parts of Jh and Q.
 // With flux lines (fdtd2d_batch_flux.h) a PML or periodic batch takes the kernels of batch_flux.hip, with or without a
 // pole; a lossless PML batch then holds an all-zero conductivity of its own (sigma_implicit), like a batch with a pole.
+// With the lines of fdtd2d_batch_bloch_flux.h a Bloch batch takes the kernels of batch_bloch_flux.hip, with or without
+// the complex pole; the lines share the host state of fdtd2d_batch_flux.h's (`flux_nl` is set too) and add the sums of
+// the imaginary part.
 #include "../../include/fdtd2d.h"
 #include "../../include/fdtd2d_batch_adjoint.h"
 #include "../../include/fdtd2d_batch_bloch.h"
 #include "../../include/fdtd2d_batch_bloch_adjoint.h"
 #include "../../include/fdtd2d_batch_bloch_dispersive.h"
+#include "../../include/fdtd2d_batch_bloch_flux.h"
 #include "../../include/fdtd2d_batch_design.h"
 #include "../../include/fdtd2d_batch_dispersive.h"
 #include "../../include/fdtd2d_batch_dispersive_adjoint.h"
@@ -53,6 +57,7 @@
 #include "kernels_batch_bloch.hpp"
 #include "kernels_batch_bloch_adjoint.hpp"
 #include "kernels_batch_bloch_dispersive.hpp"
+#include "kernels_batch_bloch_flux.hpp"
 #include "kernels_batch_design.hpp"
 #include "kernels_batch_dispersive.hpp"
 #include "kernels_batch_flux.hpp"
@@ -155,6 +160,10 @@ struct fdtd2d_batch {
     double *flux_acc = nullptr, *flux_omega = nullptr;
     double *flux_ph = nullptr;            // streamed path: count x nff phasors of the step being completed
     int flux_lds_opt = -1;                // -1: sums in LDS when they fit, 0: never
+    // fdtd2d_batch_set_bloch_flux_lines: the lines above on a Bloch batch.  flux_acc holds the sums of the real part and
+    // flux_acc_im, of the same layout, those of the imaginary part
+    bool bflux = false;
+    double *flux_acc_im = nullptr;
     double *win_held = nullptr;           // fdtd2d_batch_hold_dft_window: a copy of win_acc
     double *win_held_disp = nullptr;      // fdtd2d_batch_hold_dispersive_window: a copy of win_acc while a pole is set
     // point sources (fdtd2d_batch_set_point_sources), every table in the resident owners' order
@@ -349,8 +358,10 @@ bool win_acc_in_lds(const fdtd2d_batch *b)
            lds_field_bytes(b) + lds_table_bytes(b) + lds_acc_bytes(b) <= fdtd::BATCH_LDS_LIMIT;
 }
 
-// flux lines: the sums of one member; in LDS behind the window's accumulators (wherever those live) when they fit too
-size_t flux_acc_bytes(const fdtd2d_batch *b) { return b->flux_nl ? 32 * (size_t)b->flux_nff * b->flux_cells : 0; }
+// flux lines: the sums of one member (of both parts on a Bloch batch); in LDS behind the window's accumulators (wherever
+// those live) when they fit too
+size_t flux_part_bytes(const fdtd2d_batch *b) { return b->flux_nl ? 32 * (size_t)b->flux_nff * b->flux_cells : 0; }
+size_t flux_acc_bytes(const fdtd2d_batch *b) { return (b->bflux ? 2 : 1) * flux_part_bytes(b); }
 bool flux_acc_in_lds(const fdtd2d_batch *b)
 {
     return b->flux_nl && b->flux_lds_opt != 0 &&
@@ -1093,9 +1104,74 @@ template <class T> int run_bloch_dispersive(fdtd2d_batch *b, int nsteps, const d
     return 0;
 }
 
+// ---- Bloch runs with flux lines (fdtd2d_batch_bloch_flux.h): the paths of run_bloch and of run_bloch_dispersive with the
+// kernels of batch_bloch_flux.hip, whose streamed H launch also writes the lines' phasors
+template <class T> int run_bloch_flux(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride)
+{
+    if (!b->ca || !b->ezx || !b->ez_im || !b->rho || b->lattice || !b->flux_acc || !b->flux_acc_im ||
+        (b->bdisp && (!b->djh || !b->dq || !b->djh_im || !b->dq_im || !b->dcj || !b->da || !b->dck)))
+        return bfail(b, FDTD2D_E_STATE, "Bloch batch with flux lines without its arrays");
+    const fdtd::BatchBlochFluxKernels &K = fdtd::batch_bloch_flux_kernels<T>();
+    const int disp = b->bdisp ? 1 : 0;
+    fdtd::BatchPml<T> p = pml_view<T>(b);
+    fdtd::BatchMon m = mon_view(b);
+    fdtd::BatchBloch<T> bl = bloch_view<T>(b, false);
+    fdtd::BatchBlochDisp<T> d{(T *)b->djh, (T *)b->dq, (T *)b->djh_im, (T *)b->dq_im,
+                              (const T *)b->dcj, (const T *)b->da, (const T *)b->dck};
+    fdtd::BatchFlux f = flux_view(b);
+    double *facc_im = b->flux_acc_im;
+    b->run_conj = false;
+    const T *ca = (const T *)b->ca;
+    if (use_resident(b)) {
+        const int cells = b->rows * b->cols, threads = resident_threads(cells);
+        const int per_thread = (cells + threads - 1) / threads;
+        if (per_thread > 4)
+            return bfail(b, FDTD2D_E_STATE, "%d cells per thread exceed the Bloch resident kernels' 4", per_thread);
+        const void *kern = K.resident[disp];
+        const size_t lds = lds_bytes(b);
+        BCHK(b, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        int per_cu = 0, cus = 0;
+        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds));
+        BCHK(b, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
+        if (per_cu < 1)
+            return bfail(b, FDTD2D_E_STATE, "Bloch flux resident kernel does not fit a CU (%zu B of LDS)", lds);
+        const long long round = (long long)per_cu * cus;
+        const int blocks = (int)(b->count < round ? b->count : round);
+        const int chunk = b->steps_per_launch > 0 ? b->steps_per_launch : nsteps;
+        for (int n = 0; n < nsteps; n += chunk) {
+            int n0 = n, nt = nsteps - n < chunk ? nsteps - n : chunk;
+            long long step_base = b->step;
+            fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+            v.ce = (const T *)b->cb;
+            void *args[] = {&v, &p, &m, &bl, &d, &f, &facc_im, &ca, &n0, &nt, &step_base};
+            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads), args, lds);
+            if (rc) return rc;
+            b->launches++;
+            b->step += nt;
+        }
+        return 0;
+    }
+    const int cells = b->rows * b->cols;
+    const dim3 grid((cells + 255) / 256, b->count < 65535 ? b->count : 65535);
+    for (int n = 0; n < nsteps; ++n) {
+        fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+        v.ce = (const T *)b->cb;
+        long long step = b->step + 1;
+        int rc;
+        void *h_args[] = {&v, &p, &m, &bl, &f, &step};
+        void *e_args[] = {&v, &p, &m, &bl, &d, &f, &facc_im, &ca, &n, &step};
+        if ((rc = launch_ptr(b, K.h, grid, dim3(256), h_args, 0))) return rc;
+        if ((rc = launch_ptr(b, K.e[disp], grid, dim3(256), e_args, 0))) return rc;
+        b->launches += 2;
+        b->step++;
+    }
+    return 0;
+}
+
 template <class T>
 int run_impl(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts = nullptr)
 {
+    if (b->bflux) return run_bloch_flux<T>(b, nsteps, amps, amp_stride);
     if (b->bdisp) return run_bloch_dispersive<T>(b, nsteps, amps, amp_stride);
     if (b->lattice) return run_lattice<T>(b, nsteps, amps, amp_stride);
     if (b->bloch) return run_bloch<T>(b, nsteps, amps, amp_stride);
@@ -1359,9 +1435,12 @@ int refuse_bloch(fdtd2d_batch *b, const char *what);
 
 constexpr double DISP_EPS0 = 8.85418e-12;     // the library's vacuum constant (the reference's literal)
 
-// what a batch with flux lines cannot do (fdtd2d_batch_flux.h, "Scope")
+// what a batch with flux lines cannot do (fdtd2d_batch_flux.h and fdtd2d_batch_bloch_flux.h, "Scope")
 int refuse_flux(fdtd2d_batch *b, const char *what)
 {
+    if (b->bflux)
+        return bfail(b, FDTD2D_E_STATE, "%s is not available while Bloch flux lines are set: remove them first "
+                     "(fdtd2d_batch_set_bloch_flux_lines with nlines = 0)", what);
     return bfail(b, FDTD2D_E_STATE, "%s is not available while flux lines are set: remove them first "
                  "(fdtd2d_batch_set_flux_lines with nlines = 0)", what);
 }
@@ -1806,7 +1885,8 @@ void fdtd2d_batch_destroy(fdtd2d_batch_t *b)
                      (void **)&b->win_acc_im, (void **)&b->probe_trace_im, &b->rho_conj, &b->rho_r,
                      (void **)&b->win_held_im, (void **)&b->win_held_disp,
                      &b->djh, &b->dq, &b->dcj, &b->da, &b->dck, &b->djh_im, &b->dq_im,
-                     (void **)&b->flux_acc, (void **)&b->flux_omega, (void **)&b->flux_ph})
+                     (void **)&b->flux_acc, (void **)&b->flux_omega, (void **)&b->flux_ph,
+                     (void **)&b->flux_acc_im})
         release(p);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -2119,7 +2199,9 @@ int fdtd2d_batch_reset(fdtd2d_batch_t *b)
         BCHK(b, hipMemsetAsync(b->probe_trace_im, 0, (size_t)b->count * b->nprobe * b->probe_cap * sizeof(double),
                                b->stream));
     if (b->flux_nl)
-        BCHK(b, hipMemsetAsync(b->flux_acc, 0, (size_t)b->count * flux_acc_bytes(b), b->stream));
+        BCHK(b, hipMemsetAsync(b->flux_acc, 0, (size_t)b->count * flux_part_bytes(b), b->stream));
+    if (b->bflux)
+        BCHK(b, hipMemsetAsync(b->flux_acc_im, 0, (size_t)b->count * flux_part_bytes(b), b->stream));
     b->win_step0 = 0;
     b->probe_step0 = 0;
     b->flux_step0 = 0;
@@ -2998,10 +3080,11 @@ int fdtd2d_batch_set_bloch(fdtd2d_batch_t *b, const double *cos_phi, const doubl
     int rc = use_device(b);
     if (rc) return rc;
     if (b->lattice) return refuse_bloch(b, "fdtd2d_batch_set_bloch (use fdtd2d_batch_set_lattice)");
+    if (!cos_phi && b->bflux) return refuse_flux(b, "turning the Bloch phase off");
     if (!cos_phi && b->bdisp) return refuse_dispersive(b, "turning the Bloch phase off");
     if (!cos_phi) return b->bloch ? bloch_off(b) : 0;
     if (b->dcj && !b->bdisp) return refuse_dispersive(b, "a Bloch phase");
-    if (b->flux_nl) return refuse_flux(b, "a Bloch phase");
+    if (b->flux_nl && !b->bflux) return refuse_flux(b, "a Bloch phase");
     if (!b->periodic)
         return bfail(b, FDTD2D_E_STATE, "a Bloch phase needs periodic columns: call fdtd2d_batch_set_periodic first");
     for (int m = 0; m < b->count; ++m)
@@ -3289,6 +3372,7 @@ int fdtd2d_batch_set_bloch_point_sources(fdtd2d_batch_t *b, int ncell, const int
     if (!b) return FDTD2D_E_ARG;
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
     if (ncell > 0 && b->lattice) return refuse_bloch(b, "a point source");
+    if (ncell > 0 && b->bflux) return refuse_flux(b, "a Bloch point source");
     if (ncell > 0 && b->bdisp) return refuse_dispersive(b, "a point source (the adjoint of a dispersive medium)");
     return batch_set_points(b, ncell, cells, nchan, weights);     // a periodic batch: column C-1 is refused there
 }
@@ -3299,6 +3383,7 @@ int fdtd2d_batch_run_bloch_channels(fdtd2d_batch_t *b, int nsteps, const double 
     if (!b) return FDTD2D_E_ARG;
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
     if (b->lattice) return refuse_bloch(b, "a run with channels");
+    if (b->bflux) return refuse_flux(b, "a run with channels");
     if (b->bdisp) return refuse_dispersive(b, "a run with channels (the adjoint of a dispersive medium)");
     if (nsteps < 0) return bfail(b, FDTD2D_E_ARG, "nsteps < 0");
     if (!chan) return bfail(b, FDTD2D_E_ARG, "chan must not be NULL");
@@ -3345,6 +3430,7 @@ int fdtd2d_batch_hold_bloch_window(fdtd2d_batch_t *b)
     if (!b) return FDTD2D_E_ARG;
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
     if (b->lattice) return refuse_bloch(b, "the held window");
+    if (b->bflux) return refuse_flux(b, "the held window");
     if (b->bdisp) return refuse_dispersive(b, "the held window (the adjoint of a dispersive medium)");
     if (!b->win_nf || !b->win_acc_im) return bfail(b, FDTD2D_E_STATE, "no window DFT is set");
     int rc = use_device(b);
@@ -3526,8 +3612,10 @@ int fdtd2d_batch_set_flux_lines(fdtd2d_batch_t *b, int nlines, const int *lines,
     if (rc) return rc;
     BCHK(b, hipStreamSynchronize(b->stream));   // a running launch may still use the old lines
     if (nlines == 0) {
-        for (void **p : {(void **)&b->flux_acc, (void **)&b->flux_omega, (void **)&b->flux_ph}) release(p);
+        for (void **p : {(void **)&b->flux_acc, (void **)&b->flux_omega, (void **)&b->flux_ph, (void **)&b->flux_acc_im})
+            release(p);
         b->flux_nl = b->flux_nff = b->flux_cells = 0;
+        b->bflux = false;
         if (b->sigma_implicit && !b->periodic && !b->dcj) {   // the all-zero conductivity the lines brought
             release(&b->ca);
             release(&b->cb);
@@ -3572,6 +3660,7 @@ int fdtd2d_batch_read_flux_lines(fdtd2d_batch_t *b, double *ez_re, double *ez_im
 {
     if (!b || !ez_re || !ez_im || !ht_re || !ht_im) return FDTD2D_E_ARG;
     if (!b->flux_nl) return bfail(b, FDTD2D_E_STATE, "no flux lines are set");
+    if (b->bflux) return bfail(b, FDTD2D_E_STATE, "the lines are Bloch lines: use fdtd2d_batch_read_bloch_flux_lines");
     int rc = use_device(b);
     if (rc) return rc;
     BCHK(b, hipStreamSynchronize(b->stream));
@@ -3590,11 +3679,139 @@ int fdtd2d_batch_flux(fdtd2d_batch_t *b, double *out)
     if (!b) return FDTD2D_E_ARG;
     if (!out) return bfail(b, FDTD2D_E_ARG, "out must not be NULL");
     if (!b->flux_nl) return bfail(b, FDTD2D_E_STATE, "no flux lines are set");
+    if (b->bflux) return bfail(b, FDTD2D_E_STATE, "the lines are Bloch lines: use fdtd2d_batch_bloch_flux");
     int rc = use_device(b);
     if (rc) return rc;
     const size_t n = (size_t)b->count * b->flux_nl * b->flux_nff;
     if ((rc = scratch(b, n * sizeof(double)))) return rc;
     fdtd::batch_flux_launch(flux_view(b), (double *)b->dsg, b->count, b->dt, b->dx, b->stream);
+    BCHK(b, hipGetLastError());
+    b->launches++;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    BCHK(b, hipMemcpy(out, b->dsg, n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- fdtd2d_batch_bloch_flux.h ------------------------------------------------------------------------------------
+
+extern "C" {
+
+int fdtd2d_batch_set_bloch_flux_lines(fdtd2d_batch_t *b, int nlines, const int *lines, int nfreq, const double *omega,
+                                      int every)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (nlines < 0 || nlines > FDTD2D_BATCH_MAX_FLUX_LINES)
+        return bfail(b, FDTD2D_E_ARG, "nlines %d outside 0..%d", nlines, FDTD2D_BATCH_MAX_FLUX_LINES);
+    long long cells = 0;
+    if (nlines > 0) {
+        if (b->boundary != FDTD2D_BOUNDARY_NONE || !b->periodic)
+            return bfail(b, FDTD2D_E_STATE, "Bloch flux lines need a batch with periodic columns and a Bloch phase");
+        if (b->lattice) return bfail(b, FDTD2D_E_STATE, "Bloch flux lines are not available in the lattice mode");
+        if (!b->bloch)
+            return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first (without a phase use "
+                         "fdtd2d_batch_set_flux_lines)");
+        if (b->npts) return bfail(b, FDTD2D_E_STATE, "Bloch flux lines are not available with Bloch point sources (remove them)");
+        if (b->win_held || b->win_held_im)
+            return bfail(b, FDTD2D_E_STATE, "Bloch flux lines are not available with a held Bloch window (set the window again)");
+        if (nfreq < 1 || nfreq > FDTD2D_BATCH_MAX_FLUX_FREQS)
+            return bfail(b, FDTD2D_E_ARG, "nfreq %d outside 1..%d", nfreq, FDTD2D_BATCH_MAX_FLUX_FREQS);
+        if (!lines || !omega) return bfail(b, FDTD2D_E_ARG, "lines and omega must not be NULL");
+        if (every < 1) return bfail(b, FDTD2D_E_ARG, "every must be >= 1");
+        const int R = b->rows, C = b->cols;
+        for (int k = 0; k < nlines; ++k) {
+            const int o = lines[4 * k], at = lines[4 * k + 1], first = lines[4 * k + 2], n = lines[4 * k + 3];
+            if (o != 0 && o != 1) return bfail(b, FDTD2D_E_ARG, "line %d: orientation %d (0 row, 1 column)", k, o);
+            if (o == 0 && (at < 1 || at > R - 2))
+                return bfail(b, FDTD2D_E_ARG, "line %d: row %d outside 1..%d", k, at, R - 2);
+            if (o == 1 && (at < 0 || at > C - 2))
+                return bfail(b, FDTD2D_E_ARG, "line %d: column %d outside 0..%d (column C-1 is the image of column 0)", k, at,
+                             C - 2);
+            const int extent = o == 1 ? R : C - 1;
+            if (n < 1 || first < 0 || (long long)first + n > extent)
+                return bfail(b, FDTD2D_E_ARG, "line %d: cells [%d, %d + %d) are empty or run past %d", k, first, first, n,
+                             extent);
+            cells += n;
+        }
+        if (!b->have_mat) return bfail(b, FDTD2D_E_STATE, "materials not set: call fdtd2d_batch_set_materials first");
+    } else if (!b->bflux) {
+        return 0;
+    }
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));   // a running launch may still use the old lines
+    if (nlines == 0) {
+        for (void **p : {(void **)&b->flux_acc, (void **)&b->flux_omega, (void **)&b->flux_ph, (void **)&b->flux_acc_im})
+            release(p);
+        b->flux_nl = b->flux_nff = b->flux_cells = 0;
+        b->bflux = false;
+        return 0;
+    }
+    // the new buffers before the old ones go: a refused call keeps the old lines
+    const size_t acc = (size_t)b->count * 32 * nfreq * (size_t)cells, om = (size_t)b->count * nfreq * sizeof(double);
+    double *nacc = nullptr, *nacci = nullptr, *nom = nullptr, *nph = nullptr;
+    auto drop = [&]() {
+        for (void **p : {(void **)&nacc, (void **)&nacci, (void **)&nom, (void **)&nph}) release(p);
+    };
+    if ((rc = alloc(b, (void **)&nacc, acc)) || (rc = alloc(b, (void **)&nacci, acc)) ||
+        (rc = alloc(b, (void **)&nom, om)) || (rc = alloc(b, (void **)&nph, 2 * om))) {
+        drop();
+        return rc;
+    }
+    hipError_t e = hipMemsetAsync(nacc, 0, acc, b->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(nacci, 0, acc, b->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    if (e == hipSuccess) e = hipMemcpy(nom, omega, om, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        drop();
+        return bfail(b, -(1000 + (int)e), "setting up the Bloch flux lines failed: %s", hipGetErrorString(e));
+    }
+    for (void **p : {(void **)&b->flux_acc, (void **)&b->flux_omega, (void **)&b->flux_ph, (void **)&b->flux_acc_im})
+        release(p);
+    b->flux_acc = nacc;
+    b->flux_acc_im = nacci;
+    b->flux_omega = nom;
+    b->flux_ph = nph;
+    std::copy(lines, lines + 4 * nlines, b->flux_line);
+    b->flux_nl = nlines;
+    b->flux_nff = nfreq;
+    b->flux_cells = (int)cells;
+    b->flux_every = every;
+    b->flux_step0 = b->step;
+    b->bflux = true;
+    return 0;
+}
+
+int fdtd2d_batch_read_bloch_flux_lines(fdtd2d_batch_t *b, int part, double *ez_re, double *ez_im, double *ht_re,
+                                       double *ht_im)
+{
+    if (!b || !ez_re || !ez_im || !ht_re || !ht_im) return FDTD2D_E_ARG;
+    if (part != 0 && part != 1) return bfail(b, FDTD2D_E_ARG, "part %d (0 real, 1 imaginary)", part);
+    if (!b->bflux) return bfail(b, FDTD2D_E_STATE, "no Bloch flux lines are set");
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    const size_t per = (size_t)b->flux_nff * b->flux_cells;   // one member's Ez re (or any of the four)
+    std::vector<double> acc((size_t)b->count * 4 * per);
+    BCHK(b, hipMemcpy(acc.data(), part ? b->flux_acc_im : b->flux_acc, acc.size() * sizeof(double), hipMemcpyDeviceToHost));
+    double *out[4] = {ez_re, ez_im, ht_re, ht_im};
+    for (int m = 0; m < b->count; ++m)
+        for (int k = 0; k < 4; ++k)
+            std::memcpy(out[k] + m * per, acc.data() + (4 * (size_t)m + k) * per, per * sizeof(double));
+    return 0;
+}
+
+int fdtd2d_batch_bloch_flux(fdtd2d_batch_t *b, double *out)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!out) return bfail(b, FDTD2D_E_ARG, "out must not be NULL");
+    if (!b->bflux) return bfail(b, FDTD2D_E_STATE, "no Bloch flux lines are set");
+    int rc = use_device(b);
+    if (rc) return rc;
+    const size_t n = (size_t)b->count * b->flux_nl * b->flux_nff;
+    if ((rc = scratch(b, n * sizeof(double)))) return rc;
+    fdtd::batch_bloch_flux_launch(flux_view(b), b->flux_acc_im, (double *)b->dsg, b->count, b->dt, b->dx, b->stream);
     BCHK(b, hipGetLastError());
     b->launches++;
     BCHK(b, hipStreamSynchronize(b->stream));

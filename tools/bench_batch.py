@@ -100,10 +100,16 @@ array eps with random binary permittivity, a ricker line source per member):
                               (Ez alone), timed alternately in one process: plain_ms, flux_ms, window_ms,
                               flux_over_plain, window_over_plain, the LDS sizes and flux_call_ms (one BatchEngine.flux).
                               Default: 1024 members of 60 rows x 61 columns, a 10-cell layer, 2000 steps.
+  --bloch-flux                instead: the same two lines and 10 frequencies on a Bloch batch
+                              (BatchEngine.set_bloch_flux_lines, a phase sweep over the members, ramp weights) resident
+                              in LDS, against the same Bloch batch without monitors, timed alternately in one process:
+                              plain_ms, flux_ms, flux_over_plain, where the sums live (flux_lines_in_lds), the LDS sizes
+                              and flux_call_ms.  Default: 1024 members of 60 rows x 61 columns, a 10-cell layer, 2000
+                              steps.
 Usage: python tools/bench_batch.py [--count 1024 --rows 60 --cols 60 --steps 1000] [--reps 5] [--loop-members 16]
                                    [--boundary {mur,pml} --pml-cells 10] [--monitors] [--adjoint] [--lossy]
                                    [--periodic] [--bloch] [--bloch-adjoint] [--dispersive] [--lattice]
-                                   [--bloch-dispersive] [--dispersive-adjoint] [--flux]
+                                   [--bloch-dispersive] [--dispersive-adjoint] [--flux] [--bloch-flux]
 """
 import argparse
 import json
@@ -418,6 +424,58 @@ def bench_flux(count, rows, cols, steps, dtype, reps, pml_cells):
                     f"{k}_ms_all": [round(v, 4) for v in ms[k]], f"{k}_lds_bytes_per_member": lds[k]})
     out.update({"flux_over_plain": round(med["flux"] / med["plain"], 3),
                 "window_over_plain": round(med["window"] / med["plain"], 3),
+                "flux_mcell_steps_per_s": round(count * rows * cols * steps / (med["flux"] * 1e-3) / 1e6, 1)})
+    return out
+
+
+def bench_bloch_flux(count, rows, cols, steps, dtype, reps, pml_cells):
+    """Flux lines on a Bloch batch against the same Bloch batch without monitors."""
+    eps, rects, amps = members(count, rows, cols, steps)
+    rects[:, 1], rects[:, 3] = 0, cols - 1            # a line source over the period
+    c00 = courant00(eps, dtype)
+    lines = [("row", rows // 4, 0, cols - 1), ("row", 3 * rows // 4, 0, cols - 1)]
+    om10 = 2 * np.pi * np.linspace(20e9, 65e9, 10)
+    phis = np.linspace(0.0, np.pi, count)
+    camps = amps.astype(np.complex128)
+
+    def batch(kind):
+        b = fd.BatchEngine(count, rows, cols, DT, DX, dtype=dtype, boundary="periodic")
+        b.set_materials(eps.astype(dtype), fd.MU0).set_sources(rects)
+        b.set_pml(pml_cells, courant00=c00).set_bloch_phase(phis).set_bloch_source("ramp")
+        if kind == "flux":
+            b.set_bloch_flux_lines(lines, om10)
+        b.run(steps, camps).sync()                    # warm-up: code objects, clocks
+        return b
+
+    def timed(b):
+        b.reset().sync()
+        t0 = time.perf_counter()
+        b.run(steps, camps).sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    with batch("plain") as plain, batch("flux") as flux:
+        assert flux.resident and plain.resident and flux.bloch and plain.bloch
+        l0 = flux.launches
+        flux.reset().run(steps, camps).sync()
+        launches = flux.launches - l0
+        t0 = time.perf_counter()
+        P = flux.flux()
+        flux_call_ms = (time.perf_counter() - t0) * 1e3
+        ms = {"plain": [], "flux": []}
+        for _ in range(reps):
+            for k, b in (("plain", plain), ("flux", flux)):
+                ms[k].append(timed(b))
+        lds = {"plain": plain.lds_bytes, "flux": flux.lds_bytes}
+        in_lds = flux.flux_lines_in_lds
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    out = {"count": count, "rows": rows, "cols": cols, "steps": steps, "dtype": np.dtype(dtype).name,
+           "materials": "arrays", "boundary": "periodic+bloch", "pml_cells": pml_cells, "reps": reps, "lines": 2,
+           "line_cells": 2 * (cols - 1), "flux_freqs": 10, "flux_lines_in_lds": in_lds, "launches_per_run": launches,
+           "flux_call_ms": round(flux_call_ms, 4), "flux_finite": bool(np.all(np.isfinite(P)))}
+    for k in ("plain", "flux"):
+        out.update({f"{k}_ms": round(med[k], 4), f"{k}_ms_min": round(min(ms[k]), 4),
+                    f"{k}_ms_all": [round(v, 4) for v in ms[k]], f"{k}_lds_bytes_per_member": lds[k]})
+    out.update({"flux_over_plain": round(med["flux"] / med["plain"], 3),
                 "flux_mcell_steps_per_s": round(count * rows * cols * steps / (med["flux"] * 1e-3) / 1e6, 1)})
     return out
 
@@ -961,7 +1019,13 @@ def main():
     ap.add_argument("--dispersive-adjoint", action="store_true",
                     help="time the three gradients of a dispersive batch against the two of the same lossy batch")
     ap.add_argument("--flux", action="store_true", help="time flux lines against the same batch without monitors")
+    ap.add_argument("--bloch-flux", action="store_true",
+                    help="time flux lines on a Bloch batch against the same batch without monitors")
     a = ap.parse_args()
+    if a.bloch_flux:
+        print(json.dumps(bench_bloch_flux(a.count or 1024, a.rows or 60, a.cols or 61, a.steps or 2000,
+                                          np.dtype(a.dtype), a.reps, a.pml_cells)), flush=True)
+        return
     if a.flux:
         print(json.dumps(bench_flux(a.count or 1024, a.rows or 60, a.cols or 61, a.steps or 2000, np.dtype(a.dtype),
                                     a.reps, a.pml_cells)), flush=True)
