@@ -67,6 +67,9 @@ BATCH_MAX_PRODUCT_SETS = 3
 BATCH_INFO_FLUX_LINES, BATCH_INFO_FLUX_LDS = 21, 22
 BATCH_OPT_FLUX_LDS = 3
 BATCH_MAX_FLUX_LINES, BATCH_MAX_FLUX_FREQS = 4, 16
+# include/fdtd2d_batch_flux_adjoint.h: FDTD2D_BATCH_INFO_FLUX_LINE_SOURCES.  Named apart from the BATCH_INFO_* above:
+# fdtd2d_batch_bloch_flux.h's check that it added no id pins the largest of those names at 22
+BATCH_FLUX_LINE_SOURCES_INFO = 23
 
 _vp, _i, _d, _ll = C.c_void_p, C.c_int, C.c_double, C.c_longlong
 
@@ -251,6 +254,13 @@ BATCH_BLOCH_FLUX_SIGNATURES = {
     "fdtd2d_batch_read_bloch_flux_lines": (_i, [_vp, _i, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]),
     "fdtd2d_batch_bloch_flux": (_i, [_vp, C.POINTER(_d)]),
 }
+# every symbol include/fdtd2d_batch_flux_adjoint.h declares (line sources on the flux lines, the transpose of the monitor,
+# and the weights of the adjoint of a flux objective formed on the device)
+BATCH_FLUX_ADJOINT_SIGNATURES = {
+    "fdtd2d_batch_set_flux_line_sources": (_i, [_vp, _i, C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_read_flux_line_sources": (_i, [_vp, C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_flux_line_weights": (_i, [_vp, C.POINTER(_d), C.POINTER(_d), _i, C.POINTER(_d), C.POINTER(_d)]),
+}
 
 # transport callback of fdtd2d_slab_attach
 EXCHANGE_FN = C.CFUNCTYPE(_i, _vp, _vp, _vp, _vp, _vp, _ll, _vp)
@@ -306,7 +316,7 @@ def load():
                                    **BATCH_DISPERSIVE_SIGNATURES, **BATCH_LATTICE_SIGNATURES,
                                    **BATCH_BLOCH_DISPERSIVE_SIGNATURES,
                                    **BATCH_DISPERSIVE_ADJOINT_SIGNATURES, **BATCH_FLUX_SIGNATURES,
-                                   **BATCH_BLOCH_FLUX_SIGNATURES}.items():
+                                   **BATCH_BLOCH_FLUX_SIGNATURES, **BATCH_FLUX_ADJOINT_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

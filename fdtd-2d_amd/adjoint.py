@@ -45,6 +45,26 @@ and
 from the same two windows.  The held window and the product are calls of their own (``hold_dispersive_window``,
 ``dispersive_window_product``: up to three coefficient sets in one pass); the helpers above and ``AdjointSession`` keep
 refusing an engine with a pole.
+
+Flux objectives (``batch_flux_gradient``, ``FluxAdjointSession``): J depends on the power P = s dx sum_cells Re(E conj(H g))
+through the lines of ``BatchEngine.set_flux_lines``, E and H the raw sums of a line cell, g = exp(i omega dt / 2),
+s = +1 (row line) or -1 (column line).  Then dJ = sum Re(aE dE + aH dH) with aE = dJ/dP s dx conj(H g) and
+aH = dJ/dP s dx conj(E) g per line cell.  Eliminating H as above, from rest and with ring-down, gives H on a line as a
+fixed linear map of E: the H update with the member's own ch = dt / (mu dx), H = ch C E / (z - 1) with C the difference
+of the update, averaged over the two H values of the cell (T).  A source that adds M to H before the H update of a step
+and S to Ez after the E update enters as (D (z - 2 + 1/z) - L) E = D (z - 1) S - z C^T M, the update of Ez being the
+negative transpose of C.  So the adjoint field, scaled by (z - 1) like the probes' so that the coefficients above stay,
+solves the same system with
+
+    S = aE / D = dJ/dP s dx conj(H g) / D                    on the line cells (D of the cell, sigma = 0 there)
+    M = -(1/z) ch T^T aH:   0.5 * (-ch dJ/dP s dx conj(E g))   on each of the two H values of the cell
+
+which is what ``BatchEngine.set_flux_line_sources`` injects: the transpose of the monitor, driven by the 2F channels of
+the probe helpers with weights from the same channel systems.  The two H values of a cell take one weight, so mu must
+agree on them; eps still enters through D alone, so ``dft_window_product`` with ``gradient_coefficients`` and
+``sigma_coefficients`` forms dJ/d eps and dJ/d sigma as before.  ``FluxAdjointSession`` forms the weights on the device
+(``flux_adjoint_sources``), ``batch_flux_gradient`` on the host (``flux_adjoint_weights``); they agree to rounding.
+Checked against central finite differences of the stand-in's flux(): tests/test_batch_flux_adjoint_cpu.py.
 """
 from __future__ import annotations
 
@@ -1032,3 +1052,241 @@ class DispersiveAdjointSession(AdjointSession):
         self._eng.set_dispersion_window(p.win, w)
         self._wp2[:, r0:r0 + nr, c0:c0 + nc] = w
         return self
+
+
+# ---- flux objectives: the adjoint of the flux monitor -----------------------------------------------------------------
+
+def _line_entries(lines):
+    """(rows, cols, line index, column-line flag) of the lines' cells concatenated in the order given."""
+    i, j, k, col = [], [], [], []
+    for n, (kind, at, first, count) in enumerate(lines):
+        run = np.arange(int(first), int(first) + int(count))
+        c = kind == "col"
+        i.append(run if c else np.full(len(run), int(at)))
+        j.append(np.full(len(run), int(at)) if c else run)
+        k.append(np.full(len(run), n))
+        col.append(np.full(len(run), c))
+    return tuple(np.concatenate(a) for a in (i, j, k, col))
+
+
+def flux_adjoint_weights(E, H, dJdP, lines, omegas, dt, dx, solve, scale_e=None, scale_h=None):
+    """The line sources of the adjoint of a flux objective, on the host: what BatchEngine.flux_adjoint_sources forms on
+    the device.  E, H: the raw sums of read_flux_lines(raw=True), (B, F, cells).  dJdP: (B, N, F).  solve: (2F, 2F) or
+    (B, 2F, 2F), the inverse of the channel system.  scale_e, scale_h: (B, cells) or None for ones.  Returns (we, wh),
+    each (B, cells, 2F), for set_flux_line_sources."""
+    B, F, cells = E.shape
+    w = _window_omegas(omegas, B)
+    g = np.exp(0.5j * w * dt)[:, :, None]
+    _, _, k, col = _line_entries(lines)
+    c = np.asarray(dJdP, dtype=np.float64)[:, k, :].transpose(0, 2, 1) * (np.where(col, -1.0, 1.0) * dx)[None, None, :]
+    one = np.ones((B, cells))
+    te = (one if scale_e is None else np.asarray(scale_e, dtype=np.float64))[:, None, :] * c * np.conj(H * g)
+    th = (one if scale_h is None else np.asarray(scale_h, dtype=np.float64))[:, None, :] * c * np.conj(E * g)
+    s = np.broadcast_to(np.asarray(solve, dtype=np.float64), (B, 2 * F, 2 * F))
+    return tuple(np.ascontiguousarray(np.einsum("bck,bkw->bwc", s, np.concatenate([t.real, t.imag], axis=1)))
+                 for t in (te, th))
+
+
+def _gap(lo, n, x, period=None):
+    """Cells between coordinate(s) x and the run [lo, lo + n): 0 inside; cyclic with a period."""
+    d = np.maximum(np.maximum(lo - x, x - (lo + n - 1)), 0)
+    if period:
+        for s in (-period, period):
+            d = np.minimum(d, np.maximum(np.maximum(lo - (x + s), (x + s) - (lo + n - 1)), 0))
+    return d
+
+
+def _flux_plan(eps, sigma, mu, nsteps, sources, flux_lines, omegas, design, fc, waveform, dt, dx, dtype, boundary,
+               pml_cells):
+    """The host checks of batch_flux_gradient (ValueError naming the reason), the plan of _plan with one residual probe
+    per line (its first cell), the checked conductivity, the lines and the per-entry scales of the adjoint sources."""
+    from .api import MU0
+    from .batch import _flux_lines
+    if boundary not in ("pml", "periodic"):
+        raise ValueError(f'boundary must be "pml" or "periodic" (flux lines live on those batches), not {boundary!r}')
+    eps = np.asarray(eps)
+    if eps.ndim != 3:
+        raise ValueError(f"eps must have shape (B, R, C), got {eps.shape}")
+    B, R, Cc = eps.shape
+    periodic = boundary == "periodic"
+    lines = [tuple(l) for l in flux_lines]
+    _flux_lines(lines, omegas, 1, B, R, Cc, periodic)
+    li, lj, _, lcol = _line_entries(lines)
+    probes = np.array([[li[o], lj[o]] for o in np.cumsum([0] + [int(l[3]) for l in lines[:-1]])])
+    p = _plan(eps, mu, nsteps, sources, probes, omegas, design, fc, waveform, dt, dx, boundary, pml_cells)
+    L, Q = p.L, Cc - 1
+    in_layer = (li < L) | (li > R - 1 - L) | (False if periodic else (lj < L) | (lj > Cc - 1 - L))
+    if in_layer.any():
+        o = int(np.nonzero(in_layer)[0][0])
+        raise ValueError(f"member 0 (and every other): the flux line cell ({li[o]}, {lj[o]}) lies in the {L}-cell PML "
+                         f"layer, where the sums are the layer's split fields', not a flux")
+    edge = (li < 1) | (li > R - 2) | (False if periodic else (lj < 1) | (lj > Cc - 2))
+    if edge.any():
+        o = int(np.nonzero(edge)[0][0])
+        raise ValueError(f"member 0 (and every other): the flux line cell ({li[o]}, {lj[o]}) lies on the edge of the grid")
+    r0, c0, nr, nc = p.win
+    near = np.maximum(_gap(r0, nr, li), _gap(c0, nc, lj, Q if periodic else None)) < 2
+    if near.any():
+        o = int(np.nonzero(near)[0][0])
+        raise ValueError(f"member 0 (and every other): the flux line cell ({li[o]}, {lj[o]}) is closer than 2 cells to the "
+                         f"design window {p.win}: the adjoint sources take the permittivity there as fixed")
+    for b, (sr, sc, snr, snc) in enumerate(p.rects):
+        if snr and snc:
+            near = np.maximum(_gap(sr, snr, li), _gap(sc, snc, lj, Q if periodic else None)) < 2
+            if near.any():
+                o = int(np.nonzero(near)[0][0])
+                raise ValueError(f"member {b}: the flux line cell ({li[o]}, {lj[o]}) is closer than 2 cells to the forward "
+                                 f"source {(int(sr), int(sc), int(snr), int(snc))}, whose direct term the monitor would "
+                                 f"read")
+    s = None if sigma is None else _check_sigma(p, sigma)
+    if s is not None and np.any(s[:, li, lj] != 0):
+        b = int(np.nonzero((s[:, li, lj] != 0).any(axis=1))[0][0])
+        raise ValueError(f"member {b}: sigma is non-zero at a flux line cell; the adjoint injection there would be "
+                         f"conj(g) / (D + G), which is not implemented")
+    # the two H values of an entry take the same 0.5 s_h, so the H update's ch = dt / (mu dx) must agree on them
+    mu_e = np.broadcast_to(np.asarray(MU0 if mu is None else mu), eps.shape).astype(dtype).astype(np.float64)
+    before = mu_e[:, np.where(lcol, li, li - 1), np.where(lcol, np.where(lj == 0, Q - 1, lj - 1), lj)]
+    if np.any(mu_e[:, li, lj] != before):
+        b = int(np.nonzero((mu_e[:, li, lj] != before).any(axis=1))[0][0])
+        raise ValueError(f"member {b}: mu differs between the two H values of a flux line cell; the adjoint's magnetic "
+                         f"sheet drives both with one weight")
+    D = eps.astype(dtype).astype(np.float64)[:, li, lj] * dx / dt
+    p.lines, p.sigma = lines, s
+    p.scale_e, p.scale_h = 1.0 / D, -dt / (mu_e[:, li, lj] * dx)
+    p.solve = np.stack([np.linalg.inv(p.systems[k][1]) for k in p.which])
+    return p
+
+
+def _flux_cotangent(p, objective, P):
+    J, g = objective(P)
+    J = np.asarray(J, dtype=np.float64)
+    g = np.asarray(g, dtype=np.float64)
+    if J.shape != (p.B,) or g.shape != P.shape:
+        raise ValueError(f"objective must return J of shape ({p.B},) and dJ/dP of shape {P.shape}, got {J.shape} and "
+                         f"{g.shape}")
+    return J, g
+
+
+def batch_flux_gradient(eps, sigma=None, mu=None, *, nsteps, sources, flux_lines, omegas, design, objective, fc=30e9,
+                        waveform="ricker", dt=5e-14, dx=1e-4, dtype=np.float64, boundary="pml", pml_cells=40, device=0,
+                        engine=None):
+    """Gradient of an objective on the power through flux lines with respect to eps (and sigma) over a design window,
+    for B members at once, at the cost of two runs per member.
+
+    flux_lines: up to 4 lines as BatchEngine.set_flux_lines takes them, shared by all members; omegas: (F,) or (B, F).
+    objective(P) takes the float64 (B, N, F) array of BatchEngine.flux() and returns (J (B,), dJ/dP (B, N, F)).  The
+    other arguments are batch_material_gradient's; boundary is "pml" or "periodic".
+
+    The method (module docstring): the forward run records the window DFT over the design
+    window and the lines' sums; the cotangent of P on a line cell has an electric part, dJ/dP s dx conj(H g) / D, and a
+    magnetic part, -dJ/dP s dx conj(E g) dt / (mu dx); the adjoint run drives the same member through
+    set_flux_line_sources with the 2F channels of the probe helpers, and dft_window_product with the unchanged
+    coefficients forms the gradients.
+
+    Conditions, checked on the host before any device work (ValueError naming the reason), beside those of
+    batch_material_gradient: every line cell lies outside the PML layer and off the grid's edge, at least 2 cells from the
+    design window and from every forward source; sigma is zero at the line cells; mu agrees on the two H values of every
+    line cell.  info["residual_forward"] and info["residual_adjoint"] compare the end-of-run max|Ez| with the largest
+    sample at the first cell of each line.
+
+    Out of scope: Bloch and lattice batches, dJ/d wp2 of a dispersive member, gradients with respect to mu.
+
+    Returns (J (B,), grad_eps (B, nrows, ncols), grad_sigma (the same shape, or None without sigma), P (B, N, F), info)."""
+    p = _flux_plan(eps, sigma, mu, nsteps, sources, flux_lines, omegas, design, fc, waveform, dt, dx, dtype, boundary,
+                   pml_cells)
+    if engine is None:
+        from .batch import BatchEngine as engine
+    B = p.B
+    with engine(B, p.R, p.Cc, dt, dx, dtype=dtype, boundary=boundary, device=device) as eng:
+        _refuse_bloch(eng)
+        _setup(eng, p)
+        if p.sigma is not None:
+            eng.set_conductivity(p.sigma)
+        eng.set_flux_lines(p.lines, p.om)
+        eng.run(p.nsteps, p.amps)
+        traces = eng.read_probes(0, p.nsteps)
+        end_fwd = np.abs(eng.download()[0].astype(np.float64)).reshape(B, -1).max(axis=1)
+        eng.hold_dft_window()
+        P = eng.flux()
+        J, g = _flux_cotangent(p, objective, P)
+        E, H = eng.read_flux_lines(raw=True)
+        we, wh = flux_adjoint_weights(E, H, g, p.lines, p.om, dt, dx, p.solve, p.scale_e, p.scale_h)
+        eng.reset()
+        eng.set_flux_line_sources(we, wh)
+        eng.run(p.nsteps, None, p.channels)
+        adj_traces = eng.read_probes(0, p.nsteps)
+        end_adj = np.abs(eng.download()[0].astype(np.float64)).reshape(B, -1).max(axis=1)
+        grad = eng.dft_window_product(p.coef) * (dx / dt)
+        grad_sigma = None if p.sigma is None else eng.dft_window_product(p.coef_sigma) * (dx / 2)
+
+    def peak(tr):
+        return np.abs(tr.reshape(B, -1)).max(axis=1)
+    info = {"condition": max(s[2] for s in p.systems.values()),
+            "residual_forward": _residual(end_fwd, peak(traces)), "residual_adjoint": _residual(end_adj, peak(adj_traces)),
+            "channels_shared": p.shared}
+    return J, grad, grad_sigma, P, info
+
+
+class FluxAdjointSession(AdjointSession):
+    """batch_flux_gradient as a loop: AdjointSession for objectives on the power through flux lines.
+
+    The constructor takes batch_flux_gradient's arguments (without the objective) and makes its host checks.
+    value_and_grad(objective) returns (J, grad_eps, P, info); it forms the adjoint sources on the device
+    (BatchEngine.flux_adjoint_sources), so B * N * F powers and B * nrows * ncols gradients come down, B * N * F
+    derivatives go up, and no line spectrum, trace, field or window is read back.  set_design_eps, set_design_sigma,
+    set_conductivity, sigma_gradient and info["residual_*"] behave as in AdjointSession; a conductivity must stay zero on
+    the line cells."""
+
+    def __init__(self, eps, sigma=None, mu=None, *, nsteps, sources, flux_lines, omegas, design, fc=30e9,
+                 waveform="ricker", dt=5e-14, dx=1e-4, dtype=np.float64, boundary="pml", pml_cells=40, device=0,
+                 engine=None):
+        self._eng = None
+        p = _flux_plan(eps, sigma, mu, nsteps, sources, flux_lines, omegas, design, fc, waveform, dt, dx, dtype, boundary,
+                       pml_cells)
+        self._open(p, dtype, engine, device)
+        if p.sigma is not None:
+            self._sigma = p.sigma.copy()
+
+    def _setup_engine(self, eng):
+        p = self._p
+        _setup(eng, p)
+        if p.sigma is not None:
+            eng.set_conductivity(p.sigma)
+        eng.set_flux_lines(p.lines, p.om)
+
+    def _check_line_sigma(self, s, r0=0, c0=0):
+        li, lj, _, _ = _line_entries(self._p.lines)
+        inside = (li >= r0) & (li < r0 + s.shape[1]) & (lj >= c0) & (lj < c0 + s.shape[2])
+        if np.any(s[:, li[inside] - r0, lj[inside] - c0] != 0):
+            raise ValueError("member 0 (or another): sigma is non-zero at a flux line cell; the adjoint injection there "
+                             "would be conj(g) / (D + G), which is not implemented")
+
+    def set_conductivity(self, sigma):
+        if sigma is not None and self._eng is not None:
+            self._check_line_sigma(_check_sigma(self._p, sigma))
+        return super().set_conductivity(sigma)
+
+    def value_and_grad(self, objective):
+        """(J (B,), grad_eps (B, nrows, ncols) float64, P (B, N, F) float64, info) of the current materials."""
+        p, eng = self._p, self._eng
+        if eng is None:
+            raise RuntimeError("the session is closed")
+        self._check_engine(eng)
+        none = np.empty((p.B, 0))
+        eng.reset()
+        eng.run(p.nsteps, p.amps)
+        _, peak_fwd = self._spectra(eng, none)
+        end_fwd = self._absmax(eng)
+        self._hold(eng)
+        P = eng.flux()
+        J, g = _flux_cotangent(p, objective, P)
+        eng.flux_adjoint_sources(g, p.solve[0] if p.shared else p.solve, p.scale_e, p.scale_h)
+        eng.reset()
+        eng.run(p.nsteps, None, p.channels)
+        _, peak_adj = self._spectra(eng, none)
+        end_adj = self._absmax(eng)
+        grad = self._product(eng, p.coef) * (p.dx / p.dt)
+        self._ran = True
+        info = {"condition": self._condition, "residual_forward": _residual(end_fwd, peak_fwd),
+                "residual_adjoint": _residual(end_adj, peak_adj), "channels_shared": p.shared}
+        return J, grad, P, info

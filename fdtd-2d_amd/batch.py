@@ -579,7 +579,7 @@ class BatchEngine:
             self._ck(self._lib.fdtd2d_batch_run(self._h, nsteps, None if a is None else _dptr(a)))
             return self
         ch = np.asarray(channels, dtype=np.float64)
-        K = self._npoint[1]
+        K = self._npoint[1] or self.info(_abi.BATCH_FLUX_LINE_SOURCES_INFO)   # line sources take the same channels
         if ch.shape[-1:] != () and ch.shape[-1] >= nsteps:
             ch = ch[..., :nsteps]
         if ch.shape not in ((K, nsteps), (self.count, K, nsteps)):
@@ -959,6 +959,83 @@ class BatchEngine:
         fn = self._lib.fdtd2d_batch_bloch_flux if self._bflux else self._lib.fdtd2d_batch_flux
         self._ck(fn(self._h, _dptr(buf)))
         return out
+
+    # -- line sources on the flux lines (fdtd2d_batch_flux_adjoint.h) --------------------------------------
+    def _flux_entries(self, what):
+        if self._flux is None or self._bflux:
+            raise _abi.Fdtd2dError(_abi.E_STATE, f"{what} live on flux lines: call set_flux_lines first (not with "
+                                                 f"set_bloch_flux_lines)")
+        return int(self._flux[0][:, 3].sum())
+
+    def set_flux_line_sources(self, we, wh):
+        """Sources on the cells of set_flux_lines, the transpose of the monitor: we drives Ez and wh the tangential H
+        with the monitor's centring.  we, wh: float64 (cells, K) for every member or (B, cells, K), K <= 32, cells being
+        the lines' cells concatenated in the order of read_flux_lines (a cell on two lines has two entries); either may
+        be None, both None removes the sources.  In step n of run(nsteps, amps, channels=...) entry w forms
+        s_e = sum_c we[w, c] * channels[c, n] and s_h likewise; 0.5 * s_h is added to each of the two H values the
+        monitor averages for the cell before the H update of the step, and s_e to Ez where the point sources add theirs
+        (fdtd2d_batch_flux_adjoint.h has the order of every addition).  An electric and a magnetic sheet on one line form
+        a one-way source.  K must equal the channel count of point sources that are set too; set_flux_lines removes the
+        line sources, reset() keeps them."""
+        if we is None and wh is None:
+            self._ck(self._lib.fdtd2d_batch_set_flux_line_sources(self._h, 0, None, None))
+            return self
+        cells = self._flux_entries("line sources")
+        parts = []
+        for name, w in (("we", we), ("wh", wh)):
+            if w is None:
+                parts.append(None)
+                continue
+            w = np.asarray(w, dtype=np.float64)
+            if w.ndim == 2:
+                w = np.broadcast_to(w, (self.count,) + w.shape)
+            if w.ndim != 3 or w.shape[:2] != (self.count, cells):
+                raise ValueError(f"{name} must have shape ({cells}, K) or ({self.count}, {cells}, K), got {w.shape}")
+            parts.append(np.ascontiguousarray(w))
+        K = {int(w.shape[2]) for w in parts if w is not None}
+        if len(K) != 1:
+            raise ValueError(f"we and wh must have the same number of channels, got {sorted(K)}")
+        K = K.pop()
+        if not 1 <= K <= _abi.BATCH_MAX_CHANNELS:
+            raise ValueError(f"line sources take 1..{_abi.BATCH_MAX_CHANNELS} channels, got {K}")
+        self._ck(self._lib.fdtd2d_batch_set_flux_line_sources(self._h, K, *(None if w is None else _dptr(w)
+                                                                            for w in parts)))
+        return self
+
+    def read_flux_line_sources(self):
+        """(we, wh), each float64 (B, cells, K): the weights as the engine holds them (an absent part reads as zeros)."""
+        cells, K = self._flux_entries("line sources"), self.info(_abi.BATCH_FLUX_LINE_SOURCES_INFO)
+        out = [np.zeros((self.count, cells, K)) if K else np.zeros(1) for _ in range(2)]
+        self._ck(self._lib.fdtd2d_batch_read_flux_line_sources(self._h, *(_dptr(a) for a in out)))
+        return tuple(out)
+
+    def flux_adjoint_sources(self, dJdP, solve, scale_e=None, scale_h=None):
+        """Forms the line sources of the adjoint of a flux objective on the device, from the lines' current sums, and
+        installs them with K = 2F channels (one launch; nothing is read back).  dJdP: (B, N, F), the derivative of the
+        objective by flux().  solve: (2F, 2F) for every member or (B, 2F, 2F), the inverse of the channel system
+        (adjoint.channel_system).  scale_e, scale_h: (B, cells) real factors per entry (None: ones): the adjoint takes
+        dt / (eps dx) and -dt / (mu dx) of the cells.  With E, H the raw sums, g = exp(1j * omega * dt / 2) and
+        c = dJdP * s * dx per line, the targets are scale_e * c * conj(H g) for we and scale_h * c * conj(E g) for wh,
+        and the weights are solve @ [Re target; Im target].  flux_adjoint_weights is the same arithmetic on the host."""
+        cells = self._flux_entries("the adjoint sources")
+        ln, w = self._flux
+        N, F = len(ln), w.shape[1]
+        g = np.ascontiguousarray(dJdP, dtype=np.float64)
+        if g.shape != (self.count, N, F):
+            raise ValueError(f"dJdP must have shape ({self.count}, {N}, {F}), got {g.shape}")
+        s = np.ascontiguousarray(solve, dtype=np.float64)
+        if s.shape not in ((2 * F, 2 * F), (self.count, 2 * F, 2 * F)):
+            raise ValueError(f"solve must have shape ({2 * F}, {2 * F}) or ({self.count}, {2 * F}, {2 * F}), got {s.shape}")
+        scales = []
+        for name, a in (("scale_e", scale_e), ("scale_h", scale_h)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape != (self.count, cells):
+                    raise ValueError(f"{name} must have shape ({self.count}, {cells}), got {a.shape}")
+            scales.append(a)
+        self._ck(self._lib.fdtd2d_batch_flux_line_weights(self._h, _dptr(g), _dptr(s), int(s.ndim == 3),
+                                                          *(None if a is None else _dptr(a) for a in scales)))
+        return self
 
     @property
     def flux_lines_in_lds(self) -> bool:

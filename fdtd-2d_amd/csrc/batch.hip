@@ -35,6 +35,7 @@
 #include "../../include/fdtd2d_batch_dispersive.h"
 #include "../../include/fdtd2d_batch_dispersive_adjoint.h"
 #include "../../include/fdtd2d_batch_flux.h"
+#include "../../include/fdtd2d_batch_flux_adjoint.h"
 #include "../../include/fdtd2d_batch_lattice.h"
 #include "../../include/fdtd2d_batch_lossy.h"
 #include "../../include/fdtd2d_batch_monitor.h"
@@ -61,6 +62,7 @@
 #include "kernels_batch_design.hpp"
 #include "kernels_batch_dispersive.hpp"
 #include "kernels_batch_flux.hpp"
+#include "kernels_batch_flux_adjoint.hpp"
 #include "kernels_batch_lattice.hpp"
 #include "kernels_batch_lossy.hpp"
 #include "kernels_batch_monitor.hpp"
@@ -164,6 +166,11 @@ struct fdtd2d_batch {
     // flux_acc_im, of the same layout, those of the imaginary part
     bool bflux = false;
     double *flux_acc_im = nullptr;
+    // line sources on the flux lines (fdtd2d_batch_flux_adjoint.h): count x flux_cells x fsrc_nchan weights each
+    // (nullptr: no such part); fsrc_nchan = 0 without them
+    int fsrc_nchan = 0;
+    double *fsrc_we = nullptr, *fsrc_wh = nullptr;
+    int *fsrc_geom = nullptr;             // the lines as batch_fluxsrc_gather reads them (BatchFluxSrc::geom)
     double *win_held = nullptr;           // fdtd2d_batch_hold_dft_window: a copy of win_acc
     double *win_held_disp = nullptr;      // fdtd2d_batch_hold_dispersive_window: a copy of win_acc while a pole is set
     // point sources (fdtd2d_batch_set_point_sources), every table in the resident owners' order
@@ -855,12 +862,15 @@ fdtd::BatchFlux flux_view(const fdtd2d_batch *b)
     return f;
 }
 
+// fs: the line sources of a run with channels (nullptr: none, the kernels of batch_flux.hip; otherwise those of
+// batch_flux_adjoint.hip, which take fs behind the lines)
 template <class T>
-int run_flux(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts)
+int run_flux(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts,
+             fdtd::BatchFluxSrc *fs = nullptr)
 {
     if (!b->ca || !b->ezx || !b->flux_acc || (b->dcj && (!b->djh || !b->dq || !b->da || !b->dck)))
         return bfail(b, FDTD2D_E_STATE, "batch with flux lines without its arrays");
-    const fdtd::BatchFluxKernels &K = fdtd::batch_flux_kernels<T>();
+    const fdtd::BatchFluxKernels &K = fs ? fdtd::batch_flux_src_kernels<T>() : fdtd::batch_flux_kernels<T>();
     const int per = b->periodic ? 1 : 0, disp = b->dcj ? 1 : 0;
     fdtd::BatchPml<T> p = pml_view<T>(b);
     fdtd::BatchMon m = mon_view(b);
@@ -891,7 +901,8 @@ int run_flux(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stri
             fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
             v.ce = (const T *)b->cb;
             void *args[] = {&v, &p, &m, pts, &d, &f, &ca, &n0, &nt, &step_base};
-            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads), args, lds);
+            void *src_args[] = {&v, &p, &m, pts, &d, &f, fs, &ca, &n0, &nt, &step_base};
+            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads), fs ? src_args : args, lds);
             if (rc) return rc;
             b->launches++;
             b->step += nt;
@@ -907,8 +918,10 @@ int run_flux(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stri
         int rc;
         void *h_args[] = {&v, &p, &m, pts, &f, &n, &step};
         void *e_args[] = {&v, &p, &m, pts, &d, &f, &ca, &n, &step};
-        if ((rc = launch_ptr(b, K.h[per], grid, dim3(256), h_args, 0))) return rc;
-        if ((rc = launch_ptr(b, K.e[per][disp], grid, dim3(256), e_args, 0))) return rc;
+        void *h_src_args[] = {&v, &p, &m, pts, &f, fs, &n, &step};
+        void *e_src_args[] = {&v, &p, &m, pts, &d, &f, fs, &ca, &n, &step};
+        if ((rc = launch_ptr(b, K.h[per], grid, dim3(256), fs ? h_src_args : h_args, 0))) return rc;
+        if ((rc = launch_ptr(b, K.e[per][disp], grid, dim3(256), fs ? e_src_args : e_args, 0))) return rc;
         b->launches += 2;
         b->step++;
     }
@@ -1169,13 +1182,14 @@ template <class T> int run_bloch_flux(fdtd2d_batch *b, int nsteps, const double 
 }
 
 template <class T>
-int run_impl(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts = nullptr)
+int run_impl(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts = nullptr,
+             fdtd::BatchFluxSrc *fs = nullptr)
 {
     if (b->bflux) return run_bloch_flux<T>(b, nsteps, amps, amp_stride);
     if (b->bdisp) return run_bloch_dispersive<T>(b, nsteps, amps, amp_stride);
     if (b->lattice) return run_lattice<T>(b, nsteps, amps, amp_stride);
     if (b->bloch) return run_bloch<T>(b, nsteps, amps, amp_stride);
-    if (b->flux_nl) return run_flux<T>(b, nsteps, amps, amp_stride, pts);
+    if (b->flux_nl) return run_flux<T>(b, nsteps, amps, amp_stride, pts, fs);
     if (b->dcj) return run_dispersive<T>(b, nsteps, amps, amp_stride, pts);
     if (b->periodic) return run_periodic<T>(b, nsteps, amps, amp_stride, pts);
     if (b->ca) return run_lossy<T>(b, nsteps, amps, amp_stride, pts);
@@ -1443,6 +1457,13 @@ int refuse_flux(fdtd2d_batch *b, const char *what)
                      "(fdtd2d_batch_set_bloch_flux_lines with nlines = 0)", what);
     return bfail(b, FDTD2D_E_STATE, "%s is not available while flux lines are set: remove them first "
                  "(fdtd2d_batch_set_flux_lines with nlines = 0)", what);
+}
+
+// removes the line sources of fdtd2d_batch_flux_adjoint.h (the stream is idle)
+void fsrc_drop(fdtd2d_batch *b)
+{
+    for (void **p : {(void **)&b->fsrc_we, (void **)&b->fsrc_wh, (void **)&b->fsrc_geom}) release(p);
+    b->fsrc_nchan = 0;
 }
 
 int refuse_dispersive(fdtd2d_batch *b, const char *what)
@@ -1886,7 +1907,8 @@ void fdtd2d_batch_destroy(fdtd2d_batch_t *b)
                      (void **)&b->win_held_im, (void **)&b->win_held_disp,
                      &b->djh, &b->dq, &b->dcj, &b->da, &b->dck, &b->djh_im, &b->dq_im,
                      (void **)&b->flux_acc, (void **)&b->flux_omega, (void **)&b->flux_ph,
-                     (void **)&b->flux_acc_im})
+                     (void **)&b->flux_acc_im, (void **)&b->fsrc_we, (void **)&b->fsrc_wh,
+                     (void **)&b->fsrc_geom})
         release(p);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -1928,6 +1950,7 @@ long long fdtd2d_batch_info(const fdtd2d_batch_t *b, int what)
     case FDTD2D_BATCH_INFO_HELD_DISPERSIVE_WINDOW: return b->win_held_disp ? 1 : 0;
     case FDTD2D_BATCH_INFO_FLUX_LINES: return b->flux_nl;
     case FDTD2D_BATCH_INFO_FLUX_LDS: return use_resident(b) && flux_acc_in_lds(b) ? 1 : 0;
+    case FDTD2D_BATCH_INFO_FLUX_LINE_SOURCES: return b->fsrc_nchan;
     default: return FDTD2D_E_ARG;
     }
 }
@@ -2468,6 +2491,9 @@ static int batch_set_points(fdtd2d_batch *b, int ncell, const int *cells, int nc
         if (nchan < 1 || nchan > FDTD2D_BATCH_MAX_CHANNELS)
             return bfail(b, FDTD2D_E_ARG, "nchan %d outside 1..%d", nchan, FDTD2D_BATCH_MAX_CHANNELS);
         if (!cells || !weights) return bfail(b, FDTD2D_E_ARG, "cells and weights must not be NULL");
+        if (b->fsrc_nchan && nchan != b->fsrc_nchan)
+            return bfail(b, FDTD2D_E_STATE, "%d channels, but the line sources that are set take %d: one run drives both",
+                         nchan, b->fsrc_nchan);
         for (int m = 0; m < b->count; ++m) {
             int images = 0;
             for (int p = 0; p < ncell; ++p) {
@@ -2562,7 +2588,8 @@ int fdtd2d_batch_run_channels(fdtd2d_batch_t *b, int nsteps, const double *amps,
     if (nsteps < 0) return bfail(b, FDTD2D_E_ARG, "nsteps < 0");
     if (!chan) return bfail(b, FDTD2D_E_ARG, "chan must not be NULL");
     if (b->bloch) return refuse_bloch(b, "a run with channels");
-    if (!b->npts) return bfail(b, FDTD2D_E_STATE, "no point sources are set: call fdtd2d_batch_set_point_sources first");
+    if (!b->npts && !b->fsrc_nchan)
+        return bfail(b, FDTD2D_E_STATE, "no point sources are set: call fdtd2d_batch_set_point_sources first");
     int rc = need_ready(b);
     if (rc) return rc;
     for (int m = 0; m < b->count; ++m)
@@ -2575,19 +2602,28 @@ int fdtd2d_batch_run_channels(fdtd2d_batch_t *b, int nsteps, const double *amps,
         if ((rc = stage(b, &b->amps, &b->amps_cap, amps, (size_t)b->count * nsteps * sizeof(double)))) return rc;
         dev_amps = b->amps;
     }
-    const size_t per = (size_t)b->pts_nchan * nsteps;
+    const int nchan = b->npts ? b->pts_nchan : b->fsrc_nchan;     // equal when both are set
+    const size_t per = (size_t)nchan * nsteps;
     if ((rc = stage(b, &b->chan, &b->chan_cap, chan, (chan_per_member ? b->count : 1) * per * sizeof(double))))
         return rc;
-    fdtd::BatchPts P;
-    P.cells = b->pts_cells;
-    P.own = b->pts_own;
-    P.w = b->pts_w;
-    P.chan = b->chan;
-    P.tab = b->pts_tab;
-    P.chan_mstride = chan_per_member ? (long long)per : 0;
-    P.chan_stride = nsteps;
-    P.nc = b->npts;
-    P.nchan = b->pts_nchan;
+    fdtd::BatchPts P{};                     // nc = 0 without point sources: silent, like a run without channels
+    if (b->npts) {
+        P.cells = b->pts_cells;
+        P.own = b->pts_own;
+        P.w = b->pts_w;
+        P.chan = b->chan;
+        P.tab = b->pts_tab;
+        P.chan_mstride = chan_per_member ? (long long)per : 0;
+        P.chan_stride = nsteps;
+        P.nc = b->npts;
+        P.nchan = b->pts_nchan;
+    }
+    if (b->fsrc_nchan) {                    // line sources (fdtd2d_batch_flux_adjoint.h): the same channels
+        fdtd::BatchFluxSrc S{b->fsrc_we, b->fsrc_wh, b->chan, b->fsrc_geom, chan_per_member ? (long long)per : 0,
+                             nsteps, nchan, b->flux_cells};
+        return b->dtype == FDTD2D_F32 ? run_impl<float>(b, nsteps, dev_amps, nsteps, &P, &S)
+                                      : run_impl<double>(b, nsteps, dev_amps, nsteps, &P, &S);
+    }
     return b->dtype == FDTD2D_F32 ? run_impl<float>(b, nsteps, dev_amps, nsteps, &P)
                                   : run_impl<double>(b, nsteps, dev_amps, nsteps, &P);
 }
@@ -3616,6 +3652,7 @@ int fdtd2d_batch_set_flux_lines(fdtd2d_batch_t *b, int nlines, const int *lines,
             release(p);
         b->flux_nl = b->flux_nff = b->flux_cells = 0;
         b->bflux = false;
+        fsrc_drop(b);                                         // the line sources go with their lines
         if (b->sigma_implicit && !b->periodic && !b->dcj) {   // the all-zero conductivity the lines brought
             release(&b->ca);
             release(&b->cb);
@@ -3644,6 +3681,7 @@ int fdtd2d_batch_set_flux_lines(fdtd2d_batch_t *b, int nlines, const int *lines,
         return bfail(b, -(1000 + (int)e), "setting up the flux lines failed: %s", hipGetErrorString(e));
     }
     for (void **p : {(void **)&b->flux_acc, (void **)&b->flux_omega, (void **)&b->flux_ph}) release(p);
+    fsrc_drop(b);                               // line sources belong to the lines they were set on
     b->flux_acc = nacc;
     b->flux_omega = nom;
     b->flux_ph = nph;
@@ -3817,6 +3855,150 @@ int fdtd2d_batch_bloch_flux(fdtd2d_batch_t *b, double *out)
     BCHK(b, hipStreamSynchronize(b->stream));
     BCHK(b, hipMemcpy(out, b->dsg, n * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
+}
+
+}  // extern "C"
+
+// ---- fdtd2d_batch_flux_adjoint.h ----------------------------------------------------------------------------------
+
+namespace {
+
+// what line sources need: plain flux lines (hence a PML or periodic batch without a Bloch phase) and, when point sources
+// are set too, their channel count
+int fsrc_refuse(fdtd2d_batch *b, int nchan)
+{
+    if (!b->flux_nl || b->bflux)
+        return bfail(b, FDTD2D_E_STATE, "line sources live on flux lines: call fdtd2d_batch_set_flux_lines first (a PML or "
+                     "periodic batch without a Bloch phase)");
+    if (b->npts && b->pts_nchan != nchan)
+        return bfail(b, FDTD2D_E_STATE, "%d channels, but the point sources that are set take %d: one run drives both",
+                     nchan, b->pts_nchan);
+    return 0;
+}
+
+// replaces the line sources by the device arrays given (either may be nullptr) and uploads the lines' geometry for
+// them; on failure the arrays are released and the previous sources stay
+int fsrc_install(fdtd2d_batch *b, double *we, double *wh, int nchan)
+{
+    int geom[fdtd::BATCH_FLUXSRC_GEOM] = {};
+    int off = 0;
+    for (int k = 0; k < b->flux_nl; ++k) {
+        for (int q = 0; q < 4; ++q) geom[5 * k + q] = b->flux_line[4 * k + q];
+        geom[5 * k + 4] = off;
+        off += b->flux_line[4 * k + 3];
+    }
+    geom[5 * FDTD2D_BATCH_MAX_FLUX_LINES] = b->flux_nl;
+    int *ng = nullptr;
+    int rc = alloc(b, (void **)&ng, sizeof geom);
+    hipError_t e = rc ? hipSuccess : hipMemcpy(ng, geom, sizeof geom, hipMemcpyHostToDevice);
+    if (rc || e != hipSuccess) {
+        for (void **p : {(void **)&we, (void **)&wh, (void **)&ng}) release(p);
+        return rc ? rc : bfail(b, -(1000 + (int)e), "setting up the line sources failed: %s", hipGetErrorString(e));
+    }
+    fsrc_drop(b);
+    b->fsrc_we = we;
+    b->fsrc_wh = wh;
+    b->fsrc_geom = ng;
+    b->fsrc_nchan = nchan;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fdtd2d_batch_set_flux_line_sources(fdtd2d_batch_t *b, int nchan, const double *we, const double *wh)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if ((!we && !wh) || nchan == 0) {           // remove
+        if (!b->fsrc_nchan) return 0;
+        int rc = use_device(b);
+        if (rc) return rc;
+        BCHK(b, hipStreamSynchronize(b->stream));
+        fsrc_drop(b);
+        return 0;
+    }
+    if (nchan < 1 || nchan > FDTD2D_BATCH_MAX_CHANNELS)
+        return bfail(b, FDTD2D_E_ARG, "nchan %d outside 1..%d", nchan, FDTD2D_BATCH_MAX_CHANNELS);
+    int rc = fsrc_refuse(b, nchan);
+    if (rc) return rc;
+    const size_t n = (size_t)b->count * b->flux_cells * nchan;
+    for (const double *w : {we, wh})
+        for (size_t k = 0; w && k < n; ++k)
+            if (!std::isfinite(w[k]))
+                return bfail(b, FDTD2D_E_ARG, "member %zu: a line source weight is not finite",
+                             k / ((size_t)b->flux_cells * nchan));
+    if ((rc = use_device(b))) return rc;
+    double *ne = nullptr, *nh = nullptr;
+    if ((we && (rc = alloc(b, (void **)&ne, n * sizeof(double)))) ||
+        (wh && (rc = alloc(b, (void **)&nh, n * sizeof(double))))) {
+        for (void **p : {(void **)&ne, (void **)&nh}) release(p);
+        return rc;
+    }
+    hipError_t e = hipStreamSynchronize(b->stream);   // a running launch may still read the old weights
+    if (e == hipSuccess && we) e = hipMemcpy(ne, we, n * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess && wh) e = hipMemcpy(nh, wh, n * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        for (void **p : {(void **)&ne, (void **)&nh}) release(p);
+        return bfail(b, -(1000 + (int)e), "setting up the line sources failed: %s", hipGetErrorString(e));
+    }
+    return fsrc_install(b, ne, nh, nchan);
+}
+
+int fdtd2d_batch_read_flux_line_sources(fdtd2d_batch_t *b, double *we, double *wh)
+{
+    if (!b || !we || !wh) return FDTD2D_E_ARG;
+    if (!b->fsrc_nchan) return bfail(b, FDTD2D_E_STATE, "no line sources are set");
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    const size_t n = (size_t)b->count * b->flux_cells * b->fsrc_nchan;
+    const double *from[2] = {b->fsrc_we, b->fsrc_wh};
+    double *to[2] = {we, wh};
+    for (int k = 0; k < 2; ++k) {
+        if (from[k]) BCHK(b, hipMemcpy(to[k], from[k], n * sizeof(double), hipMemcpyDeviceToHost));
+        else std::fill(to[k], to[k] + n, 0.0);
+    }
+    return 0;
+}
+
+int fdtd2d_batch_flux_line_weights(fdtd2d_batch_t *b, const double *dJdP, const double *solve, int solve_per_member,
+                                   const double *scale_e, const double *scale_h)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!dJdP || !solve) return bfail(b, FDTD2D_E_ARG, "dJdP and solve must not be NULL");
+    const int nchan = 2 * b->flux_nff;
+    int rc = fsrc_refuse(b, nchan);
+    if (rc) return rc;
+    if ((rc = use_device(b))) return rc;
+    const size_t nj = (size_t)b->count * b->flux_nl * b->flux_nff, ns = (size_t)(solve_per_member ? b->count : 1) * nchan * nchan;
+    const size_t nc = (size_t)b->count * b->flux_cells, nw = nc * nchan;
+    // the inputs in the design loop's scratch: dJdP, solve, scale_e, scale_h
+    if ((rc = scratch(b, (nj + ns + 2 * nc) * sizeof(double)))) return rc;
+    double *dj = (double *)b->dsg, *ds = dj + nj, *dse = ds + ns, *dsh = dse + nc;
+    double *ne = nullptr, *nh = nullptr;
+    if ((rc = alloc(b, (void **)&ne, nw * sizeof(double))) || (rc = alloc(b, (void **)&nh, nw * sizeof(double)))) {
+        for (void **p : {(void **)&ne, (void **)&nh}) release(p);
+        return rc;
+    }
+    hipError_t e = hipStreamSynchronize(b->stream);
+    if (e == hipSuccess) e = hipMemcpy(dj, dJdP, nj * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ds, solve, ns * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess && scale_e) e = hipMemcpy(dse, scale_e, nc * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess && scale_h) e = hipMemcpy(dsh, scale_h, nc * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const fdtd::BatchFluxWeights W{dj, ds, scale_e ? dse : nullptr, scale_h ? dsh : nullptr, ne, nh,
+                                       solve_per_member ? (long long)nchan * nchan : 0};
+        fdtd::batch_flux_line_weights_launch(flux_view(b), W, b->count, b->dt, b->dx, b->stream);
+        e = hipGetLastError();
+        if (e == hipSuccess) b->launches++;
+        if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    }
+    if (e != hipSuccess) {
+        for (void **p : {(void **)&ne, (void **)&nh}) release(p);
+        return bfail(b, -(1000 + (int)e), "forming the line source weights failed: %s", hipGetErrorString(e));
+    }
+    return fsrc_install(b, ne, nh, nchan);
 }
 
 }  // extern "C"

@@ -106,10 +106,21 @@ array eps with random binary permittivity, a ricker line source per member):
                               plain_ms, flux_ms, flux_over_plain, where the sums live (flux_lines_in_lds), the LDS sizes
                               and flux_call_ms.  Default: 1024 members of 60 rows x 61 columns, a 10-cell layer, 2000
                               steps.
+  --flux-adjoint              instead: the adjoint of a flux objective on the members of --flux (periodic, two
+                              whole-period row lines at 10 frequencies, dt = 2e-13, a design window of 100 cells between
+                              them, 20 channels), timed alternately in one process: flux_ms (a run with the lines and a
+                              window DFT over the design window), adjoint_run_ms (the same run driven through
+                              set_flux_line_sources: E and H parts on both lines) and adjoint_run_over_flux;
+                              flux_session_ms (one FluxAdjointSession.value_and_grad, the weights formed on the device)
+                              against probe_session_ms (one AdjointSession.value_and_grad with 30 probes on the same
+                              members) and flux_over_probe_session; weights_ms (one flux_adjoint_sources) and where
+                              the weights live.  Default: 1024 members of 60 rows x 61 columns, a 10-cell layer, 2000
+                              steps.
 Usage: python tools/bench_batch.py [--count 1024 --rows 60 --cols 60 --steps 1000] [--reps 5] [--loop-members 16]
                                    [--boundary {mur,pml} --pml-cells 10] [--monitors] [--adjoint] [--lossy]
                                    [--periodic] [--bloch] [--bloch-adjoint] [--dispersive] [--lattice]
                                    [--bloch-dispersive] [--dispersive-adjoint] [--flux] [--bloch-flux]
+                                   [--flux-adjoint]
 """
 import argparse
 import json
@@ -425,6 +436,109 @@ def bench_flux(count, rows, cols, steps, dtype, reps, pml_cells):
     out.update({"flux_over_plain": round(med["flux"] / med["plain"], 3),
                 "window_over_plain": round(med["window"] / med["plain"], 3),
                 "flux_mcell_steps_per_s": round(count * rows * cols * steps / (med["flux"] * 1e-3) / 1e6, 1)})
+    return out
+
+
+def bench_flux_adjoint(count, rows, cols, steps, dtype, reps, pml_cells):
+    """The adjoint run with line sources against a flux run without them, and one FluxAdjointSession iteration against
+    one AdjointSession iteration with 30 probes, on the same periodic members."""
+    from fdtd2d_amd.adjoint import channel_system
+    dt = 2e-13                                   # as --adjoint: the channels' envelope ends by step 1200
+    rng = np.random.default_rng(0)
+    side = 10
+    design = ((rows - side) // 2, (cols - 1 - side) // 2, side, side)
+    eps = np.full((count, rows, cols), fd.EPS0)
+    eps[:, design[0]:design[0] + side, design[1]:design[1] + side] = np.where(
+        rng.random((count, side, side)) < 0.5, fd.EPS0, 5 * fd.EPS0)
+    sigma = np.zeros((count, rows, cols))        # damps the modes a periodic high-index block guides along the columns
+    sigma[:, design[0]:design[0] + side, design[1]:design[1] + side] = 0.5
+    rects = np.tile([pml_cells + 3, 0, 1, cols - 1], (count, 1))
+    lines = [("row", rows // 4, 0, cols - 1), ("row", 3 * rows // 4, 0, cols - 1)]
+    probes = np.array([[3 * rows // 4, 2 * k] for k in range(30)])
+    omegas = 2 * np.pi * np.linspace(20e9, 65e9, 10)
+    amps = np.tile(np.array([fd.ricker_amplitude(i * dt, FC) for i in range(steps)]), (count, 1))
+    chan, A = channel_system(omegas, steps, dt, FC)
+    c00 = (1 / np.sqrt(fd.EPS0 * fd.MU0) * dt) / DX
+    cells = 2 * (cols - 1)
+    common = dict(nsteps=steps, sources=rects, omegas=omegas, design=design, fc=FC, dt=dt, dx=DX, dtype=dtype,
+                  boundary="periodic", pml_cells=pml_cells)
+
+    def flux_objective(P):                       # the transmittance through the far line, summed over the frequencies
+        g = np.zeros_like(P)
+        g[:, 1, :] = 1.0
+        return P[:, 1, :].sum(axis=1), g
+
+    def probe_objective(spectra):
+        mag = np.abs(spectra)
+        return mag.mean(axis=1).sum(axis=1), spectra / np.maximum(mag, 1e-300) / spectra.shape[1]
+
+    fs = fd.FluxAdjointSession(eps, sigma, flux_lines=lines, **common)
+    ps = fd.AdjointSession(eps, probes=probes, **common)
+    ps.set_conductivity(sigma)
+    with fd.BatchEngine(count, rows, cols, dt, DX, dtype=dtype, boundary="periodic") as b:
+        b.set_materials(eps.astype(dtype), fd.MU0).set_sources(rects).set_pml(pml_cells, courant00=c00)
+        b.set_conductivity(sigma)
+        b.set_dft_window(design, omegas).set_flux_lines(lines, omegas)
+        b.set_flux_line_sources(1e-2 * rng.standard_normal((count, cells, 20)),
+                                1e-5 * rng.standard_normal((count, cells, 20)))
+        dJdP, solve = np.ones((count, 2, 10)), np.linalg.inv(A)
+
+        def flux_run():
+            b.reset().sync()
+            t0 = time.perf_counter()
+            b.run(steps, amps).sync()
+            return (time.perf_counter() - t0) * 1e3
+
+        def adjoint_run():
+            b.reset().sync()
+            t0 = time.perf_counter()
+            b.run(steps, None, chan).sync()
+            return (time.perf_counter() - t0) * 1e3
+
+        def weights():
+            t0 = time.perf_counter()
+            b.flux_adjoint_sources(dJdP, solve)
+            return (time.perf_counter() - t0) * 1e3
+
+        def flux_session():
+            t0 = time.perf_counter()
+            out = fs.value_and_grad(flux_objective)
+            return (time.perf_counter() - t0) * 1e3, out[3]
+
+        def probe_session():
+            t0 = time.perf_counter()
+            ps.value_and_grad(probe_objective)
+            return (time.perf_counter() - t0) * 1e3
+
+        flux_run(), adjoint_run(), flux_session(), probe_session()    # warm-up: code objects, clocks
+        assert b.resident and fs.engine.resident and ps.engine.resident
+        l0 = fs.engine.launches
+        info = flux_session()[1]
+        session_launches = fs.engine.launches - l0
+        t = {k: [] for k in ("flux", "adjoint_run", "weights", "flux_session", "probe_session")}
+        for _ in range(reps):
+            t["flux"].append(flux_run())
+            t["adjoint_run"].append(adjoint_run())
+            t["flux_session"].append(flux_session()[0])
+            t["probe_session"].append(probe_session())
+        for _ in range(reps):                        # last: they replace the timed run's weights
+            t["weights"].append(weights())
+        in_lds, lds = b.flux_lines_in_lds, b.lds_bytes
+    fs.close()
+    ps.close()
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    out = {"count": count, "rows": rows, "cols": cols, "steps": steps, "dtype": np.dtype(dtype).name, "dt": dt,
+           "boundary": "periodic", "pml_cells": pml_cells, "design": list(design), "lines": 2, "line_cells": cells,
+           "freqs": 10, "channels": 20, "probes": 30, "reps": reps, "weights_live_in": "global memory",
+           "flux_sums_in_lds": in_lds, "lds_bytes_per_member": lds,
+           "launches_per_flux_session_iteration": session_launches,
+           "residual_forward_max": float(np.max(info["residual_forward"])),
+           "residual_adjoint_max": float(np.max(info["residual_adjoint"]))}
+    for k in t:
+        out.update({f"{k}_ms": round(med[k], 4), f"{k}_ms_min": round(min(t[k]), 4),
+                    f"{k}_ms_all": [round(v, 4) for v in t[k]]})
+    out.update({"adjoint_run_over_flux": round(med["adjoint_run"] / med["flux"], 3),
+                "flux_over_probe_session": round(med["flux_session"] / med["probe_session"], 3)})
     return out
 
 
@@ -1021,7 +1135,13 @@ def main():
     ap.add_argument("--flux", action="store_true", help="time flux lines against the same batch without monitors")
     ap.add_argument("--bloch-flux", action="store_true",
                     help="time flux lines on a Bloch batch against the same batch without monitors")
+    ap.add_argument("--flux-adjoint", action="store_true",
+                    help="time the adjoint run with line sources and a FluxAdjointSession iteration")
     a = ap.parse_args()
+    if a.flux_adjoint:
+        print(json.dumps(bench_flux_adjoint(a.count or 1024, a.rows or 60, a.cols or 61, a.steps or 2000,
+                                            np.dtype(a.dtype), a.reps, a.pml_cells)), flush=True)
+        return
     if a.bloch_flux:
         print(json.dumps(bench_bloch_flux(a.count or 1024, a.rows or 60, a.cols or 61, a.steps or 2000,
                                           np.dtype(a.dtype), a.reps, a.pml_cells)), flush=True)
