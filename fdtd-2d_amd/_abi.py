@@ -261,6 +261,14 @@ BATCH_FLUX_ADJOINT_SIGNATURES = {
     "fdtd2d_batch_read_flux_line_sources": (_i, [_vp, C.POINTER(_d), C.POINTER(_d)]),
     "fdtd2d_batch_flux_line_weights": (_i, [_vp, C.POINTER(_d), C.POINTER(_d), _i, C.POINTER(_d), C.POINTER(_d)]),
 }
+# every symbol include/fdtd2d_batch_bloch_flux_adjoint.h declares (complex line sources on Bloch flux lines and the
+# adjoint weights formed from both parts' sums)
+BATCH_BLOCH_FLUX_ADJOINT_SIGNATURES = {
+    "fdtd2d_batch_set_bloch_flux_line_sources": (_i, [_vp, _i, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d),
+                                                      C.POINTER(_d)]),
+    "fdtd2d_batch_read_bloch_flux_line_sources": (_i, [_vp, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_bloch_flux_line_weights": (_i, [_vp, C.POINTER(_d), C.POINTER(_d), _i, C.POINTER(_d), C.POINTER(_d)]),
+}
 
 # transport callback of fdtd2d_slab_attach
 EXCHANGE_FN = C.CFUNCTYPE(_i, _vp, _vp, _vp, _vp, _vp, _ll, _vp)
@@ -316,7 +324,8 @@ def load():
                                    **BATCH_DISPERSIVE_SIGNATURES, **BATCH_LATTICE_SIGNATURES,
                                    **BATCH_BLOCH_DISPERSIVE_SIGNATURES,
                                    **BATCH_DISPERSIVE_ADJOINT_SIGNATURES, **BATCH_FLUX_SIGNATURES,
-                                   **BATCH_BLOCH_FLUX_SIGNATURES, **BATCH_FLUX_ADJOINT_SIGNATURES}.items():
+                                   **BATCH_BLOCH_FLUX_SIGNATURES, **BATCH_FLUX_ADJOINT_SIGNATURES,
+                                   **BATCH_BLOCH_FLUX_ADJOINT_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

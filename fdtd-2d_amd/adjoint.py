@@ -1079,9 +1079,17 @@ def flux_adjoint_weights(E, H, dJdP, lines, omegas, dt, dx, solve, scale_e=None,
     g = np.exp(0.5j * w * dt)[:, :, None]
     _, _, k, col = _line_entries(lines)
     c = np.asarray(dJdP, dtype=np.float64)[:, k, :].transpose(0, 2, 1) * (np.where(col, -1.0, 1.0) * dx)[None, None, :]
+    return _target_weights(c * np.conj(H * g), c * np.conj(E * g), solve, scale_e, scale_h)
+
+
+def _target_weights(ae, ah, solve, scale_e=None, scale_h=None):
+    """The core of flux_adjoint_weights: per-entry complex targets ae (the coefficient of dE in dJ = Re sum ae dE + ...)
+    and ah (that of dH, in the header's convention: times conj(g)^2, the H part being injected a step earlier), each
+    (B, F, cells); weights = solve @ [Re (scale * target); Im (scale * target)]."""
+    B, F, cells = ae.shape
     one = np.ones((B, cells))
-    te = (one if scale_e is None else np.asarray(scale_e, dtype=np.float64))[:, None, :] * c * np.conj(H * g)
-    th = (one if scale_h is None else np.asarray(scale_h, dtype=np.float64))[:, None, :] * c * np.conj(E * g)
+    te = (one if scale_e is None else np.asarray(scale_e, dtype=np.float64))[:, None, :] * ae
+    th = (one if scale_h is None else np.asarray(scale_h, dtype=np.float64))[:, None, :] * ah
     s = np.broadcast_to(np.asarray(solve, dtype=np.float64), (B, 2 * F, 2 * F))
     return tuple(np.ascontiguousarray(np.einsum("bck,bkw->bwc", s, np.concatenate([t.real, t.imag], axis=1)))
                  for t in (te, th))
@@ -1189,7 +1197,8 @@ def batch_flux_gradient(eps, sigma=None, mu=None, *, nsteps, sources, flux_lines
     line cell.  info["residual_forward"] and info["residual_adjoint"] compare the end-of-run max|Ez| with the largest
     sample at the first cell of each line.
 
-    Out of scope: Bloch and lattice batches, dJ/d wp2 of a dispersive member, gradients with respect to mu.
+    Out of scope: Bloch batches (batch_bloch_flux_gradient serves them) and lattice batches, dJ/d wp2 of a dispersive
+    member, gradients with respect to mu.
 
     Returns (J (B,), grad_eps (B, nrows, ncols), grad_sigma (the same shape, or None without sigma), P (B, N, F), info)."""
     p = _flux_plan(eps, sigma, mu, nsteps, sources, flux_lines, omegas, design, fc, waveform, dt, dx, dtype, boundary,
@@ -1283,6 +1292,224 @@ class FluxAdjointSession(AdjointSession):
         eng.flux_adjoint_sources(g, p.solve[0] if p.shared else p.solve, p.scale_e, p.scale_h)
         eng.reset()
         eng.run(p.nsteps, None, p.channels)
+        _, peak_adj = self._spectra(eng, none)
+        end_adj = self._absmax(eng)
+        grad = self._product(eng, p.coef) * (p.dx / p.dt)
+        self._ran = True
+        info = {"condition": self._condition, "residual_forward": _residual(end_fwd, peak_fwd),
+                "residual_adjoint": _residual(end_adj, peak_adj), "channels_shared": p.shared}
+        return J, grad, P, info
+
+
+# ---- flux objectives on Bloch batches: the adjoint of the complex flux monitor ------------------------------------------
+
+def _orders_targets(E, H, dJdPm, phi, first, omegas, dt, dx):
+    """The per-entry targets of an objective on flux_orders of a whole-period row line whose entries start at `first`:
+    (ae, ah), each (B, F, cells), zero off that line.  dJdPm: (B, F, Q) in np.fft.fftfreq order."""
+    B, F, cells = E.shape
+    Q = dJdPm.shape[2]
+    g = np.exp(0.5j * _window_omegas(omegas, B) * dt)[:, :, None]
+    m = np.fft.fftfreq(Q, 1 / Q)
+    ker = np.exp(-1j * (phi[:, None, None] + 2 * np.pi * m[None, :, None]) * np.arange(Q)[None, None, :] / Q)   # (B, m, j)
+    sl = slice(first, first + Q)
+    Em = np.einsum("bfj,bmj->bfm", E[:, :, sl] * g, ker) / Q
+    Hm = np.einsum("bfj,bmj->bfm", H[:, :, sl] * g, ker) / Q
+    ae, ah = np.zeros((B, F, cells), np.complex128), np.zeros((B, F, cells), np.complex128)
+    ae[:, :, sl] = dx * np.einsum("bfm,bmj->bfj", dJdPm * np.conj(Hm), ker)
+    ah[:, :, sl] = dx * np.einsum("bfm,bmj->bfj", dJdPm * np.conj(Em), ker)
+    return ae, ah
+
+
+def bloch_flux_adjoint_weights(E, H, dJdP, lines, omegas, dt, dx, solve, scale_e=None, scale_h=None, orders=None):
+    """The line sources of the adjoint of a flux objective on a Bloch batch, on the host: what
+    BatchEngine.bloch_flux_adjoint_sources forms on the device.  E, H: the raw sums of the complex fields,
+    read_flux_lines(raw=True), (B, F, cells); the other arguments are flux_adjoint_weights'.  orders: None, or
+    (line, dJdPm (B, F, Q), phi (B,)) for an objective that also depends on flux_orders(line); its cotangent is mapped
+    back to the line's cells (batch_bloch_flux_gradient has the map) and added to the targets.  Returns real (we, wh),
+    each (B, cells, 2F), for set_bloch_flux_line_sources: a real series on the real part carries any complex spectrum at
+    omega > 0, and the rotated seam term of the sources supplies the rest."""
+    B, F, cells = E.shape
+    g = np.exp(0.5j * _window_omegas(omegas, B) * dt)[:, :, None]
+    _, _, k, col = _line_entries(lines)
+    c = np.asarray(dJdP, dtype=np.float64)[:, k, :].transpose(0, 2, 1) * (np.where(col, -1.0, 1.0) * dx)[None, None, :]
+    ae, ah = c * np.conj(H * g), c * np.conj(E * g)
+    if orders is not None:
+        line, dJdPm, phi = orders
+        first = sum(int(l[3]) for l in lines[:int(line)])
+        oe, oh = _orders_targets(E, H, np.asarray(dJdPm, dtype=np.float64), np.asarray(phi, dtype=np.float64), first,
+                                 omegas, dt, dx)
+        ae, ah = ae + oe, ah + oh
+    return _target_weights(ae, ah, solve, scale_e, scale_h)
+
+
+def _bloch_flux_plan(eps, sigma, mu, bloch_phase, source_weights, nsteps, sources, flux_lines, omegas, design, fc,
+                     waveform, dt, dx, dtype, pml_cells, orders_line):
+    """The host checks of batch_bloch_flux_gradient: _flux_plan's with periodic columns, the Bloch helpers' checks of phase
+    and source weights, positive frequencies, and orders_line a whole-period row line."""
+    om = np.asarray(omegas, dtype=np.float64)
+    if om.size and not np.all(om > 0):
+        raise ValueError("omegas must be positive: the flux monitors of a Bloch batch take either sign, the channel "
+                         "system of the gradient helpers does not (a real series carries omega and -omega together)")
+    p = _flux_plan(eps, sigma, mu, nsteps, sources, flux_lines, omegas, design, fc, waveform, dt, dx, dtype, "periodic",
+                   pml_cells)
+    phi = _bloch_phases(bloch_phase, p.B)
+    weights = _check_weights(source_weights, p.B, p.Cc)
+    if orders_line is not None:
+        k = int(orders_line)
+        if not 0 <= k < len(p.lines):
+            raise ValueError(f"orders_line {orders_line} outside 0..{len(p.lines) - 1}")
+        kind, _, first, n = p.lines[k]
+        if kind != "row" or int(first) != 0 or int(n) != p.Cc - 1:
+            raise ValueError(f"orders_line {k} must be a row line over the whole period (columns 0..{p.Cc - 2}), not "
+                             f"{p.lines[k]}")
+    return p, phi, weights
+
+
+def _refuse_bloch_flux_pole(eng):
+    """An engine with the pole of set_bloch_dispersion (an engine factory that sets one, or the call on a session's
+    engine) is refused before any run: hold_bloch_window does not serve it, and dJ/d wp2 under a phase is out of scope."""
+    if getattr(eng, "dispersive", False):
+        raise ValueError("the engine carries a dispersive pole (set_bloch_dispersion): gradients of flux under a Bloch "
+                         "phase are not available with the pole")
+
+
+def _bloch_flux_cotangent(p, objective, P, Pm):
+    """(J, dJ/dP, dJ/dPm or None) of objective(P) or objective(P, Pm), shapes checked."""
+    if Pm is None:
+        J, g = _flux_cotangent(p, objective, P)
+        return J, g, None
+    J, g, gm = objective(P, Pm)
+    J, g, gm = (np.asarray(a, dtype=np.float64) for a in (J, g, gm))
+    if J.shape != (p.B,) or g.shape != P.shape or gm.shape != Pm.shape:
+        raise ValueError(f"objective must return J of shape ({p.B},), dJ/dP of shape {P.shape} and dJ/dPm of shape "
+                         f"{Pm.shape}, got {J.shape}, {g.shape} and {gm.shape}")
+    return J, g, gm
+
+
+def _bloch_flux_lines_setup(eng, p):
+    """The lines, then silent line sources with the 2F channels of the adjoint run: with them the engine accepts
+    hold_bloch_window and run_bloch_channels beside the lines."""
+    eng.set_bloch_flux_lines(p.lines, p.om)
+    cells = sum(int(l[3]) for l in p.lines)
+    zero = np.zeros((cells, 2 * p.F))
+    eng.set_bloch_flux_line_sources(zero, zero)
+
+
+def batch_bloch_flux_gradient(eps, sigma=None, mu=None, *, bloch_phase, source_weights=None, nsteps, sources, flux_lines,
+                              omegas, design, objective, orders_line=None, fc=30e9, waveform="ricker", dt=5e-14,
+                              dx=1e-4, dtype=np.float64, pml_cells=40, device=0, engine=None):
+    """batch_flux_gradient for Bloch batches: the gradient of an objective on the power through flux lines of complex
+    fields, and on its split over the diffraction orders, with respect to eps (and sigma) over a design window.
+
+    bloch_phase, source_weights: as in batch_bloch_gradient.  flux_lines: as BatchEngine.set_bloch_flux_lines takes them;
+    omegas must be positive (ValueError: the monitors take either sign, the channel system of the adjoint does not).
+    Without orders_line, objective(P) takes flux() (B, N, F) and returns (J (B,), dJ/dP).  With orders_line = k, a row
+    line over the whole period, objective(P, Pm) also takes flux_orders(k) (B, F, Q) and returns (J, dJ/dP, dJ/dPm).
+    The other arguments and host checks are batch_flux_gradient's with boundary="periodic" (line cells outside the layer,
+    2 cells from the design window and the sources, sigma zero on them) and batch_bloch_gradient's; an engine with the
+    pole of set_bloch_dispersion is refused.
+
+    The method: set_bloch_flux_lines; silent line sources with K = 2F (set_bloch_flux_line_sources), which make the
+    engine accept the next calls beside the lines; the forward run; hold_bloch_window; flux() and the orders; the
+    cotangent and the weights (bloch_flux_adjoint_weights); reset; run_bloch_channels(conjugate=True), which drives the
+    line sources with the rotation conjugated, the seam term with it; two bloch_window_products with the unchanged
+    coefficients.
+
+    The orders.  With ker[m, j] = exp(-1j * (phi + 2 pi m) * j / Q), E_m = (1/Q) sum_j ker[m, j] E_j and H_m likewise (H
+    with the half-step factor g), Pm = dx Q Re(E_m conj(H_m)) is bilinear in the harmonics, which are linear in the line
+    spectra, so dJ = Re sum_j (ae_j dE_j + ...) with
+        ae_j = dx sum_m dJ/dPm conj(H_m) ker[m, j]        ah_j = dx sum_m dJ/dPm conj(E_m g) ker[m, j]
+    added to the line's own targets dJ/dP dx conj(H_j), dJ/dP dx conj(E_j g).  sum_m conj(ker[m, j']) ker[m, j] = Q
+    delta(j, j'), so dJ/dPm = 1 gives exactly the targets of dJ/dP = 1 on that line (Parseval).
+
+    Mind the ring-down, as in batch_bloch_gradient: it depends on phi.
+
+    Returns (J (B,), grad_eps (B, nrows, ncols), grad_sigma or None, P (B, N, F), info) with batch_eps_gradient's info
+    keys; the residuals compare the end fields with the largest sample at the first cell of each line."""
+    p, phi, weights = _bloch_flux_plan(eps, sigma, mu, bloch_phase, source_weights, nsteps, sources, flux_lines, omegas,
+                                       design, fc, waveform, dt, dx, dtype, pml_cells, orders_line)
+    if engine is None:
+        from .batch import BatchEngine as engine
+    B = p.B
+    with engine(B, p.R, p.Cc, dt, dx, dtype=dtype, boundary="periodic", device=device) as eng:
+        _bloch_setup(eng, p, p.sigma, phi, weights)
+        _refuse_bloch_flux_pole(eng)
+        _bloch_flux_lines_setup(eng, p)
+        eng.run(p.nsteps, p.amps)
+        traces = eng.read_probes(0, p.nsteps)
+        end_fwd = _part_peak(eng.download()[0][:, :, :-1])
+        eng.hold_bloch_window()
+        P = eng.flux()
+        Pm = None if orders_line is None else eng.flux_orders(int(orders_line))
+        J, g, gm = _bloch_flux_cotangent(p, objective, P, Pm)
+        E, H = eng.read_flux_lines(raw=True)
+        we, wh = bloch_flux_adjoint_weights(E, H, g, p.lines, p.om, dt, dx, p.solve, p.scale_e, p.scale_h,
+                                            None if gm is None else (int(orders_line), gm, phi))
+        eng.reset()
+        eng.set_bloch_flux_line_sources(we, wh)
+        eng.run_bloch_channels(p.nsteps, None, p.channels, conjugate=True)
+        adj_traces = eng.read_probes(0, p.nsteps)
+        end_adj = _part_peak(eng.download()[0][:, :, :-1])
+        grad = eng.bloch_window_product(p.coef) * (dx / dt)
+        grad_sigma = None if p.sigma is None else eng.bloch_window_product(p.coef_sigma) * (dx / 2)
+    info = {"condition": max(v[2] for v in p.systems.values()),
+            "residual_forward": _residual(end_fwd, _part_peak(traces)),
+            "residual_adjoint": _residual(end_adj, _part_peak(adj_traces)), "channels_shared": p.shared}
+    return J, grad, grad_sigma, P, info
+
+
+class BlochFluxAdjointSession(FluxAdjointSession, BlochAdjointSession):
+    """batch_bloch_flux_gradient as a loop: BlochAdjointSession's standing engine with FluxAdjointSession's objective.
+
+    The constructor takes batch_bloch_flux_gradient's arguments (without the objective) and makes its host checks.
+    value_and_grad(objective) returns (J, grad_eps, P, info).  For an objective on P it forms the adjoint sources on
+    the device (BatchEngine.bloch_flux_adjoint_sources) and reads no line spectrum, trace, field or window back.  With
+    orders_line it reads the line spectra back (flux_orders and the weights are host arithmetic over them) and installs
+    the weights from the host.  set_design_eps, set_design_sigma, set_conductivity (zero on the line cells) and
+    sigma_gradient are FluxAdjointSession's; set_bloch_phase is BlochAdjointSession's and keeps the lines."""
+
+    def __init__(self, eps, sigma=None, mu=None, *, bloch_phase, source_weights=None, nsteps, sources, flux_lines,
+                 omegas, design, orders_line=None, fc=30e9, waveform="ricker", dt=5e-14, dx=1e-4, dtype=np.float64,
+                 pml_cells=40, device=0, engine=None):
+        self._eng = None
+        p, self._phi, self._weights = _bloch_flux_plan(eps, sigma, mu, bloch_phase, source_weights, nsteps, sources,
+                                                       flux_lines, omegas, design, fc, waveform, dt, dx, dtype,
+                                                       pml_cells, orders_line)
+        self._orders_line = None if orders_line is None else int(orders_line)
+        self._open(p, dtype, engine, device)
+        if p.sigma is not None:
+            self._sigma = p.sigma.copy()
+
+    _check_engine = staticmethod(_refuse_bloch_flux_pole)
+
+    def _setup_engine(self, eng):
+        p = self._p
+        _bloch_setup(eng, p, p.sigma, self._phi, self._weights)
+        _bloch_flux_lines_setup(eng, p)
+
+    def value_and_grad(self, objective):
+        """(J (B,), grad_eps (B, nrows, ncols) float64, P (B, N, F) float64, info) of the current materials and phases."""
+        p, eng = self._p, self._eng
+        if eng is None:
+            raise RuntimeError("the session is closed")
+        self._check_engine(eng)
+        none = np.empty((p.B, 0))
+        eng.reset()
+        eng.run(p.nsteps, p.amps)
+        _, peak_fwd = self._spectra(eng, none)
+        end_fwd = self._absmax(eng)
+        self._hold(eng)
+        P = eng.flux()
+        k = self._orders_line
+        J, g, gm = _bloch_flux_cotangent(p, objective, P, None if k is None else eng.flux_orders(k))
+        if gm is None:
+            eng.bloch_flux_adjoint_sources(g, p.solve[0] if p.shared else p.solve, p.scale_e, p.scale_h)
+        else:
+            E, H = eng.read_flux_lines(raw=True)
+            eng.set_bloch_flux_line_sources(*bloch_flux_adjoint_weights(E, H, g, p.lines, p.om, p.dt, p.dx, p.solve,
+                                                                        p.scale_e, p.scale_h, (k, gm, self._phi)))
+        eng.reset()
+        eng.run_bloch_channels(p.nsteps, None, p.channels, conjugate=True)
         _, peak_adj = self._spectra(eng, none)
         end_adj = self._absmax(eng)
         grad = self._product(eng, p.coef) * (p.dx / p.dt)

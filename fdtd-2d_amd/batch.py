@@ -730,7 +730,8 @@ class BatchEngine:
             if np.iscomplexobj(z):
                 ai = np.ascontiguousarray(z.imag[:, :nsteps], dtype=np.float64)
         ch = np.asarray(channels, dtype=np.float64)
-        K = self._npoint[1]
+        # the line sources of set_bloch_flux_line_sources take the channels where Bloch lines exclude point sources
+        K = self._npoint[1] or (self.info(_abi.BATCH_FLUX_LINE_SOURCES_INFO) if self._bflux else 0)
         if ch.shape[-1:] != () and ch.shape[-1] >= nsteps:
             ch = ch[..., :nsteps]
         if ch.shape not in ((K, nsteps), (self.count, K, nsteps)):
@@ -885,7 +886,8 @@ class BatchEngine:
         (fdtd2d_batch_bloch_flux.h).  The frequencies may have either sign: omega and -omega are different spectra of
         a complex field.  At column 0 a column line reads its left neighbour across the seam, rotated back by the
         phase.  lines None or empty removes them.  While they are set, turning the phase off, Bloch point sources,
-        run_bloch_channels and hold_bloch_window are refused; a new phase keeps the lines and their sums."""
+        run_bloch_channels and hold_bloch_window are refused (the last two until set_bloch_flux_line_sources installs sources
+        on the lines); a new phase keeps the lines and their sums."""
         if lines is None or len(lines) == 0:
             self._ck(self._lib.fdtd2d_batch_set_bloch_flux_lines(self._h, 0, None, 0, None, 1))
             if self._bflux:
@@ -1035,6 +1037,85 @@ class BatchEngine:
             scales.append(a)
         self._ck(self._lib.fdtd2d_batch_flux_line_weights(self._h, _dptr(g), _dptr(s), int(s.ndim == 3),
                                                           *(None if a is None else _dptr(a) for a in scales)))
+        return self
+
+    # -- line sources on Bloch flux lines (fdtd2d_batch_bloch_flux_adjoint.h) ---------------------------------
+    def _bloch_flux_entries(self, what):
+        if self._flux is None or not self._bflux:
+            raise _abi.Fdtd2dError(_abi.E_STATE, f"{what} live on Bloch flux lines: call set_bloch_flux_lines first")
+        return int(self._flux[0][:, 3].sum())
+
+    def set_bloch_flux_line_sources(self, we, wh):
+        """set_flux_line_sources on the lines of set_bloch_flux_lines, with complex weights: we, wh complex (cells, K)
+        for every member or (B, cells, K), K <= 32; either may be None, both None removes the sources.  A real array is
+        accepted and its imaginary part is absent (it takes nothing).  In step n of run_bloch_channels(nsteps, amps,
+        channels) entry w forms the complex s_e = sum_c we[w, c] * channels[c, n] and s_h likewise (the channels are
+        real); s_e is added to the complex Ez where Bloch point sources would add theirs, and 0.5 * s_h to each of the
+        two H values the monitor averages for the cell, before the H update of the step.  For a column-line cell at
+        column 0 the left H value lies across the seam and takes rho * 0.5 * s_h, with the rotation the run steps with
+        (conj(rho) in a conjugated run: the transpose of the monitor's read).  With ramp weights exp(1j * phi * j / Q)
+        an electric and a magnetic sheet on a row line form a one-way source at oblique incidence.  Once sources are
+        installed (zeros included) run_bloch_channels and hold_bloch_window are accepted on a batch with Bloch lines;
+        set_bloch_flux_lines removes them, reset(), a new phase and set_bloch_dispersion keep them."""
+        if we is None and wh is None:
+            self._ck(self._lib.fdtd2d_batch_set_bloch_flux_line_sources(self._h, 0, None, None, None, None))
+            return self
+        cells = self._bloch_flux_entries("Bloch line sources")
+        parts = []
+        for name, w in (("we", we), ("wh", wh)):
+            if w is None:
+                parts += [None, None]
+                continue
+            w = np.asarray(w)
+            cplx = np.iscomplexobj(w)
+            if w.ndim == 2:
+                w = np.broadcast_to(w, (self.count,) + w.shape)
+            if w.ndim != 3 or w.shape[:2] != (self.count, cells):
+                raise ValueError(f"{name} must have shape ({cells}, K) or ({self.count}, {cells}, K), got {w.shape}")
+            parts.append(np.ascontiguousarray(w.real, dtype=np.float64))
+            parts.append(np.ascontiguousarray(w.imag, dtype=np.float64) if cplx else None)
+        K = {int(w.shape[2]) for w in parts if w is not None}
+        if len(K) != 1:
+            raise ValueError(f"we and wh must have the same number of channels, got {sorted(K)}")
+        K = K.pop()
+        if not 1 <= K <= _abi.BATCH_MAX_CHANNELS:
+            raise ValueError(f"line sources take 1..{_abi.BATCH_MAX_CHANNELS} channels, got {K}")
+        self._ck(self._lib.fdtd2d_batch_set_bloch_flux_line_sources(self._h, K, *(None if w is None else _dptr(w)
+                                                                                  for w in parts)))
+        return self
+
+    def read_bloch_flux_line_sources(self):
+        """(we, wh), each complex128 (B, cells, K): the weights as the engine holds them (an absent part reads as
+        zeros)."""
+        cells = self._bloch_flux_entries("Bloch line sources")
+        K = self.info(_abi.BATCH_FLUX_LINE_SOURCES_INFO)
+        out = [np.zeros((self.count, cells, K)) if K else np.zeros(1) for _ in range(4)]
+        self._ck(self._lib.fdtd2d_batch_read_bloch_flux_line_sources(self._h, *(_dptr(a) for a in out)))
+        return out[0] + 1j * out[1], out[2] + 1j * out[3]
+
+    def bloch_flux_adjoint_sources(self, dJdP, solve, scale_e=None, scale_h=None):
+        """flux_adjoint_sources on the lines of set_bloch_flux_lines: forms the line sources of the adjoint of an
+        objective on flux() on the device, from both parts' current sums, and installs them as real weights with
+        K = 2F channels (one launch; nothing is read back).  The arguments are those of flux_adjoint_sources; E and H
+        are the raw sums of the complex fields.  bloch_flux_adjoint_weights is the same arithmetic on the host."""
+        cells = self._bloch_flux_entries("the adjoint sources")
+        ln, w = self._flux
+        N, F = len(ln), w.shape[1]
+        g = np.ascontiguousarray(dJdP, dtype=np.float64)
+        if g.shape != (self.count, N, F):
+            raise ValueError(f"dJdP must have shape ({self.count}, {N}, {F}), got {g.shape}")
+        s = np.ascontiguousarray(solve, dtype=np.float64)
+        if s.shape not in ((2 * F, 2 * F), (self.count, 2 * F, 2 * F)):
+            raise ValueError(f"solve must have shape ({2 * F}, {2 * F}) or ({self.count}, {2 * F}, {2 * F}), got {s.shape}")
+        scales = []
+        for name, a in (("scale_e", scale_e), ("scale_h", scale_h)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape != (self.count, cells):
+                    raise ValueError(f"{name} must have shape ({self.count}, {cells}), got {a.shape}")
+            scales.append(a)
+        self._ck(self._lib.fdtd2d_batch_bloch_flux_line_weights(self._h, _dptr(g), _dptr(s), int(s.ndim == 3),
+                                                                *(None if a is None else _dptr(a) for a in scales)))
         return self
 
     @property

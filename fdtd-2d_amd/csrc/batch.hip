@@ -31,6 +31,7 @@
 #include "../../include/fdtd2d_batch_bloch_adjoint.h"
 #include "../../include/fdtd2d_batch_bloch_dispersive.h"
 #include "../../include/fdtd2d_batch_bloch_flux.h"
+#include "../../include/fdtd2d_batch_bloch_flux_adjoint.h"
 #include "../../include/fdtd2d_batch_design.h"
 #include "../../include/fdtd2d_batch_dispersive.h"
 #include "../../include/fdtd2d_batch_dispersive_adjoint.h"
@@ -59,6 +60,7 @@
 #include "kernels_batch_bloch_adjoint.hpp"
 #include "kernels_batch_bloch_dispersive.hpp"
 #include "kernels_batch_bloch_flux.hpp"
+#include "kernels_batch_bloch_flux_adjoint.hpp"
 #include "kernels_batch_design.hpp"
 #include "kernels_batch_dispersive.hpp"
 #include "kernels_batch_flux.hpp"
@@ -170,6 +172,8 @@ struct fdtd2d_batch {
     // (nullptr: no such part); fsrc_nchan = 0 without them
     int fsrc_nchan = 0;
     double *fsrc_we = nullptr, *fsrc_wh = nullptr;
+    // on Bloch lines (fdtd2d_batch_bloch_flux_adjoint.h) fsrc_we, fsrc_wh are the real parts and these the imaginary ones
+    double *fsrc_we_im = nullptr, *fsrc_wh_im = nullptr;
     int *fsrc_geom = nullptr;             // the lines as batch_fluxsrc_gather reads them (BatchFluxSrc::geom)
     double *win_held = nullptr;           // fdtd2d_batch_hold_dft_window: a copy of win_acc
     double *win_held_disp = nullptr;      // fdtd2d_batch_hold_dispersive_window: a copy of win_acc while a pole is set
@@ -1119,21 +1123,26 @@ template <class T> int run_bloch_dispersive(fdtd2d_batch *b, int nsteps, const d
 
 // ---- Bloch runs with flux lines (fdtd2d_batch_bloch_flux.h): the paths of run_bloch and of run_bloch_dispersive with the
 // kernels of batch_bloch_flux.hip, whose streamed H launch also writes the lines' phasors
-template <class T> int run_bloch_flux(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride)
+// fs: the line sources of a run with channels (nullptr: none, the kernels of batch_bloch_flux.hip; otherwise those of
+// batch_bloch_flux_adjoint.hip, which take fs behind facc_im); conj: step with (c, -s)
+template <class T>
+int run_bloch_flux(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride,
+                   fdtd::BatchBlochFluxSrc *fs = nullptr, bool conj = false)
 {
     if (!b->ca || !b->ezx || !b->ez_im || !b->rho || b->lattice || !b->flux_acc || !b->flux_acc_im ||
         (b->bdisp && (!b->djh || !b->dq || !b->djh_im || !b->dq_im || !b->dcj || !b->da || !b->dck)))
         return bfail(b, FDTD2D_E_STATE, "Bloch batch with flux lines without its arrays");
-    const fdtd::BatchBlochFluxKernels &K = fdtd::batch_bloch_flux_kernels<T>();
+    if (conj && !b->rho_conj) return bfail(b, FDTD2D_E_STATE, "Bloch batch without its conjugated rotations");
+    const fdtd::BatchBlochFluxKernels &K = fs ? fdtd::batch_bloch_flux_src_kernels<T>() : fdtd::batch_bloch_flux_kernels<T>();
     const int disp = b->bdisp ? 1 : 0;
     fdtd::BatchPml<T> p = pml_view<T>(b);
     fdtd::BatchMon m = mon_view(b);
-    fdtd::BatchBloch<T> bl = bloch_view<T>(b, false);
+    fdtd::BatchBloch<T> bl = bloch_view<T>(b, conj);
     fdtd::BatchBlochDisp<T> d{(T *)b->djh, (T *)b->dq, (T *)b->djh_im, (T *)b->dq_im,
                               (const T *)b->dcj, (const T *)b->da, (const T *)b->dck};
     fdtd::BatchFlux f = flux_view(b);
     double *facc_im = b->flux_acc_im;
-    b->run_conj = false;
+    b->run_conj = conj;
     const T *ca = (const T *)b->ca;
     if (use_resident(b)) {
         const int cells = b->rows * b->cols, threads = resident_threads(cells);
@@ -1157,7 +1166,8 @@ template <class T> int run_bloch_flux(fdtd2d_batch *b, int nsteps, const double 
             fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
             v.ce = (const T *)b->cb;
             void *args[] = {&v, &p, &m, &bl, &d, &f, &facc_im, &ca, &n0, &nt, &step_base};
-            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads), args, lds);
+            void *src_args[] = {&v, &p, &m, &bl, &d, &f, &facc_im, fs, &ca, &n0, &nt, &step_base};
+            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads), fs ? src_args : args, lds);
             if (rc) return rc;
             b->launches++;
             b->step += nt;
@@ -1173,8 +1183,10 @@ template <class T> int run_bloch_flux(fdtd2d_batch *b, int nsteps, const double 
         int rc;
         void *h_args[] = {&v, &p, &m, &bl, &f, &step};
         void *e_args[] = {&v, &p, &m, &bl, &d, &f, &facc_im, &ca, &n, &step};
-        if ((rc = launch_ptr(b, K.h, grid, dim3(256), h_args, 0))) return rc;
-        if ((rc = launch_ptr(b, K.e[disp], grid, dim3(256), e_args, 0))) return rc;
+        void *h_src_args[] = {&v, &p, &m, &bl, &f, fs, &n, &step};
+        void *e_src_args[] = {&v, &p, &m, &bl, &d, &f, &facc_im, fs, &ca, &n, &step};
+        if ((rc = launch_ptr(b, K.h, grid, dim3(256), fs ? h_src_args : h_args, 0))) return rc;
+        if ((rc = launch_ptr(b, K.e[disp], grid, dim3(256), fs ? e_src_args : e_args, 0))) return rc;
         b->launches += 2;
         b->step++;
     }
@@ -1462,7 +1474,9 @@ int refuse_flux(fdtd2d_batch *b, const char *what)
 // removes the line sources of fdtd2d_batch_flux_adjoint.h (the stream is idle)
 void fsrc_drop(fdtd2d_batch *b)
 {
-    for (void **p : {(void **)&b->fsrc_we, (void **)&b->fsrc_wh, (void **)&b->fsrc_geom}) release(p);
+    for (void **p : {(void **)&b->fsrc_we, (void **)&b->fsrc_wh, (void **)&b->fsrc_geom, (void **)&b->fsrc_we_im,
+                     (void **)&b->fsrc_wh_im})
+        release(p);
     b->fsrc_nchan = 0;
 }
 
@@ -1908,7 +1922,7 @@ void fdtd2d_batch_destroy(fdtd2d_batch_t *b)
                      &b->djh, &b->dq, &b->dcj, &b->da, &b->dck, &b->djh_im, &b->dq_im,
                      (void **)&b->flux_acc, (void **)&b->flux_omega, (void **)&b->flux_ph,
                      (void **)&b->flux_acc_im, (void **)&b->fsrc_we, (void **)&b->fsrc_wh,
-                     (void **)&b->fsrc_geom})
+                     (void **)&b->fsrc_geom, (void **)&b->fsrc_we_im, (void **)&b->fsrc_wh_im})
         release(p);
     if (b->own_stream) (void)hipStreamDestroy(b->own_stream);
     delete b;
@@ -3419,12 +3433,13 @@ int fdtd2d_batch_run_bloch_channels(fdtd2d_batch_t *b, int nsteps, const double 
     if (!b) return FDTD2D_E_ARG;
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
     if (b->lattice) return refuse_bloch(b, "a run with channels");
-    if (b->bflux) return refuse_flux(b, "a run with channels");
-    if (b->bdisp) return refuse_dispersive(b, "a run with channels (the adjoint of a dispersive medium)");
+    const bool lsrc = b->bflux && b->fsrc_nchan;   // line sources on the Bloch lines: they take the channels
+    if (b->bflux && !lsrc) return refuse_flux(b, "a run with channels");
+    if (b->bdisp && !lsrc) return refuse_dispersive(b, "a run with channels (the adjoint of a dispersive medium)");
     if (nsteps < 0) return bfail(b, FDTD2D_E_ARG, "nsteps < 0");
     if (!chan) return bfail(b, FDTD2D_E_ARG, "chan must not be NULL");
     if (amps_im && !amps_re) return bfail(b, FDTD2D_E_ARG, "amps_im needs amps_re (zeros for a purely imaginary source)");
-    if (!b->npts)
+    if (!b->npts && !lsrc)
         return bfail(b, FDTD2D_E_STATE, "no point sources are set: call fdtd2d_batch_set_bloch_point_sources first");
     int rc = need_ready(b);
     if (rc) return rc;
@@ -3444,9 +3459,15 @@ int fdtd2d_batch_run_bloch_channels(fdtd2d_batch_t *b, int nsteps, const double 
             b->run_amps_im = b->amps_im;
         }
     }
-    const size_t per = (size_t)b->pts_nchan * nsteps;
+    const size_t per = (size_t)(lsrc ? b->fsrc_nchan : b->pts_nchan) * nsteps;
     if ((rc = stage(b, &b->chan, &b->chan_cap, chan, (chan_per_member ? b->count : 1) * per * sizeof(double))))
         return rc;
+    if (lsrc) {                             // fdtd2d_batch_bloch_flux_adjoint.h: Bloch lines exclude point sources
+        fdtd::BatchBlochFluxSrc S{b->fsrc_we, b->fsrc_we_im, b->fsrc_wh, b->fsrc_wh_im, b->chan, b->fsrc_geom,
+                                  chan_per_member ? (long long)per : 0, nsteps, b->fsrc_nchan, b->flux_cells};
+        return b->dtype == FDTD2D_F32 ? run_bloch_flux<float>(b, nsteps, dev_amps, nsteps, &S, conjugate != 0)
+                                      : run_bloch_flux<double>(b, nsteps, dev_amps, nsteps, &S, conjugate != 0);
+    }
     fdtd::BatchPts P;
     P.cells = b->pts_cells;
     P.own = b->pts_own;
@@ -3466,7 +3487,7 @@ int fdtd2d_batch_hold_bloch_window(fdtd2d_batch_t *b)
     if (!b) return FDTD2D_E_ARG;
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
     if (b->lattice) return refuse_bloch(b, "the held window");
-    if (b->bflux) return refuse_flux(b, "the held window");
+    if (b->bflux && !b->fsrc_nchan) return refuse_flux(b, "the held window");   // accepted once line sources are set
     if (b->bdisp) return refuse_dispersive(b, "the held window (the adjoint of a dispersive medium)");
     if (!b->win_nf || !b->win_acc_im) return bfail(b, FDTD2D_E_STATE, "no window DFT is set");
     int rc = use_device(b);
@@ -3784,6 +3805,7 @@ int fdtd2d_batch_set_bloch_flux_lines(fdtd2d_batch_t *b, int nlines, const int *
             release(p);
         b->flux_nl = b->flux_nff = b->flux_cells = 0;
         b->bflux = false;
+        fsrc_drop(b);                           // the line sources go with their lines
         return 0;
     }
     // the new buffers before the old ones go: a refused call keeps the old lines
@@ -3807,6 +3829,7 @@ int fdtd2d_batch_set_bloch_flux_lines(fdtd2d_batch_t *b, int nlines, const int *
     }
     for (void **p : {(void **)&b->flux_acc, (void **)&b->flux_omega, (void **)&b->flux_ph, (void **)&b->flux_acc_im})
         release(p);
+    fsrc_drop(b);                               // line sources belong to the lines they were set on
     b->flux_acc = nacc;
     b->flux_acc_im = nacci;
     b->flux_omega = nom;
@@ -3878,7 +3901,7 @@ int fsrc_refuse(fdtd2d_batch *b, int nchan)
 
 // replaces the line sources by the device arrays given (either may be nullptr) and uploads the lines' geometry for
 // them; on failure the arrays are released and the previous sources stay
-int fsrc_install(fdtd2d_batch *b, double *we, double *wh, int nchan)
+int fsrc_install(fdtd2d_batch *b, double *we, double *wh, int nchan, double *we_im = nullptr, double *wh_im = nullptr)
 {
     int geom[fdtd::BATCH_FLUXSRC_GEOM] = {};
     int off = 0;
@@ -3892,12 +3915,14 @@ int fsrc_install(fdtd2d_batch *b, double *we, double *wh, int nchan)
     int rc = alloc(b, (void **)&ng, sizeof geom);
     hipError_t e = rc ? hipSuccess : hipMemcpy(ng, geom, sizeof geom, hipMemcpyHostToDevice);
     if (rc || e != hipSuccess) {
-        for (void **p : {(void **)&we, (void **)&wh, (void **)&ng}) release(p);
+        for (void **p : {(void **)&we, (void **)&wh, (void **)&ng, (void **)&we_im, (void **)&wh_im}) release(p);
         return rc ? rc : bfail(b, -(1000 + (int)e), "setting up the line sources failed: %s", hipGetErrorString(e));
     }
     fsrc_drop(b);
     b->fsrc_we = we;
     b->fsrc_wh = wh;
+    b->fsrc_we_im = we_im;
+    b->fsrc_wh_im = wh_im;
     b->fsrc_geom = ng;
     b->fsrc_nchan = nchan;
     return 0;
@@ -3948,7 +3973,7 @@ int fdtd2d_batch_set_flux_line_sources(fdtd2d_batch_t *b, int nchan, const doubl
 int fdtd2d_batch_read_flux_line_sources(fdtd2d_batch_t *b, double *we, double *wh)
 {
     if (!b || !we || !wh) return FDTD2D_E_ARG;
-    if (!b->fsrc_nchan) return bfail(b, FDTD2D_E_STATE, "no line sources are set");
+    if (!b->fsrc_nchan || b->bflux) return bfail(b, FDTD2D_E_STATE, "no line sources are set");
     int rc = use_device(b);
     if (rc) return rc;
     BCHK(b, hipStreamSynchronize(b->stream));
@@ -3990,6 +4015,116 @@ int fdtd2d_batch_flux_line_weights(fdtd2d_batch_t *b, const double *dJdP, const 
         const fdtd::BatchFluxWeights W{dj, ds, scale_e ? dse : nullptr, scale_h ? dsh : nullptr, ne, nh,
                                        solve_per_member ? (long long)nchan * nchan : 0};
         fdtd::batch_flux_line_weights_launch(flux_view(b), W, b->count, b->dt, b->dx, b->stream);
+        e = hipGetLastError();
+        if (e == hipSuccess) b->launches++;
+        if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    }
+    if (e != hipSuccess) {
+        for (void **p : {(void **)&ne, (void **)&nh}) release(p);
+        return bfail(b, -(1000 + (int)e), "forming the line source weights failed: %s", hipGetErrorString(e));
+    }
+    return fsrc_install(b, ne, nh, nchan);
+}
+
+}  // extern "C"
+
+// ---- fdtd2d_batch_bloch_flux_adjoint.h ----------------------------------------------------------------------------
+
+extern "C" {
+
+int fdtd2d_batch_set_bloch_flux_line_sources(fdtd2d_batch_t *b, int nchan, const double *we_re, const double *we_im,
+                                             const double *wh_re, const double *wh_im)
+{
+    if (!b) return FDTD2D_E_ARG;
+    const double *host[4] = {we_re, wh_re, we_im, wh_im};
+    if ((!we_re && !we_im && !wh_re && !wh_im) || nchan == 0) {   // remove
+        if (!b->bflux || !b->fsrc_nchan) return 0;
+        int rc = use_device(b);
+        if (rc) return rc;
+        BCHK(b, hipStreamSynchronize(b->stream));
+        fsrc_drop(b);
+        return 0;
+    }
+    if (nchan < 1 || nchan > FDTD2D_BATCH_MAX_CHANNELS)
+        return bfail(b, FDTD2D_E_ARG, "nchan %d outside 1..%d", nchan, FDTD2D_BATCH_MAX_CHANNELS);
+    if (!b->bflux)
+        return bfail(b, FDTD2D_E_STATE, "Bloch line sources live on Bloch flux lines: call "
+                     "fdtd2d_batch_set_bloch_flux_lines first");
+    const size_t n = (size_t)b->count * b->flux_cells * nchan;
+    for (const double *w : host)
+        for (size_t k = 0; w && k < n; ++k)
+            if (!std::isfinite(w[k]))
+                return bfail(b, FDTD2D_E_ARG, "member %zu: a line source weight is not finite",
+                             k / ((size_t)b->flux_cells * nchan));
+    int rc = use_device(b);
+    if (rc) return rc;
+    double *dev[4] = {nullptr, nullptr, nullptr, nullptr};
+    auto drop = [&]() {
+        for (double *&p : dev) release((void **)&p);
+    };
+    for (int k = 0; k < 4; ++k)
+        if (host[k] && (rc = alloc(b, (void **)&dev[k], n * sizeof(double)))) {
+            drop();
+            return rc;
+        }
+    hipError_t e = hipStreamSynchronize(b->stream);   // a running launch may still read the old weights
+    for (int k = 0; k < 4; ++k)
+        if (e == hipSuccess && host[k]) e = hipMemcpy(dev[k], host[k], n * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        drop();
+        return bfail(b, -(1000 + (int)e), "setting up the line sources failed: %s", hipGetErrorString(e));
+    }
+    return fsrc_install(b, dev[0], dev[1], nchan, dev[2], dev[3]);
+}
+
+int fdtd2d_batch_read_bloch_flux_line_sources(fdtd2d_batch_t *b, double *we_re, double *we_im, double *wh_re,
+                                              double *wh_im)
+{
+    if (!b || !we_re || !we_im || !wh_re || !wh_im) return FDTD2D_E_ARG;
+    if (!b->bflux || !b->fsrc_nchan) return bfail(b, FDTD2D_E_STATE, "no line sources are set on Bloch flux lines");
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    const size_t n = (size_t)b->count * b->flux_cells * b->fsrc_nchan;
+    const double *from[4] = {b->fsrc_we, b->fsrc_we_im, b->fsrc_wh, b->fsrc_wh_im};
+    double *to[4] = {we_re, we_im, wh_re, wh_im};
+    for (int k = 0; k < 4; ++k) {
+        if (from[k]) BCHK(b, hipMemcpy(to[k], from[k], n * sizeof(double), hipMemcpyDeviceToHost));
+        else std::fill(to[k], to[k] + n, 0.0);
+    }
+    return 0;
+}
+
+int fdtd2d_batch_bloch_flux_line_weights(fdtd2d_batch_t *b, const double *dJdP, const double *solve,
+                                         int solve_per_member, const double *scale_e, const double *scale_h)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!dJdP || !solve) return bfail(b, FDTD2D_E_ARG, "dJdP and solve must not be NULL");
+    if (!b->bflux || !b->flux_acc_im)
+        return bfail(b, FDTD2D_E_STATE, "Bloch line sources live on Bloch flux lines: call "
+                     "fdtd2d_batch_set_bloch_flux_lines first");
+    const int nchan = 2 * b->flux_nff;
+    int rc = use_device(b);
+    if (rc) return rc;
+    const size_t nj = (size_t)b->count * b->flux_nl * b->flux_nff, ns = (size_t)(solve_per_member ? b->count : 1) * nchan * nchan;
+    const size_t nc = (size_t)b->count * b->flux_cells, nw = nc * nchan;
+    // the inputs in the design loop's scratch: dJdP, solve, scale_e, scale_h
+    if ((rc = scratch(b, (nj + ns + 2 * nc) * sizeof(double)))) return rc;
+    double *dj = (double *)b->dsg, *ds = dj + nj, *dse = ds + ns, *dsh = dse + nc;
+    double *ne = nullptr, *nh = nullptr;
+    if ((rc = alloc(b, (void **)&ne, nw * sizeof(double))) || (rc = alloc(b, (void **)&nh, nw * sizeof(double)))) {
+        for (void **p : {(void **)&ne, (void **)&nh}) release(p);
+        return rc;
+    }
+    hipError_t e = hipStreamSynchronize(b->stream);
+    if (e == hipSuccess) e = hipMemcpy(dj, dJdP, nj * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ds, solve, ns * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess && scale_e) e = hipMemcpy(dse, scale_e, nc * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess && scale_h) e = hipMemcpy(dsh, scale_h, nc * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const fdtd::BatchFluxWeights W{dj, ds, scale_e ? dse : nullptr, scale_h ? dsh : nullptr, ne, nh,
+                                       solve_per_member ? (long long)nchan * nchan : 0};
+        fdtd::batch_bloch_flux_line_weights_launch(flux_view(b), b->flux_acc_im, W, b->count, b->dt, b->dx, b->stream);
         e = hipGetLastError();
         if (e == hipSuccess) b->launches++;
         if (e == hipSuccess) e = hipStreamSynchronize(b->stream);

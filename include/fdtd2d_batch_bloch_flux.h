@@ -30,7 +30,8 @@
  * Scope.  FDTD2D_E_STATE without a Bloch phase, in the lattice mode, on a batch created with the Mur frame or without
  * periodic columns, while Bloch point sources or a held Bloch window are set, and without materials.  While Bloch lines
  * are set, turning the phase off, the lattice mode, switching periodic columns, fdtd2d_batch_set_bloch_point_sources,
- * fdtd2d_batch_run_bloch_channels and fdtd2d_batch_hold_bloch_window are refused with FDTD2D_E_STATE.  A new phase
+ * fdtd2d_batch_run_bloch_channels and fdtd2d_batch_hold_bloch_window are refused with FDTD2D_E_STATE (the last two until
+ * line sources are installed on the lines: fdtd2d_batch_bloch_flux_adjoint.h).  A new phase
  * keeps the lines and their sums, and so do fdtd2d_batch_set_bloch_dispersion and the removal of the pole: the batch
  * switches kernel family.  fdtd2d_batch_set_flux_lines keeps refusing a batch with a Bloch phase; the real lines'
  * fdtd2d_batch_read_flux_lines and fdtd2d_batch_flux refuse Bloch lines (FDTD2D_E_STATE).

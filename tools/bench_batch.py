@@ -116,11 +116,22 @@ array eps with random binary permittivity, a ricker line source per member):
                               members) and flux_over_probe_session; weights_ms (one flux_adjoint_sources) and where
                               the weights live.  Default: 1024 members of 60 rows x 61 columns, a 10-cell layer, 2000
                               steps.
+  --bloch-flux-adjoint        instead: the adjoint of a flux objective on the members of --bloch-flux (a phase sweep over
+                              the members, ramp weights, two whole-period row lines at 10 frequencies; dt = 2e-13 and the
+                              design window of --flux-adjoint, 20 channels), timed alternately in one process: flux_ms
+                              (the --bloch-flux run of this batch, with a window DFT over the design window),
+                              adjoint_run_ms (run_bloch_channels(conjugate=True) driven through
+                              set_bloch_flux_line_sources: E and H parts on both lines) and adjoint_run_over_flux;
+                              flux_session_ms (one BlochFluxAdjointSession.value_and_grad, the weights formed on the
+                              device) against probe_session_ms (one BlochAdjointSession.value_and_grad with 30 probes on
+                              the same members) and flux_over_probe_session; weights_ms (one
+                              bloch_flux_adjoint_sources) and the launches per iteration.  Default: 1024 members of 60
+                              rows x 61 columns, a 10-cell layer, 2000 steps.
 Usage: python tools/bench_batch.py [--count 1024 --rows 60 --cols 60 --steps 1000] [--reps 5] [--loop-members 16]
                                    [--boundary {mur,pml} --pml-cells 10] [--monitors] [--adjoint] [--lossy]
                                    [--periodic] [--bloch] [--bloch-adjoint] [--dispersive] [--lattice]
                                    [--bloch-dispersive] [--dispersive-adjoint] [--flux] [--bloch-flux]
-                                   [--flux-adjoint]
+                                   [--flux-adjoint] [--bloch-flux-adjoint]
 """
 import argparse
 import json
@@ -532,6 +543,114 @@ def bench_flux_adjoint(count, rows, cols, steps, dtype, reps, pml_cells):
            "freqs": 10, "channels": 20, "probes": 30, "reps": reps, "weights_live_in": "global memory",
            "flux_sums_in_lds": in_lds, "lds_bytes_per_member": lds,
            "launches_per_flux_session_iteration": session_launches,
+           "residual_forward_max": float(np.max(info["residual_forward"])),
+           "residual_adjoint_max": float(np.max(info["residual_adjoint"]))}
+    for k in t:
+        out.update({f"{k}_ms": round(med[k], 4), f"{k}_ms_min": round(min(t[k]), 4),
+                    f"{k}_ms_all": [round(v, 4) for v in t[k]]})
+    out.update({"adjoint_run_over_flux": round(med["adjoint_run"] / med["flux"], 3),
+                "flux_over_probe_session": round(med["flux_session"] / med["probe_session"], 3)})
+    return out
+
+
+def bench_bloch_flux_adjoint(count, rows, cols, steps, dtype, reps, pml_cells):
+    """The conjugated adjoint run with line sources against the Bloch flux run without them, and one
+    BlochFluxAdjointSession iteration against one BlochAdjointSession iteration with 30 probes, on the same members."""
+    from fdtd2d_amd.adjoint import channel_system
+    dt = 2e-13                                   # as --flux-adjoint: the channels' envelope ends by step 1200
+    rng = np.random.default_rng(0)
+    side = 10
+    design = ((rows - side) // 2, (cols - 1 - side) // 2, side, side)
+    eps = np.full((count, rows, cols), fd.EPS0)
+    eps[:, design[0]:design[0] + side, design[1]:design[1] + side] = np.where(
+        rng.random((count, side, side)) < 0.5, fd.EPS0, 5 * fd.EPS0)
+    sigma = np.zeros((count, rows, cols))
+    sigma[:, design[0]:design[0] + side, design[1]:design[1] + side] = 0.5
+    rects = np.tile([pml_cells + 3, 0, 1, cols - 1], (count, 1))
+    lines = [("row", rows // 4, 0, cols - 1), ("row", 3 * rows // 4, 0, cols - 1)]
+    probes = np.array([[3 * rows // 4, 2 * k] for k in range(30)])
+    omegas = 2 * np.pi * np.linspace(20e9, 65e9, 10)
+    phis = np.linspace(0.0, np.pi, count)
+    amps = np.tile(np.array([fd.ricker_amplitude(i * dt, FC) for i in range(steps)]), (count, 1))
+    camps = amps.astype(np.complex128)
+    chan, A = channel_system(omegas, steps, dt, FC)
+    c00 = (1 / np.sqrt(fd.EPS0 * fd.MU0) * dt) / DX
+    cells = 2 * (cols - 1)
+    common = dict(bloch_phase=phis, source_weights="ramp", nsteps=steps, sources=rects, omegas=omegas, design=design,
+                  fc=FC, dt=dt, dx=DX, dtype=dtype, pml_cells=pml_cells)
+
+    def flux_objective(P):                       # the transmittance through the far line, summed over the frequencies
+        g = np.zeros_like(P)
+        g[:, 1, :] = 1.0
+        return P[:, 1, :].sum(axis=1), g
+
+    def probe_objective(spectra):
+        mag = np.abs(spectra)
+        return mag.mean(axis=1).sum(axis=1), spectra / np.maximum(mag, 1e-300) / spectra.shape[1]
+
+    fs = fd.BlochFluxAdjointSession(eps, sigma, flux_lines=lines, **common)
+    ps = fd.BlochAdjointSession(eps, probes=probes, **common)
+    ps.set_conductivity(sigma)
+    with fd.BatchEngine(count, rows, cols, dt, DX, dtype=dtype, boundary="periodic") as b:
+        b.set_materials(eps.astype(dtype), fd.MU0).set_sources(rects).set_pml(pml_cells, courant00=c00)
+        b.set_conductivity(sigma)
+        b.set_bloch_phase(phis).set_bloch_source("ramp")
+        b.set_dft_window(design, omegas).set_bloch_flux_lines(lines, omegas)
+        b.set_bloch_flux_line_sources(1e-2 * rng.standard_normal((count, cells, 20)),
+                                      1e-5 * rng.standard_normal((count, cells, 20)))
+        dJdP, solve = np.ones((count, 2, 10)), np.linalg.inv(A)
+
+        def flux_run():
+            b.reset().sync()
+            t0 = time.perf_counter()
+            b.run(steps, camps).sync()
+            return (time.perf_counter() - t0) * 1e3
+
+        def adjoint_run():
+            b.reset().sync()
+            t0 = time.perf_counter()
+            b.run_bloch_channels(steps, None, chan, conjugate=True).sync()
+            return (time.perf_counter() - t0) * 1e3
+
+        def weights():
+            t0 = time.perf_counter()
+            b.bloch_flux_adjoint_sources(dJdP, solve)
+            return (time.perf_counter() - t0) * 1e3
+
+        def flux_session():
+            t0 = time.perf_counter()
+            out = fs.value_and_grad(flux_objective)
+            return (time.perf_counter() - t0) * 1e3, out[3]
+
+        def probe_session():
+            t0 = time.perf_counter()
+            ps.value_and_grad(probe_objective)
+            return (time.perf_counter() - t0) * 1e3
+
+        flux_run(), adjoint_run(), flux_session(), probe_session()    # warm-up: code objects, clocks
+        assert b.resident and fs.engine.resident and ps.engine.resident and b.bloch
+        l0, p0 = fs.engine.launches, ps.engine.launches
+        info = flux_session()[1]
+        probe_session()
+        session_launches, probe_launches = fs.engine.launches - l0, ps.engine.launches - p0
+        t = {k: [] for k in ("flux", "adjoint_run", "weights", "flux_session", "probe_session")}
+        for _ in range(reps):
+            t["flux"].append(flux_run())
+            t["adjoint_run"].append(adjoint_run())
+            t["flux_session"].append(flux_session()[0])
+            t["probe_session"].append(probe_session())
+        for _ in range(reps):                        # last: they replace the timed run's weights
+            t["weights"].append(weights())
+        in_lds, lds = b.flux_lines_in_lds, b.lds_bytes
+    fs.close()
+    ps.close()
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    out = {"count": count, "rows": rows, "cols": cols, "steps": steps, "dtype": np.dtype(dtype).name, "dt": dt,
+           "boundary": "periodic+bloch", "pml_cells": pml_cells, "design": list(design), "lines": 2, "line_cells": cells,
+           "freqs": 10, "channels": 20, "probes": 30, "reps": reps, "weights_live_in": "global memory",
+           "flux_sums_in_lds": in_lds, "lds_bytes_per_member": lds,
+           "launches_per_flux_session_iteration": session_launches,
+           "launches_per_probe_session_iteration": probe_launches,
            "residual_forward_max": float(np.max(info["residual_forward"])),
            "residual_adjoint_max": float(np.max(info["residual_adjoint"]))}
     for k in t:
@@ -1135,12 +1254,18 @@ def main():
     ap.add_argument("--flux", action="store_true", help="time flux lines against the same batch without monitors")
     ap.add_argument("--bloch-flux", action="store_true",
                     help="time flux lines on a Bloch batch against the same batch without monitors")
+    ap.add_argument("--bloch-flux-adjoint", action="store_true",
+                    help="time the adjoint of a flux objective on a Bloch batch (line sources, conjugated run, session)")
     ap.add_argument("--flux-adjoint", action="store_true",
                     help="time the adjoint run with line sources and a FluxAdjointSession iteration")
     a = ap.parse_args()
     if a.flux_adjoint:
         print(json.dumps(bench_flux_adjoint(a.count or 1024, a.rows or 60, a.cols or 61, a.steps or 2000,
                                             np.dtype(a.dtype), a.reps, a.pml_cells)), flush=True)
+        return
+    if a.bloch_flux_adjoint:
+        print(json.dumps(bench_bloch_flux_adjoint(a.count or 1024, a.rows or 60, a.cols or 61, a.steps or 2000,
+                                                  np.dtype(a.dtype).type, a.reps, a.pml_cells)))
         return
     if a.bloch_flux:
         print(json.dumps(bench_bloch_flux(a.count or 1024, a.rows or 60, a.cols or 61, a.steps or 2000,
