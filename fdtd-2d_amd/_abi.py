@@ -269,6 +269,16 @@ BATCH_BLOCH_FLUX_ADJOINT_SIGNATURES = {
     "fdtd2d_batch_read_bloch_flux_line_sources": (_i, [_vp, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]),
     "fdtd2d_batch_bloch_flux_line_weights": (_i, [_vp, C.POINTER(_d), C.POINTER(_d), _i, C.POINTER(_d), C.POINTER(_d)]),
 }
+# every symbol include/fdtd2d_batch_hz.h declares (the Hz polarisation of PML and periodic batches, with a conductivity and
+# a Drude-Lorentz pole on Ex and Ey); the polarisation has a query of its own, no numbered info id
+POL_EZ, POL_HZ = 0, 1
+BATCH_HZ_SIGNATURES = {
+    "fdtd2d_batch_set_polarization": (_i, [_vp, _i]),
+    "fdtd2d_batch_polarization": (_i, [_vp]),
+    "fdtd2d_batch_set_hz_conductivity": (_i, [_vp, _vp, _i]),
+    "fdtd2d_batch_set_hz_dispersion": (_i, [_vp, _vp, _i, C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_transfer_hz_dispersion": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i]),
+}
 
 # transport callback of fdtd2d_slab_attach
 EXCHANGE_FN = C.CFUNCTYPE(_i, _vp, _vp, _vp, _vp, _vp, _ll, _vp)
@@ -325,7 +335,7 @@ def load():
                                    **BATCH_BLOCH_DISPERSIVE_SIGNATURES,
                                    **BATCH_DISPERSIVE_ADJOINT_SIGNATURES, **BATCH_FLUX_SIGNATURES,
                                    **BATCH_BLOCH_FLUX_SIGNATURES, **BATCH_FLUX_ADJOINT_SIGNATURES,
-                                   **BATCH_BLOCH_FLUX_ADJOINT_SIGNATURES}.items():
+                                   **BATCH_BLOCH_FLUX_ADJOINT_SIGNATURES, **BATCH_HZ_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

@@ -303,9 +303,19 @@ def _refuse_bloch(eng):
     _refuse_dispersion(eng)
 
 
+def _refuse_hz(eng):
+    """The adjoint of the Hz polarisation is not implemented: an engine in it (an engine factory that calls
+    set_polarization("hz"), or the call on a session's engine) is refused before any run."""
+    if getattr(eng, "polarization", "ez") == "hz":
+        from ._abi import E_STATE, Fdtd2dError
+        raise Fdtd2dError(E_STATE, "adjoint gradients are not available in the Hz polarisation "
+                          '(set_polarization("hz")): its adjoint is not implemented')
+
+
 def _refuse_dispersion(eng):
     """The adjoint of a dispersive medium is not implemented: an engine with a Drude-Lorentz pole (an engine factory
     that sets one, or set_dispersion / set_bloch_dispersion on a session's engine) is refused before any run."""
+    _refuse_hz(eng)
     if getattr(eng, "dispersive", False):
         from ._abi import E_STATE, Fdtd2dError
         raise Fdtd2dError(E_STATE, "adjoint gradients are not available while a dispersive pole is set: the adjoint of a "
@@ -844,6 +854,7 @@ def pole_coefficients(omegas, dt, gamma, omega0):
 
 def _refuse_phase(eng):
     """_refuse_bloch without its refusal of a pole: complex fields are refused, the pole is what these calls are for."""
+    _refuse_hz(eng)
     if getattr(eng, "_bloch", None) is not None:
         from ._abi import E_STATE, Fdtd2dError
         raise Fdtd2dError(E_STATE, "adjoint gradients are not available while a Bloch phase is set (complex fields)")
@@ -1368,6 +1379,7 @@ def _bloch_flux_plan(eps, sigma, mu, bloch_phase, source_weights, nsteps, source
 def _refuse_bloch_flux_pole(eng):
     """An engine with the pole of set_bloch_dispersion (an engine factory that sets one, or the call on a session's
     engine) is refused before any run: hold_bloch_window does not serve it, and dJ/d wp2 under a phase is out of scope."""
+    _refuse_hz(eng)
     if getattr(eng, "dispersive", False):
         raise ValueError("the engine carries a dispersive pole (set_bloch_dispersion): gradients of flux under a Bloch "
                          "phase are not available with the pole")

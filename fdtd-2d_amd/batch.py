@@ -21,6 +21,9 @@ per cell (metals, absorption lines; fdtd2d_batch_dispersive.h); the batch then r
 (fdtd2d_batch_dispersive_adjoint.h).
 ``set_bloch_dispersion`` is that pole for a batch with complex fields (a Bloch phase or the lattice mode;
 fdtd2d_batch_bloch_dispersive.h): a metal unit cell with one angle of incidence or one k-point per member.
+``set_polarization("hz")`` turns a "pml" or "periodic" batch to the other polarisation: Hz with Ex and Ey, the electric field
+in the plane, with ``set_conductivity`` and ``set_dispersion`` acting on Ex and Ey (metal strips, wire grids, plasmonic
+gratings seen by in-plane E; fdtd2d_batch_hz.h).
 ``boundary="lattice"`` makes every member the unit cell of a rectangular 2D lattice: row R-1 is the image of row 0 and
 column C-1 the image of column 0, the fields are complex, and ``set_lattice_phase`` gives every member one Bloch phase
 across each pair of edges (band diagrams of 2D photonic crystals: a k-path is one batch; fdtd2d_batch_lattice.h).
@@ -136,6 +139,7 @@ class BatchEngine:
     Bloch phases of every member (zero until then), there is no layer, and the engine starts with vacuum materials.
     """
     _lattice = None               # ((cr, sr), (cc, sc)): the (B,) rotations of a lattice engine (None: not one)
+    _hz = False                   # set_polarization("hz"): Hz with Ex, Ey (fdtd2d_batch_hz.h)
 
     def __init__(self, count, rows, cols, dt=5e-14, dx=1e-4, dtype=np.float32, boundary="mur", device=0):
         self._lib = _abi.load()
@@ -229,6 +233,7 @@ class BatchEngine:
         their phases alone."""
         if self.boundary != "lattice":
             raise _abi.Fdtd2dError(_abi.E_STATE, f'set_lattice_phase needs boundary="lattice", not {self.boundary!r}')
+        self._no_hz("the lattice mode")
         if rotation is not None:
             if len(rotation) != 2 or any(not isinstance(r, (tuple, list)) or len(r) != 2 for r in rotation):
                 raise ValueError(f"rotation must be two pairs ((cr, sr), (cc, sc)), got {rotation!r}")
@@ -248,6 +253,38 @@ class BatchEngine:
         self._bloch = (cc, sc)        # upload, download, run and the monitors then behave as on a Bloch engine
         self._phi = None if ph is None else np.ascontiguousarray(np.broadcast_to(ph[1], (self.count,)))
         return self
+
+    # -- the polarisation (fdtd2d_batch_hz.h) ---------------------------------------------------------------------------
+    @property
+    def polarization(self) -> str:
+        """"ez" (Ez with Hx, Hy: the electric field along the invariant axis) or "hz" (Hz with Ex, Ey)."""
+        return "hz" if self._hz else "ez"
+
+    def set_polarization(self, polarization):
+        """"hz" turns a boundary="pml" or "periodic" batch to the Hz polarisation, "ez" back; call it right after
+        creation (``BatchEngine(..., boundary="periodic").set_polarization("hz")``).  The batch's storage serves both:
+        upload / download then carry (Hz, Ex, Ey) of the shapes of (Ez, Hx, Hy), upload_ezx / download_ezx carry Hzx,
+        sources, the DFTs and the probes act on Hz, eps[i, j] is the permittivity of Ex[i, j] and Ey[i, j] and mu[i, j]
+        the permeability of Hz[i, j].  set_conductivity and set_dispersion then act on Ex and Ey (fdtd2d_batch_hz.h).
+        A change zeroes the fields as reset() does.  The library refuses (E_STATE) a change beside a conductivity or a
+        pole of the polarisation being left, flux lines or a held window; "mur" and "lattice" batches and a Bloch
+        phase have no Hz kernels.  Not available in the Hz polarisation: the adjoint helpers and sessions, the flux
+        API, the Bloch API, the held window and the window patchers."""
+        if polarization not in ("ez", "hz"):
+            raise ValueError(f'polarization must be "ez" or "hz", got {polarization!r}')
+        if polarization == "hz" and self.boundary not in ("pml", "periodic"):
+            raise _abi.Fdtd2dError(_abi.E_STATE, f'the Hz polarisation needs boundary="pml" or "periodic", not '
+                                   f'{self.boundary!r}: the Mur frame, a plain box and the lattice mode have no Hz kernels')
+        if polarization == "hz":
+            self._no_bloch("the Hz polarisation")
+        self._ck(self._lib.fdtd2d_batch_set_polarization(self._h, _abi.POL_HZ if polarization == "hz" else _abi.POL_EZ))
+        self._hz = bool(self._lib.fdtd2d_batch_polarization(self._h) == _abi.POL_HZ)
+        return self
+
+    def _no_hz(self, what):
+        """The library's refusal of `what` in the Hz polarisation, before the call."""
+        if self._hz:
+            raise _abi.Fdtd2dError(_abi.E_STATE, f"{what} is not available in the Hz polarisation")
 
     def _no_dispersion(self, what):
         """The library's refusal of `what` while a dispersive pole is set, before the call."""
@@ -278,6 +315,7 @@ class BatchEngine:
                 self._npoint = (0, 0)         # the point sources of a Bloch batch go with the phase
             self._bloch = self._phi = None
             return self
+        self._no_hz("a Bloch phase")
         if rotation is not None:
             if len(rotation) != 2:
                 raise ValueError(f"rotation must be a pair (c, s), got {rotation!r}")
@@ -492,7 +530,8 @@ class BatchEngine:
 
     def upload(self, Ez=None, Hx=None, Hy=None):
         """Host -> device, any float dtype; a field given as None is left as is.  With a Bloch phase the fields may be
-        complex (a real array has a zero imaginary part)."""
+        complex (a real array has a zero imaginary part).  In the Hz polarisation the three slots are (Hz, Ex, Ey):
+        Hz (B, R, C), Ex (B, R, C-1), Ey (B, R-1, C), the physical fields with no hidden sign."""
         if any(a is not None and np.iscomplexobj(a) for a in (Ez, Hx, Hy)) and self._bloch is None:
             raise ValueError("complex fields need a Bloch phase (set_bloch_phase)")
         if self._bloch is not None:
@@ -525,7 +564,7 @@ class BatchEngine:
 
     def download(self, dtype=None):
         """Device -> host: new arrays (Ez, Hx, Hy) of the engine dtype (or `dtype`); complex ones with a Bloch phase,
-        the image column of Ez then rotated by the member's phase."""
+        the image column of Ez then rotated by the member's phase.  In the Hz polarisation the three are (Hz, Ex, Ey)."""
         dt = self.dtype if dtype is None else np.dtype(dtype)
         out = [np.empty(s, dt) for s in self._field_shapes()]
         self._ck(self._lib.fdtd2d_batch_download(self._h, *(a.ctypes.data for a in out), _code(dt)))
@@ -615,6 +654,7 @@ class BatchEngine:
 
     def hold_dft_window(self):
         """Keep a device copy of the window DFT as it is now; it survives reset() and further runs."""
+        self._no_hz("the held window (the adjoint)")
         self._no_bloch("the held window")
         self._no_dispersion("the held window (the adjoint of a dispersive medium)")
         self._ck(self._lib.fdtd2d_batch_hold_dft_window(self._h))
@@ -623,6 +663,7 @@ class BatchEngine:
     def dft_window_product(self, coef) -> np.ndarray:
         """float64 (B, nrows, ncols): sum_k Re(coef[b, k] * held[b, k] * current[b, k]) over the window, on the device.
         coef: complex (F,) for every member or (B, F)."""
+        self._no_hz("the window product (the adjoint)")
         self._no_bloch("the window product")
         self._no_dispersion("the window product (the adjoint of a dispersive medium)")
         f, nr, nc = self._win or (0, 1, 1)
@@ -639,6 +680,8 @@ class BatchEngine:
     # -- the same for a batch with a dispersive pole (fdtd2d_batch_dispersive_adjoint.h) ----------------------------
     def _need_dispersion(self, what, plain):
         """The library's refusals of a dispersive adjoint call, before the call."""
+        if getattr(self, "_hz", False):
+            raise _abi.Fdtd2dError(_abi.E_STATE, f"{what} is not available in the Hz polarisation")
         self._no_bloch(what)
         if not self.dispersive:
             raise _abi.Fdtd2dError(_abi.E_STATE, f"{what} needs a dispersive pole (fdtd2d_batch_set_dispersion): a batch "
@@ -680,6 +723,7 @@ class BatchEngine:
     # -- the same for a Bloch batch (fdtd2d_batch_bloch_adjoint.h) -----------------------------------------------------
     def _need_bloch(self):
         """The library's refusal of a Bloch call without a phase, before the call."""
+        self._no_hz("the Bloch API")
         if self._bloch is None:
             raise _abi.Fdtd2dError(_abi.E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first")
 
@@ -874,6 +918,7 @@ class BatchEngine:
             self._ck(self._lib.fdtd2d_batch_set_flux_lines(self._h, 0, None, 0, None, 1))
             self._flux, self._bflux = None, False
             return self
+        self._no_hz("flux lines (the sign and the averaged component differ)")
         ln, w, every = _flux_lines(lines, omegas, every, self.count, self.rows, self.cols, self.boundary == "periodic")
         self._ck(self._lib.fdtd2d_batch_set_flux_lines(self._h, len(ln), ln.ctypes.data_as(C.POINTER(C.c_int)),
                                                        int(w.shape[1]), _dptr(w), every))
@@ -893,6 +938,7 @@ class BatchEngine:
             if self._bflux:
                 self._flux, self._bflux = None, False
             return self
+        self._no_hz("Bloch flux lines")
         ln, w, every = _flux_lines(lines, omegas, every, self.count, self.rows, self.cols, True)
         self._ck(self._lib.fdtd2d_batch_set_bloch_flux_lines(self._h, len(ln), ln.ctypes.data_as(C.POINTER(C.c_int)),
                                                              int(w.shape[1]), _dptr(w), every))
@@ -964,6 +1010,7 @@ class BatchEngine:
 
     # -- line sources on the flux lines (fdtd2d_batch_flux_adjoint.h) --------------------------------------
     def _flux_entries(self, what):
+        self._no_hz(what)
         if self._flux is None or self._bflux:
             raise _abi.Fdtd2dError(_abi.E_STATE, f"{what} live on flux lines: call set_flux_lines first (not with "
                                                  f"set_bloch_flux_lines)")
@@ -1224,14 +1271,17 @@ class BatchEngine:
         e = ca * e + (dhy - dhx) * cb with s = sigma dt / (2 eps), ca = (1 - s) / (1 + s), cb = ce / (1 + s); it
         persists across set_materials and set_eps_window.  Needs materials (a uniform batch gets coefficient arrays).
         The library refuses (E_ARG) a value that is negative, not finite, or non-zero inside the margin."""
+        setter = self._lib.fdtd2d_batch_set_hz_conductivity if self._hz else self._lib.fdtd2d_batch_set_conductivity
         if sigma is None:
-            self._ck(self._lib.fdtd2d_batch_set_conductivity(self._h, None, _code(self.dtype)))
+            self._ck(setter(self._h, None, _code(self.dtype)))
             return self
         shape = (self.count, self.rows, self.cols)
         if np.isscalar(sigma):
             g = self.conductivity_margin
             s = np.zeros(shape, np.float64)
-            if self.boundary in ("periodic", "lattice"):
+            if self._hz:
+                s[self._hz_allowed()] = float(sigma)
+            elif self.boundary in ("periodic", "lattice"):
                 s[:, g:self.rows - g, :] = float(sigma)
             else:
                 s[:, g:self.rows - g, g:self.cols - g] = float(sigma)
@@ -1240,13 +1290,25 @@ class BatchEngine:
         else:
             s = _host(sigma, "sigma")
         self._shape(s, shape, "sigma")
-        self._ck(self._lib.fdtd2d_batch_set_conductivity(self._h, s.ctypes.data, _code(s.dtype)))
+        self._ck(setter(self._h, s.ctypes.data, _code(s.dtype)))
         return self
+
+    def _hz_allowed(self):
+        """(B, R, C) bool: the cells that may conduct or carry a pole in the Hz polarisation: rows g..R-2-g and, on a
+        "pml" batch, columns g..C-2-g (Ex[i, j] lives at i + 1/2; column C-1 of a periodic batch is never read)."""
+        g = self.conductivity_margin
+        ok = np.zeros((self.count, self.rows, self.cols), bool)
+        if self.boundary == "periodic":
+            ok[:, g:self.rows - 1 - g, :] = True
+        else:
+            ok[:, g:self.rows - 1 - g, g:self.cols - 1 - g] = True
+        return ok
 
     def set_conductivity_window(self, window, sigma):
         """New conductivity for window = (row0, col0, nrows, ncols) of every member: sigma (B, nrows, ncols).  The
         engine is then as set_conductivity with the full updated array would leave it (a batch without conductivity
         starts from zero)."""
+        self._no_hz("set_conductivity_window")
         w = np.ascontiguousarray([int(v) for v in window], dtype=np.int32)
         if w.shape != (4,):
             raise ValueError(f"window must be 4 integers (row0, col0, nrows, ncols), got {window!r}")
@@ -1273,14 +1335,17 @@ class BatchEngine:
         dt^2 (omega0^2 + wp2 EPS0 / eps) + 8 dt^2 / (eps mu dx^2) <= 4; while a pole is set it refuses (E_STATE) a Bloch
         phase, removing the layer of a "pml" batch and the held window with its product."""
         self._no_lattice("a dispersive pole")
+        setter = self._lib.fdtd2d_batch_set_hz_dispersion if self._hz else self._lib.fdtd2d_batch_set_dispersion
         if wp2 is None:
-            self._ck(self._lib.fdtd2d_batch_set_dispersion(self._h, None, _code(self.dtype), None, None))
+            self._ck(setter(self._h, None, _code(self.dtype), None, None))
             return self
         shape = (self.count, self.rows, self.cols)
         if np.isscalar(wp2):
             g = self.conductivity_margin
             w = np.zeros(shape, np.float64)
-            if self.boundary == "periodic":
+            if self._hz:
+                w[self._hz_allowed()] = float(wp2)
+            elif self.boundary == "periodic":
                 w[:, g:self.rows - g, :] = float(wp2)
             else:
                 w[:, g:self.rows - g, g:self.cols - g] = float(wp2)
@@ -1295,14 +1360,14 @@ class BatchEngine:
             if a.shape not in ((), (self.count,)):
                 raise ValueError(f"{nm} must be a scalar or have shape ({self.count},), got {a.shape}")
             per.append(np.ascontiguousarray(np.broadcast_to(a, (self.count,))))
-        self._ck(self._lib.fdtd2d_batch_set_dispersion(self._h, w.ctypes.data, _code(w.dtype), _dptr(per[0]),
-                                                       _dptr(per[1])))
+        self._ck(setter(self._h, w.ctypes.data, _code(w.dtype), _dptr(per[0]), _dptr(per[1])))
         return self
 
     def set_dispersion_window(self, window, wp2):
         """New strengths for window = (row0, col0, nrows, ncols) of every member: wp2 (B, nrows, ncols).  The engine
         is then as set_dispersion with the full updated array would leave it.  Needs a pole (E_STATE)."""
         self._no_lattice("a dispersive pole")
+        self._no_hz("set_dispersion_window")
         w = np.ascontiguousarray([int(v) for v in window], dtype=np.int32)
         if w.shape != (4,):
             raise ValueError(f"window must be 4 integers (row0, col0, nrows, ncols), got {window!r}")
@@ -1319,15 +1384,25 @@ class BatchEngine:
 
     def download_dispersion(self):
         """(Jh, Q), each (B, R, C) of the engine dtype: dx times the polarisation current at the last half step, and
-        dx * P / dt (needs a pole)."""
+        dx * P / dt (needs a pole).  In the Hz polarisation four arrays: (Jx, Qx, Jy, Qy), the state of Ex and of Ey."""
         jh = np.empty((self.count, self.rows, self.cols), self.dtype)
         q = np.empty_like(jh)
+        if self._hz:
+            jy, qy = np.empty_like(jh), np.empty_like(jh)
+            self._ck(self._lib.fdtd2d_batch_transfer_hz_dispersion(self._h, jh.ctypes.data, q.ctypes.data, jy.ctypes.data,
+                                                                   qy.ctypes.data, _code(jh.dtype), 0))
+            return jh, q, jy, qy
         self._ck(self._lib.fdtd2d_batch_transfer_dispersion(self._h, jh.ctypes.data, q.ctypes.data, _code(jh.dtype), 0))
         return jh, q
 
     def upload_dispersion(self, Jh=None, Q=None):
         """(B, R, C) each, host -> device; one given as None is left as is.  On a periodic batch column C-1 is
-        overwritten with column 0 (needs a pole)."""
+        overwritten with column 0 (needs a pole).  In the Hz polarisation Jh is the pair (Jx, Jy) and Q the pair
+        (Qx, Qy), stored as given (the state has no image column): upload_hz_dispersion with the four arrays named."""
+        if self._hz:
+            jx, jy = (None, None) if Jh is None else Jh
+            qx, qy = (None, None) if Q is None else Q
+            return self.upload_hz_dispersion(jx, qx, jy, qy)
         arrs = []
         for a, nm in ((Jh, "Jh"), (Q, "Q")):
             if a is not None:
@@ -1336,6 +1411,19 @@ class BatchEngine:
             arrs.append(a)
         ptr = [None if a is None else a.ctypes.data for a in arrs]
         self._ck(self._lib.fdtd2d_batch_transfer_dispersion(self._h, ptr[0], ptr[1], _code(self.dtype), 1))
+        return self
+
+    def upload_hz_dispersion(self, Jx=None, Qx=None, Jy=None, Qy=None):
+        """The pole state of the Hz polarisation, (B, R, C) each in the order download_dispersion returns them, host ->
+        device; one given as None is left as is (needs the Hz polarisation and a pole)."""
+        arrs = []
+        for a, nm in ((Jx, "Jx"), (Qx, "Qx"), (Jy, "Jy"), (Qy, "Qy")):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=self.dtype)
+                self._shape(a, (self.count, self.rows, self.cols), nm)
+            arrs.append(a)
+        ptr = [None if a is None else a.ctypes.data for a in arrs]
+        self._ck(self._lib.fdtd2d_batch_transfer_hz_dispersion(self._h, *ptr, _code(self.dtype), 1))
         return self
 
     # -- the pole of a Bloch or lattice batch (fdtd2d_batch_bloch_dispersive.h) ----------------------------------
@@ -1439,8 +1527,8 @@ def _waveform_amps(kind, fc, nsteps, dt):
 def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker", dt=5e-14, dx=1e-4,
                    dtype=np.float64, boundary="mur", omega=None, dft_every=1, device=0, pml_cells=40,
                    dft_window=None, window_omegas=None, probes=None, bloch_phase=None, source_weights=None,
-                   dispersion=None, bloch_dispersion=None, bloch_flux_lines=None, bloch_flux_omegas=None,
-                   flux_lines=None, flux_omegas=None):
+                   dispersion=None, bloch_dispersion=None, polarization="ez", conductivity=None,
+                   bloch_flux_lines=None, bloch_flux_omegas=None, flux_lines=None, flux_omegas=None):
     """run_fdtd for B members of one shape at once: zero fields, Courant check per member, nsteps of
     H -> E -> source with t = i*dt.
 
@@ -1467,6 +1555,10 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
     `dft_every` steps; the float64 (B, N, F) flux array of BatchEngine.flux() is then appended to the returned tuple.
     bloch_flux_lines with bloch_flux_omegas (boundary "periodic" with bloch_phase): the same on the complex fields of a
     Bloch run, as set_bloch_flux_lines takes them; the flux array is appended likewise.
+    polarization "hz" (boundary "pml" or "periodic" alone, not with bloch_phase or flux lines): the run advances Hz with
+    Ex and Ey (set_polarization); the source, the DFTs and the probes act on Hz, dispersion acts on Ex and Ey, and the
+    first three returned arrays are (Hz, Ex, Ey).  conductivity: None, or a scalar or (B, R, C) as set_conductivity takes
+    it, in either polarisation.
     """
     from .api import MU0
     eps = np.asarray(eps)
@@ -1512,6 +1604,15 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
         raise ValueError("source_weights needs bloch_phase")
     if bloch_phase is not None and omega is not None:
         raise ValueError("omega (the whole-grid transform) is not available with bloch_phase: use dft_window")
+    if polarization not in ("ez", "hz"):
+        raise ValueError(f'polarization must be "ez" or "hz", got {polarization!r}')
+    if polarization == "hz":
+        if boundary not in ("pml", "periodic"):
+            raise ValueError(f'polarization="hz" needs boundary="pml" or "periodic", not {boundary!r}')
+        for given, nm in ((bloch_phase, "bloch_phase"), (flux_lines, "flux_lines"), (bloch_flux_lines, "bloch_flux_lines"),
+                          (bloch_dispersion, "bloch_dispersion")):
+            if given is not None:
+                raise ValueError(f'{nm} is not available with polarization="hz"')
     if dispersion is not None:
         if len(dispersion) != 3:
             raise ValueError("dispersion must be (wp2, gamma, omega0)")
@@ -1556,10 +1657,14 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
         if cells is not None and np.any(cells[..., 0] >= R - 1):
             raise ValueError(f'a probe lies in row {R - 1}, the image of row 0: not with boundary="lattice"')
     with BatchEngine(B, R, Cc, dt, dx, dtype=dtype, boundary=boundary, device=device) as eng:
+        if polarization == "hz":
+            eng.set_polarization("hz")
         eng.set_materials(eps, mu)
         if layered:
             eng.set_pml(L, courant00=courant00)
         eng.set_sources(sources)
+        if conductivity is not None:
+            eng.set_conductivity(conductivity)
         if dispersion is not None:
             eng.set_dispersion(*dispersion)
         if lattice:

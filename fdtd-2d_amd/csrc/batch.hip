@@ -37,6 +37,7 @@
 #include "../../include/fdtd2d_batch_dispersive_adjoint.h"
 #include "../../include/fdtd2d_batch_flux.h"
 #include "../../include/fdtd2d_batch_flux_adjoint.h"
+#include "../../include/fdtd2d_batch_hz.h"
 #include "../../include/fdtd2d_batch_lattice.h"
 #include "../../include/fdtd2d_batch_lossy.h"
 #include "../../include/fdtd2d_batch_monitor.h"
@@ -65,6 +66,7 @@
 #include "kernels_batch_dispersive.hpp"
 #include "kernels_batch_flux.hpp"
 #include "kernels_batch_flux_adjoint.hpp"
+#include "kernels_batch_hz.hpp"
 #include "kernels_batch_lattice.hpp"
 #include "kernels_batch_lossy.hpp"
 #include "kernels_batch_monitor.hpp"
@@ -103,6 +105,10 @@ struct fdtd2d_batch {
     // hold the real parts) and these hold the imaginary parts
     bool bdisp = false;
     void *djh_im = nullptr, *dq_im = nullptr;
+    // fdtd2d_batch_set_polarization: the Hz polarisation.  The Ez slot holds Hz, hx Ex, hy Ey, ezx Hzx; the batch then
+    // always holds ca / cb (sigma_implicit without a conductivity), and a pole's djh, dq are Jx, Qx and these Jy, Qy
+    bool hz = false;
+    void *djy = nullptr, *dqy = nullptr;
     void *dsg = nullptr;                  // device scratch of the design-loop entry points
     size_t dsg_cap = 0;
     // fdtd2d_batch_set_periodic: column C-1 is the image of column 0.  The batch then always holds Ezx and the factors
@@ -307,7 +313,7 @@ int zero_fields(fdtd2d_batch *b)
     for (void *p : {b->ez[0], b->ez[1], b->hx, b->hy}) BCHK(b, hipMemsetAsync(p, 0, b->field_bytes, b->stream));
     if (b->ezx) BCHK(b, hipMemsetAsync(b->ezx, 0, b->field_bytes, b->stream));
     if (b->dcj)
-        for (void *p : {b->djh, b->dq, b->djh_im, b->dq_im})
+        for (void *p : {b->djh, b->dq, b->djh_im, b->dq_im, b->djy, b->dqy})
             if (p) BCHK(b, hipMemsetAsync(p, 0, b->field_bytes, b->stream));     // the imaginary parts: a complex pole's
     if (b->bloch)
         for (void *p : {b->ez_im, b->hx_im, b->hy_im, b->ezx_im})
@@ -326,6 +332,7 @@ int zero_fields(fdtd2d_batch *b)
 // twice and cj more
 int lds_arrays(const fdtd2d_batch *b)
 {
+    if (b->hz) return b->dcj ? 12 : 7;       // Hz, Ex, Ey, Hzx, ch, cb, ca and cj, Jx, Qx, Jy, Qy
     if (b->lattice) return b->bdisp ? 14 : 9;
     if (b->bloch) return b->bdisp ? 16 : 11;
     if (b->dcj) return 10;
@@ -840,6 +847,73 @@ int run_dispersive(fdtd2d_batch *b, int nsteps, const double *amps, long long am
     return 0;
 }
 
+// ---- runs in the Hz polarisation (fdtd2d_batch_hz.h): the paths of run_dispersive with the kernels of batch_hz.hip.
+// v.ce carries cb; the first streamed launch of a step is the E half-step, the second the H half-step with the sources
+// and the monitors.
+template <class T>
+int run_hz(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts)
+{
+    if (!b->ezx)
+        return bfail(b, FDTD2D_E_STATE, "the Hz polarisation needs a PML layer (fdtd2d_batch_set_pml) or periodic columns: "
+                     "a plain box has no Hz kernels");
+    const int disp = b->dcj ? 1 : 0, per = b->periodic ? 1 : 0;
+    if (!b->ca || !b->cb || !b->ch || (disp && (!b->djh || !b->dq || !b->djy || !b->dqy || !b->da || !b->dck)))
+        return bfail(b, FDTD2D_E_STATE, "Hz batch without its arrays");
+    const fdtd::BatchHzKernels &K = fdtd::batch_hz_kernels<T>();
+    fdtd::BatchPml<T> p = pml_view<T>(b);
+    fdtd::BatchMon m = mon_view(b);
+    fdtd::BatchPts silent{};
+    if (!pts) pts = &silent;
+    fdtd::BatchHzDisp<T> d{(T *)b->djh, (T *)b->dq, (T *)b->djy, (T *)b->dqy,
+                           (const T *)b->dcj, (const T *)b->da, (const T *)b->dck};
+    const T *ca = (const T *)b->ca;
+    if (use_resident(b)) {
+        const int cells = b->rows * b->cols, threads = resident_threads(cells);
+        const int per_thread = (cells + threads - 1) / threads;
+        const int mi = per_thread <= 4 ? 0 : per_thread <= 8 ? 1 : -1;
+        const void *kern = mi < 0 ? nullptr : K.resident[per][disp][mi];
+        if (!kern)
+            return bfail(b, FDTD2D_E_STATE, "%d cells per thread exceed the Hz resident kernel's %d", per_thread,
+                         disp ? 4 : 8);
+        const size_t lds = lds_bytes(b);
+        BCHK(b, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        int per_cu = 0, cus = 0;
+        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds));
+        BCHK(b, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
+        if (per_cu < 1) return bfail(b, FDTD2D_E_STATE, "Hz resident kernel does not fit a CU (%zu B of LDS)", lds);
+        const long long round = (long long)per_cu * cus;
+        const int blocks = (int)(b->count < round ? b->count : round);
+        const int chunk = b->steps_per_launch > 0 ? b->steps_per_launch : nsteps;
+        for (int n = 0; n < nsteps; n += chunk) {
+            int n0 = n, nt = nsteps - n < chunk ? nsteps - n : chunk;
+            long long step_base = b->step;
+            fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+            v.ce = (const T *)b->cb;
+            void *args[] = {&v, &p, &m, pts, &d, &ca, &n0, &nt, &step_base};
+            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads), args, lds);
+            if (rc) return rc;
+            b->launches++;
+            b->step += nt;
+        }
+        return 0;
+    }
+    const int cells = b->rows * b->cols;
+    const dim3 grid((cells + 255) / 256, b->count < 65535 ? b->count : 65535);
+    for (int n = 0; n < nsteps; ++n) {
+        fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+        v.ce = (const T *)b->cb;
+        long long step = b->step + 1;
+        int rc;
+        void *e_args[] = {&v, &p, &m, pts, &d, &ca, &n, &step};
+        void *h_args[] = {&v, &p, &m, pts, &n, &step};
+        if ((rc = launch_ptr(b, K.e[per][disp], grid, dim3(256), e_args, 0))) return rc;
+        if ((rc = launch_ptr(b, K.h[per], grid, dim3(256), h_args, 0))) return rc;
+        b->launches += 2;
+        b->step++;
+    }
+    return 0;
+}
+
 // ---- runs with flux lines (fdtd2d_batch_flux.h): the lossy PML, the periodic or the dispersive paths with the kernels
 // of batch_flux.hip, whose streamed H launches also write the lines' phasors
 fdtd::BatchFlux flux_view(const fdtd2d_batch *b)
@@ -1197,6 +1271,7 @@ template <class T>
 int run_impl(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts = nullptr,
              fdtd::BatchFluxSrc *fs = nullptr)
 {
+    if (b->hz) return run_hz<T>(b, nsteps, amps, amp_stride, pts);
     if (b->bflux) return run_bloch_flux<T>(b, nsteps, amps, amp_stride);
     if (b->bdisp) return run_bloch_dispersive<T>(b, nsteps, amps, amp_stride);
     if (b->lattice) return run_lattice<T>(b, nsteps, amps, amp_stride);
@@ -1284,8 +1359,9 @@ int sigma_margin(const fdtd2d_batch *b, int layer)
 bool sigma_barred(const fdtd2d_batch *b, int i, int j, int mg)
 {
     if (b->lattice) return false;
-    if (b->periodic) return j < b->cols - 1 && (i < mg || i > b->rows - 1 - mg);
-    return i < mg || i > b->rows - 1 - mg || j < mg || j > b->cols - 1 - mg;
+    const int hi = b->hz ? 2 : 1;       // Hz polarisation: Ex[i,j] and Ey[i,j] live at i + 1/2 and j + 1/2
+    if (b->periodic) return j < b->cols - 1 && (i < mg || i > b->rows - hi - mg);
+    return i < mg || i > b->rows - hi - mg || j < mg || j > b->cols - hi - mg;
 }
 
 // the first cell of sigma_host that is non-zero within `margin` cells of an edge: member * cells + cell, or -1
@@ -1480,6 +1556,12 @@ void fsrc_drop(fdtd2d_batch *b)
     b->fsrc_nchan = 0;
 }
 
+// what a batch in the Hz polarisation cannot do (fdtd2d_batch_hz.h)
+int refuse_hz(fdtd2d_batch *b, const char *what)
+{
+    return bfail(b, FDTD2D_E_STATE, "%s is not available in the Hz polarisation (fdtd2d_batch_set_polarization)", what);
+}
+
 int refuse_dispersive(fdtd2d_batch *b, const char *what)
 {
     return bfail(b, FDTD2D_E_STATE, "%s is not available while a dispersive pole is set", what);
@@ -1557,7 +1639,7 @@ int disp_reform(fdtd2d_batch *b, int r0, int c0, int nr, int nc)
 
 void disp_release(fdtd2d_batch *b)
 {
-    for (void **p : {&b->djh, &b->dq, &b->dcj, &b->da, &b->dck, &b->djh_im, &b->dq_im}) release(p);
+    for (void **p : {&b->djh, &b->dq, &b->dcj, &b->da, &b->dck, &b->djh_im, &b->dq_im, &b->djy, &b->dqy}) release(p);
     release((void **)&b->win_held_disp);     // the held dispersive window goes with the pole
     b->bdisp = false;
     b->wp2_host.clear();
@@ -1637,8 +1719,9 @@ int set_disp(fdtd2d_batch *b, const int *window, const void *wp2, int dtype, con
     const bool fresh = !b->dcj;
     if (fresh) {
         const size_t mb = (size_t)b->count * b->esz;
-        for (void **p : {&b->djh, &b->dq, &b->dcj, &b->da, &b->dck, &b->djh_im, &b->dq_im}) {
+        for (void **p : {&b->djh, &b->dq, &b->dcj, &b->da, &b->dck, &b->djh_im, &b->dq_im, &b->djy, &b->dqy}) {
             if (!complex && (p == &b->djh_im || p == &b->dq_im)) continue;
+            if (!b->hz && (p == &b->djy || p == &b->dqy)) continue;
             const size_t bytes = (p == &b->da || p == &b->dck) ? mb : b->field_bytes;
             hipError_t e = hipSuccess;
             if ((rc = alloc(b, p, bytes)) || (e = hipMemsetAsync(*p, 0, bytes, b->stream)) != hipSuccess) {
@@ -1919,7 +2002,7 @@ void fdtd2d_batch_destroy(fdtd2d_batch_t *b)
                      &b->ez_im, &b->hx_im, &b->hy_im, &b->ezx_im, &b->rho, (void **)&b->bloch_w, (void **)&b->amps_im,
                      (void **)&b->win_acc_im, (void **)&b->probe_trace_im, &b->rho_conj, &b->rho_r,
                      (void **)&b->win_held_im, (void **)&b->win_held_disp,
-                     &b->djh, &b->dq, &b->dcj, &b->da, &b->dck, &b->djh_im, &b->dq_im,
+                     &b->djh, &b->dq, &b->dcj, &b->da, &b->dck, &b->djh_im, &b->dq_im, &b->djy, &b->dqy,
                      (void **)&b->flux_acc, (void **)&b->flux_omega, (void **)&b->flux_ph,
                      (void **)&b->flux_acc_im, (void **)&b->fsrc_we, (void **)&b->fsrc_wh,
                      (void **)&b->fsrc_geom, (void **)&b->fsrc_we_im, (void **)&b->fsrc_wh_im})
@@ -2056,7 +2139,7 @@ int fdtd2d_batch_set_materials(fdtd2d_batch_t *b, const void *eps, const void *m
     b->eps_out_min.clear();
     b->uniform = false;
     b->have_mat = true;
-    if (b->periodic && !b->ca) return periodic_coefficients(b);
+    if ((b->periodic || b->hz) && !b->ca) return periodic_coefficients(b);
     return b->ca ? lossy_reform(b, 0, 0, b->rows, b->cols) : 0;
 }
 
@@ -2099,7 +2182,7 @@ int fdtd2d_batch_set_materials_uniform(fdtd2d_batch_t *b, double eps, double mu)
     b->courant.assign((size_t)b->count, courant_of(eps, mu, b->dt, b->dx));
     b->uniform = true;
     b->have_mat = true;
-    return b->periodic ? periodic_coefficients(b) : 0;       // a periodic batch keeps coefficient arrays
+    return b->periodic || b->hz ? periodic_coefficients(b) : 0;   // a periodic or Hz batch keeps coefficient arrays
 }
 
 int fdtd2d_batch_set_pml(fdtd2d_batch_t *b, const void *row_factors, const void *col_factors, int host_dtype,
@@ -2645,6 +2728,7 @@ int fdtd2d_batch_run_channels(fdtd2d_batch_t *b, int nsteps, const double *amps,
 int fdtd2d_batch_hold_dft_window(fdtd2d_batch_t *b)
 {
     if (!b) return FDTD2D_E_ARG;
+    if (b->hz) return refuse_hz(b, "the held window (the adjoint)");
     if (b->bloch) return refuse_bloch(b, "the held window");
     if (b->dcj) return refuse_dispersive(b, "the held window (the adjoint of a dispersive medium)");
     if (!b->win_nf) return bfail(b, FDTD2D_E_STATE, "no window DFT is set");
@@ -2661,6 +2745,7 @@ int fdtd2d_batch_dft_window_product(fdtd2d_batch_t *b, const double *coef_re, co
 {
     if (!b) return FDTD2D_E_ARG;
     if (!coef_re || !coef_im || !out) return bfail(b, FDTD2D_E_ARG, "coef_re, coef_im and out must not be NULL");
+    if (b->hz) return refuse_hz(b, "the window product (the adjoint)");
     if (b->bloch) return refuse_bloch(b, "the window product");
     if (b->dcj) return refuse_dispersive(b, "the window product (the adjoint of a dispersive medium)");
     if (!b->win_nf) return bfail(b, FDTD2D_E_STATE, "no window DFT is set");
@@ -2836,6 +2921,8 @@ int fdtd2d_batch_set_eps_window(fdtd2d_batch_t *b, int row0, int col0, int nrows
 int fdtd2d_batch_set_conductivity(fdtd2d_batch_t *b, const void *sigma, int dtype)
 {
     if (!b) return FDTD2D_E_ARG;
+    if (b->hz) return refuse_hz(b, "fdtd2d_batch_set_conductivity (there it would be a magnetic loss; the electric one is "
+                                   "fdtd2d_batch_set_hz_conductivity)");
     if (!sigma) {                           // remove it: the other kernels again
         if (!b->ca) return 0;
         int rc = use_device(b);
@@ -2860,6 +2947,7 @@ int fdtd2d_batch_set_conductivity_window(fdtd2d_batch_t *b, const int window[4],
 {
     if (!b) return FDTD2D_E_ARG;
     if (!window) return bfail(b, FDTD2D_E_ARG, "window must not be NULL");
+    if (b->hz) return refuse_hz(b, "fdtd2d_batch_set_conductivity_window");
     int rc = set_sigma(b, window, sigma, dtype);
     if (!rc) b->sigma_implicit = false;
     return rc;
@@ -2870,6 +2958,7 @@ int fdtd2d_batch_set_conductivity_window(fdtd2d_batch_t *b, const int window[4],
 int fdtd2d_batch_set_dispersion(fdtd2d_batch_t *b, const void *wp2, int dtype, const double *gamma, const double *omega0)
 {
     if (!b) return FDTD2D_E_ARG;
+    if (b->hz) return refuse_hz(b, "fdtd2d_batch_set_dispersion (use fdtd2d_batch_set_hz_dispersion)");
     if (!wp2 && !gamma && !omega0) {        // remove the pole: the other kernels again
         if (b->bdisp) return refuse_bloch_pole(b, "fdtd2d_batch_set_dispersion", "fdtd2d_batch_set_bloch_dispersion");
         if (!b->dcj) return 0;
@@ -2894,12 +2983,14 @@ int fdtd2d_batch_set_dispersion_window(fdtd2d_batch_t *b, const int window[4], c
 {
     if (!b) return FDTD2D_E_ARG;
     if (!window) return bfail(b, FDTD2D_E_ARG, "window must not be NULL");
+    if (b->hz) return refuse_hz(b, "fdtd2d_batch_set_dispersion_window");
     return set_disp(b, window, wp2, dtype, nullptr, nullptr);
 }
 
 int fdtd2d_batch_transfer_dispersion(fdtd2d_batch_t *b, void *jh, void *q, int host_dtype, int to_device)
 {
     if (!b) return FDTD2D_E_ARG;
+    if (b->hz) return refuse_hz(b, "fdtd2d_batch_transfer_dispersion (use fdtd2d_batch_transfer_hz_dispersion)");
     if (b->bdisp)
         return refuse_bloch_pole(b, "fdtd2d_batch_transfer_dispersion", "fdtd2d_batch_transfer_bloch_dispersion");
     if (!b->dcj) return bfail(b, FDTD2D_E_STATE, "no pole is set: call fdtd2d_batch_set_dispersion first");
@@ -2912,6 +3003,112 @@ int fdtd2d_batch_transfer_dispersion(fdtd2d_batch_t *b, void *jh, void *q, int h
         if (!to_device) rc = copy_out(b, dev[k], host[k], host_dtype, b->rows, b->cols);
         else if (!(rc = copy_in(b, dev[k], host[k], host_dtype, b->rows, b->cols)) && b->periodic)
             rc = copy_image(b, dev[k]);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// ---- fdtd2d_batch_hz.h -----------------------------------------------------------------------------------------
+
+int fdtd2d_batch_polarization(const fdtd2d_batch_t *b)
+{
+    if (!b) return FDTD2D_E_ARG;
+    return b->hz ? FDTD2D_POL_HZ : FDTD2D_POL_EZ;
+}
+
+int fdtd2d_batch_set_polarization(fdtd2d_batch_t *b, int polarization)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (polarization != FDTD2D_POL_EZ && polarization != FDTD2D_POL_HZ)
+        return bfail(b, FDTD2D_E_ARG, "polarization must be FDTD2D_POL_EZ or FDTD2D_POL_HZ, not %d", polarization);
+    const bool hz = polarization == FDTD2D_POL_HZ;
+    const char *to = hz ? "the Hz polarisation" : "the Ez polarisation";
+    // the refusals, before anything changes
+    if (b->boundary != FDTD2D_BOUNDARY_NONE)
+        return bfail(b, FDTD2D_E_STATE, "a change of polarisation needs a batch created with FDTD2D_BOUNDARY_NONE: the Mur "
+                     "frame has no Hz kernels");
+    if (b->lattice) return refuse_bloch(b, "a change of polarisation (the lattice mode has no Hz kernels)");
+    if (b->bloch) return refuse_bloch(b, "a change of polarisation (a Bloch phase has no Hz kernels)");
+    if (hz == b->hz) return 0;
+    if (b->flux_nl || b->fsrc_nchan) return refuse_flux(b, "a change of polarisation");
+    if (b->win_held || b->win_held_disp || b->win_held_im)
+        return bfail(b, FDTD2D_E_STATE, "%s is not available beside a held window: set the window again first", to);
+    if (b->dcj)
+        return bfail(b, FDTD2D_E_STATE, "%s is not available while a pole of the other polarisation is set: remove it first",
+                     to);
+    if (b->ca && !b->sigma_implicit)
+        return bfail(b, FDTD2D_E_STATE, "%s is not available while a conductivity of the other polarisation is set: remove "
+                     "it first", to);
+    int rc = fdtd2d_batch_reset(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    b->hz = hz;
+    if (hz && b->have_mat && !b->ca && (rc = periodic_coefficients(b))) {     // ca = 1, cb = ce
+        b->hz = false;
+        return rc;
+    }
+    if (!hz && b->sigma_implicit && !b->periodic) {      // the all-zero conductivity the Hz polarisation brought
+        release(&b->ca);
+        release(&b->cb);
+        b->sigma_host.clear();
+        b->sigma_implicit = false;
+    }
+    return 0;
+}
+
+int fdtd2d_batch_set_hz_conductivity(fdtd2d_batch_t *b, const void *sigma, int dtype)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!b->hz)
+        return bfail(b, FDTD2D_E_STATE, "fdtd2d_batch_set_hz_conductivity needs the Hz polarisation "
+                     "(fdtd2d_batch_set_polarization); the Ez polarisation takes fdtd2d_batch_set_conductivity");
+    if (!sigma) {                           // remove it: the batch keeps its arrays, with ca = 1 and cb = ce
+        if (!b->ca || b->sigma_implicit) return 0;
+        int rc = use_device(b);
+        if (rc) return rc;
+        std::fill(b->sigma_host.begin(), b->sigma_host.end(), 0.0);
+        b->sigma_implicit = true;
+        return lossy_reform(b, 0, 0, b->rows, b->cols);
+    }
+    int rc = set_sigma(b, nullptr, sigma, dtype);
+    if (!rc) b->sigma_implicit = false;
+    return rc;
+}
+
+int fdtd2d_batch_set_hz_dispersion(fdtd2d_batch_t *b, const void *wp2, int dtype, const double *gamma,
+                                   const double *omega0)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!b->hz)
+        return bfail(b, FDTD2D_E_STATE, "fdtd2d_batch_set_hz_dispersion needs the Hz polarisation "
+                     "(fdtd2d_batch_set_polarization); the Ez polarisation takes fdtd2d_batch_set_dispersion");
+    if (!wp2 && !gamma && !omega0) {        // remove the pole: the seven-array kernels again
+        if (!b->dcj) return 0;
+        int rc = use_device(b);
+        if (rc) return rc;
+        BCHK(b, hipStreamSynchronize(b->stream));
+        disp_release(b);
+        return 0;
+    }
+    if (!wp2 || !gamma || !omega0)
+        return bfail(b, FDTD2D_E_ARG, "wp2, gamma and omega0 must all be given (or all NULL)");
+    return set_disp(b, nullptr, wp2, dtype, gamma, omega0);
+}
+
+int fdtd2d_batch_transfer_hz_dispersion(fdtd2d_batch_t *b, void *jx, void *qx, void *jy, void *qy, int host_dtype,
+                                        int to_device)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!b->hz || !b->dcj)
+        return bfail(b, FDTD2D_E_STATE, "no pole of the Hz polarisation is set: call fdtd2d_batch_set_hz_dispersion first");
+    if (host_dtype != FDTD2D_F32 && host_dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad host_dtype");
+    int rc = use_device(b);
+    if (rc) return rc;
+    void *dev[4] = {b->djh, b->dq, b->djy, b->dqy}, *host[4] = {jx, qx, jy, qy};
+    for (int k = 0; k < 4; ++k) {
+        if (!host[k]) continue;
+        rc = to_device ? copy_in(b, dev[k], host[k], host_dtype, b->rows, b->cols)
+                       : copy_out(b, dev[k], host[k], host_dtype, b->rows, b->cols);
         if (rc) return rc;
     }
     return 0;
@@ -2935,6 +3132,7 @@ int dispersive_window_state(fdtd2d_batch *b, const char *what, const char *plain
 int fdtd2d_batch_hold_dispersive_window(fdtd2d_batch_t *b)
 {
     if (!b) return FDTD2D_E_ARG;
+    if (b->hz) return refuse_hz(b, "the held dispersive window (the adjoint)");
     int rc = dispersive_window_state(b, "the held dispersive window", "fdtd2d_batch_hold_dft_window");
     if (rc) return rc;
     if ((rc = use_device(b))) return rc;
@@ -2953,6 +3151,7 @@ int fdtd2d_batch_dispersive_window_product(fdtd2d_batch_t *b, int ncoef, const d
         return bfail(b, FDTD2D_E_ARG, "coef_re, coef_im, scale and out must not be NULL");
     if (ncoef < 1 || ncoef > FDTD2D_BATCH_MAX_PRODUCT_SETS)
         return bfail(b, FDTD2D_E_ARG, "ncoef %d outside 1..%d", ncoef, (int)FDTD2D_BATCH_MAX_PRODUCT_SETS);
+    if (b->hz) return refuse_hz(b, "the dispersive window product (the adjoint)");
     int rc = dispersive_window_state(b, "the dispersive window product", "fdtd2d_batch_dft_window_product");
     if (rc) return rc;
     if (!b->win_held_disp)
@@ -3073,7 +3272,7 @@ int fdtd2d_batch_set_periodic(fdtd2d_batch_t *b, int on)
         if (b->bloch && (rc = bloch_off(b))) return rc;
         if ((rc = fdtd2d_batch_set_point_sources(b, 0, nullptr, 0, nullptr))) return rc;
         b->periodic = false;
-        if (b->sigma_implicit && !b->dcj) {
+        if (b->sigma_implicit && !b->dcj && !b->hz) {
             release(&b->ca);
             release(&b->cb);
             b->sigma_host.clear();
@@ -3116,7 +3315,8 @@ int fdtd2d_batch_set_periodic(fdtd2d_batch_t *b, int on)
     if ((rc = fdtd2d_batch_set_point_sources(b, 0, nullptr, 0, nullptr))) return undo(rc);
     if (!b->ezx && (rc = unit_layer(b))) return undo(rc);
     if ((rc = copy_image(b, b->ez[b->cur])) || (rc = copy_image(b, b->ezx))) return undo(rc);
-    if (b->dcj && ((rc = copy_image(b, b->djh)) || (rc = copy_image(b, b->dq)))) return undo(rc);
+    // (the pole state of the Hz polarisation has no image column)
+    if (b->dcj && !b->hz && ((rc = copy_image(b, b->djh)) || (rc = copy_image(b, b->dq)))) return undo(rc);
     if (b->have_mat && !b->ca && (rc = periodic_coefficients(b))) return undo(rc);
     return 0;
 }
@@ -3133,6 +3333,7 @@ int fdtd2d_batch_set_bloch(fdtd2d_batch_t *b, const double *cos_phi, const doubl
     if (!cos_phi && b->bflux) return refuse_flux(b, "turning the Bloch phase off");
     if (!cos_phi && b->bdisp) return refuse_dispersive(b, "turning the Bloch phase off");
     if (!cos_phi) return b->bloch ? bloch_off(b) : 0;
+    if (b->hz) return refuse_hz(b, "a Bloch phase");
     if (b->dcj && !b->bdisp) return refuse_dispersive(b, "a Bloch phase");
     if (b->flux_nl && !b->bflux) return refuse_flux(b, "a Bloch phase");
     if (!b->periodic)
@@ -3318,6 +3519,7 @@ int fdtd2d_batch_set_lattice(fdtd2d_batch_t *b, const double *cos_r, const doubl
     const int given = !!cos_r + !!sin_r + !!cos_c + !!sin_c;
     if (given != 0 && given != 4)
         return bfail(b, FDTD2D_E_ARG, "cos_r, sin_r, cos_c and sin_c must all be given (or all NULL)");
+    if (given && b->hz) return refuse_hz(b, "the lattice mode");
     int rc = use_device(b);
     if (rc) return rc;
     if (!given) {
@@ -3635,6 +3837,7 @@ int fdtd2d_batch_set_flux_lines(fdtd2d_batch_t *b, int nlines, const int *lines,
         return bfail(b, FDTD2D_E_ARG, "nlines %d outside 0..%d", nlines, FDTD2D_BATCH_MAX_FLUX_LINES);
     long long cells = 0;
     if (nlines > 0) {
+        if (b->hz) return refuse_hz(b, "flux lines (the sign and the averaged component differ)");
         if (b->boundary != FDTD2D_BOUNDARY_NONE)
             return bfail(b, FDTD2D_E_STATE, "flux lines need a PML or periodic batch: the kernels of the Mur frame carry none");
         if (b->lattice) return bfail(b, FDTD2D_E_STATE, "flux lines are not available in the lattice mode");
@@ -3765,6 +3968,7 @@ int fdtd2d_batch_set_bloch_flux_lines(fdtd2d_batch_t *b, int nlines, const int *
         return bfail(b, FDTD2D_E_ARG, "nlines %d outside 0..%d", nlines, FDTD2D_BATCH_MAX_FLUX_LINES);
     long long cells = 0;
     if (nlines > 0) {
+        if (b->hz) return refuse_hz(b, "Bloch flux lines");
         if (b->boundary != FDTD2D_BOUNDARY_NONE || !b->periodic)
             return bfail(b, FDTD2D_E_STATE, "Bloch flux lines need a batch with periodic columns and a Bloch phase");
         if (b->lattice) return bfail(b, FDTD2D_E_STATE, "Bloch flux lines are not available in the lattice mode");

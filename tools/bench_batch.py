@@ -50,6 +50,12 @@ array eps with random binary permittivity, a ricker line source per member):
                               same one silent point source, timed alternately in one process: periodic_ms,
                               lossy_pml_ms, periodic_over_lossy_pml, both paths and LDS sizes.  Default: 1024 members
                               of 60 rows x 61 columns, a 10-cell layer, 1000 steps.
+  --hz                        instead: the Hz polarisation (set_polarization("hz")) with a metal strip and its Drude pole
+                              against the Ez polarisation's dispersive kernels on the same periodic members, layer and
+                              strip, both resident, timed alternately in one process: hz_ms, ez_dispersive_ms,
+                              hz_over_ez_dispersive, both paths and LDS sizes.  The Hz kernel does two pole updates per
+                              cell in 12 LDS arrays against one in 10.  Default: 1024 members of 56 rows x 57 columns, a
+                              10-cell layer, 2000 steps.
   --bloch                     instead: a Bloch batch (set_bloch_phase, a phase sweep over the members, ramp weights)
                               against the plain periodic batch of the same members, layer and conductivity, timed
                               alternately in one process: bloch_ms, periodic_ms, bloch_over_periodic, both paths and
@@ -768,6 +774,57 @@ def bench_dispersive(count, rows, cols, steps, dtype, reps, pml_cells):
             "dispersive_mcell_steps_per_s": round(count * rows * cols * steps / (med_d * 1e-3) / 1e6, 1)}
 
 
+def bench_hz(count, rows, cols, steps, dtype, reps, pml_cells):
+    """The Hz polarisation with a metal strip and its pole against the Ez polarisation's dispersive kernels on the same
+    periodic members, resident, timed alternately in one process."""
+    eps, rects, amps = members(count, rows, cols, steps)
+    c00 = courant00(eps, dtype)
+    g = max(6, pml_cells)
+    wp2 = np.zeros((count, rows, cols))
+    wp2[:, rows // 2:rows // 2 + 2, :(cols - 1) // 2] = (2 * np.pi * 70e9) ** 2     # a strip over half the period
+    rects = rects.copy()
+    rects[:, 1] = np.minimum(rects[:, 1], cols - 1 - rects[:, 3])                  # off the image column
+
+    def batch(pol):
+        b = fd.BatchEngine(count, rows, cols, DT, DX, dtype=dtype, boundary="periodic").set_polarization(pol)
+        b.set_materials(eps.astype(dtype), fd.MU0).set_sources(rects)
+        b.set_pml(pml_cells, courant00=c00)
+        b.set_dispersion(wp2, 1e11, 0.0)
+        b.run(steps, amps).sync()                      # warm-up: code objects, clocks
+        return b
+
+    def timed(b):
+        b.reset().sync()
+        t0 = time.perf_counter()
+        b.run(steps, amps).sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    assert g <= rows // 2 and rows // 2 + 2 <= rows - 1 - g
+    with batch("ez") as ez, batch("hz") as hz:
+        assert ez.dispersive and hz.dispersive and hz.polarization == "hz" and ez.polarization == "ez"
+        l0 = hz.launches
+        hz.reset().run(steps, amps).sync()
+        launches = hz.launches - l0
+        ez_ms, hz_ms = [], []
+        for _ in range(reps):
+            ez_ms.append(timed(ez))
+            hz_ms.append(timed(hz))
+        paths = ["resident" if b.resident else "streamed" for b in (ez, hz)]
+        lds = [b.lds_bytes for b in (ez, hz)]
+        finite = bool(np.all(np.isfinite(hz.download()[0])))
+    med_e, med_h = float(np.median(ez_ms)), float(np.median(hz_ms))
+    return {"count": count, "rows": rows, "cols": cols, "steps": steps, "dtype": np.dtype(dtype).name,
+            "materials": "arrays", "boundary": "periodic", "pml_cells": pml_cells, "reps": reps,
+            "ez_dispersive_path": paths[0], "hz_path": paths[1], "ez_dispersive_lds_bytes_per_member": lds[0],
+            "hz_lds_bytes_per_member": lds[1], "lds_arrays": {"ez_dispersive": 10, "hz": 12},
+            "ez_dispersive_workgroups_per_cu": 163840 // lds[0], "hz_workgroups_per_cu": 163840 // lds[1],
+            "ez_dispersive_ms": round(med_e, 4), "ez_dispersive_ms_min": round(min(ez_ms), 4),
+            "ez_dispersive_ms_all": [round(v, 4) for v in ez_ms],
+            "hz_ms": round(med_h, 4), "hz_ms_min": round(min(hz_ms), 4), "hz_ms_all": [round(v, 4) for v in hz_ms],
+            "hz_over_ez_dispersive": round(med_h / med_e, 3), "launches_per_run": launches, "hz_finite": finite,
+            "hz_mcell_steps_per_s": round(count * rows * cols * steps / (med_h * 1e-3) / 1e6, 1)}
+
+
 def bench_bloch(count, rows, cols, steps, dtype, reps, pml_cells):
     eps, rects, amps = members(count, rows, cols, steps)
     c00 = courant00(eps, dtype)
@@ -1258,7 +1315,13 @@ def main():
                     help="time the adjoint of a flux objective on a Bloch batch (line sources, conjugated run, session)")
     ap.add_argument("--flux-adjoint", action="store_true",
                     help="time the adjoint run with line sources and a FluxAdjointSession iteration")
+    ap.add_argument("--hz", action="store_true",
+                    help="time the Hz polarisation with a pole against the Ez dispersive kernels on periodic members")
     a = ap.parse_args()
+    if a.hz:
+        print(json.dumps(bench_hz(a.count or 1024, a.rows or 56, a.cols or 57, a.steps or 2000, np.dtype(a.dtype),
+                                  a.reps, a.pml_cells)), flush=True)
+        return
     if a.flux_adjoint:
         print(json.dumps(bench_flux_adjoint(a.count or 1024, a.rows or 60, a.cols or 61, a.steps or 2000,
                                             np.dtype(a.dtype), a.reps, a.pml_cells)), flush=True)
