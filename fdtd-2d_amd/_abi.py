@@ -279,6 +279,13 @@ BATCH_HZ_SIGNATURES = {
     "fdtd2d_batch_set_hz_dispersion": (_i, [_vp, _vp, _i, C.POINTER(_d), C.POINTER(_d)]),
     "fdtd2d_batch_transfer_hz_dispersion": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i]),
 }
+# every symbol include/fdtd2d_batch_hz_flux.h declares (flux lines in the Hz polarisation: the transforms of Hz and of the
+# tangential E on up to 4 lines, and the power through each); the ids and the option are fdtd2d_batch_flux.h's
+BATCH_HZ_FLUX_SIGNATURES = {
+    "fdtd2d_batch_set_hz_flux_lines": (_i, [_vp, _i, C.POINTER(_i), _i, C.POINTER(_d), _i]),
+    "fdtd2d_batch_read_hz_flux_lines": (_i, [_vp, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_hz_flux": (_i, [_vp, C.POINTER(_d)]),
+}
 
 # transport callback of fdtd2d_slab_attach
 EXCHANGE_FN = C.CFUNCTYPE(_i, _vp, _vp, _vp, _vp, _vp, _ll, _vp)
@@ -335,7 +342,8 @@ def load():
                                    **BATCH_BLOCH_DISPERSIVE_SIGNATURES,
                                    **BATCH_DISPERSIVE_ADJOINT_SIGNATURES, **BATCH_FLUX_SIGNATURES,
                                    **BATCH_BLOCH_FLUX_SIGNATURES, **BATCH_FLUX_ADJOINT_SIGNATURES,
-                                   **BATCH_BLOCH_FLUX_ADJOINT_SIGNATURES, **BATCH_HZ_SIGNATURES}.items():
+                                   **BATCH_BLOCH_FLUX_ADJOINT_SIGNATURES, **BATCH_HZ_SIGNATURES,
+                                   **BATCH_HZ_FLUX_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

@@ -23,7 +23,8 @@ per cell (metals, absorption lines; fdtd2d_batch_dispersive.h); the batch then r
 fdtd2d_batch_bloch_dispersive.h): a metal unit cell with one angle of incidence or one k-point per member.
 ``set_polarization("hz")`` turns a "pml" or "periodic" batch to the other polarisation: Hz with Ex and Ey, the electric field
 in the plane, with ``set_conductivity`` and ``set_dispersion`` acting on Ex and Ey (metal strips, wire grids, plasmonic
-gratings seen by in-plane E; fdtd2d_batch_hz.h).
+gratings seen by in-plane E; fdtd2d_batch_hz.h).  ``set_hz_flux_lines`` gives such a batch flux lines: the transforms of Hz
+and of the tangential E, and through ``flux()`` the power that crosses each line (fdtd2d_batch_hz_flux.h).
 ``boundary="lattice"`` makes every member the unit cell of a rectangular 2D lattice: row R-1 is the image of row 0 and
 column C-1 the image of column 0, the fields are complex, and ``set_lattice_phase`` gives every member one Bloch phase
 across each pair of edges (band diagrams of 2D photonic crystals: a k-path is one batch; fdtd2d_batch_lattice.h).
@@ -157,6 +158,7 @@ class BatchEngine:
         self._nprobe = 0
         self._flux = None             # ((N, 4) lines, (B, F) omegas) of the flux lines
         self._bflux = False           # they are Bloch lines (set_bloch_flux_lines): complex fields, two parts
+        self._hzflux = False          # they are lines of the Hz polarisation (set_hz_flux_lines): Hz and the tangential E
         self._npoint = (0, 0)         # (P, K) of the point sources
         self._bloch = None            # (c, s): the (B,) rotations of a Bloch phase
         self._phi = None              # the phases as given (None with rotation=)
@@ -268,8 +270,9 @@ class BatchEngine:
         the permeability of Hz[i, j].  set_conductivity and set_dispersion then act on Ex and Ey (fdtd2d_batch_hz.h).
         A change zeroes the fields as reset() does.  The library refuses (E_STATE) a change beside a conductivity or a
         pole of the polarisation being left, flux lines or a held window; "mur" and "lattice" batches and a Bloch
-        phase have no Hz kernels.  Not available in the Hz polarisation: the adjoint helpers and sessions, the flux
-        API, the Bloch API, the held window and the window patchers."""
+        phase have no Hz kernels.  Not available in the Hz polarisation: the adjoint helpers and sessions,
+        set_flux_lines, set_bloch_flux_lines and the line sources (its flux lines are set_hz_flux_lines'), the Bloch API,
+        the held window and the window patchers."""
         if polarization not in ("ez", "hz"):
             raise ValueError(f'polarization must be "ez" or "hz", got {polarization!r}')
         if polarization == "hz" and self.boundary not in ("pml", "periodic"):
@@ -916,7 +919,8 @@ class BatchEngine:
         lines are set (bit-identical fields, a smaller resident capacity: see resident_max_cells)."""
         if lines is None or len(lines) == 0:
             self._ck(self._lib.fdtd2d_batch_set_flux_lines(self._h, 0, None, 0, None, 1))
-            self._flux, self._bflux = None, False
+            if not self._hzflux:
+                self._flux, self._bflux = None, False
             return self
         self._no_hz("flux lines (the sign and the averaged component differ)")
         ln, w, every = _flux_lines(lines, omegas, every, self.count, self.rows, self.cols, self.boundary == "periodic")
@@ -945,14 +949,42 @@ class BatchEngine:
         self._flux, self._bflux = (ln, w), True
         return self
 
+    def set_hz_flux_lines(self, lines, omegas, every=1):
+        """The flux lines of set_flux_lines on an engine in the Hz polarisation (set_polarization("hz")), with or without
+        set_conductivity and set_dispersion: the same lines, limits and sampling (fdtd2d_batch_hz_flux.h).  After every
+        `every`-th step n the engine adds Hz * exp(-1j * omega * n * dt) and Et * exp(-1j * omega * n * dt) on the line
+        cells in float64, Et being the tangential E of the step's E half-step centred on the cell: 0.5 * (Ex[i-1, j] +
+        Ex[i, j]) on a row line, 0.5 * (Ey[i, j-1] + Ey[i, j]) on a column line.  lines None or empty removes them.
+        read_flux_lines, flux, flux_lines_in_lds and set_flux_lds serve them; set_polarization("ez") is refused while
+        they are set."""
+        if lines is None or len(lines) == 0:
+            self._ck(self._lib.fdtd2d_batch_set_hz_flux_lines(self._h, 0, None, 0, None, 1))
+            if self._hzflux:
+                self._flux, self._hzflux = None, False
+            return self
+        if not self._hz:
+            raise _abi.Fdtd2dError(_abi.E_STATE, 'set_hz_flux_lines needs the Hz polarisation (set_polarization("hz")): '
+                                                 "the lines of the Ez polarisation are set_flux_lines'")
+        ln, w, every = _flux_lines(lines, omegas, every, self.count, self.rows, self.cols, self.boundary == "periodic")
+        self._ck(self._lib.fdtd2d_batch_set_hz_flux_lines(self._h, len(ln), ln.ctypes.data_as(C.POINTER(C.c_int)),
+                                                          int(w.shape[1]), _dptr(w), every))
+        self._flux, self._bflux, self._hzflux = (ln, w), False, True
+        return self
+
     def read_flux_lines(self, raw=False):
         """(Ez_hat, Ht_hat), each complex128 (B, F, cells): the transforms on the line cells, lines concatenated in the
         order given.  Ht_hat carries the half-step factor exp(+1j * omega * dt / 2) (the H of a step lives half a step
         before its Ez) unless raw, which returns the sums as accumulated.  Serves the lines of set_flux_lines and of
         set_bloch_flux_lines (the transforms of the complex fields: those of the real part plus 1j times those of the
-        imaginary part)."""
+        imaginary part).  With the lines of set_hz_flux_lines it returns (Et_hat, Hz_hat), the electric transform first
+        as in the other polarisation, and the factor goes on Et_hat (the E of a step lives half a step before its Hz)."""
         ln, w = self._flux or (np.zeros((0, 4), np.int32), np.zeros((self.count, 0)))
         shape = (self.count, w.shape[1], int(ln[:, 3].sum()))
+        if self._hzflux:
+            a = [np.empty(shape) for _ in range(4)]
+            self._ck(self._lib.fdtd2d_batch_read_hz_flux_lines(self._h, *(_dptr(x) for x in a)))
+            h, e = a[0] + 1j * a[1], a[2] + 1j * a[3]
+            return (e, h) if raw else (e * np.exp(0.5j * w * self.dt)[:, :, None], h)
         if self._bflux:
             (er, hr), (ei, hi) = self.read_bloch_flux_parts()
             e, h = er + 1j * ei, hr + 1j * hi
@@ -1000,11 +1032,14 @@ class BatchEngine:
     def flux(self) -> np.ndarray:
         """float64 (B, N, F): the power that crosses each line per frequency, P = s * dx * sum over the line's cells of
         Re(Ez_hat * conj(Ht_hat)), s = +1 for a row line and -1 for a column line, formed on the device.  No factor 1/2
-        and no normalisation: take ratios."""
+        and no normalisation: take ratios.  With the lines of set_hz_flux_lines the sum is of Re(Hz_hat * conj(Et_hat)) and
+        s = -1 for a row line, +1 for a column line (S_y = -Ex Hz, S_x = Ey Hz): a line counts power towards increasing
+        row or column in either polarisation."""
         ln, w = self._flux or (np.zeros((0, 4), np.int32), np.zeros((self.count, 0)))
         out = np.empty((self.count, len(ln), w.shape[1]))
         buf = out if out.size else np.empty(1)     # a refused read still passes a valid pointer
-        fn = self._lib.fdtd2d_batch_bloch_flux if self._bflux else self._lib.fdtd2d_batch_flux
+        fn = (self._lib.fdtd2d_batch_bloch_flux if self._bflux else
+              self._lib.fdtd2d_batch_hz_flux if self._hzflux else self._lib.fdtd2d_batch_flux)
         self._ck(fn(self._h, _dptr(buf)))
         return out
 
@@ -1528,7 +1563,7 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
                    dtype=np.float64, boundary="mur", omega=None, dft_every=1, device=0, pml_cells=40,
                    dft_window=None, window_omegas=None, probes=None, bloch_phase=None, source_weights=None,
                    dispersion=None, bloch_dispersion=None, polarization="ez", conductivity=None,
-                   bloch_flux_lines=None, bloch_flux_omegas=None, flux_lines=None, flux_omegas=None):
+                   hz_flux_lines=None, hz_flux_omegas=None, bloch_flux_lines=None, bloch_flux_omegas=None, flux_lines=None, flux_omegas=None):
     """run_fdtd for B members of one shape at once: zero fields, Courant check per member, nsteps of
     H -> E -> source with t = i*dt.
 
@@ -1555,10 +1590,12 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
     `dft_every` steps; the float64 (B, N, F) flux array of BatchEngine.flux() is then appended to the returned tuple.
     bloch_flux_lines with bloch_flux_omegas (boundary "periodic" with bloch_phase): the same on the complex fields of a
     Bloch run, as set_bloch_flux_lines takes them; the flux array is appended likewise.
-    polarization "hz" (boundary "pml" or "periodic" alone, not with bloch_phase or flux lines): the run advances Hz with
-    Ex and Ey (set_polarization); the source, the DFTs and the probes act on Hz, dispersion acts on Ex and Ey, and the
-    first three returned arrays are (Hz, Ex, Ey).  conductivity: None, or a scalar or (B, R, C) as set_conductivity takes
-    it, in either polarisation.
+    polarization "hz" (boundary "pml" or "periodic" alone, not with bloch_phase, flux_lines or bloch_flux_lines): the run
+    advances Hz with Ex and Ey (set_polarization); the source, the DFTs and the probes act on Hz, dispersion acts on Ex
+    and Ey, and the first three returned arrays are (Hz, Ex, Ey).  conductivity: None, or a scalar or (B, R, C) as
+    set_conductivity takes it, in either polarisation.  hz_flux_lines with hz_flux_omegas (polarization "hz" alone): flux
+    monitors as set_hz_flux_lines takes them, sampled every `dft_every` steps; the flux array is appended as with
+    flux_lines.
     """
     from .api import MU0
     eps = np.asarray(eps)
@@ -1613,6 +1650,12 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
                           (bloch_dispersion, "bloch_dispersion")):
             if given is not None:
                 raise ValueError(f'{nm} is not available with polarization="hz"')
+    if (hz_flux_lines is None) != (hz_flux_omegas is None):
+        raise ValueError("hz_flux_lines and hz_flux_omegas must be given together")
+    if hz_flux_lines is not None:
+        if polarization != "hz":
+            raise ValueError('hz_flux_lines needs polarization="hz": in the Ez polarisation use flux_lines')
+        _flux_lines(hz_flux_lines, hz_flux_omegas, dft_every, B, R, Cc, boundary == "periodic")
     if dispersion is not None:
         if len(dispersion) != 3:
             raise ValueError("dispersion must be (wp2, gamma, omega0)")
@@ -1686,6 +1729,8 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
             eng.set_flux_lines(flux_lines, flux_omegas, dft_every)
         if bloch_flux_lines is not None:
             eng.set_bloch_flux_lines(bloch_flux_lines, bloch_flux_omegas, dft_every)
+        if hz_flux_lines is not None:
+            eng.set_hz_flux_lines(hz_flux_lines, hz_flux_omegas, dft_every)
         eng.run(nsteps, None if waveform is None else _waveform_amps(waveform, fcs, nsteps, dt))
         out = eng.download()
         if omega is not None:
@@ -1694,7 +1739,7 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
             out += (eng.read_dft_window(),)
         if cells is not None:
             out += (eng.read_probes(0, int(nsteps)),)
-        if flux_lines is not None or bloch_flux_lines is not None:
+        if flux_lines is not None or bloch_flux_lines is not None or hz_flux_lines is not None:
             out += (eng.flux(),)
         return out
 

@@ -25,6 +25,8 @@
 // With the lines of fdtd2d_batch_bloch_flux.h a Bloch batch takes the kernels of batch_bloch_flux.hip, with or without
 // the complex pole; the lines share the host state of fdtd2d_batch_flux.h's (`flux_nl` is set too) and add the sums of
 // the imaginary part.
+// With the lines of fdtd2d_batch_hz_flux.h a batch in the Hz polarisation takes the kernels of batch_hz_flux.hip, with or
+// without a conductivity and a pole; the lines share that host state too (`hzflux` beside `flux_nl`).
 #include "../../include/fdtd2d.h"
 #include "../../include/fdtd2d_batch_adjoint.h"
 #include "../../include/fdtd2d_batch_bloch.h"
@@ -38,6 +40,7 @@
 #include "../../include/fdtd2d_batch_flux.h"
 #include "../../include/fdtd2d_batch_flux_adjoint.h"
 #include "../../include/fdtd2d_batch_hz.h"
+#include "../../include/fdtd2d_batch_hz_flux.h"
 #include "../../include/fdtd2d_batch_lattice.h"
 #include "../../include/fdtd2d_batch_lossy.h"
 #include "../../include/fdtd2d_batch_monitor.h"
@@ -67,6 +70,7 @@
 #include "kernels_batch_flux.hpp"
 #include "kernels_batch_flux_adjoint.hpp"
 #include "kernels_batch_hz.hpp"
+#include "kernels_batch_hz_flux.hpp"
 #include "kernels_batch_lattice.hpp"
 #include "kernels_batch_lossy.hpp"
 #include "kernels_batch_monitor.hpp"
@@ -174,6 +178,9 @@ struct fdtd2d_batch {
     // flux_acc_im, of the same layout, those of the imaginary part
     bool bflux = false;
     double *flux_acc_im = nullptr;
+    // fdtd2d_batch_set_hz_flux_lines: the lines above on a batch in the Hz polarisation.  flux_acc holds the sums of Hz
+    // where the Ez lines hold those of Ez, and those of the tangential E where they hold those of the tangential H
+    bool hzflux = false;
     // line sources on the flux lines (fdtd2d_batch_flux_adjoint.h): count x flux_cells x fsrc_nchan weights each
     // (nullptr: no such part); fsrc_nchan = 0 without them
     int fsrc_nchan = 0;
@@ -850,6 +857,8 @@ int run_dispersive(fdtd2d_batch *b, int nsteps, const double *amps, long long am
 // ---- runs in the Hz polarisation (fdtd2d_batch_hz.h): the paths of run_dispersive with the kernels of batch_hz.hip.
 // v.ce carries cb; the first streamed launch of a step is the E half-step, the second the H half-step with the sources
 // and the monitors.
+fdtd::BatchFlux flux_view(const fdtd2d_batch *b);
+
 template <class T>
 int run_hz(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts)
 {
@@ -859,9 +868,14 @@ int run_hz(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride
     const int disp = b->dcj ? 1 : 0, per = b->periodic ? 1 : 0;
     if (!b->ca || !b->cb || !b->ch || (disp && (!b->djh || !b->dq || !b->djy || !b->dqy || !b->da || !b->dck)))
         return bfail(b, FDTD2D_E_STATE, "Hz batch without its arrays");
+    // with the lines of fdtd2d_batch_hz_flux.h: the kernels of batch_hz_flux.hip, which take the lines behind the pole
+    const bool lines = b->hzflux;
+    if (lines && !b->flux_acc) return bfail(b, FDTD2D_E_STATE, "Hz batch with flux lines without its arrays");
     const fdtd::BatchHzKernels &K = fdtd::batch_hz_kernels<T>();
+    const fdtd::BatchHzFluxKernels &KF = fdtd::batch_hz_flux_kernels<T>();
     fdtd::BatchPml<T> p = pml_view<T>(b);
     fdtd::BatchMon m = mon_view(b);
+    fdtd::BatchFlux f = flux_view(b);
     fdtd::BatchPts silent{};
     if (!pts) pts = &silent;
     fdtd::BatchHzDisp<T> d{(T *)b->djh, (T *)b->dq, (T *)b->djy, (T *)b->dqy,
@@ -871,7 +885,7 @@ int run_hz(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride
         const int cells = b->rows * b->cols, threads = resident_threads(cells);
         const int per_thread = (cells + threads - 1) / threads;
         const int mi = per_thread <= 4 ? 0 : per_thread <= 8 ? 1 : -1;
-        const void *kern = mi < 0 ? nullptr : K.resident[per][disp][mi];
+        const void *kern = mi < 0 ? nullptr : lines ? KF.resident[per][disp][mi] : K.resident[per][disp][mi];
         if (!kern)
             return bfail(b, FDTD2D_E_STATE, "%d cells per thread exceed the Hz resident kernel's %d", per_thread,
                          disp ? 4 : 8);
@@ -890,7 +904,8 @@ int run_hz(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride
             fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
             v.ce = (const T *)b->cb;
             void *args[] = {&v, &p, &m, pts, &d, &ca, &n0, &nt, &step_base};
-            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads), args, lds);
+            void *line_args[] = {&v, &p, &m, pts, &d, &f, &ca, &n0, &nt, &step_base};
+            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads), lines ? line_args : args, lds);
             if (rc) return rc;
             b->launches++;
             b->step += nt;
@@ -906,8 +921,11 @@ int run_hz(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride
         int rc;
         void *e_args[] = {&v, &p, &m, pts, &d, &ca, &n, &step};
         void *h_args[] = {&v, &p, &m, pts, &n, &step};
-        if ((rc = launch_ptr(b, K.e[per][disp], grid, dim3(256), e_args, 0))) return rc;
-        if ((rc = launch_ptr(b, K.h[per], grid, dim3(256), h_args, 0))) return rc;
+        void *e_line_args[] = {&v, &p, &m, pts, &d, &f, &ca, &n, &step};
+        void *h_line_args[] = {&v, &p, &m, pts, &f, &n, &step};
+        if ((rc = launch_ptr(b, lines ? KF.e[per][disp] : K.e[per][disp], grid, dim3(256), lines ? e_line_args : e_args, 0)))
+            return rc;
+        if ((rc = launch_ptr(b, lines ? KF.h[per] : K.h[per], grid, dim3(256), lines ? h_line_args : h_args, 0))) return rc;
         b->launches += 2;
         b->step++;
     }
@@ -1543,6 +1561,9 @@ int refuse_flux(fdtd2d_batch *b, const char *what)
     if (b->bflux)
         return bfail(b, FDTD2D_E_STATE, "%s is not available while Bloch flux lines are set: remove them first "
                      "(fdtd2d_batch_set_bloch_flux_lines with nlines = 0)", what);
+    if (b->hzflux)
+        return bfail(b, FDTD2D_E_STATE, "%s is not available while flux lines of the Hz polarisation are set: remove them "
+                     "first (fdtd2d_batch_set_hz_flux_lines with nlines = 0)", what);
     return bfail(b, FDTD2D_E_STATE, "%s is not available while flux lines are set: remove them first "
                  "(fdtd2d_batch_set_flux_lines with nlines = 0)", what);
 }
@@ -3865,7 +3886,7 @@ int fdtd2d_batch_set_flux_lines(fdtd2d_batch_t *b, int nlines, const int *lines,
             cells += n;
         }
         if (!b->have_mat) return bfail(b, FDTD2D_E_STATE, "materials not set: call fdtd2d_batch_set_materials first");
-    } else if (!b->flux_nl) {
+    } else if (!b->flux_nl || b->hzflux) {      // the lines of fdtd2d_batch_hz_flux.h are not this call's to remove
         return 0;
     }
     int rc = use_device(b);
@@ -3923,6 +3944,7 @@ int fdtd2d_batch_read_flux_lines(fdtd2d_batch_t *b, double *ez_re, double *ez_im
     if (!b || !ez_re || !ez_im || !ht_re || !ht_im) return FDTD2D_E_ARG;
     if (!b->flux_nl) return bfail(b, FDTD2D_E_STATE, "no flux lines are set");
     if (b->bflux) return bfail(b, FDTD2D_E_STATE, "the lines are Bloch lines: use fdtd2d_batch_read_bloch_flux_lines");
+    if (b->hzflux) return bfail(b, FDTD2D_E_STATE, "the lines are those of the Hz polarisation: use fdtd2d_batch_read_hz_flux_lines");
     int rc = use_device(b);
     if (rc) return rc;
     BCHK(b, hipStreamSynchronize(b->stream));
@@ -3942,11 +3964,129 @@ int fdtd2d_batch_flux(fdtd2d_batch_t *b, double *out)
     if (!out) return bfail(b, FDTD2D_E_ARG, "out must not be NULL");
     if (!b->flux_nl) return bfail(b, FDTD2D_E_STATE, "no flux lines are set");
     if (b->bflux) return bfail(b, FDTD2D_E_STATE, "the lines are Bloch lines: use fdtd2d_batch_bloch_flux");
+    if (b->hzflux) return bfail(b, FDTD2D_E_STATE, "the lines are those of the Hz polarisation: use fdtd2d_batch_hz_flux");
     int rc = use_device(b);
     if (rc) return rc;
     const size_t n = (size_t)b->count * b->flux_nl * b->flux_nff;
     if ((rc = scratch(b, n * sizeof(double)))) return rc;
     fdtd::batch_flux_launch(flux_view(b), (double *)b->dsg, b->count, b->dt, b->dx, b->stream);
+    BCHK(b, hipGetLastError());
+    b->launches++;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    BCHK(b, hipMemcpy(out, b->dsg, n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- fdtd2d_batch_hz_flux.h ---------------------------------------------------------------------------------------
+// The lines share the host state of fdtd2d_batch_flux.h's (`flux_nl` is set too, so the capacity rule, the info ids, the
+// placement option, fdtd2d_batch_reset and the refusals while lines are set serve them as they are); run_hz takes the
+// kernels of batch_hz_flux.hip while `hzflux` is set.
+
+extern "C" {
+
+int fdtd2d_batch_set_hz_flux_lines(fdtd2d_batch_t *b, int nlines, const int *lines, int nfreq, const double *omega,
+                                   int every)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (nlines < 0 || nlines > FDTD2D_BATCH_MAX_FLUX_LINES)
+        return bfail(b, FDTD2D_E_ARG, "nlines %d outside 0..%d", nlines, FDTD2D_BATCH_MAX_FLUX_LINES);
+    long long cells = 0;
+    if (nlines > 0) {
+        if (!b->hz)
+            return bfail(b, FDTD2D_E_STATE, "fdtd2d_batch_set_hz_flux_lines needs the Hz polarisation "
+                         "(fdtd2d_batch_set_polarization): the lines of the Ez polarisation are fdtd2d_batch_set_flux_lines'");
+        if (!b->ezx && !b->periodic)
+            return bfail(b, FDTD2D_E_STATE, "flux lines need a PML layer (fdtd2d_batch_set_pml) or periodic columns");
+        if (nfreq < 1 || nfreq > FDTD2D_BATCH_MAX_FLUX_FREQS)
+            return bfail(b, FDTD2D_E_ARG, "nfreq %d outside 1..%d", nfreq, FDTD2D_BATCH_MAX_FLUX_FREQS);
+        if (!lines || !omega) return bfail(b, FDTD2D_E_ARG, "lines and omega must not be NULL");
+        if (every < 1) return bfail(b, FDTD2D_E_ARG, "every must be >= 1");
+        const int R = b->rows, C = b->cols;
+        for (int k = 0; k < nlines; ++k) {
+            const int o = lines[4 * k], at = lines[4 * k + 1], first = lines[4 * k + 2], n = lines[4 * k + 3];
+            if (o != 0 && o != 1) return bfail(b, FDTD2D_E_ARG, "line %d: orientation %d (0 row, 1 column)", k, o);
+            if (o == 0 && (at < 1 || at > R - 2))
+                return bfail(b, FDTD2D_E_ARG, "line %d: row %d outside 1..%d", k, at, R - 2);
+            const int lo = b->periodic ? 0 : 1;
+            if (o == 1 && (at < lo || at > C - 2))
+                return bfail(b, FDTD2D_E_ARG, "line %d: column %d outside %d..%d%s", k, at, lo, C - 2,
+                             b->periodic ? " (column C-1 is the image of column 0)" : "");
+            const int extent = o == 1 ? R : b->periodic ? C - 1 : C;
+            if (n < 1 || first < 0 || (long long)first + n > extent)
+                return bfail(b, FDTD2D_E_ARG, "line %d: cells [%d, %d + %d) are empty or run past %d", k, first, first, n,
+                             extent);
+            cells += n;
+        }
+        if (!b->have_mat) return bfail(b, FDTD2D_E_STATE, "materials not set: call fdtd2d_batch_set_materials first");
+    } else if (!b->hzflux) {
+        return 0;
+    }
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));   // a running launch may still use the old lines
+    if (nlines == 0) {
+        for (void **p : {(void **)&b->flux_acc, (void **)&b->flux_omega, (void **)&b->flux_ph}) release(p);
+        b->flux_nl = b->flux_nff = b->flux_cells = 0;
+        b->hzflux = false;
+        return 0;
+    }
+    const size_t acc = (size_t)b->count * 32 * nfreq * (size_t)cells, om = (size_t)b->count * nfreq * sizeof(double);
+    double *nacc = nullptr, *nom = nullptr, *nph = nullptr;
+    if ((rc = alloc(b, (void **)&nacc, acc)) || (rc = alloc(b, (void **)&nom, om)) ||
+        (rc = alloc(b, (void **)&nph, 2 * om))) {
+        for (void **p : {(void **)&nacc, (void **)&nom, (void **)&nph}) release(p);
+        return rc;
+    }
+    hipError_t e = hipMemsetAsync(nacc, 0, acc, b->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    if (e == hipSuccess) e = hipMemcpy(nom, omega, om, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        for (void **p : {(void **)&nacc, (void **)&nom, (void **)&nph}) release(p);
+        return bfail(b, -(1000 + (int)e), "setting up the flux lines failed: %s", hipGetErrorString(e));
+    }
+    for (void **p : {(void **)&b->flux_acc, (void **)&b->flux_omega, (void **)&b->flux_ph}) release(p);
+    b->flux_acc = nacc;
+    b->flux_omega = nom;
+    b->flux_ph = nph;
+    std::copy(lines, lines + 4 * nlines, b->flux_line);
+    b->flux_nl = nlines;
+    b->flux_nff = nfreq;
+    b->flux_cells = (int)cells;
+    b->flux_every = every;
+    b->flux_step0 = b->step;
+    b->hzflux = true;
+    return 0;
+}
+
+int fdtd2d_batch_read_hz_flux_lines(fdtd2d_batch_t *b, double *hz_re, double *hz_im, double *et_re, double *et_im)
+{
+    if (!b || !hz_re || !hz_im || !et_re || !et_im) return FDTD2D_E_ARG;
+    if (!b->hzflux) return bfail(b, FDTD2D_E_STATE, "no flux lines of the Hz polarisation are set");
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    const size_t per = (size_t)b->flux_nff * b->flux_cells;   // one member's Hz re (or any of the four)
+    std::vector<double> acc((size_t)b->count * 4 * per);
+    BCHK(b, hipMemcpy(acc.data(), b->flux_acc, acc.size() * sizeof(double), hipMemcpyDeviceToHost));
+    double *out[4] = {hz_re, hz_im, et_re, et_im};
+    for (int m = 0; m < b->count; ++m)
+        for (int k = 0; k < 4; ++k)
+            std::memcpy(out[k] + m * per, acc.data() + (4 * (size_t)m + k) * per, per * sizeof(double));
+    return 0;
+}
+
+int fdtd2d_batch_hz_flux(fdtd2d_batch_t *b, double *out)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!out) return bfail(b, FDTD2D_E_ARG, "out must not be NULL");
+    if (!b->hzflux) return bfail(b, FDTD2D_E_STATE, "no flux lines of the Hz polarisation are set");
+    int rc = use_device(b);
+    if (rc) return rc;
+    const size_t n = (size_t)b->count * b->flux_nl * b->flux_nff;
+    if ((rc = scratch(b, n * sizeof(double)))) return rc;
+    fdtd::batch_hz_flux_launch(flux_view(b), (double *)b->dsg, b->count, b->dt, b->dx, b->stream);
     BCHK(b, hipGetLastError());
     b->launches++;
     BCHK(b, hipStreamSynchronize(b->stream));
@@ -4094,6 +4234,7 @@ namespace {
 // are set too, their channel count
 int fsrc_refuse(fdtd2d_batch *b, int nchan)
 {
+    if (b->hz) return refuse_hz(b, "line sources on flux lines");
     if (!b->flux_nl || b->bflux)
         return bfail(b, FDTD2D_E_STATE, "line sources live on flux lines: call fdtd2d_batch_set_flux_lines first (a PML or "
                      "periodic batch without a Bloch phase)");

@@ -60,7 +60,8 @@
  * needs a layer or periodic columns (FDTD2D_E_STATE otherwise: a plain box has no Hz kernels).  Refused with
  * FDTD2D_E_STATE in the Hz polarisation: fdtd2d_batch_set_conductivity and _set_conductivity_window (in this polarisation
  * that sigma would be a magnetic loss), fdtd2d_batch_set_dispersion, _set_dispersion_window and
- * _transfer_dispersion, fdtd2d_batch_set_bloch, fdtd2d_batch_set_lattice, the flux lines and their sources, every hold of
+ * _transfer_dispersion, fdtd2d_batch_set_bloch, fdtd2d_batch_set_lattice, the flux lines of fdtd2d_batch_flux.h and
+ * fdtd2d_batch_bloch_flux.h and their sources (this polarisation's own lines are fdtd2d_batch_hz_flux.h's), every hold of
  * a window and every window product.
  * These entry points live in their own header because fdtd2d.h's batch section and the other companions are fixed
  * surfaces. */

@@ -56,6 +56,15 @@ array eps with random binary permittivity, a ricker line source per member):
                               hz_over_ez_dispersive, both paths and LDS sizes.  The Hz kernel does two pole updates per
                               cell in 12 LDS arrays against one in 10.  Default: 1024 members of 56 rows x 57 columns, a
                               10-cell layer, 2000 steps.
+  --hz-flux                   instead: flux lines in the Hz polarisation (BatchEngine.set_hz_flux_lines: two whole-period
+                              row lines, 10 frequencies) on the member of --hz (the metal strip with its pole) against the
+                              same batch without them, and the lines of --flux on a lossless Ez batch of the same shape
+                              against that batch without them, all resident, timed alternately in one process: hz_ms,
+                              hz_flux_ms, hz_flux_over_hz, ez_ms, ez_flux_ms, ez_flux_over_ez, the ratio of the two
+                              ratios, where each batch keeps its sums (LDS or global memory) and the LDS sizes; and
+                              ez_flux_global_ms, the Ez lines with their sums kept in global memory (set_flux_lds(False)),
+                              where the Hz member's live at this shape.
+                              Default: 1024 members of 56 rows x 57 columns, a 10-cell layer, 2000 steps.
   --bloch                     instead: a Bloch batch (set_bloch_phase, a phase sweep over the members, ramp weights)
                               against the plain periodic batch of the same members, layer and conductivity, timed
                               alternately in one process: bloch_ms, periodic_ms, bloch_over_periodic, both paths and
@@ -137,7 +146,7 @@ Usage: python tools/bench_batch.py [--count 1024 --rows 60 --cols 60 --steps 100
                                    [--boundary {mur,pml} --pml-cells 10] [--monitors] [--adjoint] [--lossy]
                                    [--periodic] [--bloch] [--bloch-adjoint] [--dispersive] [--lattice]
                                    [--bloch-dispersive] [--dispersive-adjoint] [--flux] [--bloch-flux]
-                                   [--flux-adjoint] [--bloch-flux-adjoint]
+                                   [--flux-adjoint] [--bloch-flux-adjoint] [--hz-flux]
 """
 import argparse
 import json
@@ -825,6 +834,77 @@ def bench_hz(count, rows, cols, steps, dtype, reps, pml_cells):
             "hz_mcell_steps_per_s": round(count * rows * cols * steps / (med_h * 1e-3) / 1e6, 1)}
 
 
+def bench_hz_flux(count, rows, cols, steps, dtype, reps, pml_cells):
+    """Two whole-period row lines at 10 frequencies on the Hz member of --hz against the same member without them, and
+    the same lines on the lossless Ez member of --flux at this shape against that member without them."""
+    eps, rects, amps = members(count, rows, cols, steps)
+    rects[:, 1], rects[:, 3] = 0, cols - 1            # a line source over the period
+    c00 = courant00(eps, dtype)
+    g = max(6, pml_cells)
+    wp2 = np.zeros((count, rows, cols))
+    wp2[:, rows // 2:rows // 2 + 2, :(cols - 1) // 2] = (2 * np.pi * 70e9) ** 2     # a strip over half the period
+    lines = [("row", rows // 4, 0, cols - 1), ("row", 3 * rows // 4, 0, cols - 1)]
+    om10 = 2 * np.pi * np.linspace(20e9, 65e9, 10)
+    assert g <= rows // 2 and rows // 2 + 2 <= rows - 1 - g
+
+    def batch(kind):
+        hz = kind.startswith("hz")
+        b = fd.BatchEngine(count, rows, cols, DT, DX, dtype=dtype, boundary="periodic")
+        b.set_polarization("hz" if hz else "ez")
+        b.set_materials(eps.astype(dtype), fd.MU0).set_sources(rects)
+        b.set_pml(pml_cells, courant00=c00)
+        if hz:
+            b.set_dispersion(wp2, 1e11, 0.0)
+        if kind == "hz_flux":
+            b.set_hz_flux_lines(lines, om10)
+        if kind in ("ez_flux", "ez_flux_global"):     # the second with its sums in global memory, where the Hz member's
+            b.set_flux_lines(lines, om10)             # live when the pole's twelve arrays leave them no room in LDS
+            b.set_flux_lds(kind == "ez_flux")
+        b.run(steps, amps).sync()                     # warm-up: code objects, clocks
+        return b
+
+    def timed(b):
+        b.reset().sync()
+        t0 = time.perf_counter()
+        b.run(steps, amps).sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    kinds = ("hz", "hz_flux", "ez", "ez_flux", "ez_flux_global")
+    with batch("hz") as hz, batch("hz_flux") as hzf, batch("ez") as ez, batch("ez_flux") as ezf, \
+            batch("ez_flux_global") as ezg:
+        bs = dict(zip(kinds, (hz, hzf, ez, ezf, ezg)))
+        assert all(b.resident for b in bs.values()) and hz.dispersive and hzf.dispersive
+        assert hzf.polarization == "hz" and ezf.polarization == "ez"
+        l0 = hzf.launches
+        hzf.reset().run(steps, amps).sync()
+        launches = hzf.launches - l0
+        t0 = time.perf_counter()
+        P = hzf.flux()
+        flux_call_ms = (time.perf_counter() - t0) * 1e3
+        ms = {k: [] for k in kinds}
+        for _ in range(reps):
+            for k in kinds:
+                ms[k].append(timed(bs[k]))
+        lds = {k: b.lds_bytes for k, b in bs.items()}
+        in_lds = {k: b.flux_lines_in_lds for k, b in bs.items() if "flux" in k}
+        assert not in_lds["ez_flux_global"]
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    out = {"count": count, "rows": rows, "cols": cols, "steps": steps, "dtype": np.dtype(dtype).name,
+           "materials": "arrays", "boundary": "periodic", "pml_cells": pml_cells, "reps": reps, "lines": 2,
+           "line_cells": 2 * (cols - 1), "flux_freqs": 10, "launches_per_run": launches,
+           "flux_call_ms": round(flux_call_ms, 4), "flux_finite": bool(np.all(np.isfinite(P))),
+           "hz_flux_lines_in_lds": in_lds["hz_flux"], "ez_flux_lines_in_lds": in_lds["ez_flux"]}
+    for k in kinds:
+        out.update({f"{k}_ms": round(med[k], 4), f"{k}_ms_min": round(min(ms[k]), 4),
+                    f"{k}_ms_all": [round(v, 4) for v in ms[k]], f"{k}_lds_bytes_per_member": lds[k]})
+    r_hz, r_ez = med["hz_flux"] / med["hz"], med["ez_flux"] / med["ez"]
+    out.update({"hz_flux_over_hz": round(r_hz, 3), "ez_flux_over_ez": round(r_ez, 3),
+                "ez_flux_global_over_ez": round(med["ez_flux_global"] / med["ez"], 3),
+                "hz_ratio_over_ez_ratio": round(r_hz / r_ez, 3),
+                "hz_flux_mcell_steps_per_s": round(count * rows * cols * steps / (med["hz_flux"] * 1e-3) / 1e6, 1)})
+    return out
+
+
 def bench_bloch(count, rows, cols, steps, dtype, reps, pml_cells):
     eps, rects, amps = members(count, rows, cols, steps)
     c00 = courant00(eps, dtype)
@@ -1315,9 +1395,15 @@ def main():
                     help="time the adjoint of a flux objective on a Bloch batch (line sources, conjugated run, session)")
     ap.add_argument("--flux-adjoint", action="store_true",
                     help="time the adjoint run with line sources and a FluxAdjointSession iteration")
+    ap.add_argument("--hz-flux", action="store_true",
+                    help="time flux lines in the Hz polarisation against the same batch without them, beside the Ez lines")
     ap.add_argument("--hz", action="store_true",
                     help="time the Hz polarisation with a pole against the Ez dispersive kernels on periodic members")
     a = ap.parse_args()
+    if a.hz_flux:
+        print(json.dumps(bench_hz_flux(a.count or 1024, a.rows or 56, a.cols or 57, a.steps or 2000, np.dtype(a.dtype),
+                                       a.reps, a.pml_cells)), flush=True)
+        return
     if a.hz:
         print(json.dumps(bench_hz(a.count or 1024, a.rows or 56, a.cols or 57, a.steps or 2000, np.dtype(a.dtype),
                                   a.reps, a.pml_cells)), flush=True)
