@@ -360,16 +360,32 @@ template <class T> int launch_pass(fdtd2d *h, int nt, int band_lo, int band_hi, 
         if (sd > 1) h->shape_now.waves = 4;
         const int OW = pass_strip_ow(nt, V, 4, sd);
         p.nstrips = (h->cols + OW - 1) / OW;
+        // Waves per strip of a window with none given (no option, no given shape): split_waves_for's size thresholds on
+        // the cells the launch COVERS -- its rows times the columns its strips write -- not on rows x grid columns.  On
+        // 16384 columns a window of 768 rows launches 4 to 8 of the 74 strips and is a small launch by every measure the
+        // thresholds came from (dense 16-step passes 38 us on 8 waves against 56 on 4 at 2048^2), yet counted as 12 Mi
+        // cells.  Decided once, here, and handed on in shape_now.waves, so the band-height rule below, nw_now, the zone
+        // workgroups and the launch in launch_pass_impl all see one answer.  Launched cells never exceed rows x grid
+        // columns: a window the old quantity put on 8 waves stays there.
+        if (windowed && !h->split_waves && !h->shape_now.waves && nt <= 16 && h->use_level_split(nt, band_lo, band_hi)) {
+            const long long ncols = std::min<long long>(h->cols, (long long)(win->n_inner + (win->edges ? 2 : 0)) * OW);
+            const size_t cells = (size_t)std::max(0, band_hi - band_lo) * (size_t)ncols;
+            h->shape_now.waves = cells < (nt == 16 ? (size_t)12 << 20 : (size_t)3 << 20) ? 8 : 4;
+        }
     }
     if (br <= 0 && windowed) {
         // A window is a small launch: one round of workgroups where the strips allow it (a band lives its rows plus
         // ~3 nt ticks of fill and drain, so one tall band per strip would set the launch time), bands of at least 32
         // rows (shorter ones are mostly fill), at most the tallest the tuner ever tries.  DERIVED, NOT TUNED: the slot
         // count (256 CUs x 16 wave slots / waves per workgroup, 90 % of it), the 32 and the 448 are reasoned from the
-        // dense launch's figures, and split_waves_for below sees the WINDOW's row count, so windows of fewer than
-        // 12 Mi (8-step passes: 3 Mi) cells run 8 waves per strip.  No shape sweep of windowed launches exists; what
-        // is measured is whole runs against the dense ones at 3072^2, 4096^2, 8192^2 and 16384^2, where the window
-        // covers 1 to 27 % of the grid (profiles/active_window.txt).
+        // dense launch's figures.  The waves come from the rule above (shape_now.waves, through split_waves_for):
+        // launches that cover fewer than 12 Mi (8-step passes: 3 Mi) cells run 8 waves per strip.  That threshold is
+        // the dense sweep's, checked on windows: the benchmark's run forced to 4 and to 8 waves, dispatch by dispatch,
+        // crosses over at 9-10 M launched cells (8 waves take 0.70-0.75 of the time of 4 at 0.6-2.6 M cells, 0.8-0.9
+        // at 4-6 M, the same at 9-10 M, 1.02-1.09 from there to 16 M): within a factor of 1.5 of 12 Mi, so 12 Mi
+        // stays (profiles/active_window_waves.txt).  No sweep of band heights of windowed launches exists; what is measured
+        // is whole runs against the dense ones at 3072^2, 4096^2, 8192^2 and 16384^2, where the window covers 1 to
+        // 27 % of the grid (profiles/active_window.txt).
         const int region = std::max(0, band_hi - band_lo);
         const bool split4 = h->use_level_split(nt, band_lo, band_hi);
         const int nw = split4 ? std::max(1, h->split_waves_for(nt, band_lo, band_hi)) : 1;
