@@ -26,6 +26,7 @@ FIELD_EZ, FIELD_HX, FIELD_HY = 0, 1, 2
 
 OPT_MAX_PASS_STEPS, OPT_BAND_ROWS, OPT_ZONE_SPLIT, OPT_LEVEL_SPLIT, OPT_SPLIT_WAVES, OPT_AUTOTUNE, OPT_XCD_MAP, OPT_SIDE_WAVES = 0, 1, 2, 3, 4, 5, 7, 8
 OPT_ACTIVE_WINDOW = 9
+OPT_WINDOW_OCTAGON = 10
 
 E_ARG, E_NODEVICE, E_NOMEM, E_STATE, E_COURANT = -1, -2, -3, -4, -5
 
@@ -39,6 +40,9 @@ E_ARG, E_NODEVICE, E_NOMEM, E_STATE, E_COURANT = -1, -2, -3, -4, -5
 # what the last windowed pass launched (read-only; fdtd2d.h)
 (INFO_WIN_BAND_ROWS, INFO_WIN_WAVES, INFO_WIN_STRIP_FIRST, INFO_WIN_INNER, INFO_WIN_N_SRC, INFO_WIN_EDGES, INFO_WIN_ZTOP,
  INFO_WIN_ZBOT, INFO_WIN_XCD_MAP, INFO_WIN_XCD_PAD, INFO_WIN_EDGE_ROWS) = range(31, 42)
+# its diagonal bounds (closed ranges of i + j and of i - j) and the bulk tasks skipped for them
+(OCT_INFO_SUM_LO, OCT_INFO_SUM_HI, OCT_INFO_DIFF_LO, OCT_INFO_DIFF_HI, OCT_INFO_SKIPPED) = range(42, 47)
+OCT_UNBOUNDED = 1 << 29
 
 (BATCH_INFO_COUNT, BATCH_INFO_ROWS, BATCH_INFO_COLS, BATCH_INFO_DTYPE, BATCH_INFO_STEP, BATCH_INFO_RESIDENT,
  BATCH_INFO_LAUNCHES, BATCH_INFO_RESIDENT_MAX_CELLS, BATCH_INFO_LDS_BYTES, BATCH_INFO_PITCH) = range(10)

@@ -71,43 +71,152 @@ inline Rect grow(const Rect &w, int n, int R, int C)
     return Rect{lo(w.r0, n), hi(w.r1, n, R), lo(w.c0, n), hi(w.c1, n, C)};
 }
 
+// Diagonal bounds beside a rectangle: every cell (i, j) of the set has  s0 <= i + j <= s1  and  d0 <= i - j <= d1
+// (closed).  Rectangle and bounds together are an octagon.
+//
+// Why they hold.  Away from the frame, ONE leapfrog step moves the joint support of (Ez, Hx, Hy) by at most one cell
+// in L1 distance, not merely one cell per axis:
+//   Hx'[i,j] <- Hx[i,j], Ez[i+1,j], Ez[i,j]          Hy'[i,j] <- Hy[i,j], Ez[i,j+1], Ez[i,j]
+//   Ez'[i,j] <- Ez[i,j], Hy'[i,j], Hy'[i,j-1], Hx'[i,j], Hx'[i-1,j]
+//            <- Ez, Hx, Hy at (i,j), Ez[i,j+1], Ez[i+1,j], Hy[i,j-1], Ez[i,j-1], Hx[i-1,j], Ez[i-1,j]
+// every cell read differs from (i, j) in ONE index by one.  (The new H rows read by Ez' never reach a diagonal
+// neighbour: Hy'[i,j-1] reads Ez[i,j], not Ez[i,j-2] or Ez[i+1,j-1].)  So i + j and i - j each move by at most one per
+// step, and by at most one per half-step of the single-step kernels.  The support of a source rectangle after n steps
+// is the rectangle grown by n with its corners cut at 45 degrees: about half of a point source's window holds zeros.
+//
+// Where they hold.  The argument is the interior stencil's.  The frame rules of mur_rules.hpp read up to 3 cells
+// inward, diagonally too (stage D), so the bounds are kept only while no frame rule can have had a non-zero input:
+// while the rectangle they stand beside has no side within MARGIN of a grid edge (a snapped side lies at distance 0).
+// By the derivation above a frame cell turns non-zero only in a step whose grown rectangle snaps, and then the bounds
+// of that same grown rectangle are already dropped.  Dropped means unbounded, and `support` never gets them back
+// before reset(): its sides only ever move outward.
+//
+// Transitions, beside the rectangles' table above:
+//   reset                 empty                            invalidate, uncommitted     unbounded
+//   add_source, unite     hull: min / max of each bound    commit_pass(src, n)         hull with the source, then -+ n
+//   half_step             -+ 1                             copied_to_other             dirty_other: unbounded
+//   dirty_other           takes the old support's bounds on commit_pass, their hull with its own on half_step
+struct Oct {
+    static constexpr int BIG = 1 << 29;
+    int s0 = BIG, s1 = -BIG, d0 = BIG, d1 = -BIG;        // default: empty
+    static Oct unbounded() { return Oct{-BIG, BIG, -BIG, BIG}; }
+    static Oct of(const Rect &r)
+    {
+        if (r.empty()) return Oct{};
+        return Oct{r.r0 + r.c0, r.r1 - 1 + r.c1 - 1, r.r0 - (r.c1 - 1), r.r1 - 1 - r.c0};
+    }
+    bool empty() const { return s0 > s1 || d0 > d1; }
+    bool bounded() const { return s0 > -BIG || s1 < BIG || d0 > -BIG || d1 < BIG; }
+    bool contains(int i, int j) const { return i + j >= s0 && i + j <= s1 && i - j >= d0 && i - j <= d1; }
+    // does the rectangle of cells [ra, rb) x [ca, cb) (non-empty) meet the four half-planes?  The test of strip_of_block.
+    bool meets(int ra, int rb, int ca, int cb) const
+    {
+        return rb - 1 + cb - 1 >= s0 && ra + ca <= s1 && rb - 1 - ca >= d0 && ra - (cb - 1) <= d1;
+    }
+};
+
+inline Oct hull(const Oct &a, const Oct &b)
+{
+    return Oct{std::min(a.s0, b.s0), std::max(a.s1, b.s1), std::min(a.d0, b.d0), std::max(a.d1, b.d1)};
+}
+
+inline Oct grow(const Oct &o, int n)
+{
+    if (o.empty()) return o;
+    auto lo = [&](int v) { return v <= -Oct::BIG ? -Oct::BIG : std::max(v - n, -Oct::BIG); };
+    auto hi = [&](int v) { return v >= Oct::BIG ? Oct::BIG : std::min(v + n, Oct::BIG); };
+    return Oct{lo(o.s0), hi(o.s1), lo(o.d0), hi(o.d1)};
+}
+
 struct ActiveWindow {
     int R = 0, C = 0;
     bool tracking = false;       // false: both rectangles stay full (slabs, PML engines)
     Rect support, dirty_other;
+    Oct support_oct = Oct::unbounded(), dirty_oct = Oct::unbounded();      // diagonal bounds of the two rectangles
+    bool oct_lost = true;        // a side of `support` has come within MARGIN of an edge since reset(): unbounded from then on
 
     Rect full() const { return Rect{0, R, 0, C}; }
+    // a rectangle beside which diagonal bounds may stand
+    bool clear_of_frame(const Rect &r) const
+    {
+        return r.empty() || (r.r0 >= MARGIN && r.r1 <= R - MARGIN && r.c0 >= MARGIN && r.c1 <= C - MARGIN);
+    }
+    void check_oct()
+    {
+        if (!clear_of_frame(support)) oct_lost = true;
+        if (oct_lost) support_oct = Oct::unbounded();
+        if (!clear_of_frame(dirty_other)) dirty_oct = Oct::unbounded();
+    }
     void init(int rows, int cols, bool track)
     {
         R = rows;
         C = cols;
         tracking = track;
         support = dirty_other = full();
+        support_oct = dirty_oct = Oct::unbounded();
+        oct_lost = true;
     }
     void reset()
     {
-        if (tracking) support = dirty_other = Rect{};
+        if (!tracking) return;
+        support = dirty_other = Rect{};
+        support_oct = dirty_oct = Oct{};
+        oct_lost = false;
     }
-    void invalidate() { support = dirty_other = full(); }
-    void uncommitted() { dirty_other = full(); }
-    void copied_to_other() { dirty_other = unite(dirty_other, support); }
-    void add_source(const Rect &src) { support = unite(support, clip(src)); }
+    void invalidate()
+    {
+        support = dirty_other = full();
+        support_oct = dirty_oct = Oct::unbounded();
+        oct_lost = true;
+    }
+    void uncommitted()
+    {
+        dirty_other = full();
+        dirty_oct = Oct::unbounded();
+    }
+    void copied_to_other()
+    {
+        dirty_other = unite(dirty_other, support);
+        dirty_oct = Oct::unbounded();     // (a measuring tool's copy: the next pass writes its whole rectangle)
+    }
+    void add_source(const Rect &src)
+    {
+        support = unite(support, clip(src));
+        support_oct = hull(support_oct, Oct::of(clip(src)));
+        check_oct();
+    }
     void half_step()
     {
         const Rect old = support;
+        const Oct old_oct = support_oct;
         support = grow(old, 1, R, C);
+        support_oct = grow(old_oct, 1);
         dirty_other = unite(dirty_other, old);
+        dirty_oct = hull(dirty_oct, old_oct);
+        check_oct();
     }
     void commit_pass(const Rect &src, int nsteps)
     {
         const Rect old = support;
+        const Oct old_oct = support_oct;
         support = grow(unite(old, clip(src)), nsteps, R, C);
+        support_oct = grow(hull(old_oct, Oct::of(clip(src))), nsteps);
         dirty_other = old;
+        dirty_oct = old_oct;
+        check_oct();
     }
     // what a committed pass of nsteps steps has to write
     Rect window(const Rect &src, int nsteps) const
     {
         return unite(grow(unite(support, clip(src)), nsteps, R, C), dirty_other);
+    }
+    // ... and the diagonal bounds of that: the hull of the grown support's and dirty_other's.  Cells of window() outside
+    // them are zero in the new state and zero in the target already.
+    Oct window_oct(const Rect &src, int nsteps) const
+    {
+        const Rect grown = grow(unite(support, clip(src)), nsteps, R, C);
+        if (oct_lost || !clear_of_frame(grown) || !clear_of_frame(dirty_other)) return Oct::unbounded();
+        return hull(grow(hull(support_oct, Oct::of(clip(src))), nsteps), dirty_oct);
     }
     Rect clip(const Rect &s) const
     {
@@ -132,6 +241,7 @@ struct Launch {
     bool ztop = false, zbot = false; // zone tiles (all columns) of that side
     int strip_first = 1, n_inner = 0;
     bool edges = false;              // both edge strips
+    Oct oct = Oct::unbounded();      // diagonal bounds of the window (the caller's, from window_oct): tasks outside do nothing
 };
 
 // w: the window (non-empty); src: the source rectangle, whose columns the launched strips must hold (empty: no source);

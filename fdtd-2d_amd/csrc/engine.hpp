@@ -232,6 +232,9 @@ struct fdtd2d {
         int band_rows = 0, waves = 0, strip_first = 0, inner = 0, n_src = 0, edges = 0, ztop = 0, zbot = 0, xcd_map = 0,
             xcd_pad = 0, edge_rows = 0;
     } win_last;
+    int window_octagon = 1;      // FDTD2D_OPT_WINDOW_OCTAGON: windowed passes also carry the window's diagonal bounds
+    fdtd_aw::Oct win_oct = fdtd_aw::Oct::unbounded();    // FDTD2D_INFO_WIN_OCT_*: those of the last windowed pass,
+    long long win_oct_skipped = 0;                       // and the bulk tasks it skipped for them
     // (FDTD2D_INFO_WINDOW_ENABLED.)  The automatic mode is off for a handle whose launches the caller pins with
     // fdtd2d_set_shape -- such a caller measures or replays the whole-grid launch of that shape -- and for one whose
     // device pointers are out.

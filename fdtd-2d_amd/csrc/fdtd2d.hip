@@ -727,6 +727,11 @@ long long fdtd2d_info(const fdtd2d_t *h, int what)
     case FDTD2D_INFO_WIN_XCD_MAP: return h->win_last.xcd_map;
     case FDTD2D_INFO_WIN_XCD_PAD: return h->win_last.xcd_pad;
     case FDTD2D_INFO_WIN_EDGE_ROWS: return h->win_last.edge_rows;
+    case FDTD2D_OCT_INFO_SUM_LO: return h->win_oct.s0;
+    case FDTD2D_OCT_INFO_SUM_HI: return h->win_oct.s1;
+    case FDTD2D_OCT_INFO_DIFF_LO: return h->win_oct.d0;
+    case FDTD2D_OCT_INFO_DIFF_HI: return h->win_oct.d1;
+    case FDTD2D_OCT_INFO_SKIPPED: return h->win_oct_skipped;
     default: return FDTD2D_E_ARG;
     }
 }
@@ -1386,6 +1391,8 @@ static int run_impl(fdtd2d_t *h, int nsteps, int src_row, int src_col, const dou
                     const int hc = fdtd::stream_hc(nt), ow = 64 * (h->dtype == FDTD2D_F32 ? 4 : 2) - 2 * hc;
                     L.band_lo = L.band_hi = lo;                  // (empty window: nothing to launch)
                     if (!W.empty()) L = fdtd_aw::restrict_launch(W, src, h->rows, h->cols, nt, lo, hi, ow, hc, (h->cols + ow - 1) / ow);
+                    // (the zone tiles are never skipped: a window that reaches them has snapped and lost its bounds)
+                    if (!W.empty() && h->window_octagon) L.oct = h->aw.window_oct(src, nlev);
                     b_lo = L.band_lo, b_hi = L.band_hi, zt = L.ztop, zb = L.zbot;
                     windowed = true;
                 }
@@ -1581,6 +1588,10 @@ int fdtd2d_set_option(fdtd2d_t *h, int option, long long value)
         if (value < -1 || value > 1) return fail(h, FDTD2D_E_ARG, "active window must be -1, 0 or 1");
         h->active_window = (int)value;
         if (value == 1) h->aw_ptr_out = false;     // the caller vouches for what it writes through device pointers
+        return 0;
+    case FDTD2D_OPT_WINDOW_OCTAGON:
+        if (value != 0 && value != 1) return fail(h, FDTD2D_E_ARG, "window octagon must be 0 or 1");
+        h->window_octagon = (int)value;
         return 0;
     default: return fail(h, FDTD2D_E_ARG, "unknown option %d", option);
     }

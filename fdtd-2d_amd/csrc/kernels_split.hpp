@@ -287,14 +287,32 @@ __device__ __forceinline__ void split_body(const PassParams<T> &p, const int str
         r.y = ldn<V>(reinterpret_cast<const T *>(row_ptr(p.hy_in, ic) + lo));
         if (CE_ARR) r.ce = ldn<V>(reinterpret_cast<const T *>(row_ptr(p.ce, ic) + lo));
         if (CH_ARR) r.ch = ldn<V>(reinterpret_cast<const T *>(row_ptr(p.ch, ic) + lo));
+    };
+    // GENERAL: lanes outside the grid must hold zeros and the coefficient rows their update masks -- applied when the
+    // row becomes the wave's INPUT row (mask_input, PF ticks after its load), not at the load.  Written at the load,
+    // the selects turn into control flow around it: the loads go out under an exec mask through per-lane 64-bit
+    // addresses, the compiler waits for them in the tick that issues them, and the loading wave -- the one the others
+    // wait for -- pays the whole memory round trip every tick (profiles/active_window_octagon.txt).  Every lane's
+    // address is valid (col is 0 where !ld_ok), so the loads need no mask.  The empty asm ties the selects to this
+    // place (not volatile, like lane_off_now); nothing reads a slot between its load and this, DPP reads included.
+    auto mask_input = [&](Row &r) {
         if (GENERAL) {
 #pragma unroll
             for (int v = 0; v < V; ++v) {
+                asm("" : "+v"(r.e.v[v]));
+                asm("" : "+v"(r.x.v[v]));
+                asm("" : "+v"(r.y.v[v]));
                 r.e.v[v] = m.ld_ok ? r.e.v[v] : T(0);
                 r.x.v[v] = m.ld_ok ? r.x.v[v] : T(0);
                 r.y.v[v] = m.ld_ok ? r.y.v[v] : T(0);
-                if (CE_ARR) r.ce.v[v] = (m.ld_ok && m.m_e[v]) ? r.ce.v[v] : T(0);
-                if (CH_ARR) r.ch.v[v] = (m.ld_ok && m.m_h[v]) ? r.ch.v[v] : T(0);
+                if (CE_ARR) {
+                    asm("" : "+v"(r.ce.v[v]));
+                    r.ce.v[v] = (m.ld_ok && m.m_e[v]) ? r.ce.v[v] : T(0);
+                }
+                if (CH_ARR) {
+                    asm("" : "+v"(r.ch.v[v]));
+                    r.ch.v[v] = (m.ld_ok && m.m_h[v]) ? r.ch.v[v] : T(0);
+                }
             }
         }
     };
@@ -315,6 +333,7 @@ __device__ __forceinline__ void split_body(const PassParams<T> &p, const int str
             const int r = tau - shift;              // input row of this wave, level t0; lives in slot k
             if (ROLE == 0) {
                 load_global(slot[(k + PF) % S], r + PF);
+                mask_input(slot[k]);
             } else {                                // row r: written by wave w-1 in the previous tick
                 const int dr = (tau + 1) & 1;
                 Row &in = slot[k];
@@ -408,7 +427,7 @@ __global__ __launch_bounds__(64 * SPLIT_NW * SD) void k_bulk_split(const PassPar
         if (!p.zone_last) b -= nzone;
     }
     int strip, ra, rb;
-    if (!strip_of_block(p, b, &strip, &ra, &rb)) return;
+    if (!strip_of_block(p, b, &strip, &ra, &rb, strip_width(LV, V, SD) - 2 * stream_hc(NT))) return;
     const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int w = SD == 1 ? wid : wid % SPLIT_NW, side = SD == 1 ? 0 : wid / SPLIT_NW;
     // the columns of THIS wave's window decide which body it runs: only the waves at the grid's edges and on the

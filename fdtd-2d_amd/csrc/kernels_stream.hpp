@@ -43,6 +43,8 @@ constexpr int STREAM_MAX_NT = 20;   // longest pass: 8 levels in one wave; 16 (4
 // edge) and a multiple of 4 so that every lane's 16-byte access stays aligned
 constexpr int stream_hc(int nt) { return nt <= 4 ? 4 : (nt <= 8 ? 8 : (nt <= 16 ? 16 : 20)); }
 
+constexpr int LIVE_RUNS = 64;       // runs of live tasks a compacted launch can describe (one per strip it launches)
+
 template <class T> struct PassParams {
     const T *ez_in, *hx_in, *hy_in;
     T *ez_out, *hx_out, *hy_out;
@@ -77,6 +79,15 @@ template <class T> struct PassParams {
     int src_row1, src_col1;    // [src_row, src_row1) x [src_col, src_col1) (all four very negative: none)
     int nlev;                  // time levels this launch really advances (<= NT; the level-split
                                // kernel, the zone tiles and the probe tile skip the rest)
+    int oct_s0, oct_s1;        // diagonal bounds of what this launch has to write (active_window.hpp, Oct): cells with
+    int oct_d0, oct_d1;        // i + j outside [oct_s0, oct_s1] or i - j outside [oct_d0, oct_d1] are zero before and after
+                               // the pass; a bulk task whose written cells all lie there does nothing (strip_of_block).
+                               // Unbounded (-+ 2^29) for every launch that is not a window launched on the rule.
+    // Compacted bulk (launch_pass_impl): only the tasks that meet the bounds are in the grid.  They are live_n runs of
+    // consecutive task indices (the bounds cut every strip in one row interval): run i starts at task live_b0[i], and
+    // live_end[i] tasks lie in the runs 0 .. i.  live_n = 0: every task is launched (and tested on the device).
+    int live_n;
+    unsigned short live_b0[LIVE_RUNS], live_end[LIVE_RUNS];
     double amp[STREAM_MAX_NT]; // amplitude added after step s = 1..NT of this pass
 #ifdef FDTD2D_TRACE              // profiling build only (tools/Makefile.trace): per-workgroup time stamps
     unsigned long long *trace;
@@ -181,9 +192,31 @@ __device__ __forceinline__ int strip_x0(const PassParams<T> &p, int strip)
 
 // Launch order of the (band, strip) tasks: first the edge strips (0 and last: their GENERAL body
 // is the slower one), then strips 1, 2, ...; all bands of one strip are consecutive.
+// ow: the columns a strip writes.  A task whose written cells  [ra, rb) x [strip ow, min((strip + 1) ow, C))  lie
+// entirely outside one of the launch's four diagonal half-planes is no task: it would write zeros over zeros.
 template <class T>
-__device__ __forceinline__ bool strip_of_block(const PassParams<T> &p, int b, int *strip, int *ra, int *rb)
+__host__ __device__ __forceinline__ bool strip_of_block_rect(const PassParams<T> &p, int b, int *strip, int *ra, int *rb);
+template <class T>
+__host__ __device__ __forceinline__ bool task_meets_oct(const PassParams<T> &p, int strip, int ra, int rb, int ow)
 {
+    const int ca = strip * ow, cb = (strip + 1) * ow < p.g.C ? (strip + 1) * ow : p.g.C;
+    return rb - 1 + cb - 1 >= p.oct_s0 && ra + ca <= p.oct_s1 && rb - 1 - ca >= p.oct_d0 && ra - (cb - 1) <= p.oct_d1;
+}
+template <class T>
+__host__ __device__ __forceinline__ bool strip_of_block(const PassParams<T> &p, int b, int *strip, int *ra, int *rb, int ow)
+{
+    if (p.live_n > 0) {         // a compacted launch: block b is the b-th live task (wave-uniform scalar scan)
+        int i = 0, before = 0;
+        while (i < p.live_n && b >= (int)p.live_end[i]) before = (int)p.live_end[i++];
+        if (i >= p.live_n) return false;
+        b = (int)p.live_b0[i] + (b - before);
+    }
+    return strip_of_block_rect(p, b, strip, ra, rb) && task_meets_oct(p, *strip, *ra, *rb, ow);
+}
+template <class T>
+__host__ __device__ __forceinline__ bool strip_of_block_rect(const PassParams<T> &p, int b, int *strip, int *ra, int *rb)
+{
+    auto min = [](int x, int y) { return x < y ? x : y; };
     if (b < 2 * p.nbands_e) {
         const int sidx = b / p.nbands_e, band = b - sidx * p.nbands_e;
         if (sidx == 1 && p.nstrips == 1) return false;    // the second edge slot stays empty
@@ -594,7 +627,7 @@ void k_bulk(const PassParams<T> p)
         b -= nzone;
     }
     int strip, ra, rb;
-    if (!strip_of_block(p, b, &strip, &ra, &rb)) return;
+    if (!strip_of_block(p, b, &strip, &ra, &rb, 64 * V - 2 * stream_hc(NT))) return;
     const int x0 = strip_x0<T, NT, V>(p, strip);
     // wave-uniform choice: all SW columns plain interior (5 <= j <= C-6) and the source cell
     // outside the rows/columns this wave ever touches -> mask-free body

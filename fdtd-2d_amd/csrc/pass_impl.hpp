@@ -108,6 +108,40 @@ int launch_pass_impl(fdtd2d *h, fdtd::PassParams<T> &p, const fdtd_aw::Launch *w
     if (win)        // the path a test can assert (FDTD2D_INFO_WIN_*): as decoded by strip_of_block and the zone tiles
         h->win_last = fdtd2d::WinLast{p.band_rows, nw_now, p.strip_first, win->n_inner, p.n_src, win->edges ? 1 : 0,
                                       p.zone_top ? 1 : 0, p.zone_bot ? 1 : 0, p.xcd_map, p.main_pad, p.band_rows_e};
+    if (win) {      // ... and its diagonal bounds, with the tasks they empty: the kernel's own decoding, run over the launch
+        h->win_oct = win->oct;
+        h->win_oct_skipped = 0;
+        if (win->oct.bounded()) {
+            const int ow = 64 * V - 2 * fdtd::stream_hc(NT);      // (a window launches the narrowest strips: one wave wide)
+            // Skipped workgroups end at once, but the dispatcher has dealt them CUs like the others: in launches of more
+            // than 256 tasks the LIVE ones still came two to a CU (49 of 185 CUs after 800 steps of the benchmark) and ran
+            // 1.3x slower per tick.  So the launch is compacted: the live tasks as runs of consecutive indices (one run per
+            // strip: the bounds cut a strip in one row interval), only they in the grid.  The XCD map interleaves the strips
+            // band by band -- no runs, no compaction; nor with more runs than the table holds.  Every FDTD2D_INFO_WIN_*
+            // value is as before.
+            int runs = 0;
+            long long live = 0;
+            bool in_run = false, fits = p.xcd_map == 0 && bulk <= 65535;
+            for (long long b = 0; b < bulk; ++b) {
+                int strip, ra, rb;
+                const bool task = fdtd::strip_of_block_rect(p, (int)b, &strip, &ra, &rb);
+                const bool meets = task && fdtd::task_meets_oct(p, strip, ra, rb, ow);
+                if (task && !meets) h->win_oct_skipped++;
+                if (meets && fits) {
+                    if (!in_run && runs == fdtd::LIVE_RUNS) fits = false;
+                    else {
+                        if (!in_run) p.live_b0[runs++] = (unsigned short)b;
+                        p.live_end[runs - 1] = (unsigned short)++live;
+                    }
+                }
+                in_run = meets;
+            }
+            if (fits && live > 0 && live < bulk) {
+                p.live_n = runs;
+                bulk = live;
+            }
+        }
+    }
     if (bulk + zones == 0) return 0;
     if constexpr (NT >= 8) {
         if (h->use_level_split(NT, p.band_lo, p.band_hi)) {     // 4 waves per (band, strip), 2 levels each
@@ -453,6 +487,12 @@ template <class T> int launch_pass(fdtd2d *h, int nt, int band_lo, int band_hi, 
     p.src_lo = p.src_hi = band_hi;
     p.nsrc_top = p.nsrc_mid = 0;
     p.nlev = nlev > 0 ? std::min(nlev, nt) : nt;
+    {   // diagonal bounds: a window's own; unbounded for everything else (whole-grid passes, trials, PML, slab pieces)
+        const fdtd_aw::Oct oct = windowed ? win->oct : fdtd_aw::Oct::unbounded();
+        p.oct_s0 = oct.s0, p.oct_s1 = oct.s1, p.oct_d0 = oct.d0, p.oct_d1 = oct.d1;
+        p.live_n = 0;
+        for (int i = 0; i < fdtd::LIVE_RUNS; ++i) p.live_b0[i] = p.live_end[i] = 0;
+    }
     if (p.nlev != nt && !h->use_level_split(nt, band_lo, band_hi) && !h->pml_split(nt))
         return fail(h, FDTD2D_E_ARG, "short passes run on the level-split kernels only");
     for (int s = 0; s < fdtd::STREAM_MAX_NT; ++s) p.amp[s] = (amps && s < p.nlev) ? amps[s] : 0.0;

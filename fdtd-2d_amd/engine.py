@@ -317,7 +317,8 @@ class Engine:
         return self
 
     def set_option(self, max_pass_steps=None, band_rows=None, zone_split=None, level_split=None,
-                   split_waves=None, autotune=None, xcd_map=None, side_waves=None, active_window=None):
+                   split_waves=None, autotune=None, xcd_map=None, side_waves=None, active_window=None,
+                   window_octagon=None):
         """Speed knobs of run(): longest temporally blocked pass (0 = single-step kernels
         only) and rows per streaming band.  Results do not depend on them."""
         if max_pass_steps is not None:
@@ -338,6 +339,8 @@ class Engine:
             self._ck(self._lib.fdtd2d_set_option(self._h, _abi.OPT_XCD_MAP, int(xcd_map)))
         if active_window is not None:      # -1 automatic (>= 4 Mi cells), 0 off, 1 on at any size
             self._ck(self._lib.fdtd2d_set_option(self._h, _abi.OPT_ACTIVE_WINDOW, int(active_window)))
+        if window_octagon is not None:     # 1 (default): windows skip the tasks outside their diagonal bounds; 0: rectangle only
+            self._ck(self._lib.fdtd2d_set_option(self._h, _abi.OPT_WINDOW_OCTAGON, int(window_octagon)))
         return self
 
     def set_shape(self, shape, pass_steps=0):
@@ -516,6 +519,14 @@ class Engine:
         keys = ("band_rows", "waves", "strip_first", "inner", "n_src", "edges", "ztop", "zbot", "xcd_map", "xcd_pad",
                 "edge_rows")
         return {k: self.info(_abi.INFO_WIN_BAND_ROWS + n) for n, k in enumerate(keys)}
+
+    @property
+    def last_window_octagon(self) -> dict:
+        """Diagonal bounds of what the last windowed pass had to write -- sum_lo <= i + j <= sum_hi and diff_lo <= i - j
+        <= diff_hi, -2**29 / 2**29 where unbounded -- and the (band, strip) tasks of its bulk that lay outside them and
+        did nothing (`skipped`)."""
+        keys = ("sum_lo", "sum_hi", "diff_lo", "diff_hi", "skipped")
+        return {k: self.info(_abi.OCT_INFO_SUM_LO + n) for n, k in enumerate(keys)}
 
     @property
     def window_enabled(self) -> bool:

@@ -111,6 +111,14 @@ typedef struct fdtd2d fdtd2d_t;
 #define FDTD2D_INFO_WIN_XCD_MAP     39 /* 1 if its inner tasks were dealt out XCD by XCD */
 #define FDTD2D_INFO_WIN_XCD_PAD     40 /* empty workgroups in front of them then (0..7) */
 #define FDTD2D_INFO_WIN_EDGE_ROWS   41 /* band height of its first / last strip */
+/* 42-46: the diagonal bounds of what that pass had to write (FDTD2D_OPT_WINDOW_OCTAGON): every cell (i, j) it could
+   change has 42 <= i + j <= 43 and 44 <= i - j <= 45; -2^29 / 2^29 where a side is unbounded.  46: the (band, strip)
+   tasks of its bulk that lay outside those bounds and did nothing. */
+#define FDTD2D_OCT_INFO_SUM_LO  42
+#define FDTD2D_OCT_INFO_SUM_HI  43
+#define FDTD2D_OCT_INFO_DIFF_LO 44
+#define FDTD2D_OCT_INFO_DIFF_HI 45
+#define FDTD2D_OCT_INFO_SKIPPED 46
 
 /* ---- lifetime ------------------------------------------------------------------ */
 
@@ -294,6 +302,10 @@ int fdtd2d_sync(fdtd2d_t *h);
                                          for the sign of zeros.  -1 (default): on for grids of >= 4 Mi cells; 0: off;
                                          1: on at any size.  fdtd2d_time_launches and the tuner's trial launches always
                                          sweep the whole grid. */
+#define FDTD2D_OPT_WINDOW_OCTAGON  10  /* 1 (default): away from the frame the bound also has diagonal sides -- the fields
+                                         spread one cell per step in L1 distance -- and the (band, strip) tasks of a
+                                         window that lie wholly outside them do nothing (about half the tasks of a point
+                                         source's window).  0: the rectangle alone.  Same results either way. */
 int fdtd2d_set_option(fdtd2d_t *h, int option, long long value);
 
 /* Launch shape of the temporally blocked passes of `pass_steps` steps (0 = the full-length passes, 16 or 8): re-use
