@@ -158,3 +158,7 @@ class LossyOracle(SessionOracle):
             if a is not None:
                 getattr(self, name)[...] = np.asarray(a).astype(self.dtype)
         return self
+
+    def upload_ezx(self, Ezx):
+        self.Ezx[...] = np.asarray(Ezx).astype(self.dtype)
+        return self
