@@ -290,6 +290,18 @@ BATCH_HZ_FLUX_SIGNATURES = {
     "fdtd2d_batch_read_hz_flux_lines": (_i, [_vp, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]),
     "fdtd2d_batch_hz_flux": (_i, [_vp, C.POINTER(_d)]),
 }
+# every symbol include/fdtd2d_batch_hz_bloch.h declares (a Bloch phase in the Hz polarisation: complex Hz, Ex, Ey, Hzx
+# and pole state).  FDTD2D_BATCH_INFO_HZ_BLOCH is named apart from the BATCH_INFO_* above, like the line sources' id
+BATCH_HZ_BLOCH_INFO = 24
+BATCH_HZ_BLOCH_SIGNATURES = {
+    "fdtd2d_batch_set_hz_bloch": (_i, [_vp, C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_set_hz_bloch_source": (_i, [_vp, C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_run_hz_bloch": (_i, [_vp, _i, C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_transfer_hz_bloch": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i]),
+    "fdtd2d_batch_transfer_hz_bloch_dispersion": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i]),
+    "fdtd2d_batch_read_dft_window_hz_bloch": (_i, [_vp, C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_read_probes_hz_bloch": (_i, [_vp, C.POINTER(_d), _ll, _ll]),
+}
 
 # transport callback of fdtd2d_slab_attach
 EXCHANGE_FN = C.CFUNCTYPE(_i, _vp, _vp, _vp, _vp, _vp, _ll, _vp)
@@ -347,7 +359,7 @@ def load():
                                    **BATCH_DISPERSIVE_ADJOINT_SIGNATURES, **BATCH_FLUX_SIGNATURES,
                                    **BATCH_BLOCH_FLUX_SIGNATURES, **BATCH_FLUX_ADJOINT_SIGNATURES,
                                    **BATCH_BLOCH_FLUX_ADJOINT_SIGNATURES, **BATCH_HZ_SIGNATURES,
-                                   **BATCH_HZ_FLUX_SIGNATURES}.items():
+                                   **BATCH_HZ_FLUX_SIGNATURES, **BATCH_HZ_BLOCH_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

@@ -25,6 +25,9 @@ fdtd2d_batch_bloch_dispersive.h): a metal unit cell with one angle of incidence 
 in the plane, with ``set_conductivity`` and ``set_dispersion`` acting on Ex and Ey (metal strips, wire grids, plasmonic
 gratings seen by in-plane E; fdtd2d_batch_hz.h).  ``set_hz_flux_lines`` gives such a batch flux lines: the transforms of Hz
 and of the tangential E, and through ``flux()`` the power that crosses each line (fdtd2d_batch_hz_flux.h).
+``set_hz_bloch_phase`` gives a periodic batch in the Hz polarisation one Bloch phase per member: complex Hz, Ex, Ey, Hzx and
+pole state, with the conductivity and the pole acting under the phase (Brewster incidence, grating-coupled surface plasmons,
+angle sweeps of wire grids; fdtd2d_batch_hz_bloch.h).
 ``boundary="lattice"`` makes every member the unit cell of a rectangular 2D lattice: row R-1 is the image of row 0 and
 column C-1 the image of column 0, the fields are complex, and ``set_lattice_phase`` gives every member one Bloch phase
 across each pair of edges (band diagrams of 2D photonic crystals: a k-path is one batch; fdtd2d_batch_lattice.h).
@@ -141,6 +144,7 @@ class BatchEngine:
     """
     _lattice = None               # ((cr, sr), (cc, sc)): the (B,) rotations of a lattice engine (None: not one)
     _hz = False                   # set_polarization("hz"): Hz with Ex, Ey (fdtd2d_batch_hz.h)
+    _hzb = False                  # set_hz_bloch_phase: _bloch holds the rotations of fdtd2d_batch_hz_bloch.h's phase
 
     def __init__(self, count, rows, cols, dt=5e-14, dx=1e-4, dtype=np.float32, boundary="mur", device=0):
         self._lib = _abi.load()
@@ -217,6 +221,17 @@ class BatchEngine:
         return bool(self.info(_abi.BATCH_INFO_BLOCH))
 
     @property
+    def hz_bloch(self) -> bool:
+        """Whether the Bloch phase of the Hz polarisation is set (set_hz_bloch_phase; `bloch` stays False there)."""
+        return bool(self.info(_abi.BATCH_HZ_BLOCH_INFO))
+
+    def _bloch_fn(self, name):
+        """The entry point `name` of fdtd2d_batch_bloch.h, or on an Hz engine its counterpart of fdtd2d_batch_hz_bloch.h."""
+        hz = {"set_bloch_source": "set_hz_bloch_source", "run_bloch": "run_hz_bloch", "transfer_bloch": "transfer_hz_bloch",
+              "read_dft_window_bloch": "read_dft_window_hz_bloch", "read_probes_bloch": "read_probes_hz_bloch"}
+        return getattr(self._lib, "fdtd2d_batch_" + (hz[name] if self._hzb else name))
+
+    @property
     def lattice(self) -> bool:
         """Whether the lattice mode is on (complex fields, Bloch conditions on both pairs of edges)."""
         return bool(self._lib.fdtd2d_batch_is_lattice(self._h))
@@ -270,15 +285,18 @@ class BatchEngine:
         the permeability of Hz[i, j].  set_conductivity and set_dispersion then act on Ex and Ey (fdtd2d_batch_hz.h).
         A change zeroes the fields as reset() does.  The library refuses (E_STATE) a change beside a conductivity or a
         pole of the polarisation being left, flux lines or a held window; "mur" and "lattice" batches and a Bloch
-        phase have no Hz kernels.  Not available in the Hz polarisation: the adjoint helpers and sessions,
-        set_flux_lines, set_bloch_flux_lines and the line sources (its flux lines are set_hz_flux_lines'), the Bloch API,
-        the held window and the window patchers."""
+        phase of the Ez polarisation have no Hz kernels (the Hz polarisation's own phase is set_hz_bloch_phase, and
+        "ez" is refused while it is set).  Not available in the Hz polarisation: the adjoint helpers and sessions,
+        set_flux_lines, set_bloch_flux_lines and the line sources (its flux lines are set_hz_flux_lines'), the Ez Bloch
+        API, the held window and the window patchers."""
         if polarization not in ("ez", "hz"):
             raise ValueError(f'polarization must be "ez" or "hz", got {polarization!r}')
         if polarization == "hz" and self.boundary not in ("pml", "periodic"):
             raise _abi.Fdtd2dError(_abi.E_STATE, f'the Hz polarisation needs boundary="pml" or "periodic", not '
                                    f'{self.boundary!r}: the Mur frame, a plain box and the lattice mode have no Hz kernels')
-        if polarization == "hz":
+        if self._hzb and polarization == "ez":
+            self._no_bloch("a change of polarisation (turn the phase of set_hz_bloch_phase off first)")
+        if polarization == "hz" and not self._hzb:
             self._no_bloch("the Hz polarisation")
         self._ck(self._lib.fdtd2d_batch_set_polarization(self._h, _abi.POL_HZ if polarization == "hz" else _abi.POL_EZ))
         self._hz = bool(self._lib.fdtd2d_batch_polarization(self._h) == _abi.POL_HZ)
@@ -348,7 +366,7 @@ class BatchEngine:
         if self._bloch is None:
             raise _abi.Fdtd2dError(_abi.E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first")
         if weights is None:
-            self._ck(self._lib.fdtd2d_batch_set_bloch_source(self._h, None, None))
+            self._ck(self._bloch_fn("set_bloch_source")(self._h, None, None))
             return self
         if isinstance(weights, str):
             if weights != "ramp":
@@ -362,8 +380,61 @@ class BatchEngine:
                 raise ValueError(f"weights must have shape ({Q},) or ({self.count}, {Q}), got {w.shape}")
             w = np.broadcast_to(w, (self.count, Q))
         wr, wi = np.ascontiguousarray(w.real), np.ascontiguousarray(w.imag)
-        self._ck(self._lib.fdtd2d_batch_set_bloch_source(self._h, _dptr(wr), _dptr(wi)))
+        self._ck(self._bloch_fn("set_bloch_source")(self._h, _dptr(wr), _dptr(wi)))
         return self
+
+    # -- a Bloch phase in the Hz polarisation (fdtd2d_batch_hz_bloch.h) ---------------------------------------------------
+    def set_hz_bloch_phase(self, phi, rotation=None):
+        """set_bloch_phase for a periodic engine in the Hz polarisation (set_polarization("hz")): one Bloch phase per
+        member, the arguments of set_bloch_phase; None (and no rotation) turns it off, real parts as they are.  While it
+        is set Hz, Ex, Ey, Hzx, the pole state, the window DFT and the probes are complex (upload, download, upload_ezx,
+        download_ezx, download_dispersion, upload_hz_dispersion, read_dft_window, read_probes), run() takes complex
+        amps, and set_conductivity, set_dispersion, set_pml, set_materials, set_eps_window and reset keep working.
+        Refused while it is set: set_dft, point sources and channels, set_hz_flux_lines (and this call while such lines
+        are set), set_polarization("ez"), windows and probes touching column C-1, and everything the Hz polarisation
+        refuses without it (the Ez Bloch API, the adjoint helpers and sessions)."""
+        if not self._hz:
+            raise _abi.Fdtd2dError(_abi.E_STATE, 'set_hz_bloch_phase needs the Hz polarisation (set_polarization("hz")): '
+                                                 "the Ez polarisation takes set_bloch_phase")
+        if phi is None and rotation is None:
+            self._ck(self._lib.fdtd2d_batch_set_hz_bloch(self._h, None, None))
+            self._bloch = self._phi = None
+            self._hzb = False
+            return self
+        if rotation is not None:
+            if len(rotation) != 2:
+                raise ValueError(f"rotation must be a pair (c, s), got {rotation!r}")
+            c, s = (np.asarray(v, dtype=np.float64) for v in rotation)
+            ph = None
+        else:
+            ph = np.asarray(phi, dtype=np.float64)
+            c, s = np.cos(ph), np.sin(ph)
+        for v, nm in ((c, "c"), (s, "s")) if ph is None else ((ph, "phi"),):
+            if v.shape not in ((), (self.count,)):
+                raise ValueError(f"{nm} must be a scalar or have shape ({self.count},), got {v.shape}")
+            if not np.all(np.isfinite(v)):
+                raise ValueError(f"{nm} must be finite")
+        if self.boundary != "periodic":
+            raise _abi.Fdtd2dError(_abi.E_STATE, "a Bloch phase needs periodic columns: call fdtd2d_batch_set_periodic "
+                                   "first")
+        if self._hzflux:
+            raise _abi.Fdtd2dError(_abi.E_STATE, "a Bloch phase is not available while flux lines of the Hz polarisation "
+                                   "are set: remove them first")
+        c = np.ascontiguousarray(np.broadcast_to(c, (self.count,)))
+        s = np.ascontiguousarray(np.broadcast_to(s, (self.count,)))
+        self._ck(self._lib.fdtd2d_batch_set_hz_bloch(self._h, _dptr(c), _dptr(s)))
+        self._bloch = (c, s)
+        self._hzb = True
+        self._phi = None if ph is None else np.ascontiguousarray(np.broadcast_to(ph, (self.count,)))
+        return self
+
+    def set_hz_bloch_source(self, weights="ramp"):
+        """set_bloch_source for the phase of set_hz_bloch_phase: the complex weight of the rectangle source (which adds
+        to Hz) per column 0..C-2: "ramp", None = ones, or a complex array (C-1,) or (B, C-1)."""
+        if not self._hzb:
+            raise _abi.Fdtd2dError(_abi.E_STATE, "no Bloch phase of the Hz polarisation is set: call set_hz_bloch_phase "
+                                   "first")
+        return self.set_bloch_source(weights)
 
     def _touches_image(self, what, cols):
         """The library's refusal of a monitor in column C-1 while a Bloch phase is set."""
@@ -503,7 +574,7 @@ class BatchEngine:
         self._ck(self._lib.fdtd2d_batch_transfer_ezx(self._h, a.ctypes.data, _code(a.dtype), 1))
         if self._bloch is not None:
             i = np.ascontiguousarray(z.imag, dtype=self.dtype)
-            self._ck(self._lib.fdtd2d_batch_transfer_bloch(self._h, None, None, None, i.ctypes.data, _code(i.dtype), 1))
+            self._ck(self._bloch_fn("transfer_bloch")(self._h, None, None, None, i.ctypes.data, _code(i.dtype), 1))
         return self
 
     def download_ezx(self):
@@ -513,7 +584,7 @@ class BatchEngine:
         self._ck(self._lib.fdtd2d_batch_transfer_ezx(self._h, a.ctypes.data, _code(a.dtype), 0))
         if self._bloch is not None:
             i = np.empty_like(a)
-            self._ck(self._lib.fdtd2d_batch_transfer_bloch(self._h, None, None, None, i.ctypes.data, _code(i.dtype), 0))
+            self._ck(self._bloch_fn("transfer_bloch")(self._h, None, None, None, i.ctypes.data, _code(i.dtype), 0))
             return a + 1j * i
         return a
 
@@ -546,7 +617,7 @@ class BatchEngine:
             Ez, Hx, Hy = (None if a is None else np.ascontiguousarray(a.real) for a in given)
             if any(a is not None for a in im):
                 ptr = [None if a is None else a.ctypes.data for a in im]
-                self._ck(self._lib.fdtd2d_batch_transfer_bloch(self._h, ptr[0], ptr[1], ptr[2], None, _abi.F64, 1))
+                self._ck(self._bloch_fn("transfer_bloch")(self._h, ptr[0], ptr[1], ptr[2], None, _abi.F64, 1))
         arrs, code = [], None
         for a, shp, nm in zip((Ez, Hx, Hy), self._field_shapes(), ("Ez", "Hx", "Hy")):
             if a is None:
@@ -573,7 +644,7 @@ class BatchEngine:
         self._ck(self._lib.fdtd2d_batch_download(self._h, *(a.ctypes.data for a in out), _code(dt)))
         if self._bloch is not None:
             im = [np.empty(s, dt) for s in self._field_shapes()]
-            self._ck(self._lib.fdtd2d_batch_transfer_bloch(self._h, *(a.ctypes.data for a in im), None, _code(dt), 0))
+            self._ck(self._bloch_fn("transfer_bloch")(self._h, *(a.ctypes.data for a in im), None, _code(dt), 0))
             return tuple(a + 1j * b for a, b in zip(out, im))
         return tuple(out)
 
@@ -615,7 +686,7 @@ class BatchEngine:
             self._no_bloch("a run with channels")
         if ai is not None:
             ai = np.ascontiguousarray(ai[:, :nsteps], dtype=np.float64)
-            self._ck(self._lib.fdtd2d_batch_run_bloch(self._h, nsteps, _dptr(a), _dptr(ai)))
+            self._ck(self._bloch_fn("run_bloch")(self._h, nsteps, _dptr(a), _dptr(ai)))
             return self
         if channels is None:
             self._ck(self._lib.fdtd2d_batch_run(self._h, nsteps, None if a is None else _dptr(a)))
@@ -894,7 +965,7 @@ class BatchEngine:
         self._ck(self._lib.fdtd2d_batch_read_dft_window(self._h, _dptr(re), _dptr(im)))
         if self._bloch is not None:
             re2, im2 = np.empty_like(re), np.empty_like(im)
-            self._ck(self._lib.fdtd2d_batch_read_dft_window_bloch(self._h, _dptr(re2), _dptr(im2)))
+            self._ck(self._bloch_fn("read_dft_window_bloch")(self._h, _dptr(re2), _dptr(im2)))
             return (re + 1j * im) + 1j * (re2 + 1j * im2)
         return re + 1j * im
 
@@ -962,6 +1033,8 @@ class BatchEngine:
             if self._hzflux:
                 self._flux, self._hzflux = None, False
             return self
+        if self._hzb:
+            self._no_bloch("set_hz_flux_lines")
         if not self._hz:
             raise _abi.Fdtd2dError(_abi.E_STATE, 'set_hz_flux_lines needs the Hz polarisation (set_polarization("hz")): '
                                                  "the lines of the Ez polarisation are set_flux_lines'")
@@ -1242,7 +1315,7 @@ class BatchEngine:
         if self._bloch is not None:
             im = np.empty_like(out)
             buf = im if im.size else np.empty(1)
-            self._ck(self._lib.fdtd2d_batch_read_probes_bloch(self._h, _dptr(buf), int(first), int(count)))
+            self._ck(self._bloch_fn("read_probes_bloch")(self._h, _dptr(buf), int(first), int(count)))
             return out + 1j * im
         return out
 
@@ -1426,6 +1499,11 @@ class BatchEngine:
             jy, qy = np.empty_like(jh), np.empty_like(jh)
             self._ck(self._lib.fdtd2d_batch_transfer_hz_dispersion(self._h, jh.ctypes.data, q.ctypes.data, jy.ctypes.data,
                                                                    qy.ctypes.data, _code(jh.dtype), 0))
+            if self._hzb:             # complex under the phase of set_hz_bloch_phase
+                im = [np.empty_like(jh) for _ in range(4)]
+                self._ck(self._lib.fdtd2d_batch_transfer_hz_bloch_dispersion(self._h, *(a.ctypes.data for a in im),
+                                                                             _code(jh.dtype), 0))
+                return tuple(a + 1j * b for a, b in zip((jh, q, jy, qy), im))
             return jh, q, jy, qy
         self._ck(self._lib.fdtd2d_batch_transfer_dispersion(self._h, jh.ctypes.data, q.ctypes.data, _code(jh.dtype), 0))
         return jh, q
@@ -1451,14 +1529,24 @@ class BatchEngine:
     def upload_hz_dispersion(self, Jx=None, Qx=None, Jy=None, Qy=None):
         """The pole state of the Hz polarisation, (B, R, C) each in the order download_dispersion returns them, host ->
         device; one given as None is left as is (needs the Hz polarisation and a pole)."""
-        arrs = []
-        for a, nm in ((Jx, "Jx"), (Qx, "Qx"), (Jy, "Jy"), (Qy, "Qy")):
+        given = [None if a is None else np.asarray(a) for a in (Jx, Qx, Jy, Qy)]
+        if any(a is not None and np.iscomplexobj(a) for a in given) and not self._hzb:
+            raise ValueError("a complex pole state needs the phase of set_hz_bloch_phase")
+        arrs, ims = [], []
+        for a, nm in zip(given, ("Jx", "Qx", "Jy", "Qy")):
+            i = None
             if a is not None:
-                a = np.ascontiguousarray(a, dtype=self.dtype)
+                if self._hzb:
+                    i = np.ascontiguousarray(a.imag, dtype=self.dtype)
+                a = np.ascontiguousarray(a.real, dtype=self.dtype)
                 self._shape(a, (self.count, self.rows, self.cols), nm)
             arrs.append(a)
+            ims.append(i)
         ptr = [None if a is None else a.ctypes.data for a in arrs]
         self._ck(self._lib.fdtd2d_batch_transfer_hz_dispersion(self._h, *ptr, _code(self.dtype), 1))
+        if self._hzb and any(i is not None for i in ims):
+            ptr = [None if i is None else i.ctypes.data for i in ims]
+            self._ck(self._lib.fdtd2d_batch_transfer_hz_bloch_dispersion(self._h, *ptr, _code(self.dtype), 1))
         return self
 
     # -- the pole of a Bloch or lattice batch (fdtd2d_batch_bloch_dispersive.h) ----------------------------------
@@ -1563,7 +1651,8 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
                    dtype=np.float64, boundary="mur", omega=None, dft_every=1, device=0, pml_cells=40,
                    dft_window=None, window_omegas=None, probes=None, bloch_phase=None, source_weights=None,
                    dispersion=None, bloch_dispersion=None, polarization="ez", conductivity=None,
-                   hz_flux_lines=None, hz_flux_omegas=None, bloch_flux_lines=None, bloch_flux_omegas=None, flux_lines=None, flux_omegas=None):
+                   hz_bloch_phase=None, hz_flux_lines=None, hz_flux_omegas=None, bloch_flux_lines=None,
+                   bloch_flux_omegas=None, flux_lines=None, flux_omegas=None):
     """run_fdtd for B members of one shape at once: zero fields, Courant check per member, nsteps of
     H -> E -> source with t = i*dt.
 
@@ -1595,7 +1684,9 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
     and Ey, and the first three returned arrays are (Hz, Ex, Ey).  conductivity: None, or a scalar or (B, R, C) as
     set_conductivity takes it, in either polarisation.  hz_flux_lines with hz_flux_omegas (polarization "hz" alone): flux
     monitors as set_hz_flux_lines takes them, sampled every `dft_every` steps; the flux array is appended as with
-    flux_lines.
+    flux_lines.  hz_bloch_phase (polarization "hz" with boundary "periodic" alone): a scalar or (B,) in radians, the
+    Bloch phase of set_hz_bloch_phase; every returned array is then complex, dispersion and conductivity act under the
+    phase, source_weights goes to set_hz_bloch_source, and omega and hz_flux_lines are not available.
     """
     from .api import MU0
     eps = np.asarray(eps)
@@ -1637,7 +1728,7 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
             raise ValueError('dispersion is not available with boundary="lattice"')
     if bloch_phase is not None and boundary not in ("periodic", "lattice"):
         raise ValueError(f'bloch_phase needs boundary="periodic" or "lattice", not {boundary!r}')
-    if source_weights is not None and bloch_phase is None:
+    if source_weights is not None and bloch_phase is None and hz_bloch_phase is None:
         raise ValueError("source_weights needs bloch_phase")
     if bloch_phase is not None and omega is not None:
         raise ValueError("omega (the whole-grid transform) is not available with bloch_phase: use dft_window")
@@ -1650,6 +1741,19 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
                           (bloch_dispersion, "bloch_dispersion")):
             if given is not None:
                 raise ValueError(f'{nm} is not available with polarization="hz"')
+    if hz_bloch_phase is not None:
+        if polarization != "hz":
+            raise ValueError('hz_bloch_phase needs polarization="hz": in the Ez polarisation use bloch_phase')
+        if boundary != "periodic":
+            raise ValueError(f'hz_bloch_phase needs boundary="periodic", not {boundary!r}')
+        if np.shape(hz_bloch_phase) not in ((), (B,)):
+            raise ValueError(f"hz_bloch_phase must be a scalar or have shape ({B},), got {np.shape(hz_bloch_phase)}")
+        if not np.all(np.isfinite(np.asarray(hz_bloch_phase, dtype=np.float64))):
+            raise ValueError("hz_bloch_phase must be finite")
+        if omega is not None:
+            raise ValueError("omega (the whole-grid transform) is not available with hz_bloch_phase: use dft_window")
+        if hz_flux_lines is not None:
+            raise ValueError("hz_flux_lines is not available with hz_bloch_phase")
     if (hz_flux_lines is None) != (hz_flux_omegas is None):
         raise ValueError("hz_flux_lines and hz_flux_omegas must be given together")
     if hz_flux_lines is not None:
@@ -1694,6 +1798,11 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
             raise ValueError(f"dft_window {win} touches column {Cc - 1}, the image of column 0: not with bloch_phase")
         if cells is not None and np.any(cells[..., 1] >= Cc - 1):
             raise ValueError(f"a probe lies in column {Cc - 1}, the image of column 0: not with bloch_phase")
+    if hz_bloch_phase is not None:
+        if win is not None and win[1] + win[3] > Cc - 1:
+            raise ValueError(f"dft_window {win} touches column {Cc - 1}, the image of column 0: not with hz_bloch_phase")
+        if cells is not None and np.any(cells[..., 1] >= Cc - 1):
+            raise ValueError(f"a probe lies in column {Cc - 1}, the image of column 0: not with hz_bloch_phase")
     if lattice:
         if win is not None and win[0] + win[2] > R - 1:
             raise ValueError(f'dft_window {win} touches row {R - 1}, the image of row 0: not with boundary="lattice"')
@@ -1719,6 +1828,10 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
                 eng.set_bloch_source(source_weights)
         if bloch_dispersion is not None:
             eng.set_bloch_dispersion(*bloch_dispersion)
+        if hz_bloch_phase is not None:
+            eng.set_hz_bloch_phase(hz_bloch_phase)
+            if source_weights is not None:
+                eng.set_hz_bloch_source(source_weights)
         if omega is not None:
             eng.set_dft(omega, dft_every)
         if win is not None:

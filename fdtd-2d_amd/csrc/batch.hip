@@ -27,6 +27,9 @@
 // the imaginary part.
 // With the lines of fdtd2d_batch_hz_flux.h a batch in the Hz polarisation takes the kernels of batch_hz_flux.hip, with or
 // without a conductivity and a pole; the lines share that host state too (`hzflux` beside `flux_nl`).
+// With the phase of fdtd2d_batch_hz_bloch.h a periodic batch in the Hz polarisation holds `hz` and `bloch` together: the
+// imaginary parts, the rotations, the weights and the monitors are the Bloch phase's, a pole adds the imaginary parts of
+// Jx, Qx (djh_im, dq_im) and Jy, Qy (djy_im, dqy_im), and every run takes the kernels of batch_hz_bloch.hip.
 #include "../../include/fdtd2d.h"
 #include "../../include/fdtd2d_batch_adjoint.h"
 #include "../../include/fdtd2d_batch_bloch.h"
@@ -40,6 +43,7 @@
 #include "../../include/fdtd2d_batch_flux.h"
 #include "../../include/fdtd2d_batch_flux_adjoint.h"
 #include "../../include/fdtd2d_batch_hz.h"
+#include "../../include/fdtd2d_batch_hz_bloch.h"
 #include "../../include/fdtd2d_batch_hz_flux.h"
 #include "../../include/fdtd2d_batch_lattice.h"
 #include "../../include/fdtd2d_batch_lossy.h"
@@ -70,6 +74,7 @@
 #include "kernels_batch_flux.hpp"
 #include "kernels_batch_flux_adjoint.hpp"
 #include "kernels_batch_hz.hpp"
+#include "kernels_batch_hz_bloch.hpp"
 #include "kernels_batch_hz_flux.hpp"
 #include "kernels_batch_lattice.hpp"
 #include "kernels_batch_lossy.hpp"
@@ -113,6 +118,10 @@ struct fdtd2d_batch {
     // always holds ca / cb (sigma_implicit without a conductivity), and a pole's djh, dq are Jx, Qx and these Jy, Qy
     bool hz = false;
     void *djy = nullptr, *dqy = nullptr;
+    // fdtd2d_batch_set_hz_bloch: `hz` and `bloch` together; with a pole djh_im, dq_im hold the imaginary Jx, Qx and these
+    // the imaginary Jy, Qy.  hz_bloch_call: an entry point of fdtd2d_batch_hz_bloch.h is using one of the Bloch phase's
+    bool hz_bloch_call = false;
+    void *djy_im = nullptr, *dqy_im = nullptr;
     void *dsg = nullptr;                  // device scratch of the design-loop entry points
     size_t dsg_cap = 0;
     // fdtd2d_batch_set_periodic: column C-1 is the image of column 0.  The batch then always holds Ezx and the factors
@@ -320,7 +329,7 @@ int zero_fields(fdtd2d_batch *b)
     for (void *p : {b->ez[0], b->ez[1], b->hx, b->hy}) BCHK(b, hipMemsetAsync(p, 0, b->field_bytes, b->stream));
     if (b->ezx) BCHK(b, hipMemsetAsync(b->ezx, 0, b->field_bytes, b->stream));
     if (b->dcj)
-        for (void *p : {b->djh, b->dq, b->djh_im, b->dq_im, b->djy, b->dqy})
+        for (void *p : {b->djh, b->dq, b->djh_im, b->dq_im, b->djy, b->dqy, b->djy_im, b->dqy_im})
             if (p) BCHK(b, hipMemsetAsync(p, 0, b->field_bytes, b->stream));     // the imaginary parts: a complex pole's
     if (b->bloch)
         for (void *p : {b->ez_im, b->hx_im, b->hy_im, b->ezx_im})
@@ -339,6 +348,7 @@ int zero_fields(fdtd2d_batch *b)
 // twice and cj more
 int lds_arrays(const fdtd2d_batch *b)
 {
+    if (b->hz && b->bloch) return b->dcj ? 20 : 11;   // Hz, Ex, Ey, Hzx twice, ch, cb, ca and cj, Jx, Qx, Jy, Qy twice
     if (b->hz) return b->dcj ? 12 : 7;       // Hz, Ex, Ey, Hzx, ch, cb, ca and cj, Jx, Qx, Jy, Qy
     if (b->lattice) return b->bdisp ? 14 : 9;
     if (b->bloch) return b->bdisp ? 16 : 11;
@@ -1285,10 +1295,75 @@ int run_bloch_flux(fdtd2d_batch *b, int nsteps, const double *amps, long long am
     return 0;
 }
 
+// ---- Hz Bloch runs (fdtd2d_batch_hz_bloch.h): the periodic paths of run_hz with the complex-field kernels of
+// batch_hz_bloch.hip.  v.ce carries cb; the first streamed launch of a step is the E half-step.
+template <class T> int run_hz_bloch(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride)
+{
+    const int disp = b->dcj ? 1 : 0;
+    if (!b->periodic || !b->ezx || !b->ca || !b->cb || !b->ch || !b->ez_im || !b->hx_im || !b->hy_im || !b->ezx_im ||
+        !b->rho || !b->bloch_w ||
+        (disp && (!b->djh || !b->dq || !b->djy || !b->dqy || !b->djh_im || !b->dq_im || !b->djy_im || !b->dqy_im ||
+                  !b->da || !b->dck)))
+        return bfail(b, FDTD2D_E_STATE, "Hz Bloch batch without its arrays");
+    const fdtd::BatchHzBlochKernels &K = fdtd::batch_hz_bloch_kernels<T>();
+    fdtd::BatchPml<T> p = pml_view<T>(b);
+    fdtd::BatchMon m = mon_view(b);
+    fdtd::BatchBloch<T> bl = bloch_view<T>(b, false);
+    fdtd::BatchHzBlochDisp<T> d{(T *)b->djh,    (T *)b->dq,    (T *)b->djy,    (T *)b->dqy,
+                                (T *)b->djh_im, (T *)b->dq_im, (T *)b->djy_im, (T *)b->dqy_im,
+                                (const T *)b->dcj, (const T *)b->da, (const T *)b->dck};
+    b->run_conj = false;
+    const T *ca = (const T *)b->ca;
+    if (use_resident(b)) {
+        const int cells = b->rows * b->cols, threads = resident_threads(cells);
+        const int per_thread = (cells + threads - 1) / threads;
+        if (per_thread > 4)
+            return bfail(b, FDTD2D_E_STATE, "%d cells per thread exceed the Hz Bloch resident kernel's 4", per_thread);
+        const void *kern = K.resident[disp];
+        const size_t lds = lds_bytes(b);
+        BCHK(b, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        int per_cu = 0, cus = 0;
+        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds));
+        BCHK(b, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
+        if (per_cu < 1) return bfail(b, FDTD2D_E_STATE, "Hz Bloch resident kernel does not fit a CU (%zu B of LDS)", lds);
+        const long long round = (long long)per_cu * cus;
+        const int blocks = (int)(b->count < round ? b->count : round);
+        const int chunk = b->steps_per_launch > 0 ? b->steps_per_launch : nsteps;
+        for (int n = 0; n < nsteps; n += chunk) {
+            int n0 = n, nt = nsteps - n < chunk ? nsteps - n : chunk;
+            long long step_base = b->step;
+            fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+            v.ce = (const T *)b->cb;
+            void *args[] = {&v, &p, &m, &bl, &d, &ca, &n0, &nt, &step_base};
+            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads), args, lds);
+            if (rc) return rc;
+            b->launches++;
+            b->step += nt;
+        }
+        return 0;
+    }
+    const int cells = b->rows * b->cols;
+    const dim3 grid((cells + 255) / 256, b->count < 65535 ? b->count : 65535);
+    for (int n = 0; n < nsteps; ++n) {
+        fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+        v.ce = (const T *)b->cb;
+        long long step = b->step + 1;
+        int rc;
+        void *e_args[] = {&v, &p, &m, &bl, &d, &ca, &step};
+        void *h_args[] = {&v, &p, &m, &bl, &n, &step};
+        if ((rc = launch_ptr(b, K.e[disp], grid, dim3(256), e_args, 0))) return rc;
+        if ((rc = launch_ptr(b, K.h, grid, dim3(256), h_args, 0))) return rc;
+        b->launches += 2;
+        b->step++;
+    }
+    return 0;
+}
+
 template <class T>
 int run_impl(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts = nullptr,
              fdtd::BatchFluxSrc *fs = nullptr)
 {
+    if (b->hz && b->bloch) return run_hz_bloch<T>(b, nsteps, amps, amp_stride);
     if (b->hz) return run_hz<T>(b, nsteps, amps, amp_stride, pts);
     if (b->bflux) return run_bloch_flux<T>(b, nsteps, amps, amp_stride);
     if (b->bdisp) return run_bloch_dispersive<T>(b, nsteps, amps, amp_stride);
@@ -1660,7 +1735,9 @@ int disp_reform(fdtd2d_batch *b, int r0, int c0, int nr, int nc)
 
 void disp_release(fdtd2d_batch *b)
 {
-    for (void **p : {&b->djh, &b->dq, &b->dcj, &b->da, &b->dck, &b->djh_im, &b->dq_im, &b->djy, &b->dqy}) release(p);
+    for (void **p : {&b->djh, &b->dq, &b->dcj, &b->da, &b->dck, &b->djh_im, &b->dq_im, &b->djy, &b->dqy, &b->djy_im,
+                     &b->dqy_im})
+        release(p);
     release((void **)&b->win_held_disp);     // the held dispersive window goes with the pole
     b->bdisp = false;
     b->wp2_host.clear();
@@ -1692,7 +1769,7 @@ int set_disp(fdtd2d_batch *b, const int *window, const void *wp2, int dtype, con
     if (!b->ezx && !b->periodic)
         return bfail(b, FDTD2D_E_STATE, "a dispersive pole needs a PML layer (fdtd2d_batch_set_pml) or periodic columns: a "
                      "plain box has no dispersive kernels");
-    if (b->bloch && !complex) return refuse_bloch(b, "a dispersive pole");
+    if (b->bloch && !complex && !b->hz) return refuse_bloch(b, "a dispersive pole");
     if (!b->have_mat) return bfail(b, FDTD2D_E_STATE, "materials not set: call fdtd2d_batch_set_materials first");
     if (!wp2) return bfail(b, FDTD2D_E_ARG, "wp2 must not be NULL");
     if (dtype != FDTD2D_F32 && dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad dtype");
@@ -1740,9 +1817,12 @@ int set_disp(fdtd2d_batch *b, const int *window, const void *wp2, int dtype, con
     const bool fresh = !b->dcj;
     if (fresh) {
         const size_t mb = (size_t)b->count * b->esz;
-        for (void **p : {&b->djh, &b->dq, &b->dcj, &b->da, &b->dck, &b->djh_im, &b->dq_im, &b->djy, &b->dqy}) {
-            if (!complex && (p == &b->djh_im || p == &b->dq_im)) continue;
+        const bool hzb = b->hz && b->bloch;      // fdtd2d_batch_hz_bloch.h: both parts of Jx, Qx, Jy, Qy
+        for (void **p : {&b->djh, &b->dq, &b->dcj, &b->da, &b->dck, &b->djh_im, &b->dq_im, &b->djy, &b->dqy, &b->djy_im,
+                         &b->dqy_im}) {
+            if (!complex && !hzb && (p == &b->djh_im || p == &b->dq_im)) continue;
             if (!b->hz && (p == &b->djy || p == &b->dqy)) continue;
+            if (!hzb && (p == &b->djy_im || p == &b->dqy_im)) continue;
             const size_t bytes = (p == &b->da || p == &b->dck) ? mb : b->field_bytes;
             hipError_t e = hipSuccess;
             if ((rc = alloc(b, p, bytes)) || (e = hipMemsetAsync(*p, 0, bytes, b->stream)) != hipSuccess) {
@@ -1908,6 +1988,8 @@ int bloch_off(fdtd2d_batch *b)
     b->rho_host.clear();
     b->rho_r_host.clear();
     b->bloch = b->run_conj = b->lattice = false;
+    if (b->hz)                              // fdtd2d_batch_hz_bloch.h: the imaginary parts of the pole state go too
+        for (void **p : {&b->djh_im, &b->dq_im, &b->djy_im, &b->dqy_im}) release(p);
     return batch_set_points(b, 0, nullptr, 0, nullptr);      // the point sources of a Bloch batch go with the phase
 }
 
@@ -2024,7 +2106,7 @@ void fdtd2d_batch_destroy(fdtd2d_batch_t *b)
                      (void **)&b->win_acc_im, (void **)&b->probe_trace_im, &b->rho_conj, &b->rho_r,
                      (void **)&b->win_held_im, (void **)&b->win_held_disp,
                      &b->djh, &b->dq, &b->dcj, &b->da, &b->dck, &b->djh_im, &b->dq_im, &b->djy, &b->dqy,
-                     (void **)&b->flux_acc, (void **)&b->flux_omega, (void **)&b->flux_ph,
+                     &b->djy_im, &b->dqy_im, (void **)&b->flux_acc, (void **)&b->flux_omega, (void **)&b->flux_ph,
                      (void **)&b->flux_acc_im, (void **)&b->fsrc_we, (void **)&b->fsrc_wh,
                      (void **)&b->fsrc_geom, (void **)&b->fsrc_we_im, (void **)&b->fsrc_wh_im})
         release(p);
@@ -2063,7 +2145,8 @@ long long fdtd2d_batch_info(const fdtd2d_batch_t *b, int what)
     case FDTD2D_BATCH_INFO_HELD_BLOCH_WINDOW: return b->win_held && b->win_held_im && b->bloch ? 1 : 0;
     case FDTD2D_BATCH_INFO_LOSSY: return b->ca && !b->sigma_implicit ? 1 : 0;
     case FDTD2D_BATCH_INFO_PERIODIC: return b->periodic ? 1 : 0;
-    case FDTD2D_BATCH_INFO_BLOCH: return b->bloch && !b->lattice ? 1 : 0;
+    case FDTD2D_BATCH_INFO_BLOCH: return b->bloch && !b->lattice && !b->hz ? 1 : 0;
+    case FDTD2D_BATCH_INFO_HZ_BLOCH: return b->bloch && b->hz ? 1 : 0;
     case FDTD2D_BATCH_INFO_DISPERSIVE: return b->dcj ? 1 : 0;
     case FDTD2D_BATCH_INFO_HELD_DISPERSIVE_WINDOW: return b->win_held_disp ? 1 : 0;
     case FDTD2D_BATCH_INFO_FLUX_LINES: return b->flux_nl;
@@ -2380,6 +2463,7 @@ int fdtd2d_batch_set_sources(fdtd2d_batch_t *b, const int *rect)
 
 int fdtd2d_batch_run(fdtd2d_batch_t *b, int nsteps, const double *amps)
 {
+    if (b && b->bloch && b->hz) return fdtd2d_batch_run_hz_bloch(b, nsteps, amps, nullptr);
     if (b && b->bloch) return fdtd2d_batch_run_bloch(b, nsteps, amps, nullptr);
     int rc = need_ready(b);
     if (rc) return rc;
@@ -3049,6 +3133,9 @@ int fdtd2d_batch_set_polarization(fdtd2d_batch_t *b, int polarization)
         return bfail(b, FDTD2D_E_STATE, "a change of polarisation needs a batch created with FDTD2D_BOUNDARY_NONE: the Mur "
                      "frame has no Hz kernels");
     if (b->lattice) return refuse_bloch(b, "a change of polarisation (the lattice mode has no Hz kernels)");
+    if (b->bloch && b->hz && hz) return 0;
+    if (b->bloch && b->hz)
+        return refuse_bloch(b, "a change of polarisation (turn the phase of fdtd2d_batch_set_hz_bloch off first)");
     if (b->bloch) return refuse_bloch(b, "a change of polarisation (a Bloch phase has no Hz kernels)");
     if (hz == b->hz) return 0;
     if (b->flux_nl || b->fsrc_nchan) return refuse_flux(b, "a change of polarisation");
@@ -3208,6 +3295,7 @@ int fdtd2d_batch_set_bloch_dispersion(fdtd2d_batch_t *b, const void *wp2, int dt
     if (!b->bloch)
         return bfail(b, FDTD2D_E_STATE, "fdtd2d_batch_set_bloch_dispersion needs a Bloch phase or the lattice mode: a batch "
                      "with real fields takes fdtd2d_batch_set_dispersion");
+    if (b->hz) return refuse_hz(b, "fdtd2d_batch_set_bloch_dispersion (use fdtd2d_batch_set_hz_dispersion)");
     if (!wp2 && !gamma && !omega0) {        // remove the pole: the Bloch or lattice kernels again
         if (!b->bdisp) return 0;
         int rc = use_device(b);
@@ -3267,6 +3355,8 @@ int fdtd2d_batch_set_periodic(fdtd2d_batch_t *b, int on)
         return bfail(b, FDTD2D_E_STATE, "periodic columns need a batch created with FDTD2D_BOUNDARY_NONE: the Mur frame "
                      "and a periodic boundary exclude each other");
     if ((on != 0) == b->periodic) return 0;
+    if (!on && b->hz && b->bloch)
+        return refuse_bloch(b, "turning periodic columns off (turn the phase of fdtd2d_batch_set_hz_bloch off first)");
     if (b->flux_nl) return refuse_flux(b, "switching periodic columns");
     int rc = use_device(b);
     if (rc) return rc;
@@ -3351,11 +3441,12 @@ int fdtd2d_batch_set_bloch(fdtd2d_batch_t *b, const double *cos_phi, const doubl
     int rc = use_device(b);
     if (rc) return rc;
     if (b->lattice) return refuse_bloch(b, "fdtd2d_batch_set_bloch (use fdtd2d_batch_set_lattice)");
+    if (b->hz && b->bloch && !b->hz_bloch_call) return refuse_hz(b, "fdtd2d_batch_set_bloch (use fdtd2d_batch_set_hz_bloch)");
     if (!cos_phi && b->bflux) return refuse_flux(b, "turning the Bloch phase off");
     if (!cos_phi && b->bdisp) return refuse_dispersive(b, "turning the Bloch phase off");
     if (!cos_phi) return b->bloch ? bloch_off(b) : 0;
-    if (b->hz) return refuse_hz(b, "a Bloch phase");
-    if (b->dcj && !b->bdisp) return refuse_dispersive(b, "a Bloch phase");
+    if (b->hz && !b->hz_bloch_call) return refuse_hz(b, "a Bloch phase");
+    if (b->dcj && !b->bdisp && !b->hz) return refuse_dispersive(b, "a Bloch phase");
     if (b->flux_nl && !b->bflux) return refuse_flux(b, "a Bloch phase");
     if (!b->periodic)
         return bfail(b, FDTD2D_E_STATE, "a Bloch phase needs periodic columns: call fdtd2d_batch_set_periodic first");
@@ -3404,6 +3495,15 @@ int fdtd2d_batch_set_bloch(fdtd2d_batch_t *b, const double *cos_phi, const doubl
         if ((rc = alloc(b, &b->rho, rt.size())) || (rc = alloc(b, &b->rho_conj, rt.size())) ||
             (rc = alloc(b, (void **)&b->bloch_w, wn * sizeof(double))))
             return undo(rc);
+        if (b->hz && b->dcj) {                  // fdtd2d_batch_hz_bloch.h: the imaginary parts of Jx, Qx, Jy, Qy as zero
+            for (void **p : {&b->djh_im, &b->dq_im, &b->djy_im, &b->dqy_im}) {
+                if ((rc = alloc(b, p, b->field_bytes))) return undo(rc);
+                if (hipMemsetAsync(*p, 0, b->field_bytes, b->stream) != hipSuccess)
+                    return undo(bfail(b, FDTD2D_E_NOMEM, "hipMemset of the imaginary pole state failed"));
+            }
+            if (hipStreamSynchronize(b->stream) != hipSuccess)
+                return undo(bfail(b, FDTD2D_E_NOMEM, "hipMemset of the imaginary pole state failed"));
+        }
         b->bloch = true;
         if ((rc = fdtd2d_batch_set_bloch_source(b, nullptr, nullptr)) || (rc = bloch_window(b)) || (rc = bloch_probes(b)))
             return undo(rc);
@@ -3419,6 +3519,8 @@ int fdtd2d_batch_set_bloch_source(fdtd2d_batch_t *b, const double *wr, const dou
 {
     if (!b) return FDTD2D_E_ARG;
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (b->hz && !b->hz_bloch_call)
+        return refuse_hz(b, "this entry point of the Ez Bloch phase (fdtd2d_batch_hz_bloch.h has the Hz ones)");
     if (!wr != !wi) return bfail(b, FDTD2D_E_ARG, "wr and wi must both be given (or both NULL)");
     const size_t Q = (size_t)b->cols - 1;
     std::vector<double> w((size_t)b->count * 2 * Q);
@@ -3442,6 +3544,8 @@ int fdtd2d_batch_run_bloch(fdtd2d_batch_t *b, int nsteps, const double *amps_re,
     int rc = need_ready(b);
     if (rc) return rc;
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (b->hz && !b->hz_bloch_call)
+        return refuse_hz(b, "this entry point of the Ez Bloch phase (fdtd2d_batch_hz_bloch.h has the Hz ones)");
     if (nsteps < 0) return bfail(b, FDTD2D_E_ARG, "nsteps < 0");
     if (amps_im && !amps_re) return bfail(b, FDTD2D_E_ARG, "amps_im needs amps_re (zeros for a purely imaginary source)");
     for (int m = 0; m < b->count; ++m)
@@ -3469,6 +3573,8 @@ int fdtd2d_batch_transfer_bloch(fdtd2d_batch_t *b, void *Ez_im, void *Hx_im, voi
 {
     if (!b) return FDTD2D_E_ARG;
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (b->hz && !b->hz_bloch_call)
+        return refuse_hz(b, "this entry point of the Ez Bloch phase (fdtd2d_batch_hz_bloch.h has the Hz ones)");
     if (host_dtype != FDTD2D_F32 && host_dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad host_dtype");
     if (b->lattice && Ezx_im) return refuse_bloch(b, "Ezx (pass Ezx_im as NULL)");
     int rc = use_device(b);
@@ -3499,6 +3605,8 @@ int fdtd2d_batch_read_dft_window_bloch(fdtd2d_batch_t *b, double *re, double *im
 {
     if (!b || !re || !im) return FDTD2D_E_ARG;
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (b->hz && !b->hz_bloch_call)
+        return refuse_hz(b, "this entry point of the Ez Bloch phase (fdtd2d_batch_hz_bloch.h has the Hz ones)");
     if (!b->win_nf || !b->win_acc_im) return bfail(b, FDTD2D_E_STATE, "no window DFT is set");
     int rc = use_device(b);
     if (rc) return rc;
@@ -3517,6 +3625,8 @@ int fdtd2d_batch_read_probes_bloch(fdtd2d_batch_t *b, double *out, long long fir
 {
     if (!b || !out) return FDTD2D_E_ARG;
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (b->hz && !b->hz_bloch_call)
+        return refuse_hz(b, "this entry point of the Ez Bloch phase (fdtd2d_batch_hz_bloch.h has the Hz ones)");
     if (!b->nprobe || !b->probe_trace_im) return bfail(b, FDTD2D_E_STATE, "no probes are set");
     if (first < 0 || count_samples < 0 || first + count_samples > b->probe_cap)
         return bfail(b, FDTD2D_E_ARG, "samples [%lld, %lld) outside the capacity %lld", first, first + count_samples,
@@ -3529,6 +3639,104 @@ int fdtd2d_batch_read_probes_bloch(fdtd2d_batch_t *b, double *out, long long fir
     BCHK(b, hipMemcpy2D(out, w, b->probe_trace_im + first, (size_t)b->probe_cap * sizeof(double), w,
                         (size_t)b->count * b->nprobe, hipMemcpyDeviceToHost));
     return 0;
+}
+
+// ---- fdtd2d_batch_hz_bloch.h -------------------------------------------------------------------------------------
+// The phase shares the host state of fdtd2d_batch_bloch.h (`bloch` beside `hz`): the entry points below make their own
+// refusals and then run the bodies above, which refuse an Hz batch unless `hz_bloch_call` is set.
+
+namespace {
+struct HzBlochCall {
+    fdtd2d_batch *b;
+    explicit HzBlochCall(fdtd2d_batch *bb) : b(bb) { b->hz_bloch_call = true; }
+    ~HzBlochCall() { b->hz_bloch_call = false; }
+};
+
+int need_hz_bloch(fdtd2d_batch *b, const char *what)
+{
+    if (!b->hz || !b->bloch)
+        return bfail(b, FDTD2D_E_STATE, "%s needs the phase of the Hz polarisation: call fdtd2d_batch_set_hz_bloch first", what);
+    return 0;
+}
+}  // namespace
+
+int fdtd2d_batch_set_hz_bloch(fdtd2d_batch_t *b, const double *cos_phi, const double *sin_phi)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!cos_phi != !sin_phi) return bfail(b, FDTD2D_E_ARG, "cos_phi and sin_phi must both be given (or both NULL)");
+    if (!b->hz)
+        return bfail(b, FDTD2D_E_STATE, "fdtd2d_batch_set_hz_bloch needs the Hz polarisation "
+                     "(fdtd2d_batch_set_polarization); the Ez polarisation takes fdtd2d_batch_set_bloch");
+    if (!cos_phi && !b->bloch) return 0;
+    if (cos_phi && b->hzflux) return refuse_flux(b, "a Bloch phase");
+    HzBlochCall call(b);
+    return fdtd2d_batch_set_bloch(b, cos_phi, sin_phi);
+}
+
+int fdtd2d_batch_set_hz_bloch_source(fdtd2d_batch_t *b, const double *wr, const double *wi)
+{
+    if (!b) return FDTD2D_E_ARG;
+    int rc = need_hz_bloch(b, "fdtd2d_batch_set_hz_bloch_source");
+    if (rc) return rc;
+    HzBlochCall call(b);
+    return fdtd2d_batch_set_bloch_source(b, wr, wi);
+}
+
+int fdtd2d_batch_run_hz_bloch(fdtd2d_batch_t *b, int nsteps, const double *amps_re, const double *amps_im)
+{
+    if (!b) return FDTD2D_E_ARG;
+    int rc = need_hz_bloch(b, "fdtd2d_batch_run_hz_bloch");
+    if (rc) return rc;
+    HzBlochCall call(b);
+    return fdtd2d_batch_run_bloch(b, nsteps, amps_re, amps_im);
+}
+
+int fdtd2d_batch_transfer_hz_bloch(fdtd2d_batch_t *b, void *Hz_im, void *Ex_im, void *Ey_im, void *Hzx_im,
+                                   int host_dtype, int to_device)
+{
+    if (!b) return FDTD2D_E_ARG;
+    int rc = need_hz_bloch(b, "fdtd2d_batch_transfer_hz_bloch");
+    if (rc) return rc;
+    HzBlochCall call(b);
+    return fdtd2d_batch_transfer_bloch(b, Hz_im, Ex_im, Ey_im, Hzx_im, host_dtype, to_device);
+}
+
+int fdtd2d_batch_transfer_hz_bloch_dispersion(fdtd2d_batch_t *b, void *jx_im, void *qx_im, void *jy_im, void *qy_im,
+                                              int host_dtype, int to_device)
+{
+    if (!b) return FDTD2D_E_ARG;
+    int rc = need_hz_bloch(b, "fdtd2d_batch_transfer_hz_bloch_dispersion");
+    if (rc) return rc;
+    if (!b->dcj || !b->djh_im || !b->dq_im || !b->djy_im || !b->dqy_im)
+        return bfail(b, FDTD2D_E_STATE, "no pole of the Hz polarisation is set: call fdtd2d_batch_set_hz_dispersion first");
+    if (host_dtype != FDTD2D_F32 && host_dtype != FDTD2D_F64) return bfail(b, FDTD2D_E_ARG, "bad host_dtype");
+    if ((rc = use_device(b))) return rc;
+    void *dev[4] = {b->djh_im, b->dq_im, b->djy_im, b->dqy_im}, *host[4] = {jx_im, qx_im, jy_im, qy_im};
+    for (int k = 0; k < 4; ++k) {
+        if (!host[k]) continue;
+        rc = to_device ? copy_in(b, dev[k], host[k], host_dtype, b->rows, b->cols)
+                       : copy_out(b, dev[k], host[k], host_dtype, b->rows, b->cols);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int fdtd2d_batch_read_dft_window_hz_bloch(fdtd2d_batch_t *b, double *re, double *im)
+{
+    if (!b || !re || !im) return FDTD2D_E_ARG;
+    int rc = need_hz_bloch(b, "fdtd2d_batch_read_dft_window_hz_bloch");
+    if (rc) return rc;
+    HzBlochCall call(b);
+    return fdtd2d_batch_read_dft_window_bloch(b, re, im);
+}
+
+int fdtd2d_batch_read_probes_hz_bloch(fdtd2d_batch_t *b, double *out, long long first, long long count_samples)
+{
+    if (!b || !out) return FDTD2D_E_ARG;
+    int rc = need_hz_bloch(b, "fdtd2d_batch_read_probes_hz_bloch");
+    if (rc) return rc;
+    HzBlochCall call(b);
+    return fdtd2d_batch_read_probes_bloch(b, out, first, count_samples);
 }
 
 // ---- fdtd2d_batch_lattice.h --------------------------------------------------------------------------------------
@@ -3644,6 +3852,8 @@ int fdtd2d_batch_set_bloch_point_sources(fdtd2d_batch_t *b, int ncell, const int
 {
     if (!b) return FDTD2D_E_ARG;
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (b->hz && !b->hz_bloch_call)
+        return refuse_hz(b, "this entry point of the Ez Bloch phase (fdtd2d_batch_hz_bloch.h has the Hz ones)");
     if (ncell > 0 && b->lattice) return refuse_bloch(b, "a point source");
     if (ncell > 0 && b->bflux) return refuse_flux(b, "a Bloch point source");
     if (ncell > 0 && b->bdisp) return refuse_dispersive(b, "a point source (the adjoint of a dispersive medium)");
@@ -3655,6 +3865,8 @@ int fdtd2d_batch_run_bloch_channels(fdtd2d_batch_t *b, int nsteps, const double 
 {
     if (!b) return FDTD2D_E_ARG;
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (b->hz && !b->hz_bloch_call)
+        return refuse_hz(b, "this entry point of the Ez Bloch phase (fdtd2d_batch_hz_bloch.h has the Hz ones)");
     if (b->lattice) return refuse_bloch(b, "a run with channels");
     const bool lsrc = b->bflux && b->fsrc_nchan;   // line sources on the Bloch lines: they take the channels
     if (b->bflux && !lsrc) return refuse_flux(b, "a run with channels");
@@ -3709,6 +3921,8 @@ int fdtd2d_batch_hold_bloch_window(fdtd2d_batch_t *b)
 {
     if (!b) return FDTD2D_E_ARG;
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (b->hz && !b->hz_bloch_call)
+        return refuse_hz(b, "this entry point of the Ez Bloch phase (fdtd2d_batch_hz_bloch.h has the Hz ones)");
     if (b->lattice) return refuse_bloch(b, "the held window");
     if (b->bflux && !b->fsrc_nchan) return refuse_flux(b, "the held window");   // accepted once line sources are set
     if (b->bdisp) return refuse_dispersive(b, "the held window (the adjoint of a dispersive medium)");
@@ -3729,6 +3943,8 @@ int fdtd2d_batch_bloch_window_product(fdtd2d_batch_t *b, const double *coef_re, 
     if (!b) return FDTD2D_E_ARG;
     if (!coef_re || !coef_im || !out) return bfail(b, FDTD2D_E_ARG, "coef_re, coef_im and out must not be NULL");
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (b->hz && !b->hz_bloch_call)
+        return refuse_hz(b, "this entry point of the Ez Bloch phase (fdtd2d_batch_hz_bloch.h has the Hz ones)");
     if (b->lattice) return refuse_bloch(b, "the window product");
     if (b->bdisp) return refuse_dispersive(b, "the window product (the adjoint of a dispersive medium)");
     if (!b->win_nf || !b->win_acc_im) return bfail(b, FDTD2D_E_STATE, "no window DFT is set");
@@ -3760,6 +3976,8 @@ int fdtd2d_batch_bloch_probe_spectra(fdtd2d_batch_t *b, int nfreq, const double 
 {
     if (!b) return FDTD2D_E_ARG;
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (b->hz && !b->hz_bloch_call)
+        return refuse_hz(b, "this entry point of the Ez Bloch phase (fdtd2d_batch_hz_bloch.h has the Hz ones)");
     if (!b->nprobe || !b->probe_trace_im) return bfail(b, FDTD2D_E_STATE, "no probes are set");
     if (nfreq < 0 || nfreq > FDTD2D_BATCH_MAX_DFT_FREQS)
         return bfail(b, FDTD2D_E_ARG, "nfreq %d outside 0..%d", nfreq, FDTD2D_BATCH_MAX_DFT_FREQS);
@@ -3811,6 +4029,8 @@ int fdtd2d_batch_bloch_field_absmax(fdtd2d_batch_t *b, int field, double *out)
     if (!b) return FDTD2D_E_ARG;
     if (!out) return bfail(b, FDTD2D_E_ARG, "out must not be NULL");
     if (!b->bloch) return bfail(b, FDTD2D_E_STATE, "no Bloch phase is set: call fdtd2d_batch_set_bloch first");
+    if (b->hz && !b->hz_bloch_call)
+        return refuse_hz(b, "this entry point of the Ez Bloch phase (fdtd2d_batch_hz_bloch.h has the Hz ones)");
     if (field != FDTD2D_FIELD_EZ && field != FDTD2D_FIELD_HX && field != FDTD2D_FIELD_HY)
         return bfail(b, FDTD2D_E_ARG, "field %d: FDTD2D_FIELD_EZ, _HX or _HY", field);
     int rc = use_device(b);
@@ -3994,6 +4214,7 @@ int fdtd2d_batch_set_hz_flux_lines(fdtd2d_batch_t *b, int nlines, const int *lin
         return bfail(b, FDTD2D_E_ARG, "nlines %d outside 0..%d", nlines, FDTD2D_BATCH_MAX_FLUX_LINES);
     long long cells = 0;
     if (nlines > 0) {
+        if (b->hz && b->bloch) return refuse_bloch(b, "fdtd2d_batch_set_hz_flux_lines");
         if (!b->hz)
             return bfail(b, FDTD2D_E_STATE, "fdtd2d_batch_set_hz_flux_lines needs the Hz polarisation "
                          "(fdtd2d_batch_set_polarization): the lines of the Ez polarisation are fdtd2d_batch_set_flux_lines'");

@@ -56,6 +56,11 @@ array eps with random binary permittivity, a ricker line source per member):
                               hz_over_ez_dispersive, both paths and LDS sizes.  The Hz kernel does two pole updates per
                               cell in 12 LDS arrays against one in 10.  Default: 1024 members of 56 rows x 57 columns, a
                               10-cell layer, 2000 steps.
+  --hz-bloch                  instead: a Bloch phase in the Hz polarisation (BatchEngine.set_hz_bloch_phase: a phase sweep
+                              0..pi over the members, ramp weights) on 1024 periodic members of 40 x 41 with the metal strip
+                              and the pole of --hz, so that the twenty arrays stay resident, against the real Hz kernels on
+                              the same members (hz_bloch_over_hz) and against the Ez Bloch kernels with the same pole
+                              (hz_bloch_over_ez_bloch): the three medians, paths and LDS bytes per member
   --hz-flux                   instead: flux lines in the Hz polarisation (BatchEngine.set_hz_flux_lines: two whole-period
                               row lines, 10 frequencies) on the member of --hz (the metal strip with its pole) against the
                               same batch without them, and the lines of --flux on a lossless Ez batch of the same shape
@@ -146,7 +151,7 @@ Usage: python tools/bench_batch.py [--count 1024 --rows 60 --cols 60 --steps 100
                                    [--boundary {mur,pml} --pml-cells 10] [--monitors] [--adjoint] [--lossy]
                                    [--periodic] [--bloch] [--bloch-adjoint] [--dispersive] [--lattice]
                                    [--bloch-dispersive] [--dispersive-adjoint] [--flux] [--bloch-flux]
-                                   [--flux-adjoint] [--bloch-flux-adjoint] [--hz-flux]
+                                   [--flux-adjoint] [--bloch-flux-adjoint] [--hz-flux] [--hz-bloch]
 """
 import argparse
 import json
@@ -834,6 +839,69 @@ def bench_hz(count, rows, cols, steps, dtype, reps, pml_cells):
             "hz_mcell_steps_per_s": round(count * rows * cols * steps / (med_h * 1e-3) / 1e6, 1)}
 
 
+def bench_hz_bloch(count, rows, cols, steps, dtype, reps, pml_cells):
+    """A Bloch phase in the Hz polarisation (set_hz_bloch_phase, a phase sweep over the members, ramp weights) with a metal
+    strip and its pole, against the real Hz kernels on the same members and against the Ez Bloch kernels with the same
+    pole (--bloch-dispersive's family) on the same members; resident, timed alternately in one process."""
+    eps, rects, amps = members(count, rows, cols, steps)
+    c00 = courant00(eps, dtype)
+    g = max(6, pml_cells)
+    wp2 = np.zeros((count, rows, cols))
+    wp2[:, rows // 2:rows // 2 + 2, :(cols - 1) // 2] = (2 * np.pi * 70e9) ** 2     # a strip over half the period
+    rects = rects.copy()
+    rects[:, 1] = np.minimum(rects[:, 1], cols - 1 - rects[:, 3])                  # off the image column
+    phi = np.linspace(0.0, np.pi, count)
+
+    def batch(kind):
+        b = fd.BatchEngine(count, rows, cols, DT, DX, dtype=dtype, boundary="periodic")
+        b.set_polarization("ez" if kind == "ez_bloch" else "hz")
+        b.set_materials(eps.astype(dtype), fd.MU0).set_sources(rects)
+        b.set_pml(pml_cells, courant00=c00)
+        if kind == "ez_bloch":
+            b.set_bloch_phase(phi).set_bloch_source("ramp").set_bloch_dispersion(wp2, 1e11, 0.0)
+        else:
+            b.set_dispersion(wp2, 1e11, 0.0)
+        if kind == "hz_bloch":
+            b.set_hz_bloch_phase(phi).set_hz_bloch_source("ramp")
+        b.run(steps, amps).sync()                      # warm-up: code objects, clocks
+        return b
+
+    def timed(b):
+        b.reset().sync()
+        t0 = time.perf_counter()
+        b.run(steps, amps).sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    assert g <= rows // 2 and rows // 2 + 2 <= rows - 1 - g
+    kinds = ("hz", "hz_bloch", "ez_bloch")
+    with batch("hz") as hz, batch("hz_bloch") as hzb, batch("ez_bloch") as ezb:
+        engines = (hz, hzb, ezb)
+        assert all(b.dispersive for b in engines) and hzb.hz_bloch and not hz.hz_bloch and ezb.bloch and not hzb.bloch
+        l0 = hzb.launches
+        hzb.reset().run(steps, amps).sync()
+        launches = hzb.launches - l0
+        ms = {k: [] for k in kinds}
+        for _ in range(reps):
+            for k, b in zip(kinds, engines):
+                ms[k].append(timed(b))
+        paths = {k: "resident" if b.resident else "streamed" for k, b in zip(kinds, engines)}
+        lds = {k: b.lds_bytes for k, b in zip(kinds, engines)}
+        finite = bool(np.all(np.isfinite(hzb.download()[0])))
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    out = {"count": count, "rows": rows, "cols": cols, "steps": steps, "dtype": np.dtype(dtype).name,
+           "materials": "arrays", "boundary": "periodic", "pml_cells": pml_cells, "sweep": "0..pi", "reps": reps,
+           "arithmetic": fd.ARITHMETIC, "lds_arrays": {"hz": 12, "hz_bloch": 20, "ez_bloch": 16},
+           "launches_per_run": launches, "hz_bloch_finite": finite}
+    for k in kinds:
+        out.update({f"{k}_path": paths[k], f"{k}_lds_bytes_per_member": lds[k], f"{k}_workgroups_per_cu": 163840 // lds[k],
+                    f"{k}_ms": round(med[k], 4), f"{k}_ms_min": round(min(ms[k]), 4),
+                    f"{k}_ms_all": [round(v, 4) for v in ms[k]]})
+    out.update({"hz_bloch_over_hz": round(med["hz_bloch"] / med["hz"], 3),
+                "hz_bloch_over_ez_bloch": round(med["hz_bloch"] / med["ez_bloch"], 3),
+                "hz_bloch_mcell_steps_per_s": round(count * rows * cols * steps / (med["hz_bloch"] * 1e-3) / 1e6, 1)})
+    return out
+
+
 def bench_hz_flux(count, rows, cols, steps, dtype, reps, pml_cells):
     """Two whole-period row lines at 10 frequencies on the Hz member of --hz against the same member without them, and
     the same lines on the lossless Ez member of --flux at this shape against that member without them."""
@@ -1399,7 +1467,13 @@ def main():
                     help="time flux lines in the Hz polarisation against the same batch without them, beside the Ez lines")
     ap.add_argument("--hz", action="store_true",
                     help="time the Hz polarisation with a pole against the Ez dispersive kernels on periodic members")
+    ap.add_argument("--hz-bloch", action="store_true",
+                    help="time a Bloch phase in the Hz polarisation with a pole against the real Hz and the Ez Bloch kernels")
     a = ap.parse_args()
+    if a.hz_bloch:
+        print(json.dumps(bench_hz_bloch(a.count or 1024, a.rows or 40, a.cols or 41, a.steps or 2000, np.dtype(a.dtype),
+                                        a.reps, a.pml_cells)), flush=True)
+        return
     if a.hz_flux:
         print(json.dumps(bench_hz_flux(a.count or 1024, a.rows or 56, a.cols or 57, a.steps or 2000, np.dtype(a.dtype),
                                        a.reps, a.pml_cells)), flush=True)
