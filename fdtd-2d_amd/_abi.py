@@ -302,6 +302,14 @@ BATCH_HZ_BLOCH_SIGNATURES = {
     "fdtd2d_batch_read_dft_window_hz_bloch": (_i, [_vp, C.POINTER(_d), C.POINTER(_d)]),
     "fdtd2d_batch_read_probes_hz_bloch": (_i, [_vp, C.POINTER(_d), _ll, _ll]),
 }
+# every symbol include/fdtd2d_batch_hz_bloch_flux.h declares (flux lines under that phase: the sums of Hz and of the
+# tangential E of the real and of the imaginary part of the fields, and the power per member, line and frequency); the
+# ids and the option are fdtd2d_batch_flux.h's
+BATCH_HZ_BLOCH_FLUX_SIGNATURES = {
+    "fdtd2d_batch_set_hz_bloch_flux_lines": (_i, [_vp, _i, C.POINTER(_i), _i, C.POINTER(_d), _i]),
+    "fdtd2d_batch_read_hz_bloch_flux_lines": (_i, [_vp, _i, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_hz_bloch_flux": (_i, [_vp, C.POINTER(_d)]),
+}
 
 # transport callback of fdtd2d_slab_attach
 EXCHANGE_FN = C.CFUNCTYPE(_i, _vp, _vp, _vp, _vp, _vp, _ll, _vp)
@@ -359,7 +367,8 @@ def load():
                                    **BATCH_DISPERSIVE_ADJOINT_SIGNATURES, **BATCH_FLUX_SIGNATURES,
                                    **BATCH_BLOCH_FLUX_SIGNATURES, **BATCH_FLUX_ADJOINT_SIGNATURES,
                                    **BATCH_BLOCH_FLUX_ADJOINT_SIGNATURES, **BATCH_HZ_SIGNATURES,
-                                   **BATCH_HZ_FLUX_SIGNATURES, **BATCH_HZ_BLOCH_SIGNATURES}.items():
+                                   **BATCH_HZ_FLUX_SIGNATURES, **BATCH_HZ_BLOCH_SIGNATURES,
+                                   **BATCH_HZ_BLOCH_FLUX_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

@@ -25,6 +25,8 @@ fdtd2d_batch_bloch_dispersive.h): a metal unit cell with one angle of incidence 
 in the plane, with ``set_conductivity`` and ``set_dispersion`` acting on Ex and Ey (metal strips, wire grids, plasmonic
 gratings seen by in-plane E; fdtd2d_batch_hz.h).  ``set_hz_flux_lines`` gives such a batch flux lines: the transforms of Hz
 and of the tangential E, and through ``flux()`` the power that crosses each line (fdtd2d_batch_hz_flux.h).
+``set_hz_bloch_flux_lines`` gives the batch of ``set_hz_bloch_phase`` (below) those lines under the phase: the power per
+k-point, with ``flux_orders`` a metal grating's diffraction efficiencies (fdtd2d_batch_hz_bloch_flux.h).
 ``set_hz_bloch_phase`` gives a periodic batch in the Hz polarisation one Bloch phase per member: complex Hz, Ex, Ey, Hzx and
 pole state, with the conductivity and the pole acting under the phase (Brewster incidence, grating-coupled surface plasmons,
 angle sweeps of wire grids; fdtd2d_batch_hz_bloch.h).
@@ -144,6 +146,7 @@ class BatchEngine:
     """
     _lattice = None               # ((cr, sr), (cc, sc)): the (B,) rotations of a lattice engine (None: not one)
     _hz = False                   # set_polarization("hz"): Hz with Ex, Ey (fdtd2d_batch_hz.h)
+    _hzbflux = False              # set_hz_bloch_flux_lines: the flux lines are those under set_hz_bloch_phase
     _hzb = False                  # set_hz_bloch_phase: _bloch holds the rotations of fdtd2d_batch_hz_bloch.h's phase
 
     def __init__(self, count, rows, cols, dt=5e-14, dx=1e-4, dtype=np.float32, boundary="mur", device=0):
@@ -163,6 +166,7 @@ class BatchEngine:
         self._flux = None             # ((N, 4) lines, (B, F) omegas) of the flux lines
         self._bflux = False           # they are Bloch lines (set_bloch_flux_lines): complex fields, two parts
         self._hzflux = False          # they are lines of the Hz polarisation (set_hz_flux_lines): Hz and the tangential E
+        self._hzbflux = False         # they are lines under set_hz_bloch_phase (set_hz_bloch_flux_lines): two parts of those
         self._npoint = (0, 0)         # (P, K) of the point sources
         self._bloch = None            # (c, s): the (B,) rotations of a Bloch phase
         self._phi = None              # the phases as given (None with rotation=)
@@ -391,12 +395,16 @@ class BatchEngine:
         download_ezx, download_dispersion, upload_hz_dispersion, read_dft_window, read_probes), run() takes complex
         amps, and set_conductivity, set_dispersion, set_pml, set_materials, set_eps_window and reset keep working.
         Refused while it is set: set_dft, point sources and channels, set_hz_flux_lines (and this call while such lines
-        are set), set_polarization("ez"), windows and probes touching column C-1, and everything the Hz polarisation
-        refuses without it (the Ez Bloch API, the adjoint helpers and sessions)."""
+        are set; flux lines under the phase are set_hz_bloch_flux_lines', and turning the phase off is refused while
+        those are set), set_polarization("ez"), windows and probes touching column C-1, and everything the Hz
+        polarisation refuses without it (the Ez Bloch API, the adjoint helpers and sessions)."""
         if not self._hz:
             raise _abi.Fdtd2dError(_abi.E_STATE, 'set_hz_bloch_phase needs the Hz polarisation (set_polarization("hz")): '
                                                  "the Ez polarisation takes set_bloch_phase")
         if phi is None and rotation is None:
+            if self._hzbflux:
+                raise _abi.Fdtd2dError(_abi.E_STATE, "turning the Bloch phase off is not available while flux lines of the "
+                                       "Hz Bloch phase are set: remove them first (set_hz_bloch_flux_lines(None, None))")
             self._ck(self._lib.fdtd2d_batch_set_hz_bloch(self._h, None, None))
             self._bloch = self._phi = None
             self._hzb = False
@@ -990,7 +998,7 @@ class BatchEngine:
         lines are set (bit-identical fields, a smaller resident capacity: see resident_max_cells)."""
         if lines is None or len(lines) == 0:
             self._ck(self._lib.fdtd2d_batch_set_flux_lines(self._h, 0, None, 0, None, 1))
-            if not self._hzflux:
+            if not self._hzflux and not self._hzbflux:
                 self._flux, self._bflux = None, False
             return self
         self._no_hz("flux lines (the sign and the averaged component differ)")
@@ -1044,15 +1052,43 @@ class BatchEngine:
         self._flux, self._bflux, self._hzflux = (ln, w), False, True
         return self
 
+    def set_hz_bloch_flux_lines(self, lines, omegas, every=1):
+        """The flux lines of set_hz_flux_lines on a "periodic" engine in the Hz polarisation with the phase of
+        set_hz_bloch_phase, with or without set_conductivity and set_dispersion: the same lines, limits and sampling, the
+        sums taken on the real and on the imaginary part of Hz and of the tangential E (fdtd2d_batch_hz_bloch_flux.h).  On
+        a column line at column 0 the left neighbour of Ey is the one the step itself uses, rotated back across the seam.
+        The frequencies may have either sign.  lines None or empty removes them.  read_flux_lines,
+        read_hz_bloch_flux_parts, flux, flux_orders, flux_lines_in_lds and set_flux_lds serve them; a new phase,
+        set_conductivity, set_dispersion and reset() keep them, set_hz_bloch_phase(None) is refused while they are set."""
+        if lines is None or len(lines) == 0:
+            self._ck(self._lib.fdtd2d_batch_set_hz_bloch_flux_lines(self._h, 0, None, 0, None, 1))
+            if self._hzbflux:
+                self._flux, self._hzbflux = None, False
+            return self
+        if not self._hzb:
+            raise _abi.Fdtd2dError(_abi.E_STATE, "set_hz_bloch_flux_lines needs the phase of the Hz polarisation: call "
+                                   "set_hz_bloch_phase first (without a phase use set_hz_flux_lines, in the Ez "
+                                   "polarisation set_bloch_flux_lines)")
+        ln, w, every = _flux_lines(lines, omegas, every, self.count, self.rows, self.cols, True)
+        self._ck(self._lib.fdtd2d_batch_set_hz_bloch_flux_lines(self._h, len(ln), ln.ctypes.data_as(C.POINTER(C.c_int)),
+                                                                int(w.shape[1]), _dptr(w), every))
+        self._flux, self._bflux, self._hzflux, self._hzbflux = (ln, w), False, False, True
+        return self
+
     def read_flux_lines(self, raw=False):
         """(Ez_hat, Ht_hat), each complex128 (B, F, cells): the transforms on the line cells, lines concatenated in the
         order given.  Ht_hat carries the half-step factor exp(+1j * omega * dt / 2) (the H of a step lives half a step
         before its Ez) unless raw, which returns the sums as accumulated.  Serves the lines of set_flux_lines and of
         set_bloch_flux_lines (the transforms of the complex fields: those of the real part plus 1j times those of the
         imaginary part).  With the lines of set_hz_flux_lines it returns (Et_hat, Hz_hat), the electric transform first
-        as in the other polarisation, and the factor goes on Et_hat (the E of a step lives half a step before its Hz)."""
+        as in the other polarisation, and the factor goes on Et_hat (the E of a step lives half a step before its Hz);
+        with those of set_hz_bloch_flux_lines likewise, each the sum of the two parts as on the Ez Bloch lines."""
         ln, w = self._flux or (np.zeros((0, 4), np.int32), np.zeros((self.count, 0)))
         shape = (self.count, w.shape[1], int(ln[:, 3].sum()))
+        if self._hzbflux:
+            (hr, er), (hi, ei) = self.read_hz_bloch_flux_parts()
+            e, h = er + 1j * ei, hr + 1j * hi
+            return (e, h) if raw else (e * np.exp(0.5j * w * self.dt)[:, :, None], h)
         if self._hzflux:
             a = [np.empty(shape) for _ in range(4)]
             self._ck(self._lib.fdtd2d_batch_read_hz_flux_lines(self._h, *(_dptr(x) for x in a)))
@@ -1079,13 +1115,26 @@ class BatchEngine:
             out.append((a[0] + 1j * a[1], a[2] + 1j * a[3]))
         return tuple(out)
 
+    def read_hz_bloch_flux_parts(self):
+        """The raw sums of set_hz_bloch_flux_lines as the engine holds them: ((Hz_hat, Et_hat) of the real part of the
+        fields, (Hz_hat, Et_hat) of the imaginary part), each complex128 (B, F, cells), without the half-step factor."""
+        ln, w = self._flux if self._hzbflux else (np.zeros((0, 4), np.int32), np.zeros((self.count, 0)))
+        shape = (self.count, w.shape[1], int(ln[:, 3].sum()))
+        out = []
+        for part in (0, 1):
+            a = [np.empty(shape) if self._hzbflux else np.empty(1) for _ in range(4)]
+            self._ck(self._lib.fdtd2d_batch_read_hz_bloch_flux_lines(self._h, part, *(_dptr(x) for x in a)))
+            out.append((a[0] + 1j * a[1], a[2] + 1j * a[3]))
+        return tuple(out)
+
     def flux_orders(self, line=0):
         """float64 (B, F, Q), Q = C - 1: the power through a whole-period row line of set_bloch_flux_lines split over the
         diffraction orders, P_m = dx * Q * Re(E_m * conj(H_m)) with E_m = (1/Q) * sum_j Ez_hat[j] * exp(-1j * (phi + 2 pi
         m) * j / Q) and H_m likewise (Ht_hat with the half-step factor), m in np.fft.fftfreq(Q, 1/Q) order.  By Parseval
         the orders sum to flux()[:, line, :]: these are a grating's diffraction efficiencies before normalisation.
-        Host NumPy over read_flux_lines()."""
-        if not self._bflux:
+        Host NumPy over read_flux_lines().  On the lines of set_hz_bloch_flux_lines, with the phase of
+        set_hz_bloch_phase: P_m = -dx * Q * Re(H_m * conj(E_m)) from Hz_hat and Et_hat (the half-step factor on Et_hat)."""
+        if not self._bflux and not self._hzbflux:
             raise _abi.Fdtd2dError(_abi.E_STATE, "no Bloch flux lines are set")
         ln, _ = self._flux
         Q = self.cols - 1
@@ -1100,6 +1149,8 @@ class BatchEngine:
         E, H = (a[:, :, o:o + Q] for a in self.read_flux_lines())
         envelope = np.exp(-1j * phi[:, None, None] * np.arange(Q)[None, None, :] / Q)
         Em, Hm = np.fft.fft(E * envelope, axis=2) / Q, np.fft.fft(H * envelope, axis=2) / Q
+        if not self._bflux:           # the Hz polarisation: S_y = -Ex Hz
+            return -self.dx * Q * np.real(Hm * np.conj(Em))
         return self.dx * Q * np.real(Em * np.conj(Hm))
 
     def flux(self) -> np.ndarray:
@@ -1107,12 +1158,13 @@ class BatchEngine:
         Re(Ez_hat * conj(Ht_hat)), s = +1 for a row line and -1 for a column line, formed on the device.  No factor 1/2
         and no normalisation: take ratios.  With the lines of set_hz_flux_lines the sum is of Re(Hz_hat * conj(Et_hat)) and
         s = -1 for a row line, +1 for a column line (S_y = -Ex Hz, S_x = Ey Hz): a line counts power towards increasing
-        row or column in either polarisation."""
+        row or column in either polarisation.  The lines of set_hz_bloch_flux_lines: the same on the complex spectra."""
         ln, w = self._flux or (np.zeros((0, 4), np.int32), np.zeros((self.count, 0)))
         out = np.empty((self.count, len(ln), w.shape[1]))
         buf = out if out.size else np.empty(1)     # a refused read still passes a valid pointer
         fn = (self._lib.fdtd2d_batch_bloch_flux if self._bflux else
-              self._lib.fdtd2d_batch_hz_flux if self._hzflux else self._lib.fdtd2d_batch_flux)
+              self._lib.fdtd2d_batch_hz_flux if self._hzflux else
+              self._lib.fdtd2d_batch_hz_bloch_flux if self._hzbflux else self._lib.fdtd2d_batch_flux)
         self._ck(fn(self._h, _dptr(buf)))
         return out
 
@@ -1651,8 +1703,9 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
                    dtype=np.float64, boundary="mur", omega=None, dft_every=1, device=0, pml_cells=40,
                    dft_window=None, window_omegas=None, probes=None, bloch_phase=None, source_weights=None,
                    dispersion=None, bloch_dispersion=None, polarization="ez", conductivity=None,
-                   hz_bloch_phase=None, hz_flux_lines=None, hz_flux_omegas=None, bloch_flux_lines=None,
-                   bloch_flux_omegas=None, flux_lines=None, flux_omegas=None):
+                   hz_bloch_phase=None, hz_flux_lines=None, hz_flux_omegas=None, hz_bloch_flux_lines=None,
+                   hz_bloch_flux_omegas=None, bloch_flux_lines=None, bloch_flux_omegas=None, flux_lines=None,
+                   flux_omegas=None):
     """run_fdtd for B members of one shape at once: zero fields, Courant check per member, nsteps of
     H -> E -> source with t = i*dt.
 
@@ -1687,6 +1740,8 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
     flux_lines.  hz_bloch_phase (polarization "hz" with boundary "periodic" alone): a scalar or (B,) in radians, the
     Bloch phase of set_hz_bloch_phase; every returned array is then complex, dispersion and conductivity act under the
     phase, source_weights goes to set_hz_bloch_source, and omega and hz_flux_lines are not available.
+    hz_bloch_flux_lines with hz_bloch_flux_omegas (with hz_bloch_phase alone): flux monitors as set_hz_bloch_flux_lines
+    takes them, sampled every `dft_every` steps; the flux array is appended as with flux_lines.
     """
     from .api import MU0
     eps = np.asarray(eps)
@@ -1754,6 +1809,12 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
             raise ValueError("omega (the whole-grid transform) is not available with hz_bloch_phase: use dft_window")
         if hz_flux_lines is not None:
             raise ValueError("hz_flux_lines is not available with hz_bloch_phase")
+    if (hz_bloch_flux_lines is None) != (hz_bloch_flux_omegas is None):
+        raise ValueError("hz_bloch_flux_lines and hz_bloch_flux_omegas must be given together")
+    if hz_bloch_flux_lines is not None:
+        if hz_bloch_phase is None:
+            raise ValueError("hz_bloch_flux_lines needs hz_bloch_phase: without a phase use hz_flux_lines")
+        _flux_lines(hz_bloch_flux_lines, hz_bloch_flux_omegas, dft_every, B, R, Cc, True)
     if (hz_flux_lines is None) != (hz_flux_omegas is None):
         raise ValueError("hz_flux_lines and hz_flux_omegas must be given together")
     if hz_flux_lines is not None:
@@ -1844,6 +1905,8 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
             eng.set_bloch_flux_lines(bloch_flux_lines, bloch_flux_omegas, dft_every)
         if hz_flux_lines is not None:
             eng.set_hz_flux_lines(hz_flux_lines, hz_flux_omegas, dft_every)
+        if hz_bloch_flux_lines is not None:
+            eng.set_hz_bloch_flux_lines(hz_bloch_flux_lines, hz_bloch_flux_omegas, dft_every)
         eng.run(nsteps, None if waveform is None else _waveform_amps(waveform, fcs, nsteps, dt))
         out = eng.download()
         if omega is not None:
@@ -1852,7 +1915,8 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
             out += (eng.read_dft_window(),)
         if cells is not None:
             out += (eng.read_probes(0, int(nsteps)),)
-        if flux_lines is not None or bloch_flux_lines is not None or hz_flux_lines is not None:
+        if (flux_lines is not None or bloch_flux_lines is not None or hz_flux_lines is not None or
+                hz_bloch_flux_lines is not None):
             out += (eng.flux(),)
         return out
 

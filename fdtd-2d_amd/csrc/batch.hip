@@ -27,6 +27,8 @@
 // the imaginary part.
 // With the lines of fdtd2d_batch_hz_flux.h a batch in the Hz polarisation takes the kernels of batch_hz_flux.hip, with or
 // without a conductivity and a pole; the lines share that host state too (`hzflux` beside `flux_nl`).
+// With the lines of fdtd2d_batch_hz_bloch_flux.h an Hz Bloch batch takes the kernels of batch_hz_bloch_flux.hip; the lines
+// share the host state of the Ez Bloch lines (`hzbflux` beside `flux_nl`, the imaginary part's sums in flux_acc_im).
 // With the phase of fdtd2d_batch_hz_bloch.h a periodic batch in the Hz polarisation holds `hz` and `bloch` together: the
 // imaginary parts, the rotations, the weights and the monitors are the Bloch phase's, a pole adds the imaginary parts of
 // Jx, Qx (djh_im, dq_im) and Jy, Qy (djy_im, dqy_im), and every run takes the kernels of batch_hz_bloch.hip.
@@ -44,6 +46,7 @@
 #include "../../include/fdtd2d_batch_flux_adjoint.h"
 #include "../../include/fdtd2d_batch_hz.h"
 #include "../../include/fdtd2d_batch_hz_bloch.h"
+#include "../../include/fdtd2d_batch_hz_bloch_flux.h"
 #include "../../include/fdtd2d_batch_hz_flux.h"
 #include "../../include/fdtd2d_batch_lattice.h"
 #include "../../include/fdtd2d_batch_lossy.h"
@@ -75,6 +78,7 @@
 #include "kernels_batch_flux_adjoint.hpp"
 #include "kernels_batch_hz.hpp"
 #include "kernels_batch_hz_bloch.hpp"
+#include "kernels_batch_hz_bloch_flux.hpp"
 #include "kernels_batch_hz_flux.hpp"
 #include "kernels_batch_lattice.hpp"
 #include "kernels_batch_lossy.hpp"
@@ -190,6 +194,9 @@ struct fdtd2d_batch {
     // fdtd2d_batch_set_hz_flux_lines: the lines above on a batch in the Hz polarisation.  flux_acc holds the sums of Hz
     // where the Ez lines hold those of Ez, and those of the tangential E where they hold those of the tangential H
     bool hzflux = false;
+    // fdtd2d_batch_set_hz_bloch_flux_lines: the lines above on an Hz Bloch batch.  flux_acc holds the sums of Hz and of the
+    // tangential E of the real part of the fields and flux_acc_im, of the same layout, those of the imaginary part
+    bool hzbflux = false;
     // line sources on the flux lines (fdtd2d_batch_flux_adjoint.h): count x flux_cells x fsrc_nchan weights each
     // (nullptr: no such part); fsrc_nchan = 0 without them
     int fsrc_nchan = 0;
@@ -396,7 +403,7 @@ bool win_acc_in_lds(const fdtd2d_batch *b)
 // flux lines: the sums of one member (of both parts on a Bloch batch); in LDS behind the window's accumulators (wherever
 // those live) when they fit too
 size_t flux_part_bytes(const fdtd2d_batch *b) { return b->flux_nl ? 32 * (size_t)b->flux_nff * b->flux_cells : 0; }
-size_t flux_acc_bytes(const fdtd2d_batch *b) { return (b->bflux ? 2 : 1) * flux_part_bytes(b); }
+size_t flux_acc_bytes(const fdtd2d_batch *b) { return (b->bflux || b->hzbflux ? 2 : 1) * flux_part_bytes(b); }
 bool flux_acc_in_lds(const fdtd2d_batch *b)
 {
     return b->flux_nl && b->flux_lds_opt != 0 &&
@@ -1359,10 +1366,78 @@ template <class T> int run_hz_bloch(fdtd2d_batch *b, int nsteps, const double *a
     return 0;
 }
 
+// ---- Hz Bloch runs with flux lines (fdtd2d_batch_hz_bloch_flux.h): the paths of run_hz_bloch with the kernels of
+// batch_hz_bloch_flux.hip, whose streamed E launch also writes the lines' phasors
+template <class T> int run_hz_bloch_flux(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride)
+{
+    const int disp = b->dcj ? 1 : 0;
+    if (!b->periodic || !b->ezx || !b->ca || !b->cb || !b->ch || !b->ez_im || !b->hx_im || !b->hy_im || !b->ezx_im ||
+        !b->rho || !b->bloch_w || !b->flux_acc || !b->flux_acc_im || !b->flux_omega || !b->flux_ph ||
+        (disp && (!b->djh || !b->dq || !b->djy || !b->dqy || !b->djh_im || !b->dq_im || !b->djy_im || !b->dqy_im ||
+                  !b->da || !b->dck)))
+        return bfail(b, FDTD2D_E_STATE, "Hz Bloch batch with flux lines without its arrays");
+    const fdtd::BatchHzBlochFluxKernels &K = fdtd::batch_hz_bloch_flux_kernels<T>();
+    fdtd::BatchPml<T> p = pml_view<T>(b);
+    fdtd::BatchMon m = mon_view(b);
+    fdtd::BatchBloch<T> bl = bloch_view<T>(b, false);
+    fdtd::BatchHzBlochDisp<T> d{(T *)b->djh,    (T *)b->dq,    (T *)b->djy,    (T *)b->dqy,
+                                (T *)b->djh_im, (T *)b->dq_im, (T *)b->djy_im, (T *)b->dqy_im,
+                                (const T *)b->dcj, (const T *)b->da, (const T *)b->dck};
+    fdtd::BatchFlux f = flux_view(b);
+    double *facc_im = b->flux_acc_im;
+    b->run_conj = false;
+    const T *ca = (const T *)b->ca;
+    if (use_resident(b)) {
+        const int cells = b->rows * b->cols, threads = resident_threads(cells);
+        const int per_thread = (cells + threads - 1) / threads;
+        if (per_thread > 4)
+            return bfail(b, FDTD2D_E_STATE, "%d cells per thread exceed the Hz Bloch resident kernel's 4", per_thread);
+        const void *kern = K.resident[disp];
+        const size_t lds = lds_bytes(b);
+        BCHK(b, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        int per_cu = 0, cus = 0;
+        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds));
+        BCHK(b, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
+        if (per_cu < 1)
+            return bfail(b, FDTD2D_E_STATE, "Hz Bloch flux resident kernel does not fit a CU (%zu B of LDS)", lds);
+        const long long round = (long long)per_cu * cus;
+        const int blocks = (int)(b->count < round ? b->count : round);
+        const int chunk = b->steps_per_launch > 0 ? b->steps_per_launch : nsteps;
+        for (int n = 0; n < nsteps; n += chunk) {
+            int n0 = n, nt = nsteps - n < chunk ? nsteps - n : chunk;
+            long long step_base = b->step;
+            fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+            v.ce = (const T *)b->cb;
+            void *args[] = {&v, &p, &m, &bl, &d, &f, &facc_im, &ca, &n0, &nt, &step_base};
+            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads), args, lds);
+            if (rc) return rc;
+            b->launches++;
+            b->step += nt;
+        }
+        return 0;
+    }
+    const int cells = b->rows * b->cols;
+    const dim3 grid((cells + 255) / 256, b->count < 65535 ? b->count : 65535);
+    for (int n = 0; n < nsteps; ++n) {
+        fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+        v.ce = (const T *)b->cb;
+        long long step = b->step + 1;
+        int rc;
+        void *e_args[] = {&v, &p, &m, &bl, &d, &f, &ca, &step};
+        void *h_args[] = {&v, &p, &m, &bl, &f, &facc_im, &n, &step};
+        if ((rc = launch_ptr(b, K.e[disp], grid, dim3(256), e_args, 0))) return rc;
+        if ((rc = launch_ptr(b, K.h, grid, dim3(256), h_args, 0))) return rc;
+        b->launches += 2;
+        b->step++;
+    }
+    return 0;
+}
+
 template <class T>
 int run_impl(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride, fdtd::BatchPts *pts = nullptr,
              fdtd::BatchFluxSrc *fs = nullptr)
 {
+    if (b->hzbflux) return run_hz_bloch_flux<T>(b, nsteps, amps, amp_stride);
     if (b->hz && b->bloch) return run_hz_bloch<T>(b, nsteps, amps, amp_stride);
     if (b->hz) return run_hz<T>(b, nsteps, amps, amp_stride, pts);
     if (b->bflux) return run_bloch_flux<T>(b, nsteps, amps, amp_stride);
@@ -1639,6 +1714,9 @@ int refuse_flux(fdtd2d_batch *b, const char *what)
     if (b->hzflux)
         return bfail(b, FDTD2D_E_STATE, "%s is not available while flux lines of the Hz polarisation are set: remove them "
                      "first (fdtd2d_batch_set_hz_flux_lines with nlines = 0)", what);
+    if (b->hzbflux)
+        return bfail(b, FDTD2D_E_STATE, "%s is not available while flux lines of the Hz Bloch phase are set: remove them "
+                     "first (fdtd2d_batch_set_hz_bloch_flux_lines with nlines = 0)", what);
     return bfail(b, FDTD2D_E_STATE, "%s is not available while flux lines are set: remove them first "
                  "(fdtd2d_batch_set_flux_lines with nlines = 0)", what);
 }
@@ -2424,7 +2502,7 @@ int fdtd2d_batch_reset(fdtd2d_batch_t *b)
                                b->stream));
     if (b->flux_nl)
         BCHK(b, hipMemsetAsync(b->flux_acc, 0, (size_t)b->count * flux_part_bytes(b), b->stream));
-    if (b->bflux)
+    if (b->bflux || b->hzbflux)
         BCHK(b, hipMemsetAsync(b->flux_acc_im, 0, (size_t)b->count * flux_part_bytes(b), b->stream));
     b->win_step0 = 0;
     b->probe_step0 = 0;
@@ -3447,7 +3525,7 @@ int fdtd2d_batch_set_bloch(fdtd2d_batch_t *b, const double *cos_phi, const doubl
     if (!cos_phi) return b->bloch ? bloch_off(b) : 0;
     if (b->hz && !b->hz_bloch_call) return refuse_hz(b, "a Bloch phase");
     if (b->dcj && !b->bdisp && !b->hz) return refuse_dispersive(b, "a Bloch phase");
-    if (b->flux_nl && !b->bflux) return refuse_flux(b, "a Bloch phase");
+    if (b->flux_nl && !b->bflux && !b->hzbflux) return refuse_flux(b, "a Bloch phase");
     if (!b->periodic)
         return bfail(b, FDTD2D_E_STATE, "a Bloch phase needs periodic columns: call fdtd2d_batch_set_periodic first");
     for (int m = 0; m < b->count; ++m)
@@ -3669,6 +3747,7 @@ int fdtd2d_batch_set_hz_bloch(fdtd2d_batch_t *b, const double *cos_phi, const do
                      "(fdtd2d_batch_set_polarization); the Ez polarisation takes fdtd2d_batch_set_bloch");
     if (!cos_phi && !b->bloch) return 0;
     if (cos_phi && b->hzflux) return refuse_flux(b, "a Bloch phase");
+    if (!cos_phi && b->hzbflux) return refuse_flux(b, "turning the Bloch phase off");
     HzBlochCall call(b);
     return fdtd2d_batch_set_bloch(b, cos_phi, sin_phi);
 }
@@ -4106,7 +4185,7 @@ int fdtd2d_batch_set_flux_lines(fdtd2d_batch_t *b, int nlines, const int *lines,
             cells += n;
         }
         if (!b->have_mat) return bfail(b, FDTD2D_E_STATE, "materials not set: call fdtd2d_batch_set_materials first");
-    } else if (!b->flux_nl || b->hzflux) {      // the lines of fdtd2d_batch_hz_flux.h are not this call's to remove
+    } else if (!b->flux_nl || b->hzflux || b->hzbflux) {   // the lines of the Hz headers are not this call's to remove
         return 0;
     }
     int rc = use_device(b);
@@ -4165,6 +4244,8 @@ int fdtd2d_batch_read_flux_lines(fdtd2d_batch_t *b, double *ez_re, double *ez_im
     if (!b->flux_nl) return bfail(b, FDTD2D_E_STATE, "no flux lines are set");
     if (b->bflux) return bfail(b, FDTD2D_E_STATE, "the lines are Bloch lines: use fdtd2d_batch_read_bloch_flux_lines");
     if (b->hzflux) return bfail(b, FDTD2D_E_STATE, "the lines are those of the Hz polarisation: use fdtd2d_batch_read_hz_flux_lines");
+    if (b->hzbflux)
+        return bfail(b, FDTD2D_E_STATE, "the lines are those of the Hz Bloch phase: use fdtd2d_batch_read_hz_bloch_flux_lines");
     int rc = use_device(b);
     if (rc) return rc;
     BCHK(b, hipStreamSynchronize(b->stream));
@@ -4185,6 +4266,7 @@ int fdtd2d_batch_flux(fdtd2d_batch_t *b, double *out)
     if (!b->flux_nl) return bfail(b, FDTD2D_E_STATE, "no flux lines are set");
     if (b->bflux) return bfail(b, FDTD2D_E_STATE, "the lines are Bloch lines: use fdtd2d_batch_bloch_flux");
     if (b->hzflux) return bfail(b, FDTD2D_E_STATE, "the lines are those of the Hz polarisation: use fdtd2d_batch_hz_flux");
+    if (b->hzbflux) return bfail(b, FDTD2D_E_STATE, "the lines are those of the Hz Bloch phase: use fdtd2d_batch_hz_bloch_flux");
     int rc = use_device(b);
     if (rc) return rc;
     const size_t n = (size_t)b->count * b->flux_nl * b->flux_nff;
@@ -4284,6 +4366,8 @@ int fdtd2d_batch_set_hz_flux_lines(fdtd2d_batch_t *b, int nlines, const int *lin
 int fdtd2d_batch_read_hz_flux_lines(fdtd2d_batch_t *b, double *hz_re, double *hz_im, double *et_re, double *et_im)
 {
     if (!b || !hz_re || !hz_im || !et_re || !et_im) return FDTD2D_E_ARG;
+    if (b->hzbflux)
+        return bfail(b, FDTD2D_E_STATE, "the lines are those of the Hz Bloch phase: use fdtd2d_batch_read_hz_bloch_flux_lines");
     if (!b->hzflux) return bfail(b, FDTD2D_E_STATE, "no flux lines of the Hz polarisation are set");
     int rc = use_device(b);
     if (rc) return rc;
@@ -4302,12 +4386,139 @@ int fdtd2d_batch_hz_flux(fdtd2d_batch_t *b, double *out)
 {
     if (!b) return FDTD2D_E_ARG;
     if (!out) return bfail(b, FDTD2D_E_ARG, "out must not be NULL");
+    if (b->hzbflux) return bfail(b, FDTD2D_E_STATE, "the lines are those of the Hz Bloch phase: use fdtd2d_batch_hz_bloch_flux");
     if (!b->hzflux) return bfail(b, FDTD2D_E_STATE, "no flux lines of the Hz polarisation are set");
     int rc = use_device(b);
     if (rc) return rc;
     const size_t n = (size_t)b->count * b->flux_nl * b->flux_nff;
     if ((rc = scratch(b, n * sizeof(double)))) return rc;
     fdtd::batch_hz_flux_launch(flux_view(b), (double *)b->dsg, b->count, b->dt, b->dx, b->stream);
+    BCHK(b, hipGetLastError());
+    b->launches++;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    BCHK(b, hipMemcpy(out, b->dsg, n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- fdtd2d_batch_hz_bloch_flux.h ---------------------------------------------------------------------------------
+// The lines share the host state of fdtd2d_batch_flux.h's (`flux_nl` is set too, so the capacity rule, the info ids, the
+// placement option and the refusals while lines are set serve them as they are) and flux_acc_im of the Ez Bloch lines;
+// run_impl takes the kernels of batch_hz_bloch_flux.hip while `hzbflux` is set.
+
+extern "C" {
+
+int fdtd2d_batch_set_hz_bloch_flux_lines(fdtd2d_batch_t *b, int nlines, const int *lines, int nfreq, const double *omega,
+                                         int every)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (nlines < 0 || nlines > FDTD2D_BATCH_MAX_FLUX_LINES)
+        return bfail(b, FDTD2D_E_ARG, "nlines %d outside 0..%d", nlines, FDTD2D_BATCH_MAX_FLUX_LINES);
+    long long cells = 0;
+    if (nlines > 0) {
+        if (!b->hz || !b->bloch || !b->periodic || b->lattice)
+            return bfail(b, FDTD2D_E_STATE, "fdtd2d_batch_set_hz_bloch_flux_lines needs the phase of the Hz polarisation: "
+                         "call fdtd2d_batch_set_hz_bloch first (without a phase use fdtd2d_batch_set_hz_flux_lines, in the Ez "
+                         "polarisation fdtd2d_batch_set_bloch_flux_lines)");
+        if (nfreq < 1 || nfreq > FDTD2D_BATCH_MAX_FLUX_FREQS)
+            return bfail(b, FDTD2D_E_ARG, "nfreq %d outside 1..%d", nfreq, FDTD2D_BATCH_MAX_FLUX_FREQS);
+        if (!lines || !omega) return bfail(b, FDTD2D_E_ARG, "lines and omega must not be NULL");
+        if (every < 1) return bfail(b, FDTD2D_E_ARG, "every must be >= 1");
+        const int R = b->rows, C = b->cols;
+        for (int k = 0; k < nlines; ++k) {
+            const int o = lines[4 * k], at = lines[4 * k + 1], first = lines[4 * k + 2], n = lines[4 * k + 3];
+            if (o != 0 && o != 1) return bfail(b, FDTD2D_E_ARG, "line %d: orientation %d (0 row, 1 column)", k, o);
+            if (o == 0 && (at < 1 || at > R - 2))
+                return bfail(b, FDTD2D_E_ARG, "line %d: row %d outside 1..%d", k, at, R - 2);
+            if (o == 1 && (at < 0 || at > C - 2))
+                return bfail(b, FDTD2D_E_ARG, "line %d: column %d outside 0..%d (column C-1 is the image of column 0)", k, at,
+                             C - 2);
+            const int extent = o == 1 ? R : C - 1;
+            if (n < 1 || first < 0 || (long long)first + n > extent)
+                return bfail(b, FDTD2D_E_ARG, "line %d: cells [%d, %d + %d) are empty or run past %d", k, first, first, n,
+                             extent);
+            cells += n;
+        }
+        if (!b->have_mat) return bfail(b, FDTD2D_E_STATE, "materials not set: call fdtd2d_batch_set_materials first");
+    } else if (!b->hzbflux) {
+        return 0;
+    }
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));   // a running launch may still use the old lines
+    if (nlines == 0) {
+        for (void **p : {(void **)&b->flux_acc, (void **)&b->flux_omega, (void **)&b->flux_ph, (void **)&b->flux_acc_im})
+            release(p);
+        b->flux_nl = b->flux_nff = b->flux_cells = 0;
+        b->hzbflux = false;
+        return 0;
+    }
+    // the new buffers before the old ones go: a refused call keeps the old lines
+    const size_t acc = (size_t)b->count * 32 * nfreq * (size_t)cells, om = (size_t)b->count * nfreq * sizeof(double);
+    double *nacc = nullptr, *nacci = nullptr, *nom = nullptr, *nph = nullptr;
+    auto drop = [&]() {
+        for (void **p : {(void **)&nacc, (void **)&nacci, (void **)&nom, (void **)&nph}) release(p);
+    };
+    if ((rc = alloc(b, (void **)&nacc, acc)) || (rc = alloc(b, (void **)&nacci, acc)) ||
+        (rc = alloc(b, (void **)&nom, om)) || (rc = alloc(b, (void **)&nph, 2 * om))) {
+        drop();
+        return rc;
+    }
+    hipError_t e = hipMemsetAsync(nacc, 0, acc, b->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(nacci, 0, acc, b->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(nph, 0, 2 * om, b->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    if (e == hipSuccess) e = hipMemcpy(nom, omega, om, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        drop();
+        return bfail(b, -(1000 + (int)e), "setting up the flux lines of the Hz Bloch phase failed: %s", hipGetErrorString(e));
+    }
+    for (void **p : {(void **)&b->flux_acc, (void **)&b->flux_omega, (void **)&b->flux_ph, (void **)&b->flux_acc_im})
+        release(p);
+    b->flux_acc = nacc;
+    b->flux_acc_im = nacci;
+    b->flux_omega = nom;
+    b->flux_ph = nph;
+    std::copy(lines, lines + 4 * nlines, b->flux_line);
+    b->flux_nl = nlines;
+    b->flux_nff = nfreq;
+    b->flux_cells = (int)cells;
+    b->flux_every = every;
+    b->flux_step0 = b->step;
+    b->hzbflux = true;
+    return 0;
+}
+
+int fdtd2d_batch_read_hz_bloch_flux_lines(fdtd2d_batch_t *b, int part, double *hz_re, double *hz_im, double *et_re,
+                                          double *et_im)
+{
+    if (!b || !hz_re || !hz_im || !et_re || !et_im) return FDTD2D_E_ARG;
+    if (part != 0 && part != 1) return bfail(b, FDTD2D_E_ARG, "part %d (0 real, 1 imaginary)", part);
+    if (!b->hzbflux) return bfail(b, FDTD2D_E_STATE, "no flux lines of the Hz Bloch phase are set");
+    int rc = use_device(b);
+    if (rc) return rc;
+    BCHK(b, hipStreamSynchronize(b->stream));
+    const size_t per = (size_t)b->flux_nff * b->flux_cells;   // one member's Hz re (or any of the four)
+    std::vector<double> acc((size_t)b->count * 4 * per);
+    BCHK(b, hipMemcpy(acc.data(), part ? b->flux_acc_im : b->flux_acc, acc.size() * sizeof(double), hipMemcpyDeviceToHost));
+    double *out[4] = {hz_re, hz_im, et_re, et_im};
+    for (int m = 0; m < b->count; ++m)
+        for (int k = 0; k < 4; ++k)
+            std::memcpy(out[k] + m * per, acc.data() + (4 * (size_t)m + k) * per, per * sizeof(double));
+    return 0;
+}
+
+int fdtd2d_batch_hz_bloch_flux(fdtd2d_batch_t *b, double *out)
+{
+    if (!b) return FDTD2D_E_ARG;
+    if (!out) return bfail(b, FDTD2D_E_ARG, "out must not be NULL");
+    if (!b->hzbflux) return bfail(b, FDTD2D_E_STATE, "no flux lines of the Hz Bloch phase are set");
+    int rc = use_device(b);
+    if (rc) return rc;
+    const size_t n = (size_t)b->count * b->flux_nl * b->flux_nff;
+    if ((rc = scratch(b, n * sizeof(double)))) return rc;
+    fdtd::batch_hz_bloch_flux_launch(flux_view(b), b->flux_acc_im, (double *)b->dsg, b->count, b->dt, b->dx, b->stream);
     BCHK(b, hipGetLastError());
     b->launches++;
     BCHK(b, hipStreamSynchronize(b->stream));
@@ -4414,6 +4625,8 @@ int fdtd2d_batch_read_bloch_flux_lines(fdtd2d_batch_t *b, int part, double *ez_r
 {
     if (!b || !ez_re || !ez_im || !ht_re || !ht_im) return FDTD2D_E_ARG;
     if (part != 0 && part != 1) return bfail(b, FDTD2D_E_ARG, "part %d (0 real, 1 imaginary)", part);
+    if (b->hzbflux)
+        return bfail(b, FDTD2D_E_STATE, "the lines are those of the Hz Bloch phase: use fdtd2d_batch_read_hz_bloch_flux_lines");
     if (!b->bflux) return bfail(b, FDTD2D_E_STATE, "no Bloch flux lines are set");
     int rc = use_device(b);
     if (rc) return rc;
@@ -4432,6 +4645,7 @@ int fdtd2d_batch_bloch_flux(fdtd2d_batch_t *b, double *out)
 {
     if (!b) return FDTD2D_E_ARG;
     if (!out) return bfail(b, FDTD2D_E_ARG, "out must not be NULL");
+    if (b->hzbflux) return bfail(b, FDTD2D_E_STATE, "the lines are those of the Hz Bloch phase: use fdtd2d_batch_hz_bloch_flux");
     if (!b->bflux) return bfail(b, FDTD2D_E_STATE, "no Bloch flux lines are set");
     int rc = use_device(b);
     if (rc) return rc;

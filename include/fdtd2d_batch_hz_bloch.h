@@ -59,8 +59,9 @@
  * whole-grid fdtd2d_batch_set_dft, fdtd2d_batch_set_point_sources and fdtd2d_batch_run_channels,
  * fdtd2d_batch_set_hz_flux_lines (and this header's phase while such lines are set), fdtd2d_batch_set_polarization to
  * the Ez polarisation, fdtd2d_batch_set_periodic(b, 0), and everything the Hz polarisation refuses without a phase,
- * fdtd2d_batch_set_bloch and the other entry points of the Ez Bloch headers included (all FDTD2D_E_STATE).  Not
- * available: the lattice mode, flux lines under the phase, adjoints. */
+ * fdtd2d_batch_set_bloch and the other entry points of the Ez Bloch headers included (all FDTD2D_E_STATE).  Flux lines
+ * under the phase are fdtd2d_batch_hz_bloch_flux.h's (fdtd2d_batch_set_hz_bloch_flux_lines); while they are set, turning
+ * the phase off is refused (FDTD2D_E_STATE) and a new phase keeps them.  Not available: the lattice mode, adjoints. */
 #ifndef FDTD2D_BATCH_HZ_BLOCH_H
 #define FDTD2D_BATCH_HZ_BLOCH_H
 
@@ -78,11 +79,12 @@ extern "C" {
 enum { FDTD2D_BATCH_INFO_HZ_BLOCH = FDTD2D_BATCH_INFO_FLUX_LDS + 2 };
 
 /* cos_phi, sin_phi: count float64 values each, rounded to the batch dtype.  Needs the Hz polarisation and periodic
- * columns (FDTD2D_E_STATE otherwise), no whole-grid transform, point sources or flux lines (FDTD2D_E_STATE), no window or
- * probe touching column C-1 and finite values (FDTD2D_E_ARG).  The first call allocates the imaginary Hz, Ex, Ey and Hzx
- * as zero, the unit source weights, the imaginary parts of the monitors that are set and, if a pole is set, the
- * imaginary Jx, Qx, Jy, Qy as zero; a later call changes the rotations alone.  NULL, NULL turns the phase off and frees
- * them: the batch is a plain periodic Hz batch again, its real parts as they are.  Synchronous. */
+ * columns (FDTD2D_E_STATE otherwise), no whole-grid transform, point sources or lines of fdtd2d_batch_hz_flux.h
+ * (FDTD2D_E_STATE), no window or probe touching column C-1 and finite values (FDTD2D_E_ARG).  The first call allocates
+ * the imaginary Hz, Ex, Ey and Hzx as zero, the unit source weights, the imaginary parts of the monitors that are set
+ * and, if a pole is set, the imaginary Jx, Qx, Jy, Qy as zero; a later call changes the rotations alone.  NULL, NULL
+ * turns the phase off and frees them: the batch is a plain periodic Hz batch again, its real parts as they are.
+ * Synchronous. */
 int fdtd2d_batch_set_hz_bloch(fdtd2d_batch_t *b, const double *cos_phi, const double *sin_phi);
 
 /* The source weights: wr, wi of shape (count, C-1), float64, finite; NULL, NULL restores ones.  Needs the phase. */

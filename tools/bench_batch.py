@@ -61,6 +61,10 @@ array eps with random binary permittivity, a ricker line source per member):
                               and the pole of --hz, so that the twenty arrays stay resident, against the real Hz kernels on
                               the same members (hz_bloch_over_hz) and against the Ez Bloch kernels with the same pole
                               (hz_bloch_over_ez_bloch): the three medians, paths and LDS bytes per member
+  --hz-bloch-flux             instead: flux lines under that phase (BatchEngine.set_hz_bloch_flux_lines: two whole-period row
+                              lines, 10 frequencies) on the member of --hz-bloch against the same batch without them, both
+                              resident, timed alternately in one process: hz_bloch_ms, hz_bloch_flux_ms, their ratio,
+                              where the sums live (LDS or global memory) and the LDS bytes per member
   --hz-flux                   instead: flux lines in the Hz polarisation (BatchEngine.set_hz_flux_lines: two whole-period
                               row lines, 10 frequencies) on the member of --hz (the metal strip with its pole) against the
                               same batch without them, and the lines of --flux on a lossless Ez batch of the same shape
@@ -151,7 +155,7 @@ Usage: python tools/bench_batch.py [--count 1024 --rows 60 --cols 60 --steps 100
                                    [--boundary {mur,pml} --pml-cells 10] [--monitors] [--adjoint] [--lossy]
                                    [--periodic] [--bloch] [--bloch-adjoint] [--dispersive] [--lattice]
                                    [--bloch-dispersive] [--dispersive-adjoint] [--flux] [--bloch-flux]
-                                   [--flux-adjoint] [--bloch-flux-adjoint] [--hz-flux] [--hz-bloch]
+                                   [--flux-adjoint] [--bloch-flux-adjoint] [--hz-flux] [--hz-bloch] [--hz-bloch-flux]
 """
 import argparse
 import json
@@ -902,6 +906,70 @@ def bench_hz_bloch(count, rows, cols, steps, dtype, reps, pml_cells):
     return out
 
 
+def bench_hz_bloch_flux(count, rows, cols, steps, dtype, reps, pml_cells):
+    """Two whole-period row lines at 10 frequencies on the member of --hz-bloch (a phase sweep, ramp weights, the metal
+    strip with its pole) against the same member without them; resident, timed alternately in one process."""
+    eps, rects, amps = members(count, rows, cols, steps)
+    c00 = courant00(eps, dtype)
+    g = max(6, pml_cells)
+    wp2 = np.zeros((count, rows, cols))
+    wp2[:, rows // 2:rows // 2 + 2, :(cols - 1) // 2] = (2 * np.pi * 70e9) ** 2     # a strip over half the period
+    rects = rects.copy()
+    rects[:, 1] = np.minimum(rects[:, 1], cols - 1 - rects[:, 3])                  # off the image column
+    phi = np.linspace(0.0, np.pi, count)
+    lines = [("row", rows // 4, 0, cols - 1), ("row", 3 * rows // 4, 0, cols - 1)]
+    om10 = 2 * np.pi * np.linspace(20e9, 65e9, 10)
+    assert g <= rows // 2 and rows // 2 + 2 <= rows - 1 - g
+
+    def batch(kind):
+        b = fd.BatchEngine(count, rows, cols, DT, DX, dtype=dtype, boundary="periodic")
+        b.set_polarization("hz")
+        b.set_materials(eps.astype(dtype), fd.MU0).set_sources(rects)
+        b.set_pml(pml_cells, courant00=c00)
+        b.set_dispersion(wp2, 1e11, 0.0)
+        b.set_hz_bloch_phase(phi).set_hz_bloch_source("ramp")
+        if kind == "hz_bloch_flux":
+            b.set_hz_bloch_flux_lines(lines, om10)
+        b.run(steps, amps).sync()                      # warm-up: code objects, clocks
+        return b
+
+    def timed(b):
+        b.reset().sync()
+        t0 = time.perf_counter()
+        b.run(steps, amps).sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    kinds = ("hz_bloch", "hz_bloch_flux")
+    with batch("hz_bloch") as hzb, batch("hz_bloch_flux") as hzf:
+        bs = dict(zip(kinds, (hzb, hzf)))
+        assert all(b.resident and b.dispersive and b.hz_bloch for b in bs.values())
+        l0 = hzf.launches
+        hzf.reset().run(steps, amps).sync()
+        launches = hzf.launches - l0
+        t0 = time.perf_counter()
+        P = hzf.flux()
+        flux_call_ms = (time.perf_counter() - t0) * 1e3
+        ms = {k: [] for k in kinds}
+        for _ in range(reps):
+            for k in kinds:
+                ms[k].append(timed(bs[k]))
+        lds = {k: b.lds_bytes for k, b in bs.items()}
+        in_lds = hzf.flux_lines_in_lds
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    out = {"count": count, "rows": rows, "cols": cols, "steps": steps, "dtype": np.dtype(dtype).name,
+           "materials": "arrays", "boundary": "periodic", "pml_cells": pml_cells, "sweep": "0..pi", "reps": reps,
+           "arithmetic": fd.ARITHMETIC, "lines": 2, "line_cells": 2 * (cols - 1), "flux_freqs": 10,
+           "launches_per_run": launches, "flux_call_ms": round(flux_call_ms, 4),
+           "flux_finite": bool(np.all(np.isfinite(P))), "hz_bloch_flux_lines_in_lds": in_lds,
+           "hz_bloch_flux_sums": "lds" if in_lds else "global", "sums_bytes_per_member": 64 * 10 * 2 * (cols - 1)}
+    for k in kinds:
+        out.update({f"{k}_ms": round(med[k], 4), f"{k}_ms_min": round(min(ms[k]), 4),
+                    f"{k}_ms_all": [round(v, 4) for v in ms[k]], f"{k}_lds_bytes_per_member": lds[k]})
+    out.update({"hz_bloch_flux_over_hz_bloch": round(med["hz_bloch_flux"] / med["hz_bloch"], 3),
+                "hz_bloch_flux_mcell_steps_per_s": round(count * rows * cols * steps / (med["hz_bloch_flux"] * 1e-3) / 1e6, 1)})
+    return out
+
+
 def bench_hz_flux(count, rows, cols, steps, dtype, reps, pml_cells):
     """Two whole-period row lines at 10 frequencies on the Hz member of --hz against the same member without them, and
     the same lines on the lossless Ez member of --flux at this shape against that member without them."""
@@ -1469,7 +1537,13 @@ def main():
                     help="time the Hz polarisation with a pole against the Ez dispersive kernels on periodic members")
     ap.add_argument("--hz-bloch", action="store_true",
                     help="time a Bloch phase in the Hz polarisation with a pole against the real Hz and the Ez Bloch kernels")
+    ap.add_argument("--hz-bloch-flux", action="store_true",
+                    help="time flux lines under the Bloch phase of the Hz polarisation against the same batch without them")
     a = ap.parse_args()
+    if a.hz_bloch_flux:
+        print(json.dumps(bench_hz_bloch_flux(a.count or 1024, a.rows or 40, a.cols or 41, a.steps or 2000,
+                                             np.dtype(a.dtype), a.reps, a.pml_cells)), flush=True)
+        return
     if a.hz_bloch:
         print(json.dumps(bench_hz_bloch(a.count or 1024, a.rows or 40, a.cols or 41, a.steps or 2000, np.dtype(a.dtype),
                                         a.reps, a.pml_cells)), flush=True)
