@@ -310,6 +310,13 @@ BATCH_HZ_BLOCH_FLUX_SIGNATURES = {
     "fdtd2d_batch_read_hz_bloch_flux_lines": (_i, [_vp, _i, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]),
     "fdtd2d_batch_hz_bloch_flux": (_i, [_vp, C.POINTER(_d)]),
 }
+# every symbol include/fdtd2d_batch_hz_lattice.h declares (the lattice mode in the Hz polarisation: both seams, complex
+# Hz, Ex, Ey and pole state).  FDTD2D_BATCH_INFO_HZ_LATTICE is 25, written relative to the Hz Bloch phase's id
+BATCH_HZ_LATTICE_INFO_ID = BATCH_HZ_BLOCH_INFO + 1
+BATCH_HZ_LATTICE_SIGNATURES = {
+    "fdtd2d_batch_set_hz_lattice": (_i, [_vp, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]),
+    "fdtd2d_batch_is_hz_lattice": (_i, [_vp]),
+}
 
 # transport callback of fdtd2d_slab_attach
 EXCHANGE_FN = C.CFUNCTYPE(_i, _vp, _vp, _vp, _vp, _vp, _ll, _vp)
@@ -368,7 +375,7 @@ def load():
                                    **BATCH_BLOCH_FLUX_SIGNATURES, **BATCH_FLUX_ADJOINT_SIGNATURES,
                                    **BATCH_BLOCH_FLUX_ADJOINT_SIGNATURES, **BATCH_HZ_SIGNATURES,
                                    **BATCH_HZ_FLUX_SIGNATURES, **BATCH_HZ_BLOCH_SIGNATURES,
-                                   **BATCH_HZ_BLOCH_FLUX_SIGNATURES}.items():
+                                   **BATCH_HZ_BLOCH_FLUX_SIGNATURES, **BATCH_HZ_LATTICE_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

@@ -33,6 +33,8 @@ angle sweeps of wire grids; fdtd2d_batch_hz_bloch.h).
 ``boundary="lattice"`` makes every member the unit cell of a rectangular 2D lattice: row R-1 is the image of row 0 and
 column C-1 the image of column 0, the fields are complex, and ``set_lattice_phase`` gives every member one Bloch phase
 across each pair of edges (band diagrams of 2D photonic crystals: a k-path is one batch; fdtd2d_batch_lattice.h).
+``set_hz_lattice_phase`` gives a periodic batch in the Hz polarisation that lattice mode: the band structure with E in the
+plane, with the conductivity and the pole anywhere in the period (metallic crystals; fdtd2d_batch_hz_lattice.h).
 """
 from __future__ import annotations
 
@@ -148,6 +150,7 @@ class BatchEngine:
     _hz = False                   # set_polarization("hz"): Hz with Ex, Ey (fdtd2d_batch_hz.h)
     _hzbflux = False              # set_hz_bloch_flux_lines: the flux lines are those under set_hz_bloch_phase
     _hzb = False                  # set_hz_bloch_phase: _bloch holds the rotations of fdtd2d_batch_hz_bloch.h's phase
+    _hzlat = False                # set_hz_lattice_phase: _lattice holds the rotations of fdtd2d_batch_hz_lattice.h's mode
 
     def __init__(self, count, rows, cols, dt=5e-14, dx=1e-4, dtype=np.float32, boundary="mur", device=0):
         self._lib = _abi.load()
@@ -239,6 +242,12 @@ class BatchEngine:
     def lattice(self) -> bool:
         """Whether the lattice mode is on (complex fields, Bloch conditions on both pairs of edges)."""
         return bool(self._lib.fdtd2d_batch_is_lattice(self._h))
+
+    @property
+    def hz_lattice(self) -> bool:
+        """Whether the lattice mode of the Hz polarisation is on (set_hz_lattice_phase; `lattice`, `bloch` and `hz_bloch`
+        stay False there)."""
+        return bool(self._lib.fdtd2d_batch_is_hz_lattice(self._h))
 
     def _no_lattice(self, what):
         """The library's refusal of `what` in the lattice mode, before the call."""
@@ -401,6 +410,7 @@ class BatchEngine:
         if not self._hz:
             raise _abi.Fdtd2dError(_abi.E_STATE, 'set_hz_bloch_phase needs the Hz polarisation (set_polarization("hz")): '
                                                  "the Ez polarisation takes set_bloch_phase")
+        self._no_lattice("set_hz_bloch_phase (use set_hz_lattice_phase)")
         if phi is None and rotation is None:
             if self._hzbflux:
                 raise _abi.Fdtd2dError(_abi.E_STATE, "turning the Bloch phase off is not available while flux lines of the "
@@ -434,6 +444,69 @@ class BatchEngine:
         self._bloch = (c, s)
         self._hzb = True
         self._phi = None if ph is None else np.ascontiguousarray(np.broadcast_to(ph, (self.count,)))
+        return self
+
+    # -- the lattice mode in the Hz polarisation (fdtd2d_batch_hz_lattice.h) ----------------------------------------------
+    def set_hz_lattice_phase(self, phi_rows, phi_cols, rotation=None):
+        """The lattice mode of a boundary="periodic" engine in the Hz polarisation (set_polarization("hz")): row R-1
+        becomes the image of row 0 as column C-1 is of column 0, the fields are complex and every member takes one Bloch
+        phase across each pair of edges, the arguments of set_lattice_phase (scalars or (B,) in radians, or
+        rotation=((cr, sr), (cc, sc)) for exact rotations).  None, None turns the mode off: a plain periodic Hz batch
+        again, real parts as they are (refused while a conductivity or a pole sits in rows that batch forbids).  A later
+        call changes the phases alone.  While the mode is on Hz, Ex, Ey, the pole state, the window DFT and the probes
+        are complex (upload, download, download_dispersion, upload_hz_dispersion, read_dft_window, read_probes), run()
+        takes complex amps, set_hz_bloch_source("ramp") uses the column phase, and set_conductivity and set_dispersion may
+        be non-zero in every cell of the period.  Refused while it is on: a layer, set_hz_bloch_phase, the flux lines of
+        either Hz call, set_dft, point sources and channels, set_polarization("ez"), and windows, probes and sources
+        touching row R-1 or column C-1."""
+        if not self._hz:
+            raise _abi.Fdtd2dError(_abi.E_STATE, 'set_hz_lattice_phase needs the Hz polarisation (set_polarization("hz")): '
+                                                 'the Ez polarisation takes boundary="lattice" and set_lattice_phase')
+        if phi_rows is None and phi_cols is None and rotation is None:
+            self._ck(self._lib.fdtd2d_batch_set_hz_lattice(self._h, None, None, None, None))
+            if self._hzlat:
+                self._lattice = self._bloch = self._phi = None
+                self._hzb = self._hzlat = False
+            return self
+        if rotation is not None:
+            if len(rotation) != 2 or any(not isinstance(r, (tuple, list)) or len(r) != 2 for r in rotation):
+                raise ValueError(f"rotation must be two pairs ((cr, sr), (cc, sc)), got {rotation!r}")
+            vals = [np.asarray(v, dtype=np.float64) for r in rotation for v in r]
+            names = ("cr", "sr", "cc", "sc")
+            ph = None
+        else:
+            if phi_rows is None or phi_cols is None:
+                raise ValueError("phi_rows and phi_cols must both be given (or both None)")
+            ph = [np.asarray(phi_rows, dtype=np.float64), np.asarray(phi_cols, dtype=np.float64)]
+            vals = [np.cos(ph[0]), np.sin(ph[0]), np.cos(ph[1]), np.sin(ph[1])]
+            names = ("phi_rows", "phi_rows", "phi_cols", "phi_cols")
+        for v, nm in zip(vals if ph is None else (ph[0], ph[0], ph[1], ph[1]), names):
+            if v.shape not in ((), (self.count,)):
+                raise ValueError(f"{nm} must be a scalar or have shape ({self.count},), got {v.shape}")
+            if not np.all(np.isfinite(v)):
+                raise ValueError(f"{nm} must be finite")
+        if self.boundary != "periodic":
+            raise _abi.Fdtd2dError(_abi.E_STATE, "the lattice mode of the Hz polarisation needs periodic columns "
+                                   f'(boundary="periodic"), not {self.boundary!r}')
+        if not self._hzlat:
+            if self._pml_on:
+                raise _abi.Fdtd2dError(_abi.E_STATE, "the lattice mode of the Hz polarisation has no layer: remove it "
+                                       "(clear_pml) first")
+            if self._hzb:
+                raise _abi.Fdtd2dError(_abi.E_STATE, "the lattice mode of the Hz polarisation is not available while a "
+                                       "Bloch phase is set: turn it off first (set_hz_bloch_phase(None))")
+            if self._flux is not None:
+                raise _abi.Fdtd2dError(_abi.E_STATE, "the lattice mode of the Hz polarisation is not available while flux "
+                                       "lines are set: remove them first")
+            if self._npoint[0]:
+                raise _abi.Fdtd2dError(_abi.E_STATE, "a point source is not available in the lattice mode of the Hz "
+                                       "polarisation (remove them)")
+        cr, sr, cc, sc = (np.ascontiguousarray(np.broadcast_to(v, (self.count,))) for v in vals)
+        self._ck(self._lib.fdtd2d_batch_set_hz_lattice(self._h, _dptr(cr), _dptr(sr), _dptr(cc), _dptr(sc)))
+        self._lattice = ((cr, sr), (cc, sc))
+        self._bloch = (cc, sc)        # upload, download, run and the monitors then behave as under set_hz_bloch_phase
+        self._hzb = self._hzlat = True
+        self._phi = None if ph is None else np.ascontiguousarray(np.broadcast_to(ph[1], (self.count,)))
         return self
 
     def set_hz_bloch_source(self, weights="ramp"):
@@ -1065,6 +1138,7 @@ class BatchEngine:
             if self._hzbflux:
                 self._flux, self._hzbflux = None, False
             return self
+        self._no_lattice("set_hz_bloch_flux_lines")
         if not self._hzb:
             raise _abi.Fdtd2dError(_abi.E_STATE, "set_hz_bloch_flux_lines needs the phase of the Hz polarisation: call "
                                    "set_hz_bloch_phase first (without a phase use set_hz_flux_lines, in the Ez "
@@ -1419,7 +1493,7 @@ class BatchEngine:
         it counts rows alone (the layer's depth, at least 6): every column of the period may conduct."""
         if self.boundary == "mur":
             return 6
-        if self.boundary == "lattice":
+        if self.boundary == "lattice" or self._hzlat:
             return 0                  # no edge: every cell of the period may conduct
         if self.boundary == "periodic":
             return max(6, self._pml_L)
@@ -1458,7 +1532,9 @@ class BatchEngine:
         "pml" batch, columns g..C-2-g (Ex[i, j] lives at i + 1/2; column C-1 of a periodic batch is never read)."""
         g = self.conductivity_margin
         ok = np.zeros((self.count, self.rows, self.cols), bool)
-        if self.boundary == "periodic":
+        if self._hzlat:               # every cell of the period: rows 0..R-2 and columns 0..C-2
+            ok[:, :self.rows - 1, :self.cols - 1] = True
+        elif self.boundary == "periodic":
             ok[:, g:self.rows - 1 - g, :] = True
         else:
             ok[:, g:self.rows - 1 - g, g:self.cols - 1 - g] = True
@@ -1494,7 +1570,8 @@ class BatchEngine:
         (E_ARG) a value that is negative or not finite, wp2 non-zero inside the margin, and a cell whose pole breaks
         dt^2 (omega0^2 + wp2 EPS0 / eps) + 8 dt^2 / (eps mu dx^2) <= 4; while a pole is set it refuses (E_STATE) a Bloch
         phase, removing the layer of a "pml" batch and the held window with its product."""
-        self._no_lattice("a dispersive pole")
+        if not self._hzlat:           # the lattice mode of the Hz polarisation takes the pole of set_polarization("hz")
+            self._no_lattice("a dispersive pole")
         setter = self._lib.fdtd2d_batch_set_hz_dispersion if self._hz else self._lib.fdtd2d_batch_set_dispersion
         if wp2 is None:
             self._ck(setter(self._h, None, _code(self.dtype), None, None))
@@ -1703,7 +1780,7 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
                    dtype=np.float64, boundary="mur", omega=None, dft_every=1, device=0, pml_cells=40,
                    dft_window=None, window_omegas=None, probes=None, bloch_phase=None, source_weights=None,
                    dispersion=None, bloch_dispersion=None, polarization="ez", conductivity=None,
-                   hz_bloch_phase=None, hz_flux_lines=None, hz_flux_omegas=None, hz_bloch_flux_lines=None,
+                   hz_bloch_phase=None, hz_lattice_phase=None, hz_flux_lines=None, hz_flux_omegas=None, hz_bloch_flux_lines=None,
                    hz_bloch_flux_omegas=None, bloch_flux_lines=None, bloch_flux_omegas=None, flux_lines=None,
                    flux_omegas=None):
     """run_fdtd for B members of one shape at once: zero fields, Courant check per member, nsteps of
@@ -1742,6 +1819,10 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
     phase, source_weights goes to set_hz_bloch_source, and omega and hz_flux_lines are not available.
     hz_bloch_flux_lines with hz_bloch_flux_omegas (with hz_bloch_phase alone): flux monitors as set_hz_bloch_flux_lines
     takes them, sampled every `dft_every` steps; the flux array is appended as with flux_lines.
+    hz_lattice_phase = (phi_rows, phi_cols), each a scalar or (B,) (polarization "hz" with boundary "periodic" alone,
+    without a layer: pml_cells must be 0 or None): the lattice mode of set_hz_lattice_phase, every member the unit cell of a
+    rectangular lattice with E in the plane; every returned array is complex, conductivity and dispersion may fill the
+    period, source_weights goes to set_hz_bloch_source; not with hz_bloch_phase, omega or flux lines of any kind.
     """
     from .api import MU0
     eps = np.asarray(eps)
@@ -1757,6 +1838,29 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
     assert np.all(courant <= 1.0), \
         f"Courant stability condition not met: members {np.nonzero(~(courant <= 1.0))[0].tolist()} > 1.0"
     fcs = np.broadcast_to(np.asarray(fc, dtype=np.float64), (B,))
+    if hz_lattice_phase is not None:
+        if polarization != "hz":
+            raise ValueError('hz_lattice_phase needs polarization="hz": in the Ez polarisation use boundary="lattice"')
+        if boundary != "periodic":
+            raise ValueError(f'hz_lattice_phase needs boundary="periodic", not {boundary!r}')
+        if hz_bloch_phase is not None:
+            raise ValueError("hz_lattice_phase and hz_bloch_phase exclude each other")
+        if not isinstance(hz_lattice_phase, (tuple, list)) or len(hz_lattice_phase) != 2:
+            raise ValueError(f"hz_lattice_phase must be (phi_rows, phi_cols), got {hz_lattice_phase!r}")
+        for v, nm in zip(hz_lattice_phase, ("phi_rows", "phi_cols")):
+            if np.shape(v) not in ((), (B,)):
+                raise ValueError(f"{nm} must be a scalar or have shape ({B},), got {np.shape(v)}")
+            if not np.all(np.isfinite(np.asarray(v, dtype=np.float64))):
+                raise ValueError(f"{nm} must be finite")
+        if omega is not None:
+            raise ValueError("omega (the whole-grid transform) is not available with hz_lattice_phase: use dft_window")
+        for given, nm in ((flux_lines, "flux_lines"), (bloch_flux_lines, "bloch_flux_lines"),
+                          (hz_flux_lines, "hz_flux_lines"), (hz_bloch_flux_lines, "hz_bloch_flux_lines")):
+            if given is not None:
+                raise ValueError(f"{nm} is not available with hz_lattice_phase: the lattice mode has no flux lines")
+        if pml_cells:
+            raise ValueError(f"hz_lattice_phase is not available with a layer (pml_cells={pml_cells!r}): the lattice mode "
+                             "has none, pass pml_cells=0")
     layered = boundary == "pml" or (boundary == "periodic" and pml_cells)
     if boundary == "periodic" and layered and not pml_fits(R, Cc, int(pml_cells), True):
         raise ValueError(f"a {int(pml_cells)}-cell PML does not fit {R}x{Cc} periodic members (2L + 3 <= rows): the "
@@ -1783,7 +1887,7 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
             raise ValueError('dispersion is not available with boundary="lattice"')
     if bloch_phase is not None and boundary not in ("periodic", "lattice"):
         raise ValueError(f'bloch_phase needs boundary="periodic" or "lattice", not {boundary!r}')
-    if source_weights is not None and bloch_phase is None and hz_bloch_phase is None:
+    if source_weights is not None and bloch_phase is None and hz_bloch_phase is None and hz_lattice_phase is None:
         raise ValueError("source_weights needs bloch_phase")
     if bloch_phase is not None and omega is not None:
         raise ValueError("omega (the whole-grid transform) is not available with bloch_phase: use dft_window")
@@ -1864,6 +1968,13 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
             raise ValueError(f"dft_window {win} touches column {Cc - 1}, the image of column 0: not with hz_bloch_phase")
         if cells is not None and np.any(cells[..., 1] >= Cc - 1):
             raise ValueError(f"a probe lies in column {Cc - 1}, the image of column 0: not with hz_bloch_phase")
+    if hz_lattice_phase is not None:
+        if win is not None and (win[0] + win[2] > R - 1 or win[1] + win[3] > Cc - 1):
+            raise ValueError(f"dft_window {win} touches row {R - 1} or column {Cc - 1}, the images of row 0 and column 0: "
+                             "not with hz_lattice_phase")
+        if cells is not None and (np.any(cells[..., 0] >= R - 1) or np.any(cells[..., 1] >= Cc - 1)):
+            raise ValueError(f"a probe lies in row {R - 1} or column {Cc - 1}, the images of row 0 and column 0: not with "
+                             "hz_lattice_phase")
     if lattice:
         if win is not None and win[0] + win[2] > R - 1:
             raise ValueError(f'dft_window {win} touches row {R - 1}, the image of row 0: not with boundary="lattice"')
@@ -1875,6 +1986,10 @@ def run_fdtd_batch(eps, mu=None, *, nsteps, sources, fc=30e9, waveform="ricker",
         eng.set_materials(eps, mu)
         if layered:
             eng.set_pml(L, courant00=courant00)
+        if hz_lattice_phase is not None:      # first: the mode lifts the row margin of the conductivity and the pole
+            eng.set_hz_lattice_phase(*hz_lattice_phase)
+            if source_weights is not None:
+                eng.set_hz_bloch_source(source_weights)
         eng.set_sources(sources)
         if conductivity is not None:
             eng.set_conductivity(conductivity)

@@ -29,6 +29,9 @@
 // without a conductivity and a pole; the lines share that host state too (`hzflux` beside `flux_nl`).
 // With the lines of fdtd2d_batch_hz_bloch_flux.h an Hz Bloch batch takes the kernels of batch_hz_bloch_flux.hip; the lines
 // share the host state of the Ez Bloch lines (`hzbflux` beside `flux_nl`, the imaginary part's sums in flux_acc_im).
+// In the lattice mode of the Hz polarisation (fdtd2d_batch_hz_lattice.h) a batch holds `hz`, `bloch` and `lattice`
+// together: the host state of the Hz Bloch phase with the row rotation of the lattice mode and no Hzx; every run takes the
+// kernels of batch_hz_lattice.hip.
 // With the phase of fdtd2d_batch_hz_bloch.h a periodic batch in the Hz polarisation holds `hz` and `bloch` together: the
 // imaginary parts, the rotations, the weights and the monitors are the Bloch phase's, a pole adds the imaginary parts of
 // Jx, Qx (djh_im, dq_im) and Jy, Qy (djy_im, dqy_im), and every run takes the kernels of batch_hz_bloch.hip.
@@ -47,6 +50,7 @@
 #include "../../include/fdtd2d_batch_hz.h"
 #include "../../include/fdtd2d_batch_hz_bloch.h"
 #include "../../include/fdtd2d_batch_hz_bloch_flux.h"
+#include "../../include/fdtd2d_batch_hz_lattice.h"
 #include "../../include/fdtd2d_batch_hz_flux.h"
 #include "../../include/fdtd2d_batch_lattice.h"
 #include "../../include/fdtd2d_batch_lossy.h"
@@ -79,6 +83,7 @@
 #include "kernels_batch_hz.hpp"
 #include "kernels_batch_hz_bloch.hpp"
 #include "kernels_batch_hz_bloch_flux.hpp"
+#include "kernels_batch_hz_lattice.hpp"
 #include "kernels_batch_hz_flux.hpp"
 #include "kernels_batch_lattice.hpp"
 #include "kernels_batch_lossy.hpp"
@@ -149,7 +154,8 @@ struct fdtd2d_batch {
     double *win_held_im = nullptr;
     // fdtd2d_batch_set_lattice: row R-1 is the image of row 0 too.  `bloch` is set as well (the imaginary parts, the
     // weights and the monitors are the Bloch phase's, without Ezx's imaginary part), rho / rho_host hold the column
-    // rotation and these the row rotation
+    // rotation and these the row rotation.  fdtd2d_batch_set_hz_lattice sets it beside `hz` and `bloch`: the same state
+    // with Hz, Ex, Ey in the slots and the pole state of the Hz Bloch phase
     bool lattice = false;
     void *rho_r = nullptr;
     std::vector<double> rho_r_host;       // count x {c, s} as the engine stores them
@@ -355,6 +361,7 @@ int zero_fields(fdtd2d_batch *b)
 // twice and cj more
 int lds_arrays(const fdtd2d_batch *b)
 {
+    if (b->hz && b->lattice) return b->dcj ? 18 : 9;  // Hz, Ex, Ey twice, ch, cb, ca and cj, Jx, Qx, Jy, Qy twice
     if (b->hz && b->bloch) return b->dcj ? 20 : 11;   // Hz, Ex, Ey, Hzx twice, ch, cb, ca and cj, Jx, Qx, Jy, Qy twice
     if (b->hz) return b->dcj ? 12 : 7;       // Hz, Ex, Ey, Hzx, ch, cb, ca and cj, Jx, Qx, Jy, Qy
     if (b->lattice) return b->bdisp ? 14 : 9;
@@ -1366,6 +1373,70 @@ template <class T> int run_hz_bloch(fdtd2d_batch *b, int nsteps, const double *a
     return 0;
 }
 
+// ---- Hz lattice runs (fdtd2d_batch_hz_lattice.h): the paths of run_lattice with the kernels of batch_hz_lattice.hip.
+// v.ce carries cb; the first streamed launch of a step is the E half-step.
+template <class T> int run_hz_lattice(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride)
+{
+    const int disp = b->dcj ? 1 : 0;
+    if (!b->periodic || !b->ca || !b->cb || !b->ch || !b->ez_im || !b->hx_im || !b->hy_im || !b->rho || !b->rho_r ||
+        !b->bloch_w ||
+        (disp && (!b->djh || !b->dq || !b->djy || !b->dqy || !b->djh_im || !b->dq_im || !b->djy_im || !b->dqy_im ||
+                  !b->da || !b->dck)))
+        return bfail(b, FDTD2D_E_STATE, "Hz lattice batch without its arrays");
+    const fdtd::BatchHzLatticeKernels &K = fdtd::batch_hz_lattice_kernels<T>();
+    fdtd::BatchMon m = mon_view(b);
+    fdtd::BatchLattice<T> la{(T *)b->ez_im, (T *)b->hx_im, (T *)b->hy_im, (const T *)b->rho_r, (const T *)b->rho,
+                             b->bloch_w, b->have_src ? b->run_amps_im : nullptr, b->win_acc_im, b->probe_trace_im};
+    fdtd::BatchHzBlochDisp<T> d{(T *)b->djh,    (T *)b->dq,    (T *)b->djy,    (T *)b->dqy,
+                                (T *)b->djh_im, (T *)b->dq_im, (T *)b->djy_im, (T *)b->dqy_im,
+                                (const T *)b->dcj, (const T *)b->da, (const T *)b->dck};
+    b->run_conj = false;
+    const T *ca = (const T *)b->ca;
+    if (use_resident(b)) {
+        const int cells = b->rows * b->cols, threads = resident_threads(cells);
+        const int per_thread = (cells + threads - 1) / threads;
+        const void *kern = per_thread <= 4 ? K.resident[disp][0] : per_thread <= 5 ? K.resident[disp][1] : nullptr;
+        if (!kern)
+            return bfail(b, FDTD2D_E_STATE, "%d cells per thread exceed the Hz lattice resident kernels", per_thread);
+        const size_t lds = lds_bytes(b);
+        BCHK(b, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        int per_cu = 0, cus = 0;
+        BCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds));
+        BCHK(b, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
+        if (per_cu < 1) return bfail(b, FDTD2D_E_STATE, "Hz lattice resident kernel does not fit a CU (%zu B of LDS)", lds);
+        const long long round = (long long)per_cu * cus;
+        const int blocks = (int)(b->count < round ? b->count : round);
+        const int chunk = b->steps_per_launch > 0 ? b->steps_per_launch : nsteps;
+        for (int n = 0; n < nsteps; n += chunk) {
+            int n0 = n, nt = nsteps - n < chunk ? nsteps - n : chunk;
+            long long step_base = b->step;
+            fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+            v.ce = (const T *)b->cb;
+            void *args[] = {&v, &m, &la, &d, &ca, &n0, &nt, &step_base};
+            int rc = launch_ptr(b, kern, dim3(blocks), dim3(threads), args, lds);
+            if (rc) return rc;
+            b->launches++;
+            b->step += nt;
+        }
+        return 0;
+    }
+    const int cells = b->rows * b->cols;
+    const dim3 grid((cells + 255) / 256, b->count < 65535 ? b->count : 65535);
+    for (int n = 0; n < nsteps; ++n) {
+        fdtd::BatchView<T> v = view<T>(b, amps, amp_stride);
+        v.ce = (const T *)b->cb;
+        long long step = b->step + 1;
+        int rc;
+        void *e_args[] = {&v, &m, &la, &d, &ca, &step};
+        void *h_args[] = {&v, &m, &la, &n, &step};
+        if ((rc = launch_ptr(b, K.e[disp], grid, dim3(256), e_args, 0))) return rc;
+        if ((rc = launch_ptr(b, K.h, grid, dim3(256), h_args, 0))) return rc;
+        b->launches += 2;
+        b->step++;
+    }
+    return 0;
+}
+
 // ---- Hz Bloch runs with flux lines (fdtd2d_batch_hz_bloch_flux.h): the paths of run_hz_bloch with the kernels of
 // batch_hz_bloch_flux.hip, whose streamed E launch also writes the lines' phasors
 template <class T> int run_hz_bloch_flux(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stride)
@@ -1438,6 +1509,7 @@ int run_impl(fdtd2d_batch *b, int nsteps, const double *amps, long long amp_stri
              fdtd::BatchFluxSrc *fs = nullptr)
 {
     if (b->hzbflux) return run_hz_bloch_flux<T>(b, nsteps, amps, amp_stride);
+    if (b->hz && b->lattice) return run_hz_lattice<T>(b, nsteps, amps, amp_stride);
     if (b->hz && b->bloch) return run_hz_bloch<T>(b, nsteps, amps, amp_stride);
     if (b->hz) return run_hz<T>(b, nsteps, amps, amp_stride, pts);
     if (b->bflux) return run_bloch_flux<T>(b, nsteps, amps, amp_stride);
@@ -2224,7 +2296,8 @@ long long fdtd2d_batch_info(const fdtd2d_batch_t *b, int what)
     case FDTD2D_BATCH_INFO_LOSSY: return b->ca && !b->sigma_implicit ? 1 : 0;
     case FDTD2D_BATCH_INFO_PERIODIC: return b->periodic ? 1 : 0;
     case FDTD2D_BATCH_INFO_BLOCH: return b->bloch && !b->lattice && !b->hz ? 1 : 0;
-    case FDTD2D_BATCH_INFO_HZ_BLOCH: return b->bloch && b->hz ? 1 : 0;
+    case FDTD2D_BATCH_INFO_HZ_BLOCH: return b->bloch && b->hz && !b->lattice ? 1 : 0;
+    case FDTD2D_BATCH_INFO_HZ_LATTICE: return b->lattice && b->hz ? 1 : 0;
     case FDTD2D_BATCH_INFO_DISPERSIVE: return b->dcj ? 1 : 0;
     case FDTD2D_BATCH_INFO_HELD_DISPERSIVE_WINDOW: return b->win_held_disp ? 1 : 0;
     case FDTD2D_BATCH_INFO_FLUX_LINES: return b->flux_nl;
@@ -3210,6 +3283,9 @@ int fdtd2d_batch_set_polarization(fdtd2d_batch_t *b, int polarization)
     if (b->boundary != FDTD2D_BOUNDARY_NONE)
         return bfail(b, FDTD2D_E_STATE, "a change of polarisation needs a batch created with FDTD2D_BOUNDARY_NONE: the Mur "
                      "frame has no Hz kernels");
+    if (b->lattice && b->hz && hz) return 0;
+    if (b->lattice && b->hz)
+        return refuse_bloch(b, "a change of polarisation (turn the mode of fdtd2d_batch_set_hz_lattice off first)");
     if (b->lattice) return refuse_bloch(b, "a change of polarisation (the lattice mode has no Hz kernels)");
     if (b->bloch && b->hz && hz) return 0;
     if (b->bloch && b->hz)
@@ -3433,6 +3509,8 @@ int fdtd2d_batch_set_periodic(fdtd2d_batch_t *b, int on)
         return bfail(b, FDTD2D_E_STATE, "periodic columns need a batch created with FDTD2D_BOUNDARY_NONE: the Mur frame "
                      "and a periodic boundary exclude each other");
     if ((on != 0) == b->periodic) return 0;
+    if (!on && b->hz && b->lattice)
+        return refuse_bloch(b, "turning periodic columns off (turn the mode of fdtd2d_batch_set_hz_lattice off first)");
     if (!on && b->hz && b->bloch)
         return refuse_bloch(b, "turning periodic columns off (turn the phase of fdtd2d_batch_set_hz_bloch off first)");
     if (b->flux_nl) return refuse_flux(b, "switching periodic columns");
@@ -3518,6 +3596,7 @@ int fdtd2d_batch_set_bloch(fdtd2d_batch_t *b, const double *cos_phi, const doubl
     if (!cos_phi != !sin_phi) return bfail(b, FDTD2D_E_ARG, "cos_phi and sin_phi must both be given (or both NULL)");
     int rc = use_device(b);
     if (rc) return rc;
+    if (b->lattice && b->hz) return refuse_bloch(b, "fdtd2d_batch_set_bloch or fdtd2d_batch_set_hz_bloch (use fdtd2d_batch_set_hz_lattice)");
     if (b->lattice) return refuse_bloch(b, "fdtd2d_batch_set_bloch (use fdtd2d_batch_set_lattice)");
     if (b->hz && b->bloch && !b->hz_bloch_call) return refuse_hz(b, "fdtd2d_batch_set_bloch (use fdtd2d_batch_set_hz_bloch)");
     if (!cos_phi && b->bflux) return refuse_flux(b, "turning the Bloch phase off");
@@ -3827,7 +3906,7 @@ int fdtd2d_batch_set_lattice(fdtd2d_batch_t *b, const double *cos_r, const doubl
     const int given = !!cos_r + !!sin_r + !!cos_c + !!sin_c;
     if (given != 0 && given != 4)
         return bfail(b, FDTD2D_E_ARG, "cos_r, sin_r, cos_c and sin_c must all be given (or all NULL)");
-    if (given && b->hz) return refuse_hz(b, "the lattice mode");
+    if (b->hz && (given || b->lattice)) return refuse_hz(b, "the lattice mode of the Ez polarisation (use fdtd2d_batch_set_hz_lattice)");
     int rc = use_device(b);
     if (rc) return rc;
     if (!given) {
@@ -3921,7 +4000,127 @@ int fdtd2d_batch_set_lattice(fdtd2d_batch_t *b, const double *cos_r, const doubl
 int fdtd2d_batch_is_lattice(const fdtd2d_batch_t *b)
 {
     if (!b) return FDTD2D_E_ARG;
-    return b->lattice ? 1 : 0;
+    return b->lattice && !b->hz ? 1 : 0;
+}
+
+// ---- fdtd2d_batch_hz_lattice.h -----------------------------------------------------------------------------------
+// The mode shares the host state of the Hz Bloch phase and of the lattice mode (`hz`, `bloch` and `lattice` together):
+// rho / rho_host hold the column rotation, rho_r / rho_r_host the row rotation, and the complex traffic goes through the
+// entry points of fdtd2d_batch_hz_bloch.h, whose bodies deliver both image kinds while `lattice` is set.
+
+int fdtd2d_batch_set_hz_lattice(fdtd2d_batch_t *b, const double *cos_r, const double *sin_r, const double *cos_c,
+                                const double *sin_c)
+{
+    if (!b) return FDTD2D_E_ARG;
+    const int given = !!cos_r + !!sin_r + !!cos_c + !!sin_c;
+    if (given != 0 && given != 4)
+        return bfail(b, FDTD2D_E_ARG, "cos_r, sin_r, cos_c and sin_c must all be given (or all NULL)");
+    if (!b->hz)
+        return bfail(b, FDTD2D_E_STATE, "fdtd2d_batch_set_hz_lattice needs the Hz polarisation "
+                     "(fdtd2d_batch_set_polarization); the Ez polarisation takes fdtd2d_batch_set_lattice");
+    int rc = use_device(b);
+    if (rc) return rc;
+    const bool on = b->lattice;
+    const int R = b->rows, C = b->cols;
+    if (!given) {
+        if (!on) return 0;
+        // a plain periodic Hz batch again: sigma and wp2 must lie where that batch allows them
+        b->lattice = false;
+        const int mg = sigma_margin(b, 0);
+        const long long ts = b->ca ? sigma_outside(b, mg) : -1, tw = b->dcj ? wp2_outside(b, mg) : -1;
+        b->lattice = true;
+        if (ts >= 0 || tw >= 0)
+            return bfail(b, FDTD2D_E_ARG, "member %d: %s is non-zero within %d rows of the top or bottom edge, where a periodic "
+                         "Hz batch without the lattice mode allows none: remove it first",
+                         (int)((ts >= 0 ? ts : tw) / ((long long)R * C)), ts >= 0 ? "sigma" : "wp2", mg);
+        return bloch_off(b);
+    }
+    if (!b->periodic)
+        return bfail(b, FDTD2D_E_STATE, "the lattice mode needs periodic columns: call fdtd2d_batch_set_periodic first");
+    if (!b->have_mat) return bfail(b, FDTD2D_E_STATE, "materials not set: call fdtd2d_batch_set_materials first");
+    if (!on) {
+        if (b->pml_L > 0)
+            return bfail(b, FDTD2D_E_STATE, "the lattice mode has no layer: remove it (fdtd2d_batch_set_pml with NULL) first");
+        if (b->bloch)
+            return refuse_bloch(b, "the lattice mode of the Hz polarisation (turn the phase of fdtd2d_batch_set_hz_bloch off)");
+        if (b->flux_nl) return refuse_flux(b, "the lattice mode of the Hz polarisation");
+        if (b->dft)
+            return bfail(b, FDTD2D_E_STATE, "the whole-grid transform is not available in the lattice mode (remove it, use "
+                         "fdtd2d_batch_set_dft_window)");
+        if (b->npts) return bfail(b, FDTD2D_E_STATE, "a point source is not available in the lattice mode (remove them)");
+        if (b->win_held)
+            return bfail(b, FDTD2D_E_STATE, "the held window is not available in the lattice mode (set the window again)");
+    }
+    for (int m = 0; m < b->count; ++m)
+        if (!std::isfinite(cos_r[m]) || !std::isfinite(sin_r[m]) || !std::isfinite(cos_c[m]) || !std::isfinite(sin_c[m]))
+            return bfail(b, FDTD2D_E_ARG, "member %d: the rotations (%g, %g), (%g, %g) are not finite", m, cos_r[m], sin_r[m],
+                         cos_c[m], sin_c[m]);
+    if (!on) {
+        if (b->win_nf && (b->win_c0 + b->win_nc > C - 1 || b->win_r0 + b->win_nr > R - 1))
+            return bfail(b, FDTD2D_E_ARG, "window (%d,%d)+%dx%d touches row %d or column %d, the images of row 0 and column "
+                         "0: not in the lattice mode", b->win_r0, b->win_c0, b->win_nr, b->win_nc, R - 1, C - 1);
+        const long long k = probe_in_lattice_image(b, b->probe_host);
+        if (k >= 0)
+            return bfail(b, FDTD2D_E_ARG, "member %d probe %d: cell (%d,%d) lies in row %d or column %d, the images of row 0 "
+                         "and column 0: not in the lattice mode", (int)(k / b->nprobe), (int)(k % b->nprobe),
+                         b->probe_host[k] / C, b->probe_host[k] % C, R - 1, C - 1);
+        for (int m = 0; m < b->count && !b->rect_host.empty(); ++m) {
+            const int *r = b->rect_host.data() + 4 * m;
+            if (r[2] > 0 && r[0] + r[2] > R - 1)
+                return bfail(b, FDTD2D_E_ARG, "member %d: source (%d,%d)+%dx%d reaches row %d, the image of row 0 of a "
+                             "lattice batch", m, r[0], r[1], r[2], r[3], R - 1);
+        }
+    }
+    // (c, s) of the row seam and of the column seam, as the engine stores them
+    std::vector<double> rr((size_t)b->count * 2), rc2(rr.size());
+    std::vector<unsigned char> rrt(rr.size() * b->esz), rct(rrt.size());
+    for (size_t k = 0; k < rr.size(); ++k) {
+        rr[k] = as_engine(b, k % 2 ? sin_r[k / 2] : cos_r[k / 2]);
+        rc2[k] = as_engine(b, k % 2 ? sin_c[k / 2] : cos_c[k / 2]);
+        if (b->dtype == FDTD2D_F32) {
+            ((float *)rrt.data())[k] = (float)rr[k];
+            ((float *)rct.data())[k] = (float)rc2[k];
+        } else {
+            ((double *)rrt.data())[k] = rr[k];
+            ((double *)rct.data())[k] = rc2[k];
+        }
+    }
+    BCHK(b, hipStreamSynchronize(b->stream));   // a running launch may still read the old rotations
+    if (!on) {
+        const size_t wn = (size_t)b->count * 2 * (C - 1);
+        auto undo = [&](int code) {
+            bloch_off(b);
+            return code;
+        };
+        for (void **p : {&b->ez_im, &b->hx_im, &b->hy_im, &b->djh_im, &b->dq_im, &b->djy_im, &b->dqy_im}) {
+            if (!b->dcj && p != &b->ez_im && p != &b->hx_im && p != &b->hy_im) continue;   // the pole's imaginary state
+            if ((rc = alloc(b, p, b->field_bytes))) return undo(rc);
+            if (hipMemsetAsync(*p, 0, b->field_bytes, b->stream) != hipSuccess)
+                return undo(bfail(b, FDTD2D_E_NOMEM, "hipMemset of the imaginary fields failed"));
+        }
+        if (hipStreamSynchronize(b->stream) != hipSuccess)
+            return undo(bfail(b, FDTD2D_E_NOMEM, "hipMemset of the imaginary fields failed"));
+        if ((rc = alloc(b, &b->rho, rct.size())) || (rc = alloc(b, &b->rho_r, rrt.size())) ||
+            (rc = alloc(b, (void **)&b->bloch_w, wn * sizeof(double))))
+            return undo(rc);
+        b->bloch = b->lattice = true;
+        HzBlochCall call(b);
+        if ((rc = fdtd2d_batch_set_bloch_source(b, nullptr, nullptr)) || (rc = bloch_window(b)) || (rc = bloch_probes(b)) ||
+            (rc = copy_image(b, b->ez[b->cur])) || (rc = copy_row_image(b, b->ez[b->cur])))
+            return undo(rc);
+    }
+    BCHK(b, hipMemcpy(b->rho, rct.data(), rct.size(), hipMemcpyHostToDevice));
+    BCHK(b, hipMemcpy(b->rho_r, rrt.data(), rrt.size(), hipMemcpyHostToDevice));
+    b->rho_host.swap(rc2);
+    b->rho_r_host.swap(rr);
+    b->run_conj = false;
+    return 0;
+}
+
+int fdtd2d_batch_is_hz_lattice(const fdtd2d_batch_t *b)
+{
+    if (!b) return FDTD2D_E_ARG;
+    return b->lattice && b->hz ? 1 : 0;
 }
 
 // ---- fdtd2d_batch_bloch_adjoint.h ----------------------------------------------------------------------------------

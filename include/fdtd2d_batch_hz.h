@@ -62,7 +62,8 @@
  * that sigma would be a magnetic loss), fdtd2d_batch_set_dispersion, _set_dispersion_window and
  * _transfer_dispersion, fdtd2d_batch_set_bloch, fdtd2d_batch_set_lattice, the flux lines of fdtd2d_batch_flux.h and
  * fdtd2d_batch_bloch_flux.h and their sources (this polarisation's own lines are fdtd2d_batch_hz_flux.h's), every hold of
- * a window and every window product.
+ * a window and every window product.  This polarisation's own phase is fdtd2d_batch_hz_bloch.h's and its own lattice
+ * mode fdtd2d_batch_hz_lattice.h's, each entered from a periodic batch in the Hz polarisation.
  * These entry points live in their own header because fdtd2d.h's batch section and the other companions are fixed
  * surfaces. */
 #ifndef FDTD2D_BATCH_HZ_H

@@ -61,7 +61,9 @@
  * the Ez polarisation, fdtd2d_batch_set_periodic(b, 0), and everything the Hz polarisation refuses without a phase,
  * fdtd2d_batch_set_bloch and the other entry points of the Ez Bloch headers included (all FDTD2D_E_STATE).  Flux lines
  * under the phase are fdtd2d_batch_hz_bloch_flux.h's (fdtd2d_batch_set_hz_bloch_flux_lines); while they are set, turning
- * the phase off is refused (FDTD2D_E_STATE) and a new phase keeps them.  Not available: the lattice mode, adjoints. */
+ * the phase off is refused (FDTD2D_E_STATE) and a new phase keeps them.  The lattice mode of this polarisation (a second
+ * phase, across the rows) is fdtd2d_batch_hz_lattice.h's: it excludes this header's phase and takes its complex traffic
+ * through the entry points below.  Not available: adjoints. */
 #ifndef FDTD2D_BATCH_HZ_BLOCH_H
 #define FDTD2D_BATCH_HZ_BLOCH_H
 

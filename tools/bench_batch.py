@@ -61,6 +61,13 @@ array eps with random binary permittivity, a ricker line source per member):
                               and the pole of --hz, so that the twenty arrays stay resident, against the real Hz kernels on
                               the same members (hz_bloch_over_hz) and against the Ez Bloch kernels with the same pole
                               (hz_bloch_over_ez_bloch): the three medians, paths and LDS bytes per member
+  --hz-lattice                instead: the lattice mode of the Hz polarisation (BatchEngine.set_hz_lattice_phase: the k-path
+                              Gamma-X-M-Gamma over the members, ramp weights) on 1024 members of 32 x 33 with a metal rod and
+                              its pole (18 LDS arrays), against the Ez lattice kernels with the pole of
+                              set_bloch_dispersion on the same members (14 arrays: hz_lattice_over_ez_lattice) and against
+                              the same Hz lattice batch without the pole (9 arrays: hz_lattice_over_plain), all resident,
+                              timed alternately in one process: the three medians, paths, LDS bytes per member and the
+                              workgroups per CU they leave
   --hz-bloch-flux             instead: flux lines under that phase (BatchEngine.set_hz_bloch_flux_lines: two whole-period row
                               lines, 10 frequencies) on the member of --hz-bloch against the same batch without them, both
                               resident, timed alternately in one process: hz_bloch_ms, hz_bloch_flux_ms, their ratio,
@@ -155,7 +162,7 @@ Usage: python tools/bench_batch.py [--count 1024 --rows 60 --cols 60 --steps 100
                                    [--boundary {mur,pml} --pml-cells 10] [--monitors] [--adjoint] [--lossy]
                                    [--periodic] [--bloch] [--bloch-adjoint] [--dispersive] [--lattice]
                                    [--bloch-dispersive] [--dispersive-adjoint] [--flux] [--bloch-flux]
-                                   [--flux-adjoint] [--bloch-flux-adjoint] [--hz-flux] [--hz-bloch] [--hz-bloch-flux]
+                                   [--flux-adjoint] [--bloch-flux-adjoint] [--hz-flux] [--hz-bloch] [--hz-bloch-flux] [--hz-lattice]
 """
 import argparse
 import json
@@ -906,6 +913,69 @@ def bench_hz_bloch(count, rows, cols, steps, dtype, reps, pml_cells):
     return out
 
 
+def bench_hz_lattice(count, rows, cols, steps, dtype, reps):
+    """The lattice mode of the Hz polarisation (set_hz_lattice_phase, the k-path Gamma-X-M-Gamma over the members, ramp
+    weights) with a metal rod and its pole, against the Ez lattice kernels with the pole of set_bloch_dispersion on the
+    same members and against the same Hz lattice batch without the pole; resident, timed alternately in one process."""
+    eps, rects, amps = members(count, rows, cols, steps)
+    wp2 = np.zeros((count, rows, cols))
+    wp2[:, rows // 3:2 * rows // 3, cols // 3:2 * cols // 3] = (2 * np.pi * 70e9) ** 2       # the rod
+    rects = rects.copy()
+    rects[:, 0] = np.minimum(rects[:, 0], rows - 1 - rects[:, 2])                  # off the image row
+    rects[:, 1] = np.minimum(rects[:, 1], cols - 1 - rects[:, 3])                  # off the image column
+    phi_r, phi_c = k_path(count)
+
+    def batch(kind):
+        ez = kind == "ez_lattice"
+        b = fd.BatchEngine(count, rows, cols, DT, DX, dtype=dtype, boundary="lattice" if ez else "periodic")
+        if not ez:
+            b.set_polarization("hz")
+        b.set_materials(eps.astype(dtype), fd.MU0).set_sources(rects)
+        if ez:
+            b.set_lattice_phase(phi_r, phi_c).set_bloch_source("ramp").set_bloch_dispersion(wp2, 1e11, 0.0)
+        else:
+            b.set_hz_lattice_phase(phi_r, phi_c).set_hz_bloch_source("ramp")
+            if kind == "hz_lattice":
+                b.set_dispersion(wp2, 1e11, 0.0)
+        b.run(steps, amps).sync()                      # warm-up: code objects, clocks
+        return b
+
+    def timed(b):
+        b.reset().sync()
+        t0 = time.perf_counter()
+        b.run(steps, amps).sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    kinds = ("hz_lattice", "ez_lattice", "hz_lattice_plain")
+    with batch(kinds[0]) as hzl, batch(kinds[1]) as ezl, batch(kinds[2]) as pla:
+        engines = (hzl, ezl, pla)
+        assert hzl.hz_lattice and pla.hz_lattice and ezl.lattice and not hzl.lattice and not ezl.hz_lattice
+        assert hzl.dispersive and ezl.dispersive and not pla.dispersive
+        l0 = hzl.launches
+        hzl.reset().run(steps, amps).sync()
+        launches = hzl.launches - l0
+        ms = {k: [] for k in kinds}
+        for _ in range(reps):
+            for k, b in zip(kinds, engines):
+                ms[k].append(timed(b))
+        paths = {k: "resident" if b.resident else "streamed" for k, b in zip(kinds, engines)}
+        lds = {k: b.lds_bytes for k, b in zip(kinds, engines)}
+        finite = bool(np.all(np.isfinite(hzl.download()[0])))
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    out = {"count": count, "rows": rows, "cols": cols, "steps": steps, "dtype": np.dtype(dtype).name,
+           "materials": "arrays", "boundary": "periodic", "k_path": "Gamma-X-M-Gamma", "reps": reps,
+           "arithmetic": fd.ARITHMETIC, "lds_arrays": {"hz_lattice": 18, "ez_lattice": 14, "hz_lattice_plain": 9},
+           "launches_per_run": launches, "hz_lattice_finite": finite}
+    for k in kinds:
+        out.update({f"{k}_path": paths[k], f"{k}_lds_bytes_per_member": lds[k], f"{k}_workgroups_per_cu": 163840 // lds[k],
+                    f"{k}_ms": round(med[k], 4), f"{k}_ms_min": round(min(ms[k]), 4),
+                    f"{k}_ms_all": [round(v, 4) for v in ms[k]]})
+    out.update({"hz_lattice_over_ez_lattice": round(med["hz_lattice"] / med["ez_lattice"], 3),
+                "hz_lattice_over_plain": round(med["hz_lattice"] / med["hz_lattice_plain"], 3),
+                "hz_lattice_mcell_steps_per_s": round(count * rows * cols * steps / (med["hz_lattice"] * 1e-3) / 1e6, 1)})
+    return out
+
+
 def bench_hz_bloch_flux(count, rows, cols, steps, dtype, reps, pml_cells):
     """Two whole-period row lines at 10 frequencies on the member of --hz-bloch (a phase sweep, ramp weights, the metal
     strip with its pole) against the same member without them; resident, timed alternately in one process."""
@@ -1539,7 +1609,13 @@ def main():
                     help="time a Bloch phase in the Hz polarisation with a pole against the real Hz and the Ez Bloch kernels")
     ap.add_argument("--hz-bloch-flux", action="store_true",
                     help="time flux lines under the Bloch phase of the Hz polarisation against the same batch without them")
+    ap.add_argument("--hz-lattice", action="store_true",
+                    help="time the lattice mode of the Hz polarisation with a pole against the Ez lattice with its pole")
     a = ap.parse_args()
+    if a.hz_lattice:
+        print(json.dumps(bench_hz_lattice(a.count or 1024, a.rows or 32, a.cols or 33, a.steps or 2000, np.dtype(a.dtype),
+                                          a.reps)), flush=True)
+        return
     if a.hz_bloch_flux:
         print(json.dumps(bench_hz_bloch_flux(a.count or 1024, a.rows or 40, a.cols or 41, a.steps or 2000,
                                              np.dtype(a.dtype), a.reps, a.pml_cells)), flush=True)
